@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the InstantIR denoising step on MI355X (BASELINE.json metric: denoising steps/sec).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]     (e.g. DIR = bench_outputs/, git-ignored)
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Workload (BASELINE.json configs[1], the configuration the metric is quoted on): one 1024x1024 image
@@ -19,6 +19,9 @@ MFMA-kernel launch carries a HIP start/stop event pair stamped with the kernel's
 (hipExtLaunchKernelGGL inside the library); the kernel class with the largest total time is reported against the dense
 fp16 MFMA peak (2.5 PFLOP/s, MI355X_MICROARCH.md).  Algorithmic FLOPs per launch = 2*M*N*K (GEMM /
 implicit-GEMM conv) or 4*B*h*Tq*Tkv*64 (attention).
+--dump-outputs DIR: after the timed steps, what the timed path returned in its last step (the latents it wrote back) is saved
+as DIR/<name>.npy in float32 (ranks > 0 add _rank<r>); inputs and weights are seeded, so two builds run with the same arguments
+can be compared output for output.
 cpu_baseline: the CPU fp32 oracle (oracle/, kind "port") timed on the host cores for a bounded sample
 (one UNet forward of one row at the same resolution), converted with SURVEY.md section 8d's FLOP model.
 """
@@ -34,6 +37,7 @@ import torch
 
 UNET_TFLOP_ROW = 6.833     # SURVEY.md section 8d, 1024^2
 STEP_TFLOP = 39.74         # 2 * (2 * UNet + Aggregator) per image with CFG
+DUMP_BYTES = 64 << 20      # --dump-outputs budget
 
 
 def host_cores():
@@ -47,6 +51,24 @@ def host_cores():
     except (OSError, ValueError):
         pass
     return n
+
+
+def dump_outputs(d, arrays, rank):
+    """Save each tensor as d/<name>.npy (float32).  Over DUMP_BYTES in all, every array is cut to the same fixed, seeded
+    sample of its flattened elements (ascending indices; the indices are saved beside it as <name>_index.npy)."""
+    import numpy as np
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    os.makedirs(d, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    for k, a in arrs.items():
+        if total > DUMP_BYTES:
+            n = max(1, a.size * DUMP_BYTES // (2 * total))      # values and their int32 indices take half the budget each
+            idx = np.sort(np.random.RandomState(0).choice(a.size, n, replace=False)).astype(np.int32)
+            np.save(os.path.join(d, f"{k}_index{sfx}.npy"), idx)
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, f"{k}{sfx}.npy"), a)
+    log(f"outputs of the last timed step written to {d}: {', '.join(arrs)}")
 
 
 def log(msg):
@@ -142,7 +164,11 @@ def main():
                          "restoration, 4 images per GPU, fp8-E4M3 weights on the linear layers (a parity-test configuration, "
                          "printed as its own line)")
     ap.add_argument("--fp16", action="store_true", help="--config 4 with fp16 linears (A/B of the fp8 path)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # ---- launch contract: `--gpus N` must mean N ranks.  Under torch.distributed.run WORLD_SIZE says how many there are;
     # a bare `python bench.py --gpus N` (N > 1) starts the N ranks itself as a CHILD process group (torchrun on
@@ -263,6 +289,8 @@ def main():
     rank_ms = [round(v / args.steps * 1e3, 3) for v in parallel.gather_floats(dt_local, dev)]      # a straggler shows here
     finite = bool(torch.isfinite(x).all().item())
     log(f"timed: {dt / args.steps * 1e3:.2f} ms/step")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"latents": x}, rank)      # before the VAE / roofline legs step x further
 
     # ---- VAE legs (once per image, outside the step metric): full SDXL VAE geometry ----------------------
     vae_ms = e2e = None
@@ -438,6 +466,8 @@ def config4(args, rank, world, local, dev):
     parallel.barrier()
     dt = parallel.max_over_ranks(time.perf_counter() - t1, dev)
     finite = bool(torch.isfinite(out).all().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"latents": out}, rank)    # before the roofline leg steps again
     vae_ms = roof = None
     if rank == 0 and not args.tiny and not args.no_vae:
         from instantir_amd.vae import HipVAE

@@ -4,7 +4,9 @@ Run in the build container only (needs /root/reference, read-only):
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_reference_goldens.py
 
-Outputs (committed, small): tests/golden/ip_adapter.npz, lcm_scheduler.npz, min_sdxl.npz, sft.npz.
+Outputs (committed, small): tests/golden/ip_adapter.npz, lcm_scheduler.npz, min_sdxl.npz, sft.npz, and host_math.json:
+this host's float32 exp / sin / cos / sqrt fingerprint (tests/golden/host_math.py), which tells a test whether the host
+it runs on reproduces these goldens' transcendental bits.
 Nothing here travels except those data files: inputs, the reference modules' own randomly
 initialised parameters (or the seed + inventory that re-creates them, tests/golden/seeded.py), and
 the reference's outputs.
@@ -339,8 +341,19 @@ def gen_sft():
     print("sft.npz:", len(out), "arrays")
 
 
+def gen_host_math():
+    import json
+    from host_math import fingerprint
+    with open(os.path.join(OUT, "host_math.json"), "w") as f:
+        json.dump(fingerprint(), f, indent=1)
+        f.write("\n")
+    print("host_math.json written")
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["ip", "lcm", "min_sdxl", "sft"]
+    which = sys.argv[1:] or ["host", "ip", "lcm", "min_sdxl", "sft"]
+    if "host" in which:
+        gen_host_math()
     if "ip" in which:
         gen_ip_adapter()
     _install_diffusers_shim()

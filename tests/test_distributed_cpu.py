@@ -20,6 +20,7 @@ def _free_port():
 
 def _worker(rank, world, port, q):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    torch.cuda.is_available = lambda: False                 # the gloo/CPU path on a GPU box too (else RCCL on cuda:<rank>)
     r, w, _, dev = parallel.init_from_env()
     g = torch.Generator().manual_seed(100 + rank)          # ranks start with DIFFERENT tensors
     sd = {"a.weight": torch.randn(300, 7, generator=g).half(), "b.bias": torch.randn(11, generator=g).half(),
