@@ -171,6 +171,11 @@ typedef struct iir_attn_desc {
  * and the two SDPA calls + add at :1165,:1185,:1192 (nseg=2: text KV, IP KV), head_dim 64. */
 int iir_attention_d64_f16(const iir_attn_desc* a, void* stream);
 
+/* F.scaled_dot_product_attention at head_dim 80 / 104 (CLIP ViT-H/14, bigG/14 vision towers:
+ * module/ip_adapter/utils.py:106-118); layouts as iir_attention_d64_f16 with 64 -> head_dim.
+ * head_dim 64 is routed to iir_attention_d64_f16. */
+int iir_attention_f16(const iir_attn_desc* a, int32_t head_dim, void* stream);
+
 /* nn.GroupNorm (+ fused nn.SiLU) on NHWC: module/min_sdxl.py:245,252,257,269-271,568,841.
  * workspace: iir_groupnorm_workspace_bytes(R, groups) bytes of fp32 partial sums. */
 int iir_groupnorm_nhwc_f16(const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t R, int32_t HW, int32_t C,

@@ -15,8 +15,10 @@ done
 # honoured hipcc canonicalises every operand first (one extra v_max per score); -inf (masking) stays legal.
 hipcc $FLAGS -mllvm -amdgpu-mfma-vgpr-form=1 -fno-honor-nans -c attention.hip -o build/attention.o &
 pids+=($!)
+hipcc $FLAGS -mllvm -amdgpu-mfma-vgpr-form=1 -fno-honor-nans -c attention_hd.hip -o build/attention_hd.o &
+pids+=($!)
 hipcc $FLAGS -ffp-contract=off -c pointwise.hip -o build/pointwise.o &
 pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT build/gemm_conv.o build/gemm8.o build/attention.o build/norm.o build/pointwise.o
+hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT build/gemm_conv.o build/gemm8.o build/attention.o build/attention_hd.o build/norm.o build/pointwise.o
 echo "built $(realpath $OUT)"

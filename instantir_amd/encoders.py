@@ -13,6 +13,9 @@ kernel).  LayerScale is folded into the output projections (W' = diag(lambda) W)
 projection bias (softmax rows sum to 1: (P(V + 1 b^T)) Wo^T = (P V) Wo^T + Wo b), Q|K are one GEMM, V is produced
 transposed by swapping GEMM operands.  The zero-image branch is input independent and cached per geometry
 (SURVEY.md Appendix C Q7).
+
+* `HipCLIPVision`: the CLIP vision tower of the `use_clip_encoder` branch, same kernels and padding.  Head dims 64
+  (ViT-B / ViT-L), 80 (OpenCLIP ViT-H/14) and 104 (OpenCLIP ViT-bigG/14); other head dims are refused.
 """
 from __future__ import annotations
 
@@ -23,6 +26,7 @@ import torch
 from . import ops
 
 F16 = torch.float16
+CLIP_VISION_HEAD_DIMS = (64, 80, 104)      # head dims with an attention kernel (iir_attention_d64_f16, iir_attention_f16)
 
 
 class HipDinov2:
@@ -162,8 +166,9 @@ class HipCLIPVision:
 
     Patch conv without bias + class embedding + learned position table (fixed geometry), `pre_layrnorm` (sic, the HF
     parameter name), pre-LN blocks with unmasked attention, quick-GELU or GELU MLP.  Token rows are padded to a multiple
-    of 8 (257 -> 264, pad keys masked).  Heads of dim 64 only (ViT-B/16, ViT-B/32, ViT-L/14): the attention kernel is a
-    d = 64 kernel, so ViT-H/14 (d = 80) and bigG (d = 104) are refused with that reason."""
+    of 8 (257 -> 264, pad keys masked).  Head dims 64 (ViT-B/16, ViT-B/32, ViT-L/14: `iir_attention_d64_f16`), 80
+    (OpenCLIP ViT-H/14) and 104 (OpenCLIP ViT-bigG/14; both `iir_attention_f16`); every other head dim is refused with a
+    ValueError.  `num_heads` / `hidden_act` / `eps` must come from the tower's config: D // 64 heads is only a default."""
 
     def __init__(self, sd: Dict[str, torch.Tensor], device, patch_size=None, num_heads=None, eps=1e-5, hidden_act="quick_gelu"):
         self.device = torch.device(device)
@@ -174,9 +179,10 @@ class HipCLIPVision:
         self.D = D = wp.shape[0]
         self.patch = wp.shape[-1] if patch_size is None else patch_size
         self.heads = num_heads if num_heads is not None else D // 64
-        if D // self.heads != 64:
-            raise ValueError(f"HipCLIPVision: head_dim {D // self.heads} -- the attention kernel is built for head_dim 64 "
-                             "(CLIP ViT-B / ViT-L); ViT-H/14 and bigG towers are not supported")
+        self.head_dim = D // self.heads
+        if D % self.heads or self.head_dim not in CLIP_VISION_HEAD_DIMS:
+            raise ValueError(f"HipCLIPVision: {D} features in {self.heads} heads -- the attention kernels take head dims "
+                             f"{CLIP_VISION_HEAD_DIMS} (CLIP ViT-B / ViT-L, ViT-H/14, ViT-bigG/14) only")
         kp = wp[0].numel()
         self.kpad = (kp + 63) // 64 * 64
         self.act = {"quick_gelu": ops.ACT_QUICKGELU, "gelu": ops.ACT_GELU}[hidden_act]
@@ -241,7 +247,8 @@ class HipCLIPVision:
             ops.layernorm(h, n, w[f"{i}.n1.g"], w[f"{i}.n1.b"], self.eps)
             ops.gemm(n, w[f"{i}.qk.w"], qk, bias=w[f"{i}.qk.b"])
             ops.gemm(w[f"{i}.v.w"], n, vt)
-            ops.attention(qk[:, :D], a, [(qk[:, D:], Tp, vt, Tp, T)], B, self.heads, Tp)
+            ops.attention(qk[:, :D], a, [(qk[:, D:], Tp, vt, Tp, T)], B, self.heads, Tp, scale=self.head_dim ** -0.5,
+                          head_dim=self.head_dim)
             ops.gemm(a, w[f"{i}.o.w"], h, bias=w[f"{i}.o.b"], res=h)
             ops.layernorm(h, n, w[f"{i}.n2.g"], w[f"{i}.n2.b"], self.eps)
             ops.gemm(n, w[f"{i}.fc1.w"], f, bias=w[f"{i}.fc1.b"], act=self.act)

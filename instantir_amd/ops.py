@@ -413,9 +413,11 @@ def attn_q_factor(scale=0.125):
     return float(np.float32(scale) * np.float32(ATTN_LOG2E))
 
 
-def attention(q, o, kv, batch, heads, Tq, scale=0.125, causal=False, q_prescaled=False):
-    """q, o: 2-D views (batch*Tq, heads*64).  kv: list of 1-2 tuples (k2d, k_batch_rows, vt2d, vt_batch_stride, Tkv):
-    k2d (batch*k_batch_rows, heads*64) view, vt2d (heads*64, cols) view with batch b starting at column b*vt_batch_stride."""
+def attention(q, o, kv, batch, heads, Tq, scale=0.125, causal=False, q_prescaled=False, head_dim=64):
+    """q, o: 2-D views (batch*Tq, heads*head_dim).  kv: list of 1-2 tuples (k2d, k_batch_rows, vt2d, vt_batch_stride, Tkv):
+    k2d (batch*k_batch_rows, heads*head_dim) view, vt2d (heads*head_dim, cols) view with batch b starting at column
+    b*vt_batch_stride.  head_dim 64 (the UNet, DINOv2, CLIP-B/L) runs `iir_attention_d64_f16`; 80 and 104 (CLIP ViT-H/14,
+    bigG/14 vision towers) `iir_attention_f16` (no fp8 `o`)."""
     _chk2d(q, "q")
     d = L.AttnDesc()
     if o.dtype in _FP8_DTYPES:          # the output feeds an all-fp8 `to_out` GEMM: E4M3 bytes (rounded to fp16 first)
@@ -434,9 +436,12 @@ def attention(q, o, kv, batch, heads, Tq, scale=0.125, causal=False, q_prescaled
         d.kv[i].K, d.kv[i].ldk, d.kv[i].k_batch_stride = k.data_ptr(), k.stride(0), k_rows * k.stride(0)
         d.kv[i].Vt, d.kv[i].ldvt, d.kv[i].vt_batch_stride = vt.data_ptr(), vt.stride(0), vbs
         d.kv[i].Tkv = tkv
-    with _Timed("attn_kernel", 4.0 * batch * heads * Tq * 64 * sum(k[4] for k in kv),
-                2.0 * batch * heads * 64 * (2 * Tq + 2 * sum(k[4] for k in kv))):
-        L.check(L.load().iir_attention_d64_f16(C.byref(d), _stream()), "iir_attention_d64_f16")
+    with _Timed("attn_kernel", 4.0 * batch * heads * Tq * head_dim * sum(k[4] for k in kv),
+                2.0 * batch * heads * head_dim * (2 * Tq + 2 * sum(k[4] for k in kv))):
+        if head_dim == 64:
+            L.check(L.load().iir_attention_d64_f16(C.byref(d), _stream()), "iir_attention_d64_f16")
+        else:
+            L.check(L.load().iir_attention_f16(C.byref(d), head_dim, _stream()), "iir_attention_f16")
     return o
 
 

@@ -201,11 +201,17 @@ class InstantIRPipeline:
         def tensors(m):
             return dict(m) if isinstance(m, dict) else dict(m.state_dict())
 
-        def conf(m):
-            c = getattr(m, "config", None)
+        def as_dict(c):
             if c is None:
                 return None
-            return dict(c) if hasattr(c, "keys") else {k: getattr(c, k) for k in dir(c) if not k.startswith("_") and not callable(getattr(c, k))}
+            if hasattr(c, "keys"):
+                return dict(c)
+            if hasattr(c, "to_dict"):                                      # transformers PretrainedConfig
+                return c.to_dict()
+            return {k: getattr(c, k) for k in dir(c) if not k.startswith("_") and not callable(getattr(c, k))}
+
+        def conf(m):
+            return as_dict(getattr(m, "config", None))
 
         cfg = unet_config or (loaders.unet_config_from_dict(conf(unet)) if conf(unet) else UNetConfig.sdxl())
         hv = vae
@@ -229,7 +235,18 @@ class InstantIRPipeline:
         ie = image_encoder
         if ie is not None and not isinstance(ie, (HipDinov2, HipCLIPVision)):
             sd_ie = tensors(ie)
-            ie = HipCLIPVision(sd_ie, device) if any("vision_model" in k for k in sd_ie) else HipDinov2(sd_ie, device)
+            is_clip = any("vision_model" in k for k in sd_ie)
+            c = conf(ie)
+            if c is not None and c.get("vision_config") is not None:       # a CLIPConfig: the tower's own part
+                c = as_dict(c["vision_config"])
+            if c is None:                                                  # no config: the architectures' defaults
+                kw = {}
+            else:                                                          # (a ViT-H / bigG tower is not D // 64 heads)
+                kw = {"num_heads": c.get("num_attention_heads"), "patch_size": c.get("patch_size", None if is_clip else 14),
+                      "eps": c.get("layer_norm_eps", 1e-5 if is_clip else 1e-6)}
+                if is_clip:
+                    kw["hidden_act"] = c.get("hidden_act", "quick_gelu")
+            ie = HipCLIPVision(sd_ie, device, **kw) if is_clip else HipDinov2(sd_ie, device, **kw)
         pipe = cls(cfg, tensors(unet), scheduler=scheduler, vae=hv, device=device, image_encoder=ie, text_encoder=encs[0],
                    text_encoder_2=encs[1], tokenizer=toks[0], tokenizer_2=toks[1])
         if aggregator is not None:

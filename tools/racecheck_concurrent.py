@@ -88,6 +88,13 @@ for (B, heads, T, kvs) in [(2, 20, 1024, [1024]), (2, 10, 4096, [4096]), (2, 20,
         pad = (Tk + 7) // 8 * 8
         segs.append((rnd(B * Tk, Cc), Tk, rnd(Cc, B * pad), pad, Tk))
     screen(f"attention B={B} h={heads} T={T} kv={kvs}", lambda o: ops.attention(q, o, segs, B, heads, T), [(B * T, Cc)])
+# head dims 80 / 104 (iir_attention_f16): CLIP ViT-H/14 and bigG/14 vision towers at 224 px, q | k as one fused buffer
+for D in (80, 104):
+    B, heads, T = 2, 16, 257
+    Cc, Tp = heads * D, 264
+    qk, vt = rnd(B * Tp, 2 * Cc), rnd(Cc, B * Tp)
+    screen(f"attention_f16 D={D} B={B} h={heads} T={T}",
+           lambda o: ops.attention(qk[:, :Cc], o, [(qk[:, Cc:], Tp, vt, Tp, T)], B, heads, Tp, scale=D ** -0.5, head_dim=D), [(B * Tp, Cc)])
 for (R, HW, Cg) in [(2, 1024, 1280), (2, 4096, 640), (2, 16384, 320), (2, 1024, 2560)]:
     gx, gg, gb = rnd(R * HW, Cg), rnd(Cg) + 1, rnd(Cg)
     ws = ops.gn_workspace(dev, R, 32)
