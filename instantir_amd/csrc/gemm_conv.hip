@@ -57,6 +57,17 @@ __device__ __forceinline__ void ln_merge(float& n, float& mean, float& m2, float
 
 constexpr int vmcnt_imm(int n) { return (n & 15) | 0x0F70 | ((n >> 4) << 14); }   // s_waitcnt vmcnt(n) only
 
+// GroupNorm-partial write-out (gn_out): 64-row slabs written side by side, and whether its LDS fits behind the staged output tile.
+// One definition for the kernel, its launcher and iir_gemm_gn_supported.  The 128-row loader-wave tile writes its two slabs at
+// once on 256 threads each: the thread layout of the two-per-CU 64x160 tile (id 25) it stands in for, so the partials are
+// bit-identical to that tile's (the finalize kernel merges them in a fixed order).
+constexpr int gn_par(int bm, bool lw) { return lw && bm == 128 ? 2 : 1; }
+constexpr bool gn_out_fits(int bm, int bn, int st, int nt, bool lw, bool w8 = false) {
+    const int gnt = nt / gn_par(bm, lw);
+    const long ring = (long)st * (bm * 128 + (w8 ? bn * 64 : bn * 128));
+    return bm % 64 == 0 && bn <= gnt && ((long)bm * (2 * bn + 32) + 15) / 16 * 16 + (long)gn_par(bm, lw) * (gnt / (bn / 8)) * bn * 8 <= ring;
+}
+
 // wait until at most N of this wave's vector-memory ops (the LDS-DMA loads) are outstanding, then barrier.
 // One asm statement with a memory clobber: no LDS access may be scheduled across it.
 template <int N>
@@ -89,6 +100,9 @@ __device__ __forceinline__ void wait_vm_and_barrier() {
 // 7 pieces per K tile, with its SIMD's matrix pipe idle behind it (MI355X_MICROARCH.md, LDS-DMA issue cost) -- the "serial
 // round trip" of DESIGN.md section 5.6.  Both kinds of wave meet at the one barrier per K tile; the protocol (tile kt+1 landed
 // and tile kt's buffer drained at the barrier of iteration kt) is unchanged.  All 2*NW waves share the epilogue write-out.
+// The 128x160 form (round 4, id 54) takes the 257-512-tile problems of 64x160 at one workgroup per CU: 4 loader waves issue the
+// 36 pieces of a K tile (16 activation + 20 weight row groups, 9 each), 288 line requests per CU and K tile against 448 for two
+// 64x160 workgroups.
 // F8 (round 3): BOTH operands are fp8-E4M3 bytes.  A row of 128 K values is the same 128 bytes as a row of 64 halves, so the host
 // hands the launch over with K and lda counted in 2-byte units and everything up to the fragment registers -- addresses, LDS-DMA
 // staging, swizzle, conflict-free 16-byte fragment reads -- is the fp16 path unchanged; the 16 bytes a lane holds are 16 K values,
@@ -119,8 +133,9 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     constexpr int LNP_OFF = (BM * (2 * BN + 32) + 15) / 16 * 16;              // producer partials sit behind the finished output tile
     constexpr bool LN_OUT_FITS = LNP_OFF + BM * (BN / 8) * 8 <= RING_BYTES;
     // GroupNorm partials (round 3): per-thread column statistics of a 64-row slab meet in [row groups][BN] float2 behind the tile
-    constexpr int GN_RG = NT / (BN / 8);                                     // row groups of the column-fixed write-out mapping
-    constexpr bool GN_OUT_FITS = BM % 64 == 0 && LNP_OFF + GN_RG * BN * 8 <= RING_BYTES && BN <= NT;
+    constexpr int GN_PAR = gn_par(BM, LW), GN_NT = NT / GN_PAR;              // slabs written side by side, threads per slab
+    constexpr int GN_RG = GN_NT / (BN / 8);                                  // row groups of the column-fixed write-out mapping
+    constexpr bool GN_OUT_FITS = gn_out_fits(BM, BN, ST, NT, LW, W8);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -835,13 +850,14 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
             // sample: no E[x^2] - mean^2 cancellation); per 64-row slab the RG row groups of a column are merged through LDS in
             // a fixed order by one thread per column -> (mean, M2) of the 64 stored (rounded) values of that channel.  The
             // finalize kernel merges slabs x channels of an (image, group).  No atomics: bit-reproducible.
-            constexpr int RG = NT / CPR, RPT = (64 + RG - 1) / RG;            // rows per thread and slab
-            const int cc = tid % CPR, rg = tid / CPR;
+            constexpr int RG = GN_RG, RPT = (64 + RG - 1) / RG;               // rows per thread and slab
+            const int sl = GN_PAR == 1 ? 0 : tid / GN_NT, lt = tid - sl * GN_NT;    // slab group of this thread, index inside it
+            const int cc = lt % CPR, rg = lt / CPR;
             const bool active = rg < RG;
-            float2* part = (float2*)(smem + LNP_OFF);                         // [RG][BN]
+            float2* part = (float2*)(smem + LNP_OFF) + sl * RG * BN;          // [GN_PAR][RG][BN]
             touch_next_weights();
 #pragma unroll 1
-            for (int half = 0; half < BM / 64; ++half) {
+            for (int half = sl; half < BM / 64; half += GN_PAR) {
                 E8 rr[RPT];
                 if (use_res) {
 #pragma unroll
@@ -879,18 +895,18 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
                         part[rg * BN + cc * 8 + t] = make_float2(k0[t] + s8[t] * inv, fmaxf(q8[t] - s8[t] * s8[t] * inv, 0.f));
                 }
                 __syncthreads();
-                if (tid < BN) {                                               // one thread per tile column: merge the row groups in order
+                if (lt < BN) {                                                // one thread per tile column: merge the row groups in order
                     float n = 0.f, mean = 0.f, m2 = 0.f;
 #pragma unroll 4
                     for (int q = 0; q < RG; ++q) {
-                        const float2 pq = part[q * BN + tid];
+                        const float2 pq = part[q * BN + lt];
                         const float nb = (float)((64 - q + RG - 1) / RG);     // rows row group q holds in a slab
                         const float tot = n + nb, d = pq.x - mean;
                         mean += d * (nb / tot);
                         m2 += pq.y + d * d * (n * nb / tot);
                         n = tot;
                     }
-                    ((float2*)g.gn_out)[(long)(m0 / 64 + half) * g.N + n0 + tid] = make_float2(mean, m2);
+                    ((float2*)g.gn_out)[(long)(m0 / 64 + half) * g.N + n0 + lt] = make_float2(mean, m2);
                 }
                 __syncthreads();
             }
@@ -1006,8 +1022,7 @@ int launch_t(const Geo& g0, bool conv, hipStream_t stream) {
         g.c_vec = 1; g.st_wt = 0;
     }
     if (g.gn_out) {         // producer of GroupNorm partials: whole tiles, 16-byte rows, plain epilogue, rows of an image tile-aligned (caller)
-        constexpr int RINGB = ST * (BM * 128 + (W8 ? BN * 64 : BN * 128)), NTH = 128 * WAVES_M * (LW ? 2 : 1);
-        constexpr bool fits = BM % 64 == 0 && BN <= NTH && (BM * (2 * BN + 32) + 15) / 16 * 16 + (NTH / (BN / 8)) * BN * 8 <= RINGB;
+        constexpr bool fits = gn_out_fits(BM, BN, ST, 128 * WAVES_M * (LW ? 2 : 1), LW, W8);
         if (!fits || g.epi != IIR_EPI_PLAIN || g.c_f32 || g.Ct || g.splitk == 2 || g.ln_out || g.M % BM || g.N % BN || !g.c_vec || (g.res && !g.r_vec) ||
             (conv && (g.y_img_rows | g.res_img_rows)))
             return IIR_EINVAL;
@@ -1142,6 +1157,45 @@ int pick_tile(int M, int N, bool paired, int K = 0) {
     return pick;
 }
 
+// What a 4-wave-kernel launch resolves to: the dispatch() case `id` (base tile + 10 x stages, or a loader-wave build), its tile,
+// ring depth and threads per workgroup.
+struct Resolved { int id, bm, bn, st, nt; bool lw; };
+
+// The one tile resolver.  Every question about what a launch will run -- dispatch() itself, iir_gemm_resolve_tile,
+// iir_gemm_gn_supported, iir_gemm_ln_parts, iir_gemm_fp8_out_supported -- is answered here, so a pre-check taken while a step is
+// planned and the launch it guards cannot disagree.  `tile`: 0 = automatic, 1..9 = a forced base shape (its ring depth and
+// loader waves still chosen here).  K counts 2-byte units of the operand row (all-fp8: the K of the fp8 bytes).  The cross-attention
+// epilogue, split-K and the 8-wave kernel of gemm8.hip are decided ahead of this by dispatch().
+Resolved resolve_tile(int M, int N, int K, bool conv, int dtype, bool wscale, bool f8, int tile) {
+    const bool f16 = dtype == IIR_DT_F16;
+    if (tile == 0) {
+        // (round 4) problems of 257-512 64x160 tiles (M x N = 4096 x 1280, 8192 x 640) with a long K: one 128x160 loader-wave
+        // workgroup per CU (id 54) instead of two 64x160 ones (id 25).  Per CU and K tile that is 288 128-byte line requests
+        // against 448 for the same outputs, and these launches are paced by line requests.  fp16 activations
+        // and weights only.  IIR_T4_LW=0 restores the round-3 choice (A/B switch).
+        static const bool t4_lw = !(getenv("IIR_T4_LW") && atoi(getenv("IIR_T4_LW")) == 0);
+        if (t4_lw && f16 && !wscale && !f8 && K >= one_per_cu_min_k() && M % 128 == 0 && N % 160 == 0 &&
+            (long)(M / 128) * (N / 160) <= 256 && (long)(M / 64) * (N / 160) > 256 && pick_tile(M, N, false, K) == 5)
+            return {54, 128, 160, 3, 512, true};
+        tile = pick_tile(M, N, false, K);
+    }
+    const int bm = kTiles[tile].bm, bn = kTiles[tile].bn;
+    // ring depth: with at most one workgroup per CU nothing else hides the tile latency, and a long K loop
+    // amortises the deeper prologue -> 3 stages for the 64x160 tile (measured +17..40 % on K >= 2560, M*N = 2048x1280)
+    const long blocks = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
+    const bool one_per_cu = tile == 5 && blocks <= 256 && K >= one_per_cu_min_k() && f16;
+    const int stages = one_per_cu ? one_per_cu_stages() : IIR_DEFAULT_STAGES;
+    // one workgroup per CU and a plain GEMM: the loader-wave build (kbench, warm: 2048x1280x1280 456 -> 535 TFLOP/s,
+    // K = 5120 645 -> 707; the per-tile slope stays at the ~70 GB/s per-CU L2 -> LDS fill rate, the fixed part drops)
+    static const bool lw_on = !(getenv("IIR_T5_LW") && atoi(getenv("IIR_T5_LW")) == 0);
+    static const bool lw_conv = !(getenv("IIR_T5_LWCONV") && atoi(getenv("IIR_T5_LWCONV")) == 0);
+    static const bool lw2 = getenv("IIR_T5_LW2") && atoi(getenv("IIR_T5_LW2")) == 1;     // experiment: 2-stage loader-wave build (58 KB of LDS: two kernels can share a CU)
+    if (one_per_cu && lw2 && !conv && !wscale) return {75, bm, bn, 2, 512, true};
+    if (one_per_cu && lw_on && (!conv || (lw_conv && stages == 3)) && (!wscale || (f8 && stages == 3)) && stages >= 3 && stages <= 5)
+        return {stages == 3 ? 55 : stages == 4 ? 65 : 85, bm, bn, stages, 512, true};
+    return {tile + 10 * stages, bm, bn, stages, tile >= 6 && tile <= 8 ? 512 : 256, false};     // (6, 7, 8: the 8-wave builds)
+}
+
 constexpr long SK_CNT_BYTES = 4096;     // 1024 per-tile arrival counters ahead of the slabs
 long splitk_ws_bytes(int M, int N) {
     const long t = (long)((M + 127) / 128) * ((N + 159) / 160);
@@ -1176,24 +1230,7 @@ int dispatch(const Geo& g, bool conv, int tile, hipStream_t stream) {
     // gemm8.hip (142 FLOP per staged byte against 71 for two 128x160 workgroups per CU).  IIR_G8=0 switches it off (A/B).
     if (tile == 0 && gemm8_auto(g, conv)) return iir::gemm8_launch(g, 320, stream);
     if (tile == 91 || tile == 92) return conv ? IIR_EINVAL : iir::gemm8_launch(g, tile == 91 ? 320 : 256, stream);
-    if (tile == 0) tile = pick_tile(g.M, g.N, g.epi != IIR_EPI_PLAIN, g.f8 ? 2 * g.K : g.K);
-    if (tile < 10) {
-        // ring depth: with at most one workgroup per CU nothing else hides the tile latency, and a long K loop
-        // amortises the deeper prologue -> 3 stages for the 64x160 tile (measured +17..40 % on K >= 2560, M*N = 2048x1280)
-        const long blocks = (long)((g.M + kTiles[tile].bm - 1) / kTiles[tile].bm) * ((g.N + kTiles[tile].bn - 1) / kTiles[tile].bn);
-        const bool one_per_cu = tile == 5 && blocks <= 256 && (g.f8 ? 2 * g.K : g.K) >= one_per_cu_min_k() && g.dtype == IIR_DT_F16;     // (all-fp8: g.K counts 2-byte units)
-        const int stages = one_per_cu ? one_per_cu_stages() : IIR_DEFAULT_STAGES;
-        // one workgroup per CU and a plain GEMM: the loader-wave build (kbench, warm: 2048x1280x1280 456 -> 535 TFLOP/s,
-        // K = 5120 645 -> 707; the per-tile slope stays at the ~70 GB/s per-CU L2 -> LDS fill rate, the fixed part drops)
-        static const bool lw_on = !(getenv("IIR_T5_LW") && atoi(getenv("IIR_T5_LW")) == 0);
-        static const bool lw_conv = !(getenv("IIR_T5_LWCONV") && atoi(getenv("IIR_T5_LWCONV")) == 0);
-        static const bool lw2 = getenv("IIR_T5_LW2") && atoi(getenv("IIR_T5_LW2")) == 1;     // experiment: 2-stage loader-wave build (58 KB of LDS: two kernels can share a CU)
-        if (one_per_cu && lw2 && !conv && !g.wscale && g.splitk != 2) tile = 75;
-        else
-        if (one_per_cu && lw_on && (!conv || (lw_conv && stages == 3)) && (!g.wscale || (g.f8 && stages == 3)) && g.splitk != 2 && stages >= 3 && stages <= 5) tile = stages == 3 ? 55 : stages == 4 ? 65 : 85;
-        else
-        tile += 10 * stages;
-    }
+    if (tile < 10) tile = resolve_tile(g.M, g.N, g.f8 ? 2 * g.K : g.K, conv, g.dtype, g.wscale != nullptr, g.f8 != 0, tile).id;     // (all-fp8: g.K counts 2-byte units)
     switch (tile) {
         case 21: return launch<128, 128, 2>(g, conv, stream);
         case 31: return launch<128, 128, 3>(g, conv, stream);
@@ -1205,7 +1242,8 @@ int dispatch(const Geo& g, bool conv, int tile, hipStream_t stream) {
         case 25: return launch<64, 160, 2>(g, conv, stream);
         case 35: return launch<64, 160, 3>(g, conv, stream);
         case 45: return launch<64, 160, 4>(g, conv, stream);
-        case 55: return lw_launch<64, 160, 3>(g, conv, stream);     // 4 compute + 4 loader waves (gemm only, fp16)
+        case 54: return lw_launch<128, 160, 3>(g, conv, stream);    // 4 compute + 4 loader waves, one workgroup per CU (fp16)
+        case 55: return lw_launch<64, 160, 3>(g, conv, stream);     // 4 compute + 4 loader waves (fp16)
         case 65: return lw_launch<64, 160, 4>(g, conv, stream);
         case 75: return lw_launch<64, 160, 2>(g, conv, stream);
         case 85: return lw_launch<64, 160, 5>(g, conv, stream);
@@ -1250,10 +1288,10 @@ extern "C" int iir_gemm_pick_tile(int32_t M, int32_t N, int32_t K, int32_t paire
 // Partials per row a tile = 0, plain-epilogue launch of (M, N, K) leaves in `ln_stats_out` (= N / BN of the tile it resolves to), or 0
 // when that launch cannot produce them (ragged tiles).  The buffer is [parts][M] float2.
 extern "C" int iir_gemm_ln_parts(int32_t M, int32_t N, int32_t K) {
-    const int t = pick_tile(M, N, false, K);
-    const int bm = kTiles[t].bm, bn = kTiles[t].bn;
-    if (t < 1 || t > 5 || M % bm || N % bn || N / bn > 8) return 0;      // (the consumer holds at most 8 partials per row in registers)
-    return N / bn;
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    const Resolved r = resolve_tile(M, N, K, false, IIR_DT_F16, false, false, 0);
+    if (M % r.bm || N % r.bn || N / r.bn > 8) return 0;      // (the consumer holds at most 8 partials per row in registers)
+    return N / r.bn;
 }
 
 static int fill_gemm_geo(const iir_gemm_desc* d, Geo& g);
@@ -1262,24 +1300,17 @@ static int fill_gemm_geo(const iir_gemm_desc* d, Geo& g);
 // (`gn_stats_out`): whole tiles and room for the column partials behind the staged output tile.
 extern "C" int iir_gemm_gn_supported(int32_t M, int32_t N, int32_t K, int32_t is_conv) {
     if (M <= 0 || N <= 0 || K <= 0 || M % 64) return 0;
-    const int t = pick_tile(M, N, false, K);
-    if (t < 1 || t > 5) return 0;
-    const int bm = kTiles[t].bm, bn = kTiles[t].bn;
-    if (M % bm || N % bn) return 0;
-    const long blocks = (long)(M / bm) * (N / bn);
-    const bool lw = t == 5 && blocks <= 256 && K >= one_per_cu_min_k() && one_per_cu_stages() == 3;
-    const int st = lw ? 3 : IIR_DEFAULT_STAGES, nt = lw ? 512 : 256;
-    const long ring = (long)st * (bm + bn) * 128, need = ((long)bm * (2 * bn + 32) + 15) / 16 * 16 + (long)(nt / (bn / 8)) * bn * 8;
-    (void)is_conv;
-    return bn <= nt && need <= ring ? 1 : 0;
+    const Resolved r = resolve_tile(M, N, K, is_conv != 0, IIR_DT_F16, false, false, 0);
+    if (M % r.bm || N % r.bn) return 0;
+    return gn_out_fits(r.bm, r.bn, r.st, r.nt, r.lw) ? 1 : 0;
 }
 
 // 1 when the tile = 0 all-fp8 launch of (M, N, K) can store its result as fp8 bytes (`c_fp8`): whole tiles of the tile it resolves to
 extern "C" int iir_gemm_fp8_out_supported(int32_t M, int32_t N, int32_t K, int32_t paired) {
     if (M <= 0 || N <= 0 || K <= 0 || K % 128) return 0;
-    const int t = pick_tile(M, N, paired != 0, K);
-    if (t < 1 || t > 5) return 0;
-    return (M % kTiles[t].bm == 0 && N % kTiles[t].bn == 0) ? 1 : 0;
+    (void)paired;
+    const Resolved r = resolve_tile(M, N, K, false, IIR_DT_F16, true, true, 0);
+    return (M % r.bm == 0 && N % r.bn == 0) ? 1 : 0;
 }
 
 extern "C" int iir_gemm_f16(const iir_gemm_desc* d, void* stream) {
@@ -1290,15 +1321,16 @@ extern "C" int iir_gemm_f16(const iir_gemm_desc* d, void* stream) {
     return dispatch(g, false, d->tile, (hipStream_t)stream);
 }
 
-// Which kernel / tile `iir_gemm_f16(d)` resolves to, without launching: 91 = the 8-wave 256x320 kernel (gemm8.hip), otherwise the
-// 4-wave tile id of `iir_gemm_pick_tile` (or d->tile when the caller forces one).  Used to NAME launches (bench.py roofline classes).
+// Which kernel / tile `iir_gemm_f16(d)` resolves to, without launching: 91 = the 8-wave 256x320 kernel (gemm8.hip), 93 = the
+// cross-attention tile, otherwise the dispatch() case of the 4-wave kernel (base tile + 10 x stages, or a loader-wave build such as
+// 55 / 54; id % 10 is the base shape of `iir_gemm_tile_bn`), or d->tile when the caller forces one.  Used to NAME launches (bench.py roofline classes).
 extern "C" int iir_gemm_resolve_tile(const iir_gemm_desc* d) {
     Geo g{};
     if (fill_gemm_geo(d, g) != IIR_OK) return -1;
     if (g.xa_on) return 93;
     if (d->tile != 0) return d->tile;
     if (gemm8_auto(g, false)) return 91;
-    return pick_tile(g.M, g.N, g.epi != IIR_EPI_PLAIN, g.f8 ? 2 * g.K : g.K);
+    return resolve_tile(g.M, g.N, g.f8 ? 2 * g.K : g.K, false, g.dtype, g.wscale != nullptr, g.f8 != 0, 0).id;
 }
 
 static int fill_gemm_geo(const iir_gemm_desc* d, Geo& g) {
