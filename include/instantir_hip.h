@@ -236,6 +236,27 @@ int iir_silu_f16(const void* x, void* y, int64_t n, void* stream);
 int iir_copy_add_f16(const void* src, int64_t lds, void* dst, int64_t ldd, int64_t dst_off, int64_t M, int32_t C,
                      const void* add, int64_t lda, const float* add_scale, int32_t rows_per_scale, void* stream);
 
+/* FreeU (module/min_sdxl.py:22-77 `fourier_filter` with threshold 1 and `apply_freeu`, applied to each resnet's
+ * (hidden, skip) pair before the torch.cat of CrossAttnUpBlock2D / UpBlock2D, module/unet/unet_2d_ZeroSFT_blocks.py:2600-2627,
+ * 2748-2775; switched on by `enable_freeu`, unet_2d_ZeroSFT.py:919-949).  Two launches per concat, as the two
+ * iir_copy_add_f16 calls they replace.  `rows` = R * H * W NHWC rows of R images; add / add_scale as iir_copy_add_f16 with
+ * rows_per_scale = H * W (add_scale may be NULL = 1).
+ * iir_freeu_stats_f16: the 7 fp32 sums per (image, channel) of t = skip + add * add_scale that the filter needs (sum t, and
+ * sum t cos / sum t sin of the phases of DFT frequencies (1,0), (0,1), (1,1)), per HW slab: partials float
+ * [R][IIR_FREEU_SLABS][7][C], iir_freeu_partials_bytes(rows, H, W, C) bytes.
+ * iir_freeu_concat_f16 (reads those partials in a fixed order):
+ *   cat[m][cat_off + c]      = (x + mid_add * add_scale)[m][c] * (c < cx / 2 ? b : 1),   c < cx
+ *   cat[m][cat_off + cx + c] = fourier_filter(skip + add * add_scale, threshold 1, scale s)[m][c], c < cs
+ * all in fp32, one fp16 rounding per output; s = 1, b = 1 gives exactly the two iir_copy_add_f16 results. */
+#define IIR_FREEU_SLABS 16
+int64_t iir_freeu_partials_bytes(int64_t rows, int32_t H, int32_t W, int32_t C);
+int iir_freeu_stats_f16(const void* skip, int64_t lds, const void* add, int64_t lda, const float* add_scale, int64_t rows,
+                        int32_t H, int32_t W, int32_t C, float* partials, int64_t partials_bytes, void* stream);
+int iir_freeu_concat_f16(const void* x, int64_t ldx, int32_t cx, const void* mid_add, int64_t ldm, const void* skip, int64_t lds,
+                         int32_t cs, const void* add, int64_t lda, const float* add_scale, int64_t rows, int32_t H, int32_t W,
+                         float b, float s, const float* partials, int64_t partials_bytes, void* cat, int64_t ldc,
+                         int64_t cat_off, void* stream);
+
 /* fp32 NCHW latents <-> fp16 NHWC rows (pipelines/sdxl_instantir.py:1503 cat([latents]*2) = rep 2). */
 int iir_pack_latent(const float* x, int32_t B, int32_t C, int32_t HW, void* out, int64_t ldo, int32_t rep, float scale,
                     void* stream);

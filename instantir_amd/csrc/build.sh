@@ -19,6 +19,8 @@ hipcc $FLAGS -mllvm -amdgpu-mfma-vgpr-form=1 -fno-honor-nans -c attention_hd.hip
 pids+=($!)
 hipcc $FLAGS -ffp-contract=off -c pointwise.hip -o build/pointwise.o &
 pids+=($!)
+hipcc $FLAGS -ffp-contract=off -c freeu.hip -o build/freeu.o &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT build/gemm_conv.o build/gemm8.o build/attention.o build/attention_hd.o build/norm.o build/pointwise.o
+hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT build/gemm_conv.o build/gemm8.o build/attention.o build/attention_hd.o build/norm.o build/pointwise.o build/freeu.o
 echo "built $(realpath $OUT)"

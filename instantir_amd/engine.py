@@ -633,6 +633,8 @@ class HipUNet(_Net):
         self._finish_pack()
         self._pack_resampler(sd)
         self._sized = None
+        # FreeU (module/min_sdxl.py:56-77): None, or (s1, s2, b1, b2) applied to the concats of up blocks 0 and 1
+        self.freeu = None
 
     # ---- Resampler (runs once per image batch) ------------------------------------------------
     def _pack_resampler(self, sd):
@@ -742,7 +744,7 @@ class HipUNet(_Net):
             jobs.append((kv["ipk_raw"], kv["ipk"], ada[:, sk.start:sk.start + C], ada[:, sk.start + C:sk.stop], False))
             jobs.append((kv["ipv_raw"], kv["ipvt"], ada[:, sv.start:sv.start + C], ada[:, sv.start + C:sv.stop], True))
         st["ada_jobs"], st["ada_njobs"] = ops.adaln_job_table(jobs, dev), len(jobs)
-        key = (R, H, W)
+        key = (R, H, W, self.freeu is not None)          # FreeU partials take arena room: on / off is a different layout
         if self._sized != key:
             dummy = torch.empty(R * H * W, CPAD, dtype=F16, device="meta")
             self._size_arena(lambda: self._forward(dummy, None, st, None, None, None))
@@ -802,13 +804,24 @@ class HipUNet(_Net):
                 k = len(skips)           # index of this skip in push order
                 cx, cs = x.shape[1], sk.shape[1]
                 cat = A.alloc(R * h * wd, cx + cs)
-                # torch.cat([hidden, skip], dim=1) (module/min_sdxl.py:712) written in place; ControlNet
-                # residuals (stock diffusers: skip + residual) folded into the copies.
-                o.copy_add(x, cat, 0, add=pending_mid, add_scale=res_scale if pending_mid is not None else None,
-                           rows_per_scale=h * wd)
-                pending_mid = None
-                o.copy_add(sk, cat, cx, add=down_res[k] if down_res is not None else None,
-                           add_scale=res_scale if down_res is not None else None, rows_per_scale=h * wd)
+                add = down_res[k] if down_res is not None else None
+                if self.freeu is not None and i < 2:
+                    # FreeU on the post-residual (hidden, skip) pair of up block i = resolution_idx
+                    # (unet_2d_ZeroSFT_blocks.py:2600-2627): stats of the skip, then the concat with b / s applied
+                    s_f, b_f = self.freeu[i], self.freeu[2 + i]
+                    parts = A.alloc(R * ops.FREEU_SLABS * 7, 2 * cs).view(torch.float32)
+                    o.freeu_stats(sk, parts, h, wd, add=add, add_scale=res_scale if add is not None else None)
+                    o.freeu_concat(x, sk, cat, parts, h, wd, b_f, s_f, mid_add=pending_mid, add=add,
+                                   add_scale=res_scale if (add is not None or pending_mid is not None) else None)
+                    pending_mid = None
+                else:
+                    # torch.cat([hidden, skip], dim=1) (module/min_sdxl.py:712) written in place; ControlNet
+                    # residuals (stock diffusers: skip + residual) folded into the copies.
+                    o.copy_add(x, cat, 0, add=pending_mid, add_scale=res_scale if pending_mid is not None else None,
+                               rows_per_scale=h * wd)
+                    pending_mid = None
+                    o.copy_add(sk, cat, cx, add=add, add_scale=res_scale if down_res is not None else None,
+                               rows_per_scale=h * wd)
                 x = self._resnet(f"up_blocks.{i}.resnets.{j}", cat, R, h, wd, temb_all)
                 if depth[i] > 0:
                     x = self._transformer(f"up_blocks.{i}.attentions.{j}", x, depth[i], R, h, wd, st, ada)

@@ -116,6 +116,8 @@ def build_parser():
     p.add_argument("--out_path", type=str, default="./output")
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--synthetic", choices=["tiny", "sdxl"], default=None, help="seeded synthetic weights (no checkpoints needed)")
+    p.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("S1", "S2", "B1", "B2"),
+                   help="FreeU factors (pipe.enable_freeu(s1, s2, b1, b2)); off by default. SDXL: 0.9 0.2 1.3 1.4")
     return p
 
 
@@ -160,8 +162,16 @@ def build_pipeline(args, device):
     return pipe, lcm_scheduler
 
 
+def apply_freeu(pipe, args):
+    """`--freeu S1 S2 B1 B2` -> pipe.enable_freeu(...) (an addition: the reference's infer.py has no such flag; its pipeline has
+    the switch).  Without the flag the pipeline is left as built (FreeU off)."""
+    if getattr(args, "freeu", None) is not None:
+        pipe.enable_freeu(*args.freeu)
+
+
 def main(args, device, rank=0, world=1):
     pipe, lcm_scheduler = build_pipeline(args, device)
+    apply_freeu(pipe, args)
     post_fix = f"_{args.post_fix}" if args.post_fix else ""
     out_dir = f"{args.out_path}/{post_fix}"
     os.makedirs(out_dir, exist_ok=True)

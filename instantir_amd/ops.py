@@ -549,6 +549,42 @@ def copy_add(src, dst, dst_off=0, add=None, add_scale=None, rows_per_scale=1):
     return dst
 
 
+FREEU_SLABS = 16          # IIR_FREEU_SLABS
+
+
+def freeu_partials_floats(rows, H, W, C):
+    """fp32 elements of the partials buffer freeu_stats leaves for a (rows, C) skip of H x W images."""
+    n = L.load().iir_freeu_partials_bytes(rows, H, W, C)
+    if n < 0:
+        raise ValueError(f"freeu: invalid geometry rows={rows} H={H} W={W} C={C}")
+    return n // 4
+
+
+def freeu_stats(skip, partials, H, W, add=None, add_scale=None):
+    """FreeU filter sums of t = skip + add * add_scale[row // (H*W)] per (image, channel, HW slab) into fp32 `partials`."""
+    _chk2d(skip, "skip")
+    M, Cc = skip.shape
+    L.check(L.load().iir_freeu_stats_f16(skip.data_ptr(), skip.stride(0), _p(add), add.stride(0) if add is not None else 0,
+                                         _p(add_scale), M, H, W, Cc, partials.data_ptr(), partials.numel() * 4, _stream()),
+            "iir_freeu_stats_f16")
+    return partials
+
+
+def freeu_concat(x, skip, dst, partials, H, W, b, s, dst_off=0, mid_add=None, add=None, add_scale=None):
+    """dst[:, dst_off:+cx] = (x + mid_add * add_scale), its first cx // 2 channels times b; dst[:, dst_off+cx:+cs] =
+    fourier_filter(skip + add * add_scale, threshold 1, scale s) from the sums freeu_stats left in `partials`."""
+    _chk2d(x, "x"); _chk2d(skip, "skip"); _chk2d(dst, "dst")
+    M, cx = x.shape
+    cs = skip.shape[1]
+    if skip.shape[0] != M or dst.shape[0] != M:
+        raise ValueError("freeu_concat: x, skip and dst must have the same rows")
+    L.check(L.load().iir_freeu_concat_f16(x.data_ptr(), x.stride(0), cx, _p(mid_add), mid_add.stride(0) if mid_add is not None else 0,
+                                          skip.data_ptr(), skip.stride(0), cs, _p(add), add.stride(0) if add is not None else 0,
+                                          _p(add_scale), M, H, W, float(b), float(s), partials.data_ptr(), partials.numel() * 4,
+                                          dst.data_ptr(), dst.stride(0), dst_off, _stream()), "iir_freeu_concat_f16")
+    return dst
+
+
 def pack_latent(x, out, rep=1, scale=1.0):
     """x fp32 (B,C,H,W) contiguous -> out 2-D fp16 view (rep*B*H*W, ld>=C)."""
     B, Cc, H, Wd = x.shape

@@ -107,6 +107,12 @@ class _UNetHandle:
     def enable_adapters(self):       # the loop itself decides which pass runs with the LoRA (:1543-1556)
         pass
 
+    def enable_freeu(self, s1, s2, b1, b2):     # module/unet/unet_2d_ZeroSFT.py:919-943: the pipeline's switch, one state
+        self._pipe.enable_freeu(s1, s2, b1, b2)
+
+    def disable_freeu(self):                     # :945-949
+        self._pipe.disable_freeu()
+
     def disable_adapters(self):
         pass
 
@@ -141,6 +147,7 @@ class InstantIRPipeline:
         self.overlap_streams = True
         self.overlap_sft = os.environ.get("IIR_OVERLAP_SFT", "1") != "0"     # shallow SFT heads beside the decoder's first up block
         self._guidance_scale = 7.0
+        self._freeu = None                          # (s1, s2, b1, b2) or None: see enable_freeu
 
     # ---- reference surface ----------------------------------------------------------------------
     @classmethod
@@ -273,6 +280,23 @@ class InstantIRPipeline:
     def _lora_scaling(self):
         return self._adapters[self._active_adapter][1] if self._active_adapter is not None else 1.0
 
+    def enable_freeu(self, s1, s2, b1, b2):
+        """FreeU (diffusers' StableDiffusionMixin.enable_freeu -> module/unet/unet_2d_ZeroSFT.py:919-943): in up blocks 0 and
+        1 the first half of the hidden channels is scaled by b1 / b2 and the skip goes through `fourier_filter` with scale
+        s1 / s2 (module/min_sdxl.py:22-77) before each concat, in every UNet pass (main and previewer, and
+        `restore_single_step`).  The up blocks test `s1 and s2 and b1 and b2` (unet_2d_ZeroSFT_blocks.py:2600-2605), so a
+        zero factor switches FreeU off everywhere.  SDXL values from diffusers' docs: s1=0.9, s2=0.2, b1=1.3, b2=1.4."""
+        f = tuple(float(v) for v in (s1, s2, b1, b2))
+        self._freeu = f if all(f) else None
+
+    def disable_freeu(self):
+        self._freeu = None
+
+    def _apply_freeu(self, *nets):
+        for n in nets:
+            if n is not None:
+                n.freeu = self._freeu
+
     @property
     def do_classifier_free_guidance(self):
         # pipelines/sdxl_instantir.py:1050-1051 (time_cond_proj_dim is None for SDXL)
@@ -336,6 +360,7 @@ class InstantIRPipeline:
             if self._agg_sd is None:
                 self._agg_sd = self.aggregator.from_unet()
             self._agg = HipAggregator(self.cfg, self._agg_sd, self.device)
+        self._apply_freeu(self._unet, self._unet_prev)
 
     def _loop_for(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale):
         """The step's buffers and captured hipGraphs are kept from one call to the next: a second image of the same geometry,
@@ -344,7 +369,8 @@ class InstantIRPipeline:
         at 1024^2).  Anything the captured launches depend on is part of the key; `IIR_LOOP_CACHE=0` switches it off."""
         nets = (self._unet, self._unet_prev, self._agg)
         key = (B, rep, Hl, Wl, reference_latents is not None, float(guidance_rescale or 0.0), self.use_graphs, self.overlap_streams,
-               self.overlap_sft, tuple(None if n is None else (id(n), n.arena_gen, n.inkernel_prefetch, n.gn_fuse) for n in nets))
+               self.overlap_sft, tuple(None if n is None else (id(n), n.arena_gen, n.inkernel_prefetch, n.gn_fuse) for n in nets),
+               self._freeu)           # the FreeU factors are launch arguments of the captured concats
         cached = self._loop_cache
         if cached is not None and cached[0] == key and os.environ.get("IIR_LOOP_CACHE", "1") != "0":
             if cached[1].adopt(st, st_prev, st_agg, lq, reference_latents, previewer_scheduler):
@@ -500,6 +526,7 @@ class InstantIRPipeline:
         else:
             self._build()
             net = self._unet_prev
+        self._apply_freeu(net)
         sched = previewer_scheduler if previewer_scheduler is not None else LCMSingleStepScheduler.from_config(self.scheduler.config)
         dev, cfg = self.device, self.cfg
         image = self._prepare_image(image)

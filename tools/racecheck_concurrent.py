@@ -24,7 +24,10 @@ def noise(n):
             ops.attention(nq[:, :640], nao, [(nq[:, 640:], 2048, nvt, 2048, 2048)], 2, 10, 2048)
             ops.conv2d(ncx, ncw, nco)
 bad = []
+ONLY = os.environ.get("ONLY")          # run only the cases whose name contains this substring
 def screen(name, launch, shapes, dtype=torch.half):
+    if ONLY and ONLY not in name:
+        return
     first = None; nd = 0; where = None
     for it in range(REP):
         dts = list(dtype) if isinstance(dtype, (list, tuple)) else [dtype] * len(shapes)
@@ -112,6 +115,17 @@ screen("conv3x3 2x32x32 1280->1280 tile 55 (loader waves)", lambda o: ops.conv2d
 # pointwise / glue
 ca, cadd, csc = rnd(8192, 640), rnd(8192, 640), torch.tensor([0.7, 1.0], device=dev)
 screen("copy_add 8192x640 -> cat buffer", lambda o: ops.copy_add(ca, o, 640, add=cadd, add_scale=csc, rows_per_scale=4096), [(8192, 1280)])
+# FreeU (round 5): filter sums of the skip, then the concat; the two decoder shapes of the 1024^2 step
+for (fH, fW, fcx, fcs) in [(32, 32, 1280, 1280), (64, 64, 640, 320)]:
+    frows = 2 * fH * fW
+    fx, fsk, fadd, fmid = rnd(frows, fcx), rnd(frows, fcs), rnd(frows, fcs, scale=0.5), rnd(frows, fcx, scale=0.5)
+    fsc = torch.tensor([0.8, 1.1], device=dev)
+    fparts = torch.zeros(ops.freeu_partials_floats(frows, fH, fW, fcs), dtype=torch.float32, device=dev)
+    screen(f"freeu_stats 2x{fH}x{fW} C={fcs}", lambda o: ops.freeu_stats(fsk, o.view(-1), fH, fW, add=fadd, add_scale=fsc),
+           [(fparts.numel(),)], dtype=torch.float32)
+    ops.freeu_stats(fsk, fparts, fH, fW, add=fadd, add_scale=fsc)
+    screen(f"freeu_concat 2x{fH}x{fW} {fcx}+{fcs}", lambda o: ops.freeu_concat(fx, fsk, o, fparts, fH, fW, 1.3, 0.9, mid_add=fmid, add=fadd,
+                                                                              add_scale=fsc), [(frows, fcx + fcs)])
 sil = rnd(2, 1280)
 screen("silu", lambda o: ops.silu(sil, o), [(2, 1280)])
 # the small launches of a step (few workgroups: the occupancy of the finalize kernel that failed)
