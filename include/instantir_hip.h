@@ -265,6 +265,11 @@ int iir_unpack_latent(const void* in, int64_t ldi, int32_t R, int32_t C, int32_t
 int iir_pack_latent_t(const float* x, int32_t B, int32_t C, int32_t HW, void* out, int64_t ldo, int32_t rep, float scale,
                       int32_t dtype, void* stream);
 int iir_unpack_latent_t(const void* in, int64_t ldi, int32_t R, int32_t C, int32_t HW, float* out, int32_t dtype, void* stream);
+/* iir_pack_latent_t with the scale read from device memory (`scale` = device fp32[1]): the sigma schedulers' UNet input
+ * c_in * x (scale_model_input, pipelines/sdxl_instantir.py:1503-1504) changes every step, and a host float would be baked
+ * into a captured graph.  Same expression as iir_pack_latent_t: equal scales give equal bits. */
+int iir_pack_latent_dscale(const float* x, int32_t B, int32_t C, int32_t HW, void* out, int64_t ldo, int32_t rep, const float* scale,
+                           int32_t dtype, void* stream);
 
 /* CFG + main scheduler step (pipelines/sdxl_instantir.py:1619-1633).  coef = device fp32[8]:
  * {guidance, sqrt(1-abar_t), sqrt(abar_t), k_x0, k_x, k_eps, k_noise, 0}; prev = k_x0*x0 + k_x*x + k_eps*eps
@@ -275,6 +280,16 @@ int iir_sched_step(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int3
 /* rescale_noise_cfg, pipelines/sdxl_instantir.py:181-192 (used at :1623-1626 when guidance_rescale > 0): per image
  * factor[b] = phi * std(eps_text) / std(eps_cfg) + (1 - phi) over (C,H,W); iir_sched_step multiplies the guided
  * eps of image b by eps_factor[b] (NULL = 1).  coef[0] = guidance scale, as for iir_sched_step. */
+/* iir_sched_step plus one history term, for the Euler / Euler-ancestral / DPM++ 2M schedulers, each in its own sample
+ * space: coef = device fp32[8] {guidance, sb, sa, k_x0, k_x, k_eps, k_noise, k_h};
+ * prev = k_x0*x0 + k_x*x + k_eps*eps + k_h*m_prev + k_noise*noise with x0 = (x - sb*eps)/sa
+ * (Euler: sb = sigma_i, sa = 1; DPM++: sb = sigma_i/sqrt(sigma_i^2+1), sa = 1/sqrt(sigma_i^2+1)).
+ * `hist` = fp32 NCHW (B, C, H, W), updated in place: each element reads m_prev, then stores this step's x0, so one captured
+ * launch serves every step.  It is never loaded when k_h == 0 (a solver's first step: the plane may hold garbage).
+ * `hist` must not alias x, prev or x0_out. */
+int iir_sched_step_hist(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg, const float* coef,
+                        const float* x, const float* noise, float* hist, float* prev, float* x0_out, const float* eps_factor,
+                        void* stream);
 int iir_cfg_rescale_factor(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, const float* coef,
                            float guidance_rescale, float* factor, void* stream);
 
@@ -288,6 +303,10 @@ int iir_lcm_step(const void* eps_nhwc, int64_t lde, int32_t B, int32_t rep, int3
 int iir_sched_step_f32(const float* eps, const float* x, const float* noise, const float* coef, int64_t n, float* prev,
                        float* x0_out, void* stream);
 int iir_axpby_f32(const float* x, const float* y, const float* coef, int64_t n, float* out, void* stream);
+/* iir_sched_step_f32 with the history term of iir_sched_step_hist (coef[7] = k_h, `hist` fp32[n] read iff k_h != 0,
+ * then overwritten with x0): the sigma schedulers' `.step()`.  `hist` must not alias eps, x, prev or x0_out. */
+int iir_sched_step_hist_f32(const float* eps, const float* x, const float* noise, const float* coef, float* hist, int64_t n,
+                            float* prev, float* x0_out, void* stream);
 
 /* Weight prefetch: touches every 128-byte line of [p, p+bytes) with `blocks` workgroups so the range
  * sits in the 256 MiB Infinity Cache when the GEMM/conv that streams it starts (the reference has no

@@ -6,7 +6,8 @@
 // Replaces: Timesteps (module/min_sdxl.py:205-224); nn.SiLU on temb (:263); torch.cat of skip tensors
 // (:712) with the ControlNet residual add folded in (pipelines/sdxl_instantir.py:1602-1603 and diffusers'
 // `skip + residual`); latent_model_input = cat([latents]*2) (:1503); CFG (:1619-1621); main scheduler
-// step (:1629-1633, DDPM / DDIM linear forms); LCMSingleStepScheduler.step
+// step (:1629-1633, DDPM / DDIM linear forms, and the Euler / Euler-ancestral / DPM++ 2M forms with one history
+// plane); LCMSingleStepScheduler.step
 // (schedulers/lcm_single_step_scheduler.py:455-484).
 #include "common.h"
 #include "../../include/instantir_hip.h"
@@ -187,6 +188,55 @@ __global__ void transpose_kernel(const f16* in, long ldi, int rows, int cols, f1
     }
 }
 
+// The same pack with the scale read from device memory (sigma schedulers: the UNet input c_in * x changes every step, and
+// a host float would be baked into a captured graph).  Same expression as pack_latent_kernel, so equal scales give equal bits.
+template <typename E>
+__global__ void pack_latent_dscale_kernel(const float* x, int B, int C, int HW, E* out, long ldo, int rep, const float* scale_dev) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * HW) return;
+    const float scale = *scale_dev;
+    const int b = (int)(i / HW), p = (int)(i % HW);
+    for (int c = 0; c < C; ++c) {
+        const E v = (E)(x[((long)b * C + c) * HW + p] * scale);
+        for (int k = 0; k < rep; ++k) out[((long)(k * B + b) * HW + p) * ldo + c] = v;
+    }
+}
+
+// sched_step_kernel plus one history term (multistep solvers, DPM++ 2M):
+//   prev = k_x0 * x0 + k_x * x + k_eps * eps + k_h * m_prev + k_noise * noise ,  coef[7] = k_h
+// hist (fp32 NCHW, B rows) holds m_prev on entry and this step's x0 on exit: each element is read, then overwritten by the
+// thread that owns it, so one captured launch serves every step.  With k_h == 0 the plane is never loaded (it is
+// uninitialised or stale on a solver's first step, and 0 * NaN would leak into prev).
+__global__ void sched_step_hist_kernel(const f16* eps_nhwc, long lde, int B, int C, int HW, int cfg, const float* coef,
+                                       const float* x, const float* noise, float* hist, float* prev, float* x0_out,
+                                       const float* eps_factor) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * HW) return;
+    const int b = (int)(i / HW), p = (int)(i % HW);
+    const float g = coef[0], sb = coef[1], sa = coef[2], k0 = coef[3], k1 = coef[4], k2 = coef[5], k3 = coef[6], kh = coef[7];
+    for (int c = 0; c < C; ++c) {
+        const long o = ((long)b * C + c) * HW + p;
+        float e;
+        if (cfg) {
+            const float u = (float)eps_nhwc[((long)b * HW + p) * lde + c];
+            const float t = (float)eps_nhwc[((long)(B + b) * HW + p) * lde + c];
+            e = u + g * (t - u);
+            if (eps_factor) e *= eps_factor[b];
+        } else {
+            e = (float)eps_nhwc[((long)b * HW + p) * lde + c];
+        }
+        const float xv = x[o];
+        const float x0 = (xv - sb * e) / sa;
+        float pv = k0 * x0 + k1 * xv;
+        if (k2 != 0.f) pv = pv + k2 * e;
+        if (kh != 0.f) pv = pv + kh * hist[o];
+        if (noise && k3 != 0.f) pv = pv + k3 * noise[o];
+        prev[o] = pv;
+        hist[o] = x0;
+        if (x0_out) x0_out[o] = x0;
+    }
+}
+
 inline int nblk(long n, int t) { return (int)((n + t - 1) / t); }
 
 }  // namespace
@@ -235,6 +285,16 @@ extern "C" int iir_pack_latent(const float* x, int32_t B, int32_t C, int32_t HW,
     return iir_pack_latent_t(x, B, C, HW, out, ldo, rep, scale, IIR_DT_F16, stream);
 }
 
+extern "C" int iir_pack_latent_dscale(const float* x, int32_t B, int32_t C, int32_t HW, void* out, int64_t ldo, int32_t rep,
+                                      const float* scale, int32_t dtype, void* stream) {
+    (void)hipGetLastError();
+    if (!x || !out || !scale || B <= 0 || C <= 0 || HW <= 0 || rep <= 0 || ldo < C) return IIR_EINVAL;
+    if (dtype != IIR_DT_F16 && dtype != IIR_DT_BF16) return IIR_EINVAL;
+    if (dtype == IIR_DT_BF16) hipLaunchKernelGGL(pack_latent_dscale_kernel<bf16>, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream, x, B, C, HW, (bf16*)out, (long)ldo, rep, scale);
+    else hipLaunchKernelGGL(pack_latent_dscale_kernel<f16>, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream, x, B, C, HW, (f16*)out, (long)ldo, rep, scale);
+    return iir_launch_status();
+}
+
 extern "C" int iir_unpack_latent_t(const void* in, int64_t ldi, int32_t R, int32_t C, int32_t HW, float* out, int32_t dtype,
                                    void* stream) {
     (void)hipGetLastError();
@@ -266,6 +326,18 @@ extern "C" int iir_sched_step(const void* eps_nhwc, int64_t lde, int32_t B, int3
     if (eps_factor && !cfg) return IIR_EINVAL;
     hipLaunchKernelGGL(sched_step_kernel, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const f16*)eps_nhwc, (long)lde, B, C, HW, cfg, coef, x, noise, prev, x0_out, eps_out, eps_factor);
+    return iir_launch_status();
+}
+
+extern "C" int iir_sched_step_hist(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
+                                   const float* coef, const float* x, const float* noise, float* hist, float* prev, float* x0_out,
+                                   const float* eps_factor, void* stream) {
+    (void)hipGetLastError();
+    if (!eps_nhwc || !coef || !x || !hist || !prev || B <= 0 || C <= 0 || HW <= 0 || lde < C) return IIR_EINVAL;
+    if (eps_factor && !cfg) return IIR_EINVAL;
+    if (hist == x || hist == prev || (x0_out && hist == x0_out)) return IIR_EINVAL;
+    hipLaunchKernelGGL(sched_step_hist_kernel, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const f16*)eps_nhwc, (long)lde, B, C, HW, cfg, coef, x, noise, hist, prev, x0_out, eps_factor);
     return iir_launch_status();
 }
 
@@ -328,6 +400,23 @@ __global__ void sched_step_f32_kernel(const float* eps, const float* x, const fl
     prev[i] = pv;
     if (x0_out) x0_out[i] = x0;
 }
+// sched_step_f32_kernel plus the history term of sched_step_hist_kernel (coef[7] = k_h; hist read only when k_h != 0,
+// then overwritten with x0)
+__global__ void sched_step_hist_f32_kernel(const float* eps, const float* x, const float* noise, const float* coef, float* hist,
+                                           long n, float* prev, float* x0_out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float sb = coef[1], sa = coef[2], k0 = coef[3], k1 = coef[4], k2 = coef[5], k3 = coef[6], kh = coef[7];
+    const float e = eps[i], xv = x[i];
+    const float x0 = (xv - sb * e) / sa;
+    float pv = k0 * x0 + k1 * xv;
+    if (k2 != 0.f) pv = pv + k2 * e;
+    if (kh != 0.f) pv = pv + kh * hist[i];
+    if (noise && k3 != 0.f) pv = pv + k3 * noise[i];
+    prev[i] = pv;
+    hist[i] = x0;
+    if (x0_out) x0_out[i] = x0;
+}
 // a*x + b*y elementwise fp32 (add_noise: sqrt(abar)*x + sqrt(1-abar)*noise), coef = device {a, b}
 __global__ void axpby_f32_kernel(const float* x, const float* y, const float* coef, long n, float* out) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -341,6 +430,16 @@ extern "C" int iir_sched_step_f32(const float* eps, const float* x, const float*
     (void)hipGetLastError();
     if (!eps || !x || !coef || !prev || n <= 0) return IIR_EINVAL;
     hipLaunchKernelGGL(sched_step_f32_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, noise, coef,
+                       (long)n, prev, x0_out);
+    return iir_launch_status();
+}
+
+extern "C" int iir_sched_step_hist_f32(const float* eps, const float* x, const float* noise, const float* coef, float* hist,
+                                       int64_t n, float* prev, float* x0_out, void* stream) {
+    (void)hipGetLastError();
+    if (!eps || !x || !coef || !hist || !prev || n <= 0) return IIR_EINVAL;
+    if (hist == x || hist == eps || hist == prev || (x0_out && hist == x0_out)) return IIR_EINVAL;
+    hipLaunchKernelGGL(sched_step_hist_f32_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, noise, coef, hist,
                        (long)n, prev, x0_out);
     return iir_launch_status();
 }

@@ -88,6 +88,17 @@ def shard_batches(batches, rank, world):
     return batches[lo:hi]
 
 
+# --scheduler choice -> (class in instantir_amd.schedulers, from_config overrides)
+SCHEDULERS = {
+    "ddpm": ("DDPMScheduler", {}),
+    "ddim": ("DDIMScheduler", {}),
+    "euler": ("EulerDiscreteScheduler", {}),
+    "euler_a": ("EulerAncestralDiscreteScheduler", {}),
+    "dpmpp_2m": ("DPMSolverMultistepScheduler", {"algorithm_type": "dpmsolver++"}),
+    "dpmpp_2m_sde": ("DPMSolverMultistepScheduler", {"algorithm_type": "sde-dpmsolver++"}),
+}
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="InstantIR restoration on MI355X")
     p.add_argument("--sdxl_path", type=str, default=None)
@@ -118,6 +129,9 @@ def build_parser():
     p.add_argument("--synthetic", choices=["tiny", "sdxl"], default=None, help="seeded synthetic weights (no checkpoints needed)")
     p.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("S1", "S2", "B1", "B2"),
                    help="FreeU factors (pipe.enable_freeu(s1, s2, b1, b2)); off by default. SDXL: 0.9 0.2 1.3 1.4")
+    p.add_argument("--scheduler", choices=sorted(SCHEDULERS), default="ddpm",
+                   help="main scheduler, built as Cls.from_config(pipe.scheduler.config); default ddpm (the reference's)")
+    p.add_argument("--karras", action="store_true", help="Karras sigmas (use_karras_sigmas=True) for euler / dpmpp_2m / dpmpp_2m_sde")
     return p
 
 
@@ -162,6 +176,23 @@ def build_pipeline(args, device):
     return pipe, lcm_scheduler
 
 
+def apply_scheduler(pipe, args):
+    """`--scheduler NAME [--karras]` -> pipe.scheduler = Cls.from_config(pipe.scheduler.config, ...) (an addition: the
+    reference's infer.py always runs DDPMScheduler).  The default, ddpm without --karras, leaves the pipeline as built."""
+    from . import schedulers as S
+    name = getattr(args, "scheduler", "ddpm") or "ddpm"
+    karras = bool(getattr(args, "karras", False))
+    if karras and name not in ("euler", "dpmpp_2m", "dpmpp_2m_sde"):
+        raise SystemExit(f"--karras applies to euler, dpmpp_2m and dpmpp_2m_sde, not to {name}")
+    if name == "ddpm":
+        return
+    cls_name, kw = SCHEDULERS[name]
+    kw = dict(kw)
+    if karras:
+        kw["use_karras_sigmas"] = True
+    pipe.scheduler = getattr(S, cls_name).from_config(pipe.scheduler.config, **kw)
+
+
 def apply_freeu(pipe, args):
     """`--freeu S1 S2 B1 B2` -> pipe.enable_freeu(...) (an addition: the reference's infer.py has no such flag; its pipeline has
     the switch).  Without the flag the pipeline is left as built (FreeU off)."""
@@ -172,6 +203,7 @@ def apply_freeu(pipe, args):
 def main(args, device, rank=0, world=1):
     pipe, lcm_scheduler = build_pipeline(args, device)
     apply_freeu(pipe, args)
+    apply_scheduler(pipe, args)
     post_fix = f"_{args.post_fix}" if args.post_fix else ""
     out_dir = f"{args.out_path}/{post_fix}"
     os.makedirs(out_dir, exist_ok=True)

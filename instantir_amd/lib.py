@@ -128,11 +128,14 @@ SIGNATURES = {
     "iir_unpack_latent": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P]),
     "iir_pack_latent_t": (C.c_int, [_P, _I32, _I32, _I32, _P, _I64, _I32, _F, _I32, _P]),
     "iir_unpack_latent_t": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _I32, _P]),
+    "iir_pack_latent_dscale": (C.c_int, [_P, _I32, _I32, _I32, _P, _I64, _I32, _P, _I32, _P]),
     "iir_sched_step": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "iir_sched_step_hist": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "iir_cfg_rescale_factor": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _F, _P, _P]),
     "iir_lcm_step": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
     "iir_sched_step_f32": (C.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P]),
     "iir_axpby_f32": (C.c_int, [_P, _P, _P, _I64, _P, _P]),
+    "iir_sched_step_hist_f32": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "iir_prefetch": (C.c_int, [_P, _I64, _I32, _P]),
     "iir_blend_tiles_f32": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "iir_transpose_f16": (C.c_int, [_P, _I64, _I32, _I32, _P, _I64, _I32, _P]),

@@ -594,6 +594,16 @@ def pack_latent(x, out, rep=1, scale=1.0):
     return out
 
 
+def pack_latent_dscale(x, out, scale, rep=1):
+    """pack_latent with the scale read from `scale` (fp32 CUDA tensor, one element) at launch time."""
+    B, Cc, H, Wd = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous() and out.dtype in _DT
+    assert scale.dtype == torch.float32 and scale.is_cuda and scale.numel() >= 1
+    L.check(L.load().iir_pack_latent_dscale(x.data_ptr(), B, Cc, H * Wd, out.data_ptr(), out.stride(0), rep, scale.data_ptr(),
+                                            _DT[out.dtype], _stream()), "iir_pack_latent_dscale")
+    return out
+
+
 def unpack_latent(x2d, out):
     """x2d fp16 view (R*H*W, ld) -> out fp32 (R,C,H,W)."""
     R, Cc, H, Wd = out.shape
@@ -608,6 +618,16 @@ def sched_step(eps2d, B, coef, x, prev, noise=None, cfg=True, x0_out=None, eps_o
     L.check(L.load().iir_sched_step(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(),
                                     x.data_ptr(), _p(noise), prev.data_ptr(), _p(x0_out), _p(eps_out), _p(eps_factor),
                                     _stream()), "iir_sched_step")
+    return prev
+
+
+def sched_step_hist(eps2d, B, coef, x, hist, prev, noise=None, cfg=True, x0_out=None, eps_factor=None):
+    """sched_step with the history term coef[7] * hist; `hist` (shape of x, fp32) then holds this step's x0."""
+    _, Cc, H, Wd = x.shape
+    assert hist.shape == x.shape and hist.dtype == torch.float32 and hist.is_contiguous()
+    L.check(L.load().iir_sched_step_hist(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(),
+                                         x.data_ptr(), _p(noise), hist.data_ptr(), prev.data_ptr(), _p(x0_out), _p(eps_factor),
+                                         _stream()), "iir_sched_step_hist")
     return prev
 
 
@@ -638,6 +658,13 @@ def sched_step_f32(eps, x, coef, prev, noise=None, x0_out=None):
     """fp32 contiguous tensors of equal shape; coef fp32 device (8,)."""
     L.check(L.load().iir_sched_step_f32(eps.data_ptr(), x.data_ptr(), _p(noise), coef.data_ptr(), x.numel(), prev.data_ptr(),
                                         _p(x0_out), _stream()), "iir_sched_step_f32")
+    return prev
+
+
+def sched_step_hist_f32(eps, x, coef, hist, prev, noise=None, x0_out=None):
+    """sched_step_f32 with the history term: fp32 contiguous tensors of equal shape, coef fp32 device (8,) with k_h in [7]."""
+    L.check(L.load().iir_sched_step_hist_f32(eps.data_ptr(), x.data_ptr(), _p(noise), coef.data_ptr(), hist.data_ptr(), x.numel(),
+                                             prev.data_ptr(), _p(x0_out), _stream()), "iir_sched_step_hist_f32")
     return prev
 
 

@@ -32,7 +32,8 @@ import torch
 from . import ops
 from .config import UNetConfig, VAEConfig
 from .engine import CPAD, F16, HipAggregator, HipUNet
-from .schedulers import DDIMScheduler, DDPMScheduler, LCMSingleStepScheduler  # noqa: F401
+from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,  # noqa: F401
+                         EulerDiscreteScheduler, LCMSingleStepScheduler)
 from .weights import LCM_LORA_MODULES, PREVIEWER_LORA_MODULES, lora_target
 
 
@@ -370,7 +371,8 @@ class InstantIRPipeline:
         nets = (self._unet, self._unet_prev, self._agg)
         key = (B, rep, Hl, Wl, reference_latents is not None, float(guidance_rescale or 0.0), self.use_graphs, self.overlap_streams,
                self.overlap_sft, tuple(None if n is None else (id(n), n.arena_gen, n.inkernel_prefetch, n.gn_fuse) for n in nets),
-               self._freeu)           # the FreeU factors are launch arguments of the captured concats
+               self._freeu,           # the FreeU factors are launch arguments of the captured concats
+               _sched_form(self.scheduler))   # the sigma schedulers launch the device-scale pack and the history step
         cached = self._loop_cache
         if cached is not None and cached[0] == key and os.environ.get("IIR_LOOP_CACHE", "1") != "0":
             if cached[1].adopt(st, st_prev, st_agg, lq, reference_latents, previewer_scheduler):
@@ -577,7 +579,8 @@ class InstantIRPipeline:
                  reference_latents=None, init_noise=None, step_noises=None, **kwargs):
         """Keyword arguments and defaults of pipelines/sdxl_instantir.py:1067-1115.  Two additions for
         bit-reproducible parity runs: `init_noise` (the randn of init_latents) and
-        `step_noises` (list of per-step DDPM noises) replace draws from `generator` when given.
+        `step_noises` (list of per-step DDPM / Euler-ancestral / DPM++ SDE noises) replace draws from `generator` when given.
+        With a sigma scheduler (Euler, Euler-ancestral, DPM++) `eta` is ignored, as diffusers drops it for those `step()`s.
         `image` must be the LQ *latent* (B,4,h,w) here unless a VAE is attached (`image.shape[1] == 4` branch of :1369-1382)."""
         # :1531-1535 merges the caller's dict over {"temb": emb} and hands it to both UNet passes.  What a key can do there:
         # "scale" is popped by diffusers' UNet forward and scales every LoRA layer for that pass (it also sets the text-encoder
@@ -688,11 +691,16 @@ class InstantIRPipeline:
                              f"{' x 2 (CFG)' if do_cfg else ''})")
 
         # -- timetable and gates (:1385, :1415-1425)
+        sigma_form = _sched_form(self.scheduler) == "hist"
+        if timesteps is not None and sigma_form:
+            raise ValueError(f"timesteps= is not supported with {type(self.scheduler).__name__} (custom sigma timetables are out of "
+                             "scope); pass num_inference_steps, or use DDPMScheduler / DDIMScheduler for a hand-built timetable")
         if timesteps is not None:                                                   # retrieve_timesteps, :195-237
             self.scheduler.set_timesteps(timesteps=list(timesteps), device=None)
         else:
             self.scheduler.set_timesteps(num_inference_steps, device=None)
-        ts = [int(t) for t in self.scheduler.timesteps]
+        # sigma schedulers: the float timestep reaches the UNet and the Aggregator (Karras timetables are fractional)
+        ts = [float(t) if sigma_form else int(t) for t in self.scheduler.timesteps]
         n = len(ts)
         keep, previewing = [], []
         for i in range(n):
@@ -757,7 +765,7 @@ class InstantIRPipeline:
             if step_noises is not None:
                 noise = step_noises[i]
             x0 = loop.step(mode, t, x, (compound if mode != "unet" else scale_rows).repeat(rep), guidance_scale, eta, noise,
-                           generator, want_x0=adastep_restore, want_preview=save_preview_row or adastep_restore)
+                           generator, want_x0=adastep_restore, want_preview=save_preview_row or adastep_restore, i=i)
             if mode == "preview":
                 pv = loop.preview_f32[B * (rep - 1):]
                 if save_preview_row:
@@ -790,10 +798,12 @@ class InstantIRPipeline:
                     st = self._unet.prepare(ctx, pooled, time_ids, self._unet.resampler(img), Hl, Wl)
                     if self._unet_prev is not None:
                         st_prev = self._unet_prev.prepare(ctx, pooled, time_ids, self._unet_prev.resampler(img), Hl, Wl)
-                    mean_keep = loop.previewer_mean
+                    mean_keep, hist_keep = loop.previewer_mean, loop.hist
                     loop = _DenoiseLoop(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler,
                                         guidance_rescale=guidance_rescale)
                     loop.previewer_mean = mean_keep
+                    if hist_keep is not None:                # a multistep solver's x0 history continues across the rebuild
+                        loop.hist.copy_(hist_keep)
         latents_out = x
         if output_type == "latent":
             image_out = latents_out
@@ -806,6 +816,12 @@ class InstantIRPipeline:
         if not return_dict:
             return (image_out, preview_row) if save_preview_row else (image_out,)
         return StableDiffusionXLPipelineOutput(images=image_out)
+
+
+def _sched_form(scheduler):
+    """"hist": a sigma scheduler (Euler, Euler-ancestral, DPM++) driven through `loop_coefficients`, c_in-scaled UNet input
+    and iir_sched_step_hist; "linear": DDPM / DDIM through `step_coefficients` and iir_sched_step."""
+    return "hist" if hasattr(scheduler, "loop_coefficients") else "linear"
 
 
 def _copy_state(dst, src):
@@ -861,8 +877,11 @@ class _DenoiseLoop:
         self.noise = torch.zeros_like(self.x_in)
         self.preview_f32 = torch.zeros(R, 4, H, W, dtype=torch.float32, device=dev)
         self.previewer_mean = torch.zeros_like(self.x_in)
-        # per-step scalars: [t x R | lcm coef x4 | sched coef x8 | res scale x R]
-        self.n_sc = R + 4 + 8 + R
+        self.form = _sched_form(pipe.scheduler)
+        # the x0 history of a multistep solver, read and rewritten in place by every step's iir_sched_step_hist
+        self.hist = torch.zeros_like(self.x_in) if self.form == "hist" else None
+        # per-step scalars: [t x R | lcm coef x4 | sched coef x8 (k_h in [7]) | res scale x R | c_in]
+        self.n_sc = R + 4 + 8 + R + 1
         # ring of pinned staging rows: a row is rewritten only after the H2D copy that read it has completed
         self.sc_ring = [torch.zeros(self.n_sc, dtype=torch.float32).pin_memory() for _ in range(8)]
         self.sc_events = [None] * 8
@@ -871,7 +890,8 @@ class _DenoiseLoop:
         self.t_dev = self.sc_dev[:R].view(R, 1)
         self.lcm_coef = self.sc_dev[R:R + 4]
         self.sched_coef = self.sc_dev[R + 4:R + 12]
-        self.res_scale = self.sc_dev[R + 12:]
+        self.res_scale = self.sc_dev[R + 12:2 * R + 12]
+        self.c_in = self.sc_dev[2 * R + 12:]
         self.graphs = {}
         self.side = None
 
@@ -888,11 +908,16 @@ class _DenoiseLoop:
             ops.pack_latent(reference_latents.to(self.x_in.device, torch.float32).contiguous(), self.ref16, rep=self.rep)
         self.previewer_mean = torch.zeros_like(self.x_in)
         self.cfg_factor.fill_(1.0)
+        if self.hist is not None:
+            self.hist.zero_()
         return True
 
     def _launch(self, mode, use_noise, want_x0, want_preview):
         p, B, rep = self.p, self.B, self.rep
-        ops.pack_latent(self.x_in, self.lat16, rep=rep)                      # cat([latents]*2), :1503
+        if self.form == "hist":                                              # scale_model_input(cat([latents]*2), t), :1503-1504
+            ops.pack_latent_dscale(self.x_in, self.lat16, self.c_in, rep=rep)
+        else:
+            ops.pack_latent(self.x_in, self.lat16, rep=rep)                  # cat([latents]*2), :1503
         down = mid = None
         if mode == "unet_res":       # stale residuals of the last Aggregator pass, re-scaled (see __call__)
             eps = p._unet.forward(self.lat16, self.t_dev, self.st, p._agg._out, p._agg._out_mid, self.res_scale)
@@ -951,10 +976,15 @@ class _DenoiseLoop:
         fac = None
         if rep == 2 and self.guidance_rescale > 0.0:
             fac = ops.cfg_rescale_factor(eps, B, self.sched_coef, self.x_in, self.guidance_rescale, self.cfg_factor)
+        if self.form == "hist":
+            ops.sched_step_hist(eps, B, self.sched_coef, self.x_in, self.hist, self.x_out, noise=self.noise if use_noise else None,
+                                cfg=rep == 2, x0_out=self.x0 if want_x0 else None, eps_factor=fac)
+            return
         ops.sched_step(eps, B, self.sched_coef, self.x_in, self.x_out, noise=self.noise if use_noise else None,
                        cfg=rep == 2, x0_out=self.x0 if want_x0 else None, eps_factor=fac)
 
-    def step(self, mode, t, x, res_scale_rows, guidance, eta, noise, generator, want_x0=False, want_preview=False):
+    def step(self, mode, t, x, res_scale_rows, guidance, eta, noise, generator, want_x0=False, want_preview=False, i=None):
+        """`i`: the step's index in the scheduler's timetable (the sigma schedulers' coefficients are per index)."""
         p, R = self.p, self.B * self.rep
         slot = self.sc_idx % len(self.sc_ring)
         self.sc_idx += 1
@@ -962,12 +992,24 @@ class _DenoiseLoop:
             self.sc_events[slot].synchronize()
         sc = self.sc_ring[slot]
         sc[:R] = float(t)
-        if mode == "preview":
-            sc[R:R + 4] = torch.tensor(self.prev_sched.preview_coefficients(t))
-        coef = p.scheduler.step_coefficients(t, eta=eta)
+        if self.form == "hist":
+            # eta is not an argument of these schedulers' step() (diffusers drops it): ignored
+            lc = p.scheduler.loop_coefficients(i)
+            c_in = lc["c_in"]
+            if mode == "preview":
+                # the LCM previewer gets the scaled input c_in * x (:1555-1561) and t.to(int64) (:1557): fold c_in into its
+                # coefficients so that iir_lcm_step reads the unscaled latent
+                sb, sa, c_out, c_skip = self.prev_sched.preview_coefficients(lc["t_lcm"])
+                sc[R:R + 4] = torch.tensor([sb / c_in, sa / c_in, c_out, c_skip * c_in])
+            coef = list(lc["coef"])
+            sc[2 * R + 12] = c_in
+        else:
+            if mode == "preview":
+                sc[R:R + 4] = torch.tensor(self.prev_sched.preview_coefficients(t))
+            coef = p.scheduler.step_coefficients(t, eta=eta)
         coef[0] = float(guidance)
         sc[R + 4:R + 12] = torch.tensor(coef)
-        sc[R + 12:] = res_scale_rows.float()
+        sc[R + 12:2 * R + 12] = res_scale_rows.float()
         use_noise = coef[6] != 0.0
         if use_noise:
             if noise is None:
@@ -983,7 +1025,10 @@ class _DenoiseLoop:
         if p.use_graphs:
             g = self.graphs.get(key)
             if g is None:
+                hist = self.hist.clone() if self.hist is not None else None
                 self._launch(*key)                        # warm-up: one-time attribute / workspace setup
+                if hist is not None:
+                    self.hist.copy_(hist)                 # the warm-up consumed the history: the replay below is the step
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):

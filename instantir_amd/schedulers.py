@@ -14,6 +14,10 @@ API mirrors what `pipelines/sdxl_instantir.py` touches on a scheduler object (SU
 * `DDPMScheduler` / `DDIMScheduler`: diffusers-0.28.1 classes constructed at infer.py:137 from SDXL's
   scheduler_config.json: scaled_linear betas 0.00085..0.012, 1000 train
   steps, steps_offset 1, "leading" spacing, epsilon prediction, fixed_small variance, no clipping.
+* `EulerDiscreteScheduler` / `EulerAncestralDiscreteScheduler` / `DPMSolverMultistepScheduler`: the diffusers-0.28.1 classes a
+  user swaps in with `Cls.from_config(pipe.scheduler.config)` (the reference's loop calls `scale_model_input`,
+  pipelines/sdxl_instantir.py:1503-1504).  Epsilon prediction; the options each class refuses raise ValueError naming the key.
+  `loop_coefficients(i)` drives the captured loop (`iir_pack_latent_dscale` + `iir_sched_step_hist`).
 """
 from __future__ import annotations
 
@@ -270,3 +274,318 @@ class LCMSingleStepScheduler(_Base):
         if not return_dict:
             return (out,)
         return SchedulerOutput(denoised=out)
+
+
+# ---- sigma-space schedulers (diffusers 0.28.1 EulerDiscreteScheduler, EulerAncestralDiscreteScheduler,
+# DPMSolverMultistepScheduler; epsilon prediction) -------------------------------------------------------------------
+#
+# Every update of these schedulers is, in the scheduler's own sample space, the linear form of `_Base` plus one history
+# term:  prev = k_x0*x0 + k_x*x + k_eps*eps + k_h*m_prev + k_noise*noise,  x0 = (x - sb*eps)/sa.  Host coefficients are
+# formed in fp64 from the fp32 sigma table and rounded once to fp32; the tensor update runs in iir_sched_step_hist(_f32).
+
+def _sigma_table(alphas_cumprod):
+    """sigma(t) = sqrt((1 - abar_t) / abar_t) over the training steps, fp32 (as diffusers forms it), and its fp32 log."""
+    s = (((1 - alphas_cumprod) / alphas_cumprod) ** 0.5).numpy().astype(np.float32)
+    return s, np.log(s)
+
+
+def _karras(sigma_max, sigma_min, n, rho=7.0):
+    ramp = np.linspace(0, 1, n)
+    max_inv, min_inv = sigma_max ** (1 / rho), sigma_min ** (1 / rho)
+    return (max_inv + ramp * (min_inv - max_inv)) ** rho
+
+
+def _sigma_to_t(sigma, log_sigmas):
+    """Log-sigma interpolation of a sigma onto the (fractional) training-step axis, weight clipped to [0, 1]."""
+    log_sigma = np.log(np.maximum(sigma, 1e-10))
+    dists = log_sigma - log_sigmas[:, np.newaxis]
+    low_idx = np.cumsum((dists >= 0), axis=0).argmax(axis=0).clip(max=log_sigmas.shape[0] - 2)
+    high_idx = low_idx + 1
+    low, high = log_sigmas[low_idx], log_sigmas[high_idx]
+    w = np.clip((low - log_sigma) / (low - high), 0, 1)
+    return ((1 - w) * low_idx + w * high_idx).reshape(np.shape(sigma))
+
+
+def _refuse(key, value, why):
+    raise ValueError(f"{key}={value!r} is not supported by this scheduler ({why})")
+
+
+class _SigmaBase(_Base):
+    """Shared host side of the three sigma schedulers: timetable + sigmas, step index, `loop_coefficients(i)` for the
+    denoising loop and a stateful `.step()` over the HIP entry `iir_sched_step_hist_f32`."""
+
+    _spacings = ("leading", "trailing", "linspace")
+
+    def __init__(self, rescale_betas_zero_snr: bool = False, **kw):
+        super().__init__(**kw)
+        if self.config.prediction_type != "epsilon":
+            _refuse("prediction_type", self.config.prediction_type, "epsilon prediction only")
+        if rescale_betas_zero_snr:
+            _refuse("rescale_betas_zero_snr", rescale_betas_zero_snr, "zero-SNR rescaling is not implemented")
+        if self.config.timestep_spacing not in self._spacings:
+            _refuse("timestep_spacing", self.config.timestep_spacing, f"one of {self._spacings}")
+        self.config["rescale_betas_zero_snr"] = False
+        self._sig_train, self._log_sig_train = _sigma_table(self.alphas_cumprod)
+        self.sigmas = torch.from_numpy(np.concatenate([self._sig_train[::-1], [0.0]]).astype(np.float32))
+        self._reset()
+
+    @classmethod
+    def from_config(cls, config, **kw):
+        """As diffusers: a config of any scheduler class; keys this class does not take are ignored, `kw` overrides."""
+        import inspect
+        names = set(_SDXL_DEFAULTS)
+        for k in cls.__mro__:
+            if "__init__" in vars(k):
+                names |= set(inspect.signature(k.__init__).parameters) - {"self", "kw"}
+        args = {k: v for k, v in dict(config).items() if k in names}
+        args.update(kw)
+        return cls(**args)
+
+    def _reset(self):
+        self._step_index = None
+        self._hist = None
+        self._lower_order_nums = 0
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    def index_for_timestep(self, timestep):
+        """Position of `timestep` in `self.timesteps` (the second match if it repeats, as diffusers picks)."""
+        t = float(torch.as_tensor(timestep).reshape(-1)[0])
+        idx = (self.timesteps.cpu().double() == t).nonzero().flatten()
+        if len(idx) == 0:
+            raise ValueError(f"timestep {t} is not in the scheduler's timetable")
+        return int(idx[1 if len(idx) > 1 else 0])
+
+    def _index(self, timestep):
+        return self._step_index if self._step_index is not None else self.index_for_timestep(timestep)
+
+    def _set(self, timesteps, sigmas, device):
+        self.timesteps = torch.from_numpy(np.asarray(timesteps)).to(device=device)
+        self.sigmas = torch.from_numpy(np.asarray(sigmas, dtype=np.float32))
+        self._reset()
+
+    def c_in(self, i):
+        return 1.0
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """sa_i * x0 + sb_i * noise with the noise-level pair of each row's timestep (`_noise_pair`)."""
+        ts = torch.as_tensor(timesteps).reshape(-1)
+        pairs = [self._noise_pair(self.index_for_timestep(t)) for t in ts]
+        if original_samples.is_cuda and original_samples.dtype == torch.float32 and all(p == pairs[0] for p in pairs):
+            from . import ops
+            out = torch.empty_like(original_samples)
+            ops.axpby_f32(original_samples.contiguous(), noise.contiguous().float(), _dev_coef(list(pairs[0]), original_samples.device), out)
+            return out
+        shape = (-1,) + (1,) * (original_samples.dim() - 1)
+        sa = torch.tensor([p[0] for p in pairs], dtype=original_samples.dtype, device=original_samples.device).reshape(shape)
+        sb = torch.tensor([p[1] for p in pairs], dtype=original_samples.dtype, device=original_samples.device).reshape(shape)
+        return sa * original_samples + sb * noise
+
+    def loop_coefficients(self, i):
+        """Step i of the denoising loop, run from step 0: c_in (UNet input scale), the UNet / Aggregator timestep (float),
+        the LCM preview's integer timestep (`t.to(torch.int64)`, pipelines/sdxl_instantir.py:1557) and the fp32 update
+        coefficients {0, sb, sa, k_x0, k_x, k_eps, k_noise, k_h} (coef[0] is the guidance slot the loop fills)."""
+        t = float(self.timesteps[i])
+        coef = [float(np.float32(v)) for v in self._coefficients64(i, self._order_at(i, i))]
+        return dict(c_in=float(np.float32(self.c_in(i))), t=t, t_lcm=int(t), coef=coef)
+
+    def _order_at(self, i, lower_order_nums):
+        return 1
+
+    def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict=True, s_churn=0.0, **kw):
+        from . import ops
+        if s_churn and s_churn > 0:
+            _refuse("s_churn", s_churn, "stochastic churn is not implemented")
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if not sample.is_cuda:
+            raise RuntimeError("scheduler.step: tensors must live on the GPU (the update runs in the HIP library)")
+        if self._step_index is None:
+            self._step_index = self.index_for_timestep(timestep)
+        i = self._step_index
+        c = [float(np.float32(v)) for v in self._coefficients64(i, self._order_at(i, self._lower_order_nums))]
+        need_noise = c[6] != 0.0
+        if need_noise and variance_noise is None:
+            variance_noise = torch.randn(model_output.shape, generator=generator,
+                                         device=generator.device if generator is not None else model_output.device,
+                                         dtype=torch.float32).to(model_output.device)
+        x = sample.float().contiguous()
+        e = model_output.float().contiguous()
+        if self._hist is None or self._hist.shape != x.shape or self._hist.device != x.device:
+            self._hist = torch.empty_like(x)              # never read on a first-order step (k_h == 0)
+        prev, x0 = torch.empty_like(x), torch.empty_like(x)
+        ops.sched_step_hist_f32(e, x, _dev_coef(c, x.device), self._hist, prev,
+                                noise=variance_noise.float().contiguous().to(x.device) if need_noise else None, x0_out=x0)
+        self._step_index += 1
+        self._lower_order_nums = min(self._lower_order_nums + 1, self.config.get("solver_order", 1))
+        prev, x0 = prev.to(sample.dtype), x0.to(sample.dtype)
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+
+
+class _EulerBase(_SigmaBase):
+    """Sample space VE: x = x0 + sigma * eps.  Shared timetable of EulerDiscreteScheduler and the ancestral variant."""
+
+    _karras_ok = True
+
+    def __init__(self, interpolation_type: str = "linear", use_karras_sigmas: bool = False, **kw):
+        super().__init__(**kw)
+        if interpolation_type != "linear":
+            _refuse("interpolation_type", interpolation_type, "linear interpolation only")
+        self.config["interpolation_type"] = interpolation_type
+        self.use_karras_sigmas = bool(use_karras_sigmas) and self._karras_ok
+        if self._karras_ok:
+            self.config["use_karras_sigmas"] = self.use_karras_sigmas
+
+    @property
+    def init_noise_sigma(self):
+        m = float(self.sigmas.max())
+        return m if self.config.timestep_spacing in ("linspace", "trailing") else (m ** 2 + 1) ** 0.5
+
+    def set_timesteps(self, num_inference_steps=None, device=None, timesteps=None, sigmas=None):
+        if timesteps is not None or sigmas is not None:
+            raise ValueError(f"{type(self).__name__}: custom `timesteps` / `sigmas` are not supported; pass num_inference_steps")
+        T, N = self.config.num_train_timesteps, int(num_inference_steps)
+        if N > T or N < 1:
+            raise ValueError(f"`num_inference_steps`: {N} must be in [1, {T}]")
+        self.num_inference_steps = N
+        sp = self.config.timestep_spacing
+        if sp == "linspace":
+            ts = np.linspace(0, T - 1, N, dtype=np.float32)[::-1].copy()
+        elif sp == "leading":
+            ts = (np.arange(0, N) * (T // N)).round()[::-1].copy().astype(np.float32)
+            ts += self.config.steps_offset
+        else:
+            ts = np.arange(T, 0, -T / N).round().copy().astype(np.float32)
+            ts -= 1
+        sig = np.interp(ts, np.arange(0, len(self._sig_train)), self._sig_train)
+        if self.use_karras_sigmas:
+            sig = _karras(sig[0].item(), sig[-1].item(), N)
+            ts = np.array([_sigma_to_t(s, self._log_sig_train) for s in sig])
+        self._set(np.asarray(ts).astype(np.float32), np.concatenate([sig, [0.0]]).astype(np.float32), device)
+
+    def c_in(self, i):
+        s = float(self.sigmas[i])
+        return 1.0 / (s * s + 1) ** 0.5
+
+    def scale_model_input(self, sample, timestep=None):
+        """x / sqrt(sigma_i^2 + 1)."""
+        s = float(self.sigmas[self._index(timestep)])
+        return sample / ((s * s + 1) ** 0.5)
+
+    def _noise_pair(self, i):
+        return 1.0, float(self.sigmas[i])
+
+
+class EulerDiscreteScheduler(_EulerBase):
+    """x' = x + (sigma_{i+1} - sigma_i) * eps; x0 = x - sigma_i * eps."""
+
+    def _coefficients64(self, i, order):
+        s, sn = float(self.sigmas[i]), float(self.sigmas[i + 1])
+        return [0.0, s, 1.0, 0.0, 1.0, sn - s, 0.0, 0.0]
+
+
+class EulerAncestralDiscreteScheduler(_EulerBase):
+    """x' = x + (sigma_down - sigma_i) * eps + sigma_up * noise (no Karras sigmas in this class, as in diffusers 0.28)."""
+
+    _karras_ok = False
+
+    def _coefficients64(self, i, order):
+        s, sn = float(self.sigmas[i]), float(self.sigmas[i + 1])
+        up = (sn ** 2 * (s ** 2 - sn ** 2) / s ** 2) ** 0.5
+        down = (sn ** 2 - up ** 2) ** 0.5
+        return [0.0, s, 1.0, 0.0, 1.0, down - s, up, 0.0]
+
+
+class DPMSolverMultistepScheduler(_SigmaBase):
+    """DPM-Solver++ (2M, 2M SDE) in VP space: x = alpha_i * x0 + s_i * eps with alpha_i = 1/sqrt(sigma_i^2+1),
+    s_i = sigma_i * alpha_i.  init_noise_sigma = 1 and scale_model_input is the identity.  Bare construction takes this
+    project's SDXL defaults ("leading", steps_offset 1), as the other classes here do."""
+
+    def __init__(self, solver_order: int = 2, algorithm_type: str = "dpmsolver++", solver_type: str = "midpoint",
+                 lower_order_final: bool = True, euler_at_final: bool = False, use_karras_sigmas: bool = False,
+                 use_lu_lambdas: bool = False, final_sigmas_type: str = "zero", thresholding: bool = False,
+                 variance_type=None, **kw):
+        super().__init__(**kw)
+        if algorithm_type not in ("dpmsolver++", "sde-dpmsolver++"):
+            _refuse("algorithm_type", algorithm_type, "dpmsolver++ or sde-dpmsolver++")
+        if solver_order not in (1, 2):
+            _refuse("solver_order", solver_order, "orders 1 and 2")
+        if solver_type != "midpoint":
+            _refuse("solver_type", solver_type, "the midpoint form only")
+        if thresholding:
+            _refuse("thresholding", thresholding, "dynamic thresholding is not implemented")
+        if use_lu_lambdas:
+            _refuse("use_lu_lambdas", use_lu_lambdas, "uniform-logSNR steps are not implemented")
+        if final_sigmas_type != "zero":
+            _refuse("final_sigmas_type", final_sigmas_type, "the final sigma is 0")
+        if variance_type is not None:
+            _refuse("variance_type", variance_type, "learned variance is not implemented")
+        self.config.update(solver_order=solver_order, algorithm_type=algorithm_type, solver_type=solver_type,
+                           lower_order_final=lower_order_final, euler_at_final=euler_at_final,
+                           use_karras_sigmas=bool(use_karras_sigmas), use_lu_lambdas=False, final_sigmas_type="zero",
+                           thresholding=False, variance_type=None)
+        self.use_karras_sigmas = bool(use_karras_sigmas)
+
+    @property
+    def order(self):
+        return self.config.solver_order
+
+    def set_timesteps(self, num_inference_steps=None, device=None, timesteps=None, sigmas=None):
+        if timesteps is not None or sigmas is not None:
+            raise ValueError(f"{type(self).__name__}: custom `timesteps` / `sigmas` are not supported; pass num_inference_steps")
+        T, N = self.config.num_train_timesteps, int(num_inference_steps)
+        if N > T or N < 1:
+            raise ValueError(f"`num_inference_steps`: {N} must be in [1, {T}]")
+        self.num_inference_steps = N
+        sp = self.config.timestep_spacing
+        if sp == "linspace":
+            ts = np.linspace(0, T - 1, N + 1).round()[::-1][:-1].copy().astype(np.int64)
+        elif sp == "leading":
+            ts = (np.arange(0, N + 1) * (T // (N + 1))).round()[::-1][:-1].copy().astype(np.int64)
+            ts += self.config.steps_offset
+        else:
+            ts = np.arange(T, 0, -T / N).round().copy().astype(np.int64)
+            ts -= 1
+        if self.use_karras_sigmas:
+            sig = _karras(float(self._sig_train[-1]), float(self._sig_train[0]), N)
+            ts = np.array([_sigma_to_t(s, self._log_sig_train) for s in sig]).round().astype(np.int64)
+            if len(np.unique(ts)) != len(ts):
+                raise ValueError(f"use_karras_sigmas with num_inference_steps={N} gives repeated integer timesteps {ts.tolist()}")
+        else:
+            sig = np.interp(ts, np.arange(0, len(self._sig_train)), self._sig_train)
+        self._set(ts, np.concatenate([sig, [0.0]]).astype(np.float32), device)
+
+    def _noise_pair(self, i):
+        s = float(self.sigmas[i])
+        a = 1.0 / (s * s + 1) ** 0.5
+        return a, s * a
+
+    def _order_at(self, i, lower_order_nums):
+        N = len(self.timesteps)
+        cfg = self.config
+        last_low = i == N - 1 and (cfg.euler_at_final or (cfg.lower_order_final and N < 15) or cfg.final_sigmas_type == "zero")
+        if cfg.solver_order == 1 or lower_order_nums < 1 or last_low:
+            return 1
+        return 2
+
+    def _coefficients64(self, i, order):
+        s, sn = float(self.sigmas[i]), float(self.sigmas[i + 1])
+        a, an = 1.0 / (s * s + 1) ** 0.5, 1.0 / (sn * sn + 1) ** 0.5
+        sb, snb = s * a, sn * an
+        if sn == 0.0:                           # final sigma 0: the step returns the data prediction x0
+            return [0.0, sb, a, 1.0, 0.0, 0.0, 0.0, 0.0]
+        emh = sn / s                            # e^(-h), h = log(sigma_i / sigma_{i+1})
+        sde = self.config.algorithm_type == "sde-dpmsolver++"
+        if sde:
+            k_x, base, k_noise = (snb / sb) * emh, an * (1.0 - emh * emh), snb * (1.0 - emh * emh) ** 0.5
+        else:
+            k_x, base, k_noise = snb / sb, -an * (emh - 1.0), 0.0
+        if order == 1:
+            return [0.0, sb, a, base, k_x, 0.0, k_noise, 0.0]
+        sp = float(self.sigmas[i - 1])
+        r = np.log(sp / s) / np.log(s / sn)     # h_prev / h
+        return [0.0, sb, a, base * (1.0 + 1.0 / (2.0 * r)), k_x, 0.0, k_noise, -base / (2.0 * r)]

@@ -1,0 +1,411 @@
+"""GPU: the Euler / Euler-ancestral / DPM++ 2M schedulers on the HIP path -- iir_sched_step_hist(_f32) and
+iir_pack_latent_dscale against fp32 torch, the public `.step()` over whole timetables, and the denoising loop at the tiny
+geometry against the DDIM loop (Euler is DDIM in VP space) and against an fp32 CPU loop composed here from `oracle.nets`
+with the fp64 scheduler restatement of tests/test_sigma_schedulers_cpu.py."""
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import test_sigma_schedulers_cpu as spec
+
+pytestmark = pytest.mark.gpu
+
+BAR = 50.0
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from instantir_amd import lib
+    lib.load()
+    return torch.device("cuda:0")
+
+
+def psnr(got, want):
+    import inspect
+    from conftest import record_psnr
+    mse = ((got.double() - want.double()) ** 2).mean().item()
+    peak = want.abs().max().item()
+    v = 10 * math.log10(peak * peak / max(mse, 1e-30))
+    record_psnr("sigma." + inspect.stack()[1].function, v)
+    return v
+
+
+def _ref_step(e, x, coef, m_prev, noise):
+    """The kernels' fp32 op order: x0 = (x - sb*e)/sa; prev = k0*x0 + kx*x (+ ke*e) (+ kh*m) (+ kn*noise)."""
+    g, sb, sa, k0, kx, ke, kn, kh = [torch.tensor(c, dtype=torch.float32) for c in coef]
+    x0 = (x - sb * e) / sa
+    pv = k0 * x0 + kx * x
+    if float(ke) != 0:
+        pv = pv + ke * e
+    if float(kh) != 0:
+        pv = pv + kh * m_prev
+    if noise is not None and float(kn) != 0:
+        pv = pv + kn * noise
+    return pv, x0
+
+
+def _ulps(a, b):
+    """max |a - b| in fp32 ulps of max(|a|, |b|), floored at 2^-10 of the tensor's range (cancellation near zero)"""
+    d = (a.double() - b.double()).abs()
+    floor = max(b.abs().max().item() * 2.0 ** -10, 1e-30)
+    u = torch.finfo(torch.float32).eps * torch.maximum(a.abs(), b.abs()).double().clamp_min(floor)
+    return (d / u).max().item()
+
+
+# ---- kernels --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("B,H,W", [(1, 128, 128), (2, 5, 7), (2, 16, 16)])
+@pytest.mark.parametrize("cfg", [False, True])
+@pytest.mark.parametrize("extra", ["plain", "noise", "rescale"])
+def test_sched_step_hist_matches_fp32(dev, B, H, W, cfg, extra):
+    from instantir_amd import ops
+    if extra == "rescale" and not cfg:
+        extra = "noise"
+    g = torch.Generator().manual_seed(B * 1000 + H * W)
+    C, lde, R = 4, 8, B * (2 if cfg else 1)
+    HW = H * W
+    eps16 = (torch.randn(R * HW, lde, generator=g)).half()
+    x = torch.randn(B, C, H, W, generator=g) * 3
+    m = torch.randn(B, C, H, W, generator=g)
+    nz = torch.randn(B, C, H, W, generator=g) if extra == "noise" else None
+    fac = torch.tensor([0.8, 1.3][:B]) if extra == "rescale" else None
+    coef = [6.5, 0.93, 0.37, 0.41, 0.98, 0.12, 0.07 if nz is not None else 0.0, -0.031]
+    hist = m.clone().to(dev)
+    prev, x0 = torch.empty(B, C, H, W, device=dev), torch.empty(B, C, H, W, device=dev)
+    ops.sched_step_hist(eps16.to(dev), B, torch.tensor(coef).to(dev), x.to(dev), hist, prev, noise=None if nz is None else nz.to(dev),
+                        cfg=cfg, x0_out=x0, eps_factor=None if fac is None else fac.to(dev))
+    torch.cuda.synchronize()
+    e = eps16.float()[:, :C].reshape(R, H, W, C).permute(0, 3, 1, 2)
+    if cfg:
+        u, t = e[:B], e[B:]
+        e = u + torch.tensor(coef[0]) * (t - u)
+        if fac is not None:
+            e = e * fac.view(B, 1, 1, 1)
+    want, want_x0 = _ref_step(e, x, coef, m, nz)
+    assert _ulps(prev.cpu(), want) <= 4 and _ulps(x0.cpu(), want_x0) <= 4
+    assert torch.equal(hist.cpu(), x0.cpu())                 # the plane now holds this step's x0
+
+
+def test_sched_step_hist_never_reads_history_when_kh_is_zero(dev):
+    from instantir_amd import ops
+    g = torch.Generator().manual_seed(5)
+    B, C, H, W = 2, 4, 9, 11
+    eps16 = torch.randn(2 * B * H * W, 4, generator=g).half().to(dev)
+    x = torch.randn(B, C, H, W, generator=g).to(dev)
+    coef = torch.tensor([5.0, 0.9, 0.4, 0.5, 0.9, 0.0, 0.0, 0.0]).to(dev)
+    hist = torch.full((B, C, H, W), float("nan"), device=dev)
+    prev, x0 = torch.empty_like(x), torch.empty_like(x)
+    ops.sched_step_hist(eps16, B, coef, x, hist, prev, cfg=True, x0_out=x0)
+    ref = torch.empty_like(x)
+    ops.sched_step(eps16, B, coef, x, ref, cfg=True)          # k_h == 0: the existing step, bit for bit
+    hf = torch.full((B * C * H * W,), float("nan"), device=dev)
+    e32, x32 = torch.randn(B * C * H * W, generator=g).to(dev), x.flatten().clone()
+    p32 = torch.empty_like(x32)
+    ops.sched_step_hist_f32(e32, x32, coef, hf, p32)
+    torch.cuda.synchronize()
+    assert torch.isfinite(prev).all() and torch.isfinite(p32).all()
+    assert torch.equal(prev, ref) and torch.equal(hist, x0) and torch.isfinite(hf).all()
+
+
+@pytest.mark.parametrize("B,H,W,rep", [(1, 128, 128, 2), (2, 5, 7, 1), (2, 16, 16, 2)])
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+def test_device_scale_pack_bit_identical_to_host_scale(dev, B, H, W, rep, dtype):
+    from instantir_amd import ops
+    x = (torch.randn(B, 4, H, W, generator=torch.Generator().manual_seed(H)) * 9).to(dev)
+    for s in (1.0, 0.0862, 0.7071067690849304):
+        s32 = float(np.float32(s))
+        a = torch.full((rep * B * H * W, 8), 7.0, dtype=dtype, device=dev)
+        b = a.clone()
+        ops.pack_latent(x, a, rep=rep, scale=s32)
+        ops.pack_latent_dscale(x, b, torch.tensor([s32], device=dev), rep=rep)
+        torch.cuda.synchronize()
+        assert torch.equal(a.view(torch.int16), b.view(torch.int16))
+
+
+# ---- public .step() -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["euler", "euler_karras", "euler_a", "dpm", "dpm_karras", "dpm_sde", "dpm_order1"])
+def test_public_step_over_a_timetable(dev, name):
+    from instantir_amd import schedulers as S
+    mk = {"euler": lambda: S.EulerDiscreteScheduler(), "euler_karras": lambda: S.EulerDiscreteScheduler(use_karras_sigmas=True),
+          "euler_a": lambda: S.EulerAncestralDiscreteScheduler(),
+          "dpm": lambda: S.DPMSolverMultistepScheduler(timestep_spacing="trailing"),
+          "dpm_karras": lambda: S.DPMSolverMultistepScheduler(use_karras_sigmas=True),
+          "dpm_sde": lambda: S.DPMSolverMultistepScheduler(algorithm_type="sde-dpmsolver++"),
+          "dpm_order1": lambda: S.DPMSolverMultistepScheduler(solver_order=1)}[name]
+    sch = mk()
+    n = 12
+    sch.set_timesteps(n)
+    euler = name.startswith("euler")
+    if euler:
+        _, sig = spec.spec_euler_table(n, sch.config.timestep_spacing, sch.use_karras_sigmas)
+    else:
+        _, sig = spec.spec_dpm_table(n, sch.config.timestep_spacing, sch.use_karras_sigmas)
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(2, 4, 8, 8, generator=g) * sch.init_noise_sigma
+    xg, xr, m = x.to(dev), x.double(), None
+    for i, t in enumerate(sch.timesteps):
+        e = torch.randn(2, 4, 8, 8, generator=g)
+        nz = torch.randn(2, 4, 8, 8, generator=g)
+        out = sch.step(e.to(dev), t, xg, variance_noise=nz.to(dev))
+        if euler:
+            c = spec.spec_euler_coef(sig, i, ancestral=name == "euler_a")
+        else:
+            c = spec.spec_dpm_coef(sig, i, spec.spec_dpm_second_order(i, n, sch.config.solver_order),
+                                   sde=name == "dpm_sde")
+        sb, sa, k0, kx, ke, kn, kh = c
+        x0 = (xr - sb * e.double()) / sa
+        xr = k0 * x0 + kx * xr + ke * e.double() + kn * nz.double() + (kh * m if kh != 0 else 0)
+        m = x0
+        assert torch.allclose(out.pred_original_sample.cpu().double(), x0, rtol=1e-4, atol=1e-4 * x0.abs().max().item())
+        xg = out.prev_sample
+        assert torch.allclose(xg.cpu().double(), xr, rtol=1e-4, atol=1e-4 * xr.abs().max().item()), (i, (xg.cpu().double() - xr).abs().max())
+    assert sch.step_index == n
+    sch.set_timesteps(n)
+    assert sch.step_index is None
+
+
+# ---- the denoising loop -------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def env(dev):
+    from instantir_amd import weights as W
+    from instantir_amd.config import UNetConfig
+    cfg = UNetConfig.tiny()
+    sd = W.synth_state_dict(W.unet_specs(cfg), 11)
+    sda = W.synth_state_dict(W.aggregator_specs(cfg), 12)
+    lora = W.synth_state_dict(W.lora_specs(cfg), 13)
+    g = torch.Generator().manual_seed(42)
+    B, H = 2, 16
+    inp = dict(
+        B=B, H=H,
+        lq=torch.randn(B, 4, H, H, generator=g) * 0.8,
+        pe=torch.randn(B, cfg.text_len, cfg.cross_attention_dim, generator=g).half().float(),
+        pooled=torch.randn(B, cfg.pooled_dim, generator=g).half().float(),
+        npe=torch.randn(B, cfg.text_len, cfg.cross_attention_dim, generator=g).half().float(),
+        npooled=torch.randn(B, cfg.pooled_dim, generator=g).half().float(),
+        img=torch.randn(2, B, cfg.resampler.seq_len, cfg.resampler.embedding_dim, generator=g).half().float(),
+        init_noise=torch.randn(B, 4, H, H, generator=g),
+        noises=[torch.randn(B, 4, H, H, generator=g) for _ in range(8)],
+    )
+    return cfg, sd, sda, lora, inp
+
+
+def _pipe(env, sched):
+    from instantir_amd.pipeline import InstantIRPipeline
+    cfg, sd, sda, lora, _ = env
+    pipe = InstantIRPipeline(cfg, sd, scheduler=sched)
+    pipe.aggregator.load_state_dict(sda)
+    pipe.prepare_previewers(lora, lora_alpha=16)
+    return pipe
+
+
+def _call(pipe, inp, **kw):
+    from instantir_amd.schedulers import LCMSingleStepScheduler
+    lcm = LCMSingleStepScheduler.from_config(pipe.scheduler.config)
+    return pipe(image=inp["lq"], prompt_embeds=inp["pe"], pooled_prompt_embeds=inp["pooled"],
+                negative_prompt_embeds=inp["npe"], negative_pooled_prompt_embeds=inp["npooled"],
+                ip_adapter_image_embeds=[inp["img"]], output_type="latent", previewer_scheduler=lcm,
+                init_noise=inp["init_noise"], **kw).images.float().cpu()
+
+
+def _oracle(env, kind, n, guidance_scale=5.0, preview_start=0.0, control_guidance_end=1.0, step_noises=None, karras=False,
+            adastep_restore=False):
+    """fp32 CPU loop, pipelines/sdxl_instantir.py:1385-1660 with a sigma scheduler: add_noise in the scheduler's space,
+    UNet / Aggregator input scale_model_input(cat([x]*2), t) at the float t, LCM preview on the scaled input at int(t),
+    the step from the fp64 restatement (spec_*) applied in fp32."""
+    from oracle import nets, sched
+    cfg, sd, sda, lora, inp = env
+    P = {k: v.float() for k, v in sd.items()}
+    PA = {k: v.float() for k, v in sda.items()}
+    L = {k: v.float() for k, v in lora.items()}
+    L["scaling"] = 16.0 / cfg.lora_rank
+    B = inp["B"]
+    acp = sched.make_alphas_cumprod()
+    if kind.startswith("euler"):
+        ts, sig = spec.spec_euler_table(n, "leading", karras)
+    else:
+        ts, sig = spec.spec_dpm_table(n, "leading", karras)
+    keep, previewing = sched.gating_tables(n, 0.0, control_guidance_end, preview_start, 1.0)
+    tid = torch.tensor([[128.0, 128, 0, 0, 128, 128]]).repeat(2 * B, 1)
+    ctx, text = torch.cat([inp["npe"], inp["pe"]]), torch.cat([inp["npooled"], inp["pooled"]])
+    image = torch.cat([inp["lq"]] * 2)
+    ip_main = nets.image_projection(P, [inp["img"]], cfg.resampler)[0]
+    ip_prev = nets.image_projection(P, [inp["img"]], cfg.resampler, L)[0]
+    vp = kind.startswith("dpm")
+    a0 = 1 / math.sqrt(sig[0] ** 2 + 1)
+    x = (a0 * inp["lq"] + (sig[0] * a0) * inp["init_noise"]) if vp else inp["lq"] + sig[0] * inp["init_noise"]
+    m = None
+    preview_factor = torch.ones(B, 1, 1, 1)
+    previewer_mean = torch.zeros_like(x)
+    down = mid = None
+    for i in range(n):
+        t = ts[i]
+        c_in = 1.0 if vp else float(np.float32(1 / math.sqrt(sig[i] ** 2 + 1)))
+        xin = torch.cat([x] * 2) * c_in
+        cond_scale = torch.cat([preview_factor.clamp(0.0, 1.0) * keep[i]] * 2)
+        if (cond_scale > 0.1).sum().item() > 0:
+            if previewing[i] > 0:
+                eps1 = nets.unet_forward(P, cfg, xin, t, ctx, text, tid, ip_prev, lora=L)
+                preview = sched.lcm_step(acp, eps1, int(t), xin)
+            else:
+                preview = image
+            down, mid = nets.aggregator_forward(PA, cfg, image, t, preview, text, tid)
+        down = [s * cond_scale for s in down]
+        mid = mid * cond_scale
+        eps = nets.unet_forward(P, cfg, xin, t, ctx, text, tid, ip_main, down, mid)
+        u, c = eps.chunk(2)
+        eps = u + guidance_scale * (c - u)
+        if kind == "euler":
+            coef = spec.spec_euler_coef(sig, i)
+        elif kind == "euler_a":
+            coef = spec.spec_euler_coef(sig, i, ancestral=True)
+        else:
+            coef = spec.spec_dpm_coef(sig, i, spec.spec_dpm_second_order(i, n), sde=kind == "dpm_sde")
+        c32 = [0.0] + [float(np.float32(v)) for v in coef[:6]] + [float(np.float32(coef[6]))]
+        nz = step_noises[i] if step_noises is not None else None
+        x_next, x0 = _ref_step(eps, x, c32, m, nz)
+        m = x0
+        if adastep_restore:
+            pv = preview[B:].float()
+            pred_x0_l2 = (pv - x0).pow(2).sum(dim=(1, 2, 3))
+            previewer_l2 = (pv - previewer_mean).pow(2).sum(dim=(1, 2, 3))
+            previewer_mean = preview[B:]
+            preview_factor = (pred_x0_l2 / previewer_l2).reshape(-1, 1, 1, 1)
+        x = x_next
+    return x
+
+
+def _sched(kind, karras=False):
+    from instantir_amd import schedulers as S
+    if kind == "euler":
+        return S.EulerDiscreteScheduler(use_karras_sigmas=karras)
+    if kind == "euler_a":
+        return S.EulerAncestralDiscreteScheduler()
+    return S.DPMSolverMultistepScheduler(use_karras_sigmas=karras,
+                                         algorithm_type="sde-dpmsolver++" if kind == "dpm_sde" else "dpmsolver++")
+
+
+PHASES = dict(preview_start=0.25, control_guidance_end=0.75)     # creative tail, Aggregator-only head, previewed middle
+
+
+@pytest.mark.parametrize("kind,karras,noises", [("dpm", True, False), ("dpm_sde", False, True), ("euler", True, False),
+                                               ("euler_a", False, True)])
+def test_loop_matches_fp32_oracle(env, kind, karras, noises):
+    inp = env[4]
+    n = 8
+    kw = dict(num_inference_steps=n, guidance_scale=5.0, **PHASES)
+    sn = inp["noises"] if noises else None
+    want = _oracle(env, kind, n, step_noises=sn, karras=karras, **PHASES)
+    got = _call(_pipe(env, _sched(kind, karras)), inp, step_noises=sn, **kw)
+    p = psnr(got, want)
+    print(f"{kind} karras={karras}: latent PSNR vs fp32 oracle {p:.1f} dB")
+    assert torch.isfinite(got).all() and p >= BAR, p
+
+
+def test_adastep_restore_dpm_matches_oracle(env):
+    inp = env[4]
+    want = _oracle(env, "dpm", 6, karras=True, adastep_restore=True)
+    got = _call(_pipe(env, _sched("dpm", True)), inp, num_inference_steps=6, guidance_scale=5.0, adastep_restore=True)
+    p = psnr(got, want)
+    assert torch.isfinite(got).all() and p >= BAR, p
+
+
+def test_euler_is_the_ddim_loop_in_vp_space(env):
+    """Per step through callback_on_step_end: x_VE / sqrt(sigma_{i+1}^2 + 1) against the DDIM loop's x_VP, steps 0..n-2."""
+    from instantir_amd.schedulers import DDIMScheduler
+    inp = env[4]
+    n = 6
+    seen = {"e": [], "d": []}
+
+    def rec(key):
+        def cb(pipe, i, t, kw):
+            seen[key].append(kw["latents"].float().cpu().clone())
+            return {}
+        return cb
+    e = _sched("euler")
+    _call(_pipe(env, e), inp, num_inference_steps=n, guidance_scale=5.0, callback_on_step_end=rec("e"), **PHASES)
+    _call(_pipe(env, DDIMScheduler()), inp, num_inference_steps=n, guidance_scale=5.0, callback_on_step_end=rec("d"), **PHASES)
+    for i in range(n - 1):
+        s = float(e.sigmas[i + 1])
+        p = psnr(seen["e"][i] / math.sqrt(s * s + 1), seen["d"][i])
+        assert p >= 60.0, (i, p)
+
+
+def test_graphs_on_off_and_repeat_calls_bit_identical(env):
+    from instantir_amd.schedulers import DDPMScheduler
+    inp = env[4]
+    kw = dict(num_inference_steps=6, guidance_scale=5.0, step_noises=inp["noises"], **PHASES)
+    pipe = _pipe(env, _sched("dpm_sde", False))
+    pipe.use_graphs = False
+    eager = _call(pipe, inp, **kw)
+    pipe.use_graphs = True
+    g1 = _call(pipe, inp, **kw)
+    g2 = _call(pipe, inp, **kw)                   # the loop is adopted: the history is reset
+    assert torch.equal(eager, g1) and torch.equal(g1, g2)
+    dd = DDPMScheduler()
+    pipe_d = _pipe(env, dd)
+    want_d = _call(pipe_d, inp, **kw)
+    dpm = pipe.scheduler
+    pipe.scheduler = dd
+    assert torch.equal(_call(pipe, inp, **kw), want_d)
+    pipe.scheduler = dpm
+    assert torch.equal(_call(pipe, inp, **kw), g1)
+
+
+def test_prompt_embeds_replaced_mid_loop_keeps_history(env):
+    """A callback that replaces prompt_embeds rebuilds the loop; the DPM++ history is carried over, so returning the same
+    values (a new tensor) gives the uninterrupted result bit for bit."""
+    inp = env[4]
+    kw = dict(num_inference_steps=6, guidance_scale=5.0, **PHASES)
+    pipe = _pipe(env, _sched("dpm", True))
+    want = _call(pipe, inp, **kw)
+
+    def cb(p, i, t, d):
+        return {"prompt_embeds": d["prompt_embeds"].clone()} if i == 2 else {}
+    got = _call(pipe, inp, callback_on_step_end=cb, callback_on_step_end_tensor_inputs=["latents", "prompt_embeds"], **kw)
+    assert torch.equal(got, want)
+
+
+def test_timesteps_argument_refused(env):
+    inp = env[4]
+    with pytest.raises(ValueError, match="timesteps"):
+        _call(_pipe(env, _sched("euler")), inp, timesteps=[999, 500, 1], guidance_scale=5.0)
+
+
+def test_cli_dpmpp_2m_karras_equals_python_api(tmp_path, dev):
+    from PIL import Image
+    import instantir_amd.infer as cli
+    from instantir_amd.schedulers import DPMSolverMultistepScheduler
+    src, out = tmp_path / "in", tmp_path / "out"
+    src.mkdir()
+    Image.fromarray(np.random.default_rng(0).integers(0, 255, (96, 96, 3), dtype=np.uint8)).save(src / "a.png")
+    args = cli.build_parser().parse_args(["--test_path", str(src), "--out_path", str(out), "--synthetic", "tiny",
+                                          "--num_inference_steps", "4", "--width", "128", "--height", "128", "--batch_size", "1",
+                                          "--cfg", "5.0", "--scheduler", "dpmpp_2m", "--karras"])
+    orig = cli.resize_img
+    cli.resize_img = lambda im, **kw: orig(im, max_side=128, min_side=128, **kw)
+    try:
+        torch.manual_seed(7)               # the synthetic VAE encode draws its eps from the global generator
+        cli.main(args, dev)
+        im, size = cli.resize_img(Image.open(src / "a.png").convert("RGB"), width=128, height=128)
+    finally:
+        cli.resize_img = orig
+    got = np.asarray(Image.open(out / "a.png"))
+    torch.manual_seed(7)
+    pipe, lcm = cli.build_pipeline(args, dev)
+    pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config, use_karras_sigmas=True)
+    cfg = pipe.cfg
+    g = torch.Generator().manual_seed(42)
+    kw = dict(prompt_embeds=torch.randn(1, cfg.text_len, cfg.cross_attention_dim, generator=g),
+              pooled_prompt_embeds=torch.randn(1, cfg.pooled_dim, generator=g),
+              negative_prompt_embeds=torch.randn(1, cfg.text_len, cfg.cross_attention_dim, generator=g),
+              negative_pooled_prompt_embeds=torch.randn(1, cfg.pooled_dim, generator=g),
+              ip_adapter_image_embeds=[torch.randn(2, 1, cfg.resampler.seq_len, cfg.resampler.embedding_dim, generator=g)])
+    rec = pipe(image=[im], num_inference_steps=4, generator=torch.Generator(device=dev).manual_seed(42), guidance_scale=5.0,
+               previewer_scheduler=lcm, preview_start=0.0, control_guidance_end=1.0, **kw).images[0]
+    want = np.asarray(rec.resize([size[0], size[1]], Image.BILINEAR))
+    assert got.shape == want.shape and np.array_equal(got, want)
+    assert os.path.isfile(out / "a.png")

@@ -1,0 +1,90 @@
+"""Per-scheduler denoising cost through InstantIRPipeline.__call__ (synthetic weights, latent in / latent out, CFG,
+previewer + Aggregator every step, hipGraph replay).
+
+    python tools/sched_bench.py [--size 1024] [--pairs 3] [--tiny]
+
+Prints one line per timed call and a JSON summary:
+  * ms/step of ddpm, euler and dpmpp_2m at `--steps` steps each, interleaved over `--pairs` rounds (the first call of each
+    scheduler builds and captures its loop and is not timed);
+  * wall time of a 20-step DPM++ 2M Karras call against a 30-step DDPM call.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=1024)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--pairs", type=int, default=3)
+    ap.add_argument("--tiny", action="store_true")
+    args = ap.parse_args()
+    from instantir_amd import schedulers as S, weights as W
+    from instantir_amd.config import UNetConfig
+    from instantir_amd.pipeline import InstantIRPipeline
+    dev = torch.device("cuda:0")
+    cfg = UNetConfig.tiny() if args.tiny else UNetConfig.sdxl()
+    sd = W.synth_state_dict(W.unet_specs(cfg), 1234, device=dev)
+    sda = W.synth_state_dict(W.aggregator_specs(cfg), 1235, device=dev)
+    lora = W.synth_state_dict(W.lora_specs(cfg), 1236, device=dev)
+    pipe = InstantIRPipeline(cfg, sd, scheduler=S.DDPMScheduler(), device=dev)
+    pipe.aggregator.load_state_dict(sda)
+    pipe.prepare_previewers(lora, lora_alpha=max(1, cfg.lora_rank // 8))
+    lcm = S.LCMSingleStepScheduler.from_config(pipe.scheduler.config)
+    g = torch.Generator().manual_seed(42)
+    Hl = args.size // 8
+    kw = dict(image=torch.randn(1, 4, Hl, Hl, generator=g) * 0.8,
+              prompt_embeds=torch.randn(1, cfg.text_len, cfg.cross_attention_dim, generator=g),
+              pooled_prompt_embeds=torch.randn(1, cfg.pooled_dim, generator=g),
+              negative_prompt_embeds=torch.randn(1, cfg.text_len, cfg.cross_attention_dim, generator=g),
+              negative_pooled_prompt_embeds=torch.randn(1, cfg.pooled_dim, generator=g),
+              ip_adapter_image_embeds=[torch.randn(2, 1, cfg.resampler.seq_len, cfg.resampler.embedding_dim, generator=g)],
+              init_noise=torch.randn(1, 4, Hl, Hl, generator=g), output_type="latent", previewer_scheduler=lcm, guidance_scale=7.0)
+    base = pipe.scheduler.config
+    scheds = {"ddpm": S.DDPMScheduler.from_config(base), "euler": S.EulerDiscreteScheduler.from_config(base),
+              "dpmpp_2m": S.DPMSolverMultistepScheduler.from_config(base),
+              "dpmpp_2m_karras": S.DPMSolverMultistepScheduler.from_config(base, use_karras_sigmas=True)}
+
+    def call(name, n):
+        pipe.scheduler = scheds[name]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = pipe(num_inference_steps=n, **kw).images
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        assert torch.isfinite(out).all(), name
+        return dt
+
+    # one untimed call per scheduler form (the loop cache holds one geometry x form: switching forms rebuilds and re-captures,
+    # so every timed call below is preceded by an untimed call of the same form)
+    res = {k: [] for k in ("ddpm", "euler", "dpmpp_2m")}
+    for r in range(args.pairs):
+        for name in ("ddpm", "euler", "dpmpp_2m"):
+            call(name, 2)
+            dt = call(name, args.steps)
+            res[name].append(dt / args.steps * 1e3)
+            print(f"round {r} {name}: {dt / args.steps * 1e3:.2f} ms/step (call {dt:.3f} s, {args.steps} steps)", flush=True)
+    wall = {"ddpm_30": [], "dpmpp_2m_karras_20": []}
+    for r in range(args.pairs):
+        call("ddpm", 2)
+        wall["ddpm_30"].append(call("ddpm", 30))
+        call("dpmpp_2m_karras", 2)
+        wall["dpmpp_2m_karras_20"].append(call("dpmpp_2m_karras", 20))
+        print(f"round {r} wall: ddpm 30 steps {wall['ddpm_30'][-1]:.3f} s, dpmpp_2m karras 20 steps "
+              f"{wall['dpmpp_2m_karras_20'][-1]:.3f} s", flush=True)
+    print(json.dumps({"size": args.size, "steps": args.steps,
+                      "ms_per_step_median": {k: round(statistics.median(v), 2) for k, v in res.items()},
+                      "ms_per_step_all": {k: [round(x, 2) for x in v] for k, v in res.items()},
+                      "wall_s_median": {k: round(statistics.median(v), 3) for k, v in wall.items()}}))
+
+
+if __name__ == "__main__":
+    main()
