@@ -170,6 +170,11 @@ typedef struct iir_attn_desc {
 /* Replaces F.scaled_dot_product_attention at module/ip_adapter/attention_processor.py:394 (nseg=1)
  * and the two SDPA calls + add at :1165,:1185,:1192 (nseg=2: text KV, IP KV), head_dim 64. */
 int iir_attention_d64_f16(const iir_attn_desc* a, void* stream);
+/* The same launch with identity attention on batch rows [ident_from, batch): O[b] = V[b] there (perturbed-attention
+ * guidance, PAGIdentitySelfAttnProcessor: the attention map of the perturbed rows is the identity, so the value projection
+ * passes through).  V is read from kv[0].Vt, the transposed operand the plain launch reads.  Rows below ident_from are
+ * bit-identical to iir_attention_d64_f16.  Needs 1 <= ident_from < batch, nseg == 1, kv[0].Tkv == Tq, not causal, no o_fp8. */
+int iir_attention_d64_ident_f16(const iir_attn_desc* a, int32_t ident_from, void* stream);
 
 /* F.scaled_dot_product_attention at head_dim 80 / 104 (CLIP ViT-H/14, bigG/14 vision towers:
  * module/ip_adapter/utils.py:106-118); layouts as iir_attention_d64_f16 with 64 -> head_dim.
@@ -292,6 +297,23 @@ int iir_sched_step_hist(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C,
                         void* stream);
 int iir_cfg_rescale_factor(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, const float* coef,
                            float guidance_rescale, float* factor, void* stream);
+/* Perturbed-attention guidance (PAG, Ahn et al. 2024) forms of the three launches above.  The UNet output holds one more
+ * group of B rows, the perturbed prediction p: rows [2B, 3B) with cfg, [B, 2B) without.  The guided eps is
+ * u + g*(c - u) + s*(c - p) (cfg) or c + s*(c - p), s = *pag_scale (device fp32[1], the step's s_t), formed before the
+ * rescale factor is applied (iir_cfg_rescale_factor_pag: the same sum inside eps_cfg).  s == 0 skips the term: the
+ * outputs are then bit-identical to the plain launches. */
+int iir_sched_step_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg, const float* coef,
+                       const float* pag_scale, const float* x, const float* noise, float* prev, float* x0_out, float* eps_out,
+                       const float* eps_factor, void* stream);
+int iir_sched_step_hist_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg, const float* coef,
+                            const float* pag_scale, const float* x, const float* noise, float* hist, float* prev, float* x0_out,
+                            const float* eps_factor, void* stream);
+int iir_cfg_rescale_factor_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, const float* coef,
+                               const float* pag_scale, float guidance_rescale, float* factor, void* stream);
+/* Batched copy of disjoint byte ranges in one launch: `jobs` = device int64[njobs][3] {src address, dst address, n16}, each
+ * job copying n16 x 16 bytes (addresses 16-byte aligned); max_units = the largest n16.  PAG uses it to give the perturbed
+ * rows of every Aggregator residual the cond rows' values. */
+int iir_copy_segments(const void* jobs, int32_t njobs, int64_t max_units, void* stream);
 
 /* LCMSingleStepScheduler.step, schedulers/lcm_single_step_scheduler.py:455-484.
  * coef = device fp32[4] {sqrt(1-abar_t), sqrt(abar_t), c_out, c_skip}. */

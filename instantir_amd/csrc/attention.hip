@@ -33,6 +33,8 @@ struct AGeo {
     int qpre;              // Q already multiplied by c
     float c;   // softmax scale * log2(e)
     Seg seg[2];
+    int n_attn;            // identity form: workgroups [0, n_attn) attend (batch rows below ident_from), the rest copy V
+    int ident_from;
 };
 
 constexpr int KT = 64;   // keys per tile
@@ -443,6 +445,41 @@ __device__ __forceinline__ void attn_tile(const char* kt, const char* vt, const 
     }
 }
 
+// Identity rows of perturbed-attention guidance (Ahn et al. 2024): the attention map of batch row b >= ident_from is the
+// identity, so O[b] = V[b].  One workgroup copies one (row, head, 128-token tile) of V^T -- the operand the fused q|k|v
+// GEMM already wrote -- back to token-major O through LDS: 16-byte coalesced loads along the V^T rows, 8-byte stores along
+// the O rows.  The LDS image is [64 d][130 f16] (65 dwords per row: the transposed reads of 16 lanes hit 16 banks).
+__device__ __forceinline__ void ident_tile(const AGeo& g, int c, char* smem) {
+    const int tid = threadIdx.x;
+    const int qt = c % g.qtiles, pair = c / g.qtiles;
+    const int h = pair % g.heads, b = g.ident_from + pair / g.heads;
+    const int t0 = qt * 128;
+    const Seg& s = g.seg[0];
+    const int tpad = (s.Tkv + 7) & ~7;                     // contract: V^T rows readable on [0, tpad)
+    unsigned* tile = (unsigned*)smem;
+    const f16* vbase = s.Vt + (long)(h * 64) * s.ldvt + (long)b * s.vbs;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {                          // 64 d rows x 16 chunks of 8 tokens
+        const int idx = i * 256 + tid, d = idx >> 4, ch = idx & 15;
+        const int col = min(t0 + ch * 8, tpad - 8);        // chunks past the end are read clamped and never stored
+        const uint4 v = *(const uint4*)(vbase + (long)d * s.ldvt + col);
+        unsigned* row = tile + d * 65 + ch * 4;
+        row[0] = v.x; row[1] = v.y; row[2] = v.z; row[3] = v.w;
+    }
+    __syncthreads();
+    const f16* tl = (const f16*)smem;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {                          // 128 tokens x 16 groups of 4 d
+        const int idx = i * 256 + tid, t = idx >> 4, dg = idx & 15;
+        if (t0 + t < g.Tq) {
+            f16x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = tl[(dg * 4 + j) * 130 + t];
+            *(f16x4*)(g.O + (long)b * g.obs + (long)(t0 + t) * g.ldo + h * 64 + dg * 4) = o;
+        }
+    }
+}
+
 // NB: depth of the K / V^T tile ring.  With two buffers the loads of tile t+1 have one tile's compute (~0.5 us for a workgroup
 // alone on its CU) to land; the 320-workgroup level-2 launches and the cross-attention launches waited ~1 us per tile on them.
 // NB - 1 tiles are in flight; the wait at the end of tile t is counted (`vmcnt(4 * tiles still allowed in flight)`), 4 LDS-DMA
@@ -451,18 +488,24 @@ __device__ __forceinline__ void attn_tile(const char* kt, const char* vt, const 
 // = 3 tiles).  Every tile of every segment is requested at kernel entry, there is ONE wait and one barrier, and the tile
 // bodies then run back to back -- the ring form paid a full load latency per segment plus a wait and a barrier per tile
 // for launches whose arithmetic is ~1 us (140 such launches per step, ~18 us each).
-template <int WPS, int NB, bool PRE = false>
+// IDENT: the identity form (iir_attention_d64_ident_f16).  Workgroups [0, n_attn) are the plain kernel's workgroups of rows
+// [0, ident_from); the copy workgroups come after them in dispatch order, so they fill CUs the attention tail leaves idle.
+template <int WPS, int NB, bool PRE = false, bool IDENT = false>
 __global__ __launch_bounds__(256, WPS) void attn_kernel2(const AGeo g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem;                    // [NB][64 keys][128 B]
     char* Vs = smem + NB * KT * 128;    // [NB][64 d][128 B]
 
+    if (IDENT && (int)blockIdx.x >= g.n_attn) {
+        ident_tile(g, blockIdx.x - g.n_attn, smem);
+        return;
+    }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qi = lane & 31, hh = lane >> 5;
     int lin;
     {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = blockIdx.x & 7;
+        const int nwg = IDENT ? g.n_attn : (int)gridDim.x, q = nwg >> 3, r = nwg & 7, x = blockIdx.x & 7;
         lin = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (blockIdx.x >> 3);
     }
     const int pair = lin / g.qtiles;
@@ -691,5 +734,47 @@ extern "C" int iir_attention_d64_f16(const iir_attn_desc* a, void* stream) {
         iir_launch(attn_kernel, grid, dim3(256), 0, (hipStream_t)stream, g);
     } else if (version == 3 || (version == 0 && grid.x <= 512)) launch2(attn_kernel2<2, 2>, 2);
     else launch2(attn_kernel2<3, 2>, 2);
+    return iir_launch_status();
+}
+
+extern "C" int iir_attention_d64_ident_f16(const iir_attn_desc* a, int32_t ident_from, void* stream) {
+    // (every argument is checked before the first HIP call)
+    if (!a || !a->Q || !a->O || a->nseg != 1 || a->causal || a->o_fp8) return IIR_EINVAL;
+    if (a->Tq <= 0 || a->heads <= 0 || a->batch <= 1 || ident_from < 1 || ident_from >= a->batch) return IIR_EINVAL;
+    if (a->ldq % 8 || a->ldo % 4) return IIR_EINVAL;
+    const iir_attn_kv* s = &a->kv[0];
+    if (!s->K || !s->Vt || s->Tkv != a->Tq || s->ldk % 8 || s->ldvt % 8 || s->vt_batch_stride % 8) return IIR_EINVAL;
+    (void)hipGetLastError();
+    AGeo g{};
+    g.Q = (const f16*)a->Q; g.ldq = a->ldq; g.qbs = a->q_batch_stride;
+    g.O = (f16*)a->O; g.ldo = a->ldo; g.obs = a->o_batch_stride;
+    g.Tq = a->Tq; g.nseg = 1;
+    g.c = a->scale * 1.4426950408889634f;
+    g.qpre = a->q_prescaled;
+    g.seg[0] = Seg{(const f16*)s->K, s->ldk, s->k_batch_stride, (const f16*)s->Vt, s->ldvt, s->vt_batch_stride, s->Tkv};
+    g.qtiles = (a->Tq + 127) / 128;
+    g.heads = a->heads;
+    g.npairs = a->heads * ident_from;
+    g.n_attn = g.npairs * g.qtiles;
+    g.ident_from = ident_from;
+    const dim3 grid(g.n_attn + (a->batch - ident_from) * a->heads * g.qtiles);
+    // the same instantiation choice as iir_attention_d64_f16 for the attending rows (IIR_ATTN_V = 1, the first-generation
+    // kernel, has no identity form: the default choice is used then)
+    static const int version = getenv("IIR_ATTN_V") ? atoi(getenv("IIR_ATTN_V")) : 0;
+    static const bool pre_on = !(getenv("IIR_ATTN_PRE") && atoi(getenv("IIR_ATTN_PRE")) == 0);
+    if (pre_on && (s->Tkv + KT - 1) / KT <= 4) {
+        static int attr_dev = -1;
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        if (attr_dev != dev) {
+            if (hipFuncSetAttribute((const void*)attn_kernel2<2, 4, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * KT * 128) != hipSuccess) return IIR_ELAUNCH;
+            attr_dev = dev;
+        }
+        iir_launch(attn_kernel2<2, 4, true, true>, grid, dim3(256), (size_t)4 * 2 * KT * 128, (hipStream_t)stream, g);
+    } else if (version == 3 || (version != 2 && g.n_attn <= 512)) {
+        iir_launch(attn_kernel2<2, 2, false, true>, grid, dim3(256), (size_t)2 * 2 * KT * 128, (hipStream_t)stream, g);
+    } else {
+        iir_launch(attn_kernel2<3, 2, false, true>, grid, dim3(256), (size_t)2 * 2 * KT * 128, (hipStream_t)stream, g);
+    }
     return iir_launch_status();
 }

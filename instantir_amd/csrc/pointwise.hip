@@ -88,17 +88,21 @@ __global__ void unpack_latent_kernel(const E* in, long ldi, int R, int C, int HW
 // rescale_noise_cfg (pipelines/sdxl_instantir.py:181-192): per image, over (C, H, W),
 //   factor = phi * std(eps_text) / std(eps_cfg) + (1 - phi),  eps_cfg = u + g * (text - u)   (torch.std: unbiased; the
 // N-1 cancels in the ratio).  One workgroup per image, fp32 element math, fp64 accumulation.
+// PAG: eps_cfg gains the perturbed-attention term + s * (text - perturbed) (rows [2B, 3B)), s = *pag_s, before the ratio.
+template <bool PAG>
 __global__ __launch_bounds__(1024) void cfg_rescale_kernel(const f16* eps_nhwc, long lde, int B, int C, int HW, const float* coef,
-                                                           float phi, float* factor) {
+                                                           const float* pag_s, float phi, float* factor) {
     __shared__ double red[4][16];
     const int b = blockIdx.x;
     const float g = coef[0];
+    const float ps = PAG ? *pag_s : 0.f;
     double st = 0., st2 = 0., sc = 0., sc2 = 0.;
     for (int p = threadIdx.x; p < HW; p += blockDim.x)
         for (int c = 0; c < C; ++c) {
             const float u = (float)eps_nhwc[((long)b * HW + p) * lde + c];
             const float t = (float)eps_nhwc[((long)(B + b) * HW + p) * lde + c];
-            const float e = u + g * (t - u);
+            float e = u + g * (t - u);
+            if (PAG && ps != 0.f) e = e + ps * (t - (float)eps_nhwc[((long)(2 * B + b) * HW + p) * lde + c]);
             st += t; st2 += (double)t * t; sc += e; sc2 += (double)e * e;
         }
     double v[4] = {st, st2, sc, sc2};
@@ -119,25 +123,39 @@ __global__ __launch_bounds__(1024) void cfg_rescale_kernel(const f16* eps_nhwc, 
     }
 }
 
+// Perturbed-attention guidance (PAG) form: the UNet output has one more group of B rows, the perturbed prediction p
+// (rows [2B, 3B) with CFG, [B, 2B) without), and  eps = u + g * (c - u) + s * (c - p)  (CFG) or  c + s * (c - p),  s = *pag_s
+// (device: the per-step s_t of the adaptive scale).  The term is skipped when s == 0, so s = 0 gives the plain kernel's bits.
+template <bool PAG>
+__device__ __forceinline__ float guided_eps(const f16* eps_nhwc, long lde, int B, int HW, int cfg, float g, float ps,
+                                            const float* eps_factor, int b, int p, int c) {
+    float e;
+    if (cfg) {
+        // the reference forms the guidance in the UNet dtype (fp16) -- keep fp32 here (>= precision)
+        const float u = (float)eps_nhwc[((long)b * HW + p) * lde + c];
+        const float t = (float)eps_nhwc[((long)(B + b) * HW + p) * lde + c];
+        e = u + g * (t - u);
+        if (PAG && ps != 0.f) e = e + ps * (t - (float)eps_nhwc[((long)(2 * B + b) * HW + p) * lde + c]);
+        if (eps_factor) e *= eps_factor[b];
+    } else {
+        e = (float)eps_nhwc[((long)b * HW + p) * lde + c];
+        if (PAG && ps != 0.f) e = e + ps * (e - (float)eps_nhwc[((long)(B + b) * HW + p) * lde + c]);
+    }
+    return e;
+}
+
+template <bool PAG>
 __global__ void sched_step_kernel(const f16* eps_nhwc, long lde, int B, int C, int HW, int cfg, const float* coef,
-                                  const float* x, const float* noise, float* prev, float* x0_out, float* eps_out,
-                                  const float* eps_factor) {
+                                  const float* pag_s, const float* x, const float* noise, float* prev, float* x0_out,
+                                  float* eps_out, const float* eps_factor) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)B * HW) return;
     const int b = (int)(i / HW), p = (int)(i % HW);
     const float g = coef[0], sb = coef[1], sa = coef[2], k0 = coef[3], k1 = coef[4], k2 = coef[5], k3 = coef[6];
+    const float ps = PAG ? *pag_s : 0.f;
     for (int c = 0; c < C; ++c) {
         const long o = ((long)b * C + c) * HW + p;
-        float e;
-        if (cfg) {
-            // the reference forms the guidance in the UNet dtype (fp16) -- keep fp32 here (>= precision)
-            const float u = (float)eps_nhwc[((long)b * HW + p) * lde + c];
-            const float t = (float)eps_nhwc[((long)(B + b) * HW + p) * lde + c];
-            e = u + g * (t - u);
-            if (eps_factor) e *= eps_factor[b];
-        } else {
-            e = (float)eps_nhwc[((long)b * HW + p) * lde + c];
-        }
+        const float e = guided_eps<PAG>(eps_nhwc, lde, B, HW, cfg, g, ps, eps_factor, b, p, c);
         const float xv = x[o];
         const float x0 = (xv - sb * e) / sa;
         float pv = k0 * x0 + k1 * xv;
@@ -207,24 +225,18 @@ __global__ void pack_latent_dscale_kernel(const float* x, int B, int C, int HW, 
 // hist (fp32 NCHW, B rows) holds m_prev on entry and this step's x0 on exit: each element is read, then overwritten by the
 // thread that owns it, so one captured launch serves every step.  With k_h == 0 the plane is never loaded (it is
 // uninitialised or stale on a solver's first step, and 0 * NaN would leak into prev).
+template <bool PAG>
 __global__ void sched_step_hist_kernel(const f16* eps_nhwc, long lde, int B, int C, int HW, int cfg, const float* coef,
-                                       const float* x, const float* noise, float* hist, float* prev, float* x0_out,
-                                       const float* eps_factor) {
+                                       const float* pag_s, const float* x, const float* noise, float* hist, float* prev,
+                                       float* x0_out, const float* eps_factor) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)B * HW) return;
     const int b = (int)(i / HW), p = (int)(i % HW);
     const float g = coef[0], sb = coef[1], sa = coef[2], k0 = coef[3], k1 = coef[4], k2 = coef[5], k3 = coef[6], kh = coef[7];
+    const float ps = PAG ? *pag_s : 0.f;
     for (int c = 0; c < C; ++c) {
         const long o = ((long)b * C + c) * HW + p;
-        float e;
-        if (cfg) {
-            const float u = (float)eps_nhwc[((long)b * HW + p) * lde + c];
-            const float t = (float)eps_nhwc[((long)(B + b) * HW + p) * lde + c];
-            e = u + g * (t - u);
-            if (eps_factor) e *= eps_factor[b];
-        } else {
-            e = (float)eps_nhwc[((long)b * HW + p) * lde + c];
-        }
+        const float e = guided_eps<PAG>(eps_nhwc, lde, B, HW, cfg, g, ps, eps_factor, b, p, c);
         const float xv = x[o];
         const float x0 = (xv - sb * e) / sa;
         float pv = k0 * x0 + k1 * xv;
@@ -235,6 +247,15 @@ __global__ void sched_step_hist_kernel(const f16* eps_nhwc, long lde, int B, int
         hist[o] = x0;
         if (x0_out) x0_out[o] = x0;
     }
+}
+
+// Batched 16-byte copies: job j of the device table {src, dst, units} copies `units` x 16 bytes (blockIdx.y = job).
+__global__ void copy_segments_kernel(const long long* jobs) {
+    const long long* jb = jobs + 3 * blockIdx.y;
+    const long n = (long)jb[2];
+    const uint4* src = (const uint4*)jb[0];
+    uint4* dst = (uint4*)jb[1];
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) dst[i] = src[i];
 }
 
 inline int nblk(long n, int t) { return (int)((n + t - 1) / t); }
@@ -313,8 +334,17 @@ extern "C" int iir_cfg_rescale_factor(const void* eps_nhwc, int64_t lde, int32_t
                                       float guidance_rescale, float* factor, void* stream) {
     (void)hipGetLastError();
     if (!eps_nhwc || !coef || !factor || B <= 0 || C <= 0 || HW <= 0 || lde < C || (long)C * HW < 2) return IIR_EINVAL;
-    hipLaunchKernelGGL(cfg_rescale_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, (const f16*)eps_nhwc, (long)lde, B, C, HW,
-                       coef, guidance_rescale, factor);
+    hipLaunchKernelGGL(cfg_rescale_kernel<false>, dim3(B), dim3(1024), 0, (hipStream_t)stream, (const f16*)eps_nhwc, (long)lde, B, C,
+                       HW, coef, (const float*)nullptr, guidance_rescale, factor);
+    return iir_launch_status();
+}
+
+extern "C" int iir_cfg_rescale_factor_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, const float* coef,
+                                          const float* pag_scale, float guidance_rescale, float* factor, void* stream) {
+    if (!eps_nhwc || !coef || !pag_scale || !factor || B <= 0 || C <= 0 || HW <= 0 || lde < C || (long)C * HW < 2) return IIR_EINVAL;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(cfg_rescale_kernel<true>, dim3(B), dim3(1024), 0, (hipStream_t)stream, (const f16*)eps_nhwc, (long)lde, B, C,
+                       HW, coef, pag_scale, guidance_rescale, factor);
     return iir_launch_status();
 }
 
@@ -324,8 +354,20 @@ extern "C" int iir_sched_step(const void* eps_nhwc, int64_t lde, int32_t B, int3
     (void)hipGetLastError();
     if (!eps_nhwc || !coef || !x || !prev || B <= 0 || C <= 0 || HW <= 0 || lde < C) return IIR_EINVAL;
     if (eps_factor && !cfg) return IIR_EINVAL;
-    hipLaunchKernelGGL(sched_step_kernel, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const f16*)eps_nhwc, (long)lde, B, C, HW, cfg, coef, x, noise, prev, x0_out, eps_out, eps_factor);
+    hipLaunchKernelGGL(sched_step_kernel<false>, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const f16*)eps_nhwc, (long)lde, B, C, HW, cfg, coef, (const float*)nullptr, x, noise, prev, x0_out, eps_out,
+                       eps_factor);
+    return iir_launch_status();
+}
+
+extern "C" int iir_sched_step_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
+                                  const float* coef, const float* pag_scale, const float* x, const float* noise, float* prev,
+                                  float* x0_out, float* eps_out, const float* eps_factor, void* stream) {
+    if (!eps_nhwc || !coef || !pag_scale || !x || !prev || B <= 0 || C <= 0 || HW <= 0 || lde < C) return IIR_EINVAL;
+    if (eps_factor && !cfg) return IIR_EINVAL;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(sched_step_kernel<true>, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const f16*)eps_nhwc, (long)lde, B, C, HW, cfg, coef, pag_scale, x, noise, prev, x0_out, eps_out, eps_factor);
     return iir_launch_status();
 }
 
@@ -336,8 +378,29 @@ extern "C" int iir_sched_step_hist(const void* eps_nhwc, int64_t lde, int32_t B,
     if (!eps_nhwc || !coef || !x || !hist || !prev || B <= 0 || C <= 0 || HW <= 0 || lde < C) return IIR_EINVAL;
     if (eps_factor && !cfg) return IIR_EINVAL;
     if (hist == x || hist == prev || (x0_out && hist == x0_out)) return IIR_EINVAL;
-    hipLaunchKernelGGL(sched_step_hist_kernel, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const f16*)eps_nhwc, (long)lde, B, C, HW, cfg, coef, x, noise, hist, prev, x0_out, eps_factor);
+    hipLaunchKernelGGL(sched_step_hist_kernel<false>, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const f16*)eps_nhwc, (long)lde, B, C, HW, cfg, coef, (const float*)nullptr, x, noise, hist, prev, x0_out,
+                       eps_factor);
+    return iir_launch_status();
+}
+
+extern "C" int iir_sched_step_hist_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
+                                       const float* coef, const float* pag_scale, const float* x, const float* noise, float* hist,
+                                       float* prev, float* x0_out, const float* eps_factor, void* stream) {
+    if (!eps_nhwc || !coef || !pag_scale || !x || !hist || !prev || B <= 0 || C <= 0 || HW <= 0 || lde < C) return IIR_EINVAL;
+    if (eps_factor && !cfg) return IIR_EINVAL;
+    if (hist == x || hist == prev || (x0_out && hist == x0_out)) return IIR_EINVAL;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(sched_step_hist_kernel<true>, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const f16*)eps_nhwc, (long)lde, B, C, HW, cfg, coef, pag_scale, x, noise, hist, prev, x0_out, eps_factor);
+    return iir_launch_status();
+}
+
+extern "C" int iir_copy_segments(const void* jobs, int32_t njobs, int64_t max_units, void* stream) {
+    if (!jobs || njobs <= 0 || njobs > 65535 || max_units <= 0) return IIR_EINVAL;
+    (void)hipGetLastError();
+    const int gx = (int)(max_units < 256L * 1024 ? nblk(max_units, 256) : 1024);
+    hipLaunchKernelGGL(copy_segments_kernel, dim3(gx, njobs), dim3(256), 0, (hipStream_t)stream, (const long long*)jobs);
     return iir_launch_status();
 }
 

@@ -34,7 +34,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import ops
+from . import ops, pag
 from .config import UNetConfig
 from .packing import conv_weight_nhwc, pair_rows
 from .weights import skip_channels
@@ -157,6 +157,9 @@ class _Net:
         # producer tags its output tensor with the partials, the GroupNorm that consumes it skips its statistics pass
         self.gn_fuse = os.environ.get("IIR_GN_FUSE", "1") != "0"
         self.xattn_fuse = os.environ.get("IIR_XATTN_FUSE", "1") != "0"      # attn2.to_q + cross-attention as one launch
+        # perturbed-attention guidance: None, or (frozenset of selected `attn1` paths, ident_from) -- set on the main UNet only
+        # (HipUNet.set_pag)
+        self.pag = None
         # fp8 build (BASELINE configs[4]): the activations of the transformer linears are STORED as fp8 by the launch that produces
         # them (LayerNorm, attention, GEGLU) and both operands enter the MFMA as fp8 (`ops.gemm_fp8`): the same operand bytes the
         # fp8-weight GEMM formed in registers from fp16 activations (identical results), half the 128-byte lines per FLOP
@@ -423,6 +426,7 @@ class _Net:
         m = A.mark()
         fold = lnst is not None
         if self.fp8_act and not fold and C % 128 == 0 and isinstance(w[p + ".attn1.qkv.w"], ops.Fp8Weight) and h.dtype == F16:
+            assert self.pag is None           # (set_pag refuses fp8 engines)
             self._tblock_fp8(p, h, R, T, heads, st)
             A.release(m)
             return
@@ -443,7 +447,9 @@ class _Net:
                 o.gemm(n, wqkv[:2 * C], qk, prefetch=self._pf(wqkv))
                 o.gemm(wqkv[2 * C:], n, vt)                                                   # V^T = Wv . X^T (operands swapped)
         a = A.alloc(M, C)
-        o.attention(qk[:, :C], a, [(qk[:, C:], T, vt, T, T)], R, heads, T, q_prescaled=True)
+        # PAG: the perturbed rows [ident_from, R) of a selected attn1 get the identity attention map, a = v, in the same launch
+        ident = self.pag[1] if self.pag is not None and (p + ".attn1") in self.pag[0] else 0
+        o.attention(qk[:, :C], a, [(qk[:, C:], T, vt, T, T)], R, heads, T, q_prescaled=True, ident_from=ident)
         o.gemm(a, w[p + ".attn1.to_out.0.w"], h, bias=w[p + ".attn1.to_out.0.b"], res=h,
                prefetch=self._pf(w[p + ".attn1.to_out.0.w"]), ln_out=lnst)
         # -- decoupled cross-attention (TA_IPAttnProcessor2_0, attention_processor.py:1140-1195)
@@ -635,6 +641,18 @@ class HipUNet(_Net):
         self._sized = None
         # FreeU (module/min_sdxl.py:56-77): None, or (s1, s2, b1, b2) applied to the concats of up blocks 0 and 1
         self.freeu = None
+
+    def set_pag(self, paths, ident_from):
+        """Perturbed-attention guidance: in every `attn1` named in `paths`, the batch rows [ident_from, R) of a forward take the
+        identity attention map (o = to_out(to_v(norm1(h)))); every other launch is unchanged.  `paths` None / empty: off.
+        An engine built with fp8 linears is refused (ValueError)."""
+        if not paths:
+            self.pag = None
+            return
+        pag.check_engine(self)
+        if int(ident_from) < 1:
+            raise ValueError(f"set_pag: ident_from must be >= 1, got {ident_from}")
+        self.pag = (frozenset(paths), int(ident_from))
 
     # ---- Resampler (runs once per image batch) ------------------------------------------------
     def _pack_resampler(self, sd):
@@ -861,10 +879,14 @@ class HipAggregator(_Net):
         self._sized = None
         self._out: Optional[List[torch.Tensor]] = None
 
-    def prepare(self, text_embeds, time_ids, H, W):
+    def prepare(self, text_embeds, time_ids, H, W, out_rows=None):
+        """`out_rows` (>= R): images the residual buffers hold.  The forward writes the first R; perturbed-attention guidance
+        fills the rest with the cond rows' residuals (one batched copy, see pipeline._DenoiseLoop)."""
         R = text_embeds.shape[0]
         st = {"R": R, "H": H, "W": W, "aug_emb": self._aug_emb(text_embeds, time_ids), "kv": {}}
-        key = (R, H, W)
+        Ro = R if out_rows is None else int(out_rows)
+        assert Ro >= R
+        key = (R, H, W) if Ro == R else (R, H, W, Ro)
         if self._sized != key:
             # residual outputs live outside the arena: they are consumed by the following UNet forward
             cfgc = skip_channels(self.cfg)
@@ -875,8 +897,8 @@ class HipAggregator(_Net):
                 if i < len(self.cfg.block_out_channels) - 1:
                     h, wd = (h + 1) // 2, (wd + 1) // 2
                     hs.append((h, wd))
-            self._out = [torch.empty(R * a * b, c, dtype=F16, device=self.device) for (a, b), c in zip(hs, cfgc)]
-            self._out_mid = torch.empty(R * h * wd, self.cfg.block_out_channels[-1], dtype=F16, device=self.device)
+            self._out = [torch.empty(Ro * a * b, c, dtype=F16, device=self.device) for (a, b), c in zip(hs, cfgc)]
+            self._out_mid = torch.empty(Ro * h * wd, self.cfg.block_out_channels[-1], dtype=F16, device=self.device)
             dummy = torch.empty(R * H * W, CPAD, dtype=F16, device="meta")
             self._size_arena(lambda: self._forward(dummy, dummy, None, st))
             self._sized = key
@@ -903,7 +925,7 @@ class HipAggregator(_Net):
         ref = s[h * wd:]                                   # row 0 of image 0's bottom half; image stride 2*h*w rows
         o.conv2d(actv.view(R, h, wd, cfg.sft_hidden), w[p + ".ga.w"], mod, bias=w[p + ".ga.b"], res=ref, epi=ops.EPI_SFT,
                  res_img_rows=h2 * wd)
-        o.gemm(mod, w[p + ".zero.w"], out, bias=w[p + ".zero.b"])
+        o.gemm(mod, w[p + ".zero.w"], out[:R * h * wd], bias=w[p + ".zero.b"])
         A.release(m)
 
     def _forward(self, lq, preview, t_dev, st):

@@ -132,6 +132,12 @@ def build_parser():
     p.add_argument("--scheduler", choices=sorted(SCHEDULERS), default="ddpm",
                    help="main scheduler, built as Cls.from_config(pipe.scheduler.config); default ddpm (the reference's)")
     p.add_argument("--karras", action="store_true", help="Karras sigmas (use_karras_sigmas=True) for euler / dpmpp_2m / dpmpp_2m_sde")
+    p.add_argument("--pag_scale", type=float, default=0.0,
+                   help="perturbed-attention guidance scale; 0 (default) = off, > 0 calls pipe.enable_pag(--pag_layers)")
+    p.add_argument("--pag_adaptive_scale", type=float, default=0.0,
+                   help="PAG adaptive scale: s_t = max(pag_scale - pag_adaptive_scale * (1000 - t), 0)")
+    p.add_argument("--pag_layers", type=str, default="mid",
+                   help="comma-separated PAG layer expressions over the UNet's self-attention names (default mid), e.g. mid,up_blocks.0")
     return p
 
 
@@ -200,10 +206,27 @@ def apply_freeu(pipe, args):
         pipe.enable_freeu(*args.freeu)
 
 
+def apply_pag(pipe, args):
+    """`--pag_scale S` (> 0) -> pipe.enable_pag(--pag_layers split at commas); returns the call's PAG keyword arguments (an
+    addition: the reference has no PAG).  `--pag_adaptive_scale` without `--pag_scale` is refused."""
+    scale = float(getattr(args, "pag_scale", 0.0) or 0.0)
+    adaptive = float(getattr(args, "pag_adaptive_scale", 0.0) or 0.0)
+    if scale < 0:
+        raise SystemExit(f"--pag_scale must be >= 0, got {scale}")
+    if scale == 0:
+        if adaptive:
+            raise SystemExit("--pag_adaptive_scale needs --pag_scale > 0")
+        return {}
+    layers = [e.strip() for e in str(getattr(args, "pag_layers", "mid") or "").split(",") if e.strip()]
+    pipe.enable_pag(layers)
+    return {"pag_scale": scale, "pag_adaptive_scale": adaptive}
+
+
 def main(args, device, rank=0, world=1):
     pipe, lcm_scheduler = build_pipeline(args, device)
     apply_freeu(pipe, args)
     apply_scheduler(pipe, args)
+    pag_kw = apply_pag(pipe, args)
     post_fix = f"_{args.post_fix}" if args.post_fix else ""
     out_dir = f"{args.out_path}/{post_fix}"
     os.makedirs(out_dir, exist_ok=True)
@@ -225,7 +248,8 @@ def main(args, device, rank=0, world=1):
         prompts = (list(args.prompt) if args.prompt else [DEFAULT_PROMPT]) * len(lq)
         negs = (list(args.neg_prompt) if args.neg_prompt else [DEFAULT_NEG_PROMPT]) * len(lq)
         kw = dict(image=lq, num_inference_steps=args.num_inference_steps, generator=generator, guidance_scale=args.cfg,
-                  previewer_scheduler=lcm_scheduler, preview_start=args.preview_start, control_guidance_end=args.creative_start)
+                  previewer_scheduler=lcm_scheduler, preview_start=args.preview_start, control_guidance_end=args.creative_start,
+                  **pag_kw)
         if args.synthetic:
             g = torch.Generator().manual_seed(args.seed)
             n = len(lq)

@@ -108,6 +108,7 @@ SIGNATURES = {
     "iir_gemm_ln_parts": (C.c_int, [_I32, _I32, _I32]),
     "iir_conv2d_nhwc_f16": (C.c_int, [C.POINTER(ConvDesc), _P]),
     "iir_attention_d64_f16": (C.c_int, [C.POINTER(AttnDesc), _P]),
+    "iir_attention_d64_ident_f16": (C.c_int, [C.POINTER(AttnDesc), _I32, _P]),
     "iir_attention_f16": (C.c_int, [C.POINTER(AttnDesc), _I32, _P]),
     "iir_groupnorm_nhwc_f16": (C.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _F, _I32, _P, _I64, _P]),
     "iir_groupnorm_nhwc": (C.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _F, _I32, _P, _I64, _I32, _P]),
@@ -132,6 +133,10 @@ SIGNATURES = {
     "iir_sched_step": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "iir_sched_step_hist": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "iir_cfg_rescale_factor": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _F, _P, _P]),
+    "iir_sched_step_pag": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "iir_sched_step_hist_pag": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "iir_cfg_rescale_factor_pag": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P, _F, _P, _P]),
+    "iir_copy_segments": (C.c_int, [_P, _I32, _I64, _P]),
     "iir_lcm_step": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
     "iir_sched_step_f32": (C.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P]),
     "iir_axpby_f32": (C.c_int, [_P, _P, _P, _I64, _P, _P]),

@@ -413,11 +413,12 @@ def attn_q_factor(scale=0.125):
     return float(np.float32(scale) * np.float32(ATTN_LOG2E))
 
 
-def attention(q, o, kv, batch, heads, Tq, scale=0.125, causal=False, q_prescaled=False, head_dim=64):
+def attention(q, o, kv, batch, heads, Tq, scale=0.125, causal=False, q_prescaled=False, head_dim=64, ident_from=0):
     """q, o: 2-D views (batch*Tq, heads*head_dim).  kv: list of 1-2 tuples (k2d, k_batch_rows, vt2d, vt_batch_stride, Tkv):
     k2d (batch*k_batch_rows, heads*head_dim) view, vt2d (heads*head_dim, cols) view with batch b starting at column
     b*vt_batch_stride.  head_dim 64 (the UNet, DINOv2, CLIP-B/L) runs `iir_attention_d64_f16`; 80 and 104 (CLIP ViT-H/14,
-    bigG/14 vision towers) `iir_attention_f16` (no fp8 `o`)."""
+    bigG/14 vision towers) `iir_attention_f16` (no fp8 `o`).  `ident_from` > 0: batch rows [ident_from, batch) get the
+    identity attention map, o = v (perturbed-attention guidance, `iir_attention_d64_ident_f16`)."""
     _chk2d(q, "q")
     d = L.AttnDesc()
     if o.dtype in _FP8_DTYPES:          # the output feeds an all-fp8 `to_out` GEMM: E4M3 bytes (rounded to fp16 first)
@@ -436,6 +437,13 @@ def attention(q, o, kv, batch, heads, Tq, scale=0.125, causal=False, q_prescaled
         d.kv[i].K, d.kv[i].ldk, d.kv[i].k_batch_stride = k.data_ptr(), k.stride(0), k_rows * k.stride(0)
         d.kv[i].Vt, d.kv[i].ldvt, d.kv[i].vt_batch_stride = vt.data_ptr(), vt.stride(0), vbs
         d.kv[i].Tkv = tkv
+    if ident_from:
+        if head_dim != 64:
+            raise ValueError("attention: identity rows need head_dim 64")
+        with _Timed("attn_kernel", 4.0 * ident_from * heads * Tq * head_dim * kv[0][4],
+                    2.0 * ident_from * heads * head_dim * (2 * Tq + 2 * kv[0][4]) + 4.0 * (batch - ident_from) * heads * Tq * head_dim):
+            L.check(L.load().iir_attention_d64_ident_f16(C.byref(d), int(ident_from), _stream()), "iir_attention_d64_ident_f16")
+        return o
     with _Timed("attn_kernel", 4.0 * batch * heads * Tq * head_dim * sum(k[4] for k in kv),
                 2.0 * batch * heads * head_dim * (2 * Tq + 2 * sum(k[4] for k in kv))):
         if head_dim == 64:
@@ -613,30 +621,74 @@ def unpack_latent(x2d, out):
     return out
 
 
-def sched_step(eps2d, B, coef, x, prev, noise=None, cfg=True, x0_out=None, eps_out=None, eps_factor=None):
+def _chk_pag(pag_scale):
+    if not (torch.is_tensor(pag_scale) and pag_scale.is_cuda and pag_scale.dtype == torch.float32 and pag_scale.numel() >= 1):
+        raise ValueError("pag_scale must be a CUDA fp32 tensor (the step's s_t, read at launch time)")
+
+
+def sched_step(eps2d, B, coef, x, prev, noise=None, cfg=True, x0_out=None, eps_out=None, eps_factor=None, pag_scale=None):
+    """`pag_scale` (device fp32[1]): the PAG form -- eps2d holds the perturbed rows after the cond rows (iir_sched_step_pag)."""
     _, Cc, H, Wd = x.shape
+    if pag_scale is not None:
+        _chk_pag(pag_scale)
+        L.check(L.load().iir_sched_step_pag(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(),
+                                            pag_scale.data_ptr(), x.data_ptr(), _p(noise), prev.data_ptr(), _p(x0_out), _p(eps_out),
+                                            _p(eps_factor), _stream()), "iir_sched_step_pag")
+        return prev
     L.check(L.load().iir_sched_step(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(),
                                     x.data_ptr(), _p(noise), prev.data_ptr(), _p(x0_out), _p(eps_out), _p(eps_factor),
                                     _stream()), "iir_sched_step")
     return prev
 
 
-def sched_step_hist(eps2d, B, coef, x, hist, prev, noise=None, cfg=True, x0_out=None, eps_factor=None):
+def sched_step_hist(eps2d, B, coef, x, hist, prev, noise=None, cfg=True, x0_out=None, eps_factor=None, pag_scale=None):
     """sched_step with the history term coef[7] * hist; `hist` (shape of x, fp32) then holds this step's x0."""
     _, Cc, H, Wd = x.shape
     assert hist.shape == x.shape and hist.dtype == torch.float32 and hist.is_contiguous()
+    if pag_scale is not None:
+        _chk_pag(pag_scale)
+        L.check(L.load().iir_sched_step_hist_pag(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(),
+                                                 pag_scale.data_ptr(), x.data_ptr(), _p(noise), hist.data_ptr(), prev.data_ptr(),
+                                                 _p(x0_out), _p(eps_factor), _stream()), "iir_sched_step_hist_pag")
+        return prev
     L.check(L.load().iir_sched_step_hist(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(),
                                          x.data_ptr(), _p(noise), hist.data_ptr(), prev.data_ptr(), _p(x0_out), _p(eps_factor),
                                          _stream()), "iir_sched_step_hist")
     return prev
 
 
-def cfg_rescale_factor(eps2d, B, coef, x, guidance_rescale, factor):
-    """factor (B,) fp32 device: the per-image multiplier `rescale_noise_cfg` applies to the guided eps."""
+def cfg_rescale_factor(eps2d, B, coef, x, guidance_rescale, factor, pag_scale=None):
+    """factor (B,) fp32 device: the per-image multiplier `rescale_noise_cfg` applies to the guided eps (with `pag_scale`: the
+    guided eps includes the PAG term of rows [2B, 3B))."""
     _, Cc, H, Wd = x.shape
+    if pag_scale is not None:
+        _chk_pag(pag_scale)
+        L.check(L.load().iir_cfg_rescale_factor_pag(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, coef.data_ptr(),
+                                                    pag_scale.data_ptr(), float(guidance_rescale), factor.data_ptr(), _stream()),
+                "iir_cfg_rescale_factor_pag")
+        return factor
     L.check(L.load().iir_cfg_rescale_factor(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, coef.data_ptr(),
                                             float(guidance_rescale), factor.data_ptr(), _stream()), "iir_cfg_rescale_factor")
     return factor
+
+
+def segment_job_table(jobs, device):
+    """Device int64 (n, 3) table for `copy_segments` from (src, dst) pairs of equal-size contiguous tensors.  Returns
+    (table, n, max_units)."""
+    rows = []
+    for src, dst in jobs:
+        nb = src.numel() * src.element_size()
+        if (not src.is_contiguous() or not dst.is_contiguous() or dst.numel() * dst.element_size() != nb or nb % 16
+                or src.data_ptr() % 16 or dst.data_ptr() % 16):
+            raise ValueError("copy_segments: each job needs contiguous, 16-byte aligned tensors of the same size (a multiple of 16 B)")
+        rows.append([src.data_ptr(), dst.data_ptr(), nb // 16])
+    table = torch.tensor(rows, dtype=torch.int64).to(device)
+    return table, len(rows), max(r[2] for r in rows)
+
+
+def copy_segments(table, njobs, max_units):
+    """Every job of a `segment_job_table` in one launch (iir_copy_segments)."""
+    L.check(L.load().iir_copy_segments(table.data_ptr(), int(njobs), int(max_units), _stream()), "iir_copy_segments")
 
 
 def lcm_step(eps2d, B, rep, coef, x, out2d, out_nchw=None):

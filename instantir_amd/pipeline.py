@@ -25,11 +25,11 @@ from __future__ import annotations
 
 import os
 from types import SimpleNamespace
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, List, Optional, Union
 
 import torch
 
-from . import ops
+from . import ops, pag
 from .config import UNetConfig, VAEConfig
 from .engine import CPAD, F16, HipAggregator, HipUNet
 from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,  # noqa: F401
@@ -149,6 +149,8 @@ class InstantIRPipeline:
         self.overlap_sft = os.environ.get("IIR_OVERLAP_SFT", "1") != "0"     # shallow SFT heads beside the decoder's first up block
         self._guidance_scale = 7.0
         self._freeu = None                          # (s1, s2, b1, b2) or None: see enable_freeu
+        self._pag_layers = None                     # perturbed-attention guidance: the layer list of enable_pag, or None
+        self._pag_paths = None                      # ... and the main UNet's `attn1` paths it selects
 
     # ---- reference surface ----------------------------------------------------------------------
     @classmethod
@@ -293,6 +295,36 @@ class InstantIRPipeline:
     def disable_freeu(self):
         self._freeu = None
 
+    # ---- perturbed-attention guidance (PAG; behaviour of diffusers' PAG pipelines) ----
+    def enable_pag(self, pag_applied_layers: Union[str, List[str]] = "mid"):
+        """Turn PAG on for later calls (`pag_scale`, default 3.0; `pag_adaptive_scale`).  Each entry of `pag_applied_layers` is a
+        regular expression over the main UNet's self-attention module names (e.g. 'mid', 'down_blocks.2', 'up_blocks.0',
+        'up_blocks.1.attentions.2'); see `instantir_amd.pag.select`."""
+        if self._unet is not None:
+            pag.check_engine(self._unet)
+        self.set_pag_applied_layers(pag_applied_layers)
+
+    def set_pag_applied_layers(self, pag_applied_layers: Union[str, List[str]]):
+        layers = pag.normalize_layers(pag_applied_layers)
+        self._pag_paths = tuple(pag.select(layers, pag.attn1_paths(self.cfg)))
+        self._pag_layers = layers
+
+    def disable_pag(self):
+        self._pag_layers = self._pag_paths = None
+
+    @property
+    def pag_applied_layers(self):
+        return None if self._pag_layers is None else list(self._pag_layers)
+
+    def _main_state(self, ctx, pooled, time_ids, img, Hl, Wl, B, rep, pag_on):
+        """`prepare` of the main UNet: with PAG one more group of B rows, each a copy of its cond row (rows [(rep-1)B, rep B)
+        of the prompt embeddings, pooled embeddings, time ids and IP tokens)."""
+        ip = self._unet.resampler(img)
+        if pag_on:
+            c = slice((rep - 1) * B, rep * B)
+            ctx, pooled, time_ids, ip = (torch.cat([v, v[c]], 0) for v in (ctx, pooled, time_ids, ip))
+        return self._unet.prepare(ctx, pooled, time_ids, ip, Hl, Wl)
+
     def _apply_freeu(self, *nets):
         for n in nets:
             if n is not None:
@@ -363,7 +395,7 @@ class InstantIRPipeline:
             self._agg = HipAggregator(self.cfg, self._agg_sd, self.device)
         self._apply_freeu(self._unet, self._unet_prev)
 
-    def _loop_for(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale):
+    def _loop_for(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale, pag_on=False):
         """The step's buffers and captured hipGraphs are kept from one call to the next: a second image of the same geometry,
         through the same engines, re-uses them (its hoisted K / V, embeddings and LQ latent are copied into the captured
         tensors) instead of paying the warm-up step, the capture and the graph instantiation again (~0.1 s of a 1.9 s call
@@ -372,14 +404,15 @@ class InstantIRPipeline:
         key = (B, rep, Hl, Wl, reference_latents is not None, float(guidance_rescale or 0.0), self.use_graphs, self.overlap_streams,
                self.overlap_sft, tuple(None if n is None else (id(n), n.arena_gen, n.inkernel_prefetch, n.gn_fuse) for n in nets),
                self._freeu,           # the FreeU factors are launch arguments of the captured concats
-               _sched_form(self.scheduler))   # the sigma schedulers launch the device-scale pack and the history step
+               _sched_form(self.scheduler),   # the sigma schedulers launch the device-scale pack and the history step
+               self._pag_paths if pag_on else None)     # PAG: row count and the identity launches (its scale is a device scalar)
         cached = self._loop_cache
         if cached is not None and cached[0] == key and os.environ.get("IIR_LOOP_CACHE", "1") != "0":
             if cached[1].adopt(st, st_prev, st_agg, lq, reference_latents, previewer_scheduler):
                 return cached[1]
         self._loop_cache = None                      # drop the old graphs before building the new ones
         loop = _DenoiseLoop(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler,
-                            guidance_rescale=guidance_rescale)
+                            guidance_rescale=guidance_rescale, pag_on=pag_on)
         # the entry keeps the engines alive: `id()` in the key can then not be re-issued to a NEW engine (adapter switch, LoRA
         # scale change) while graphs captured on the old one's arena and weights are still cached
         self._loop_cache = (key, loop, nets)
@@ -576,12 +609,15 @@ class InstantIRPipeline:
                  negative_original_size=None, negative_crops_coords_top_left=(0, 0), negative_target_size=None,
                  clip_skip=None, callback_on_step_end: Optional[Callable] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"], previewer_scheduler=None,
-                 reference_latents=None, init_noise=None, step_noises=None, **kwargs):
+                 reference_latents=None, init_noise=None, step_noises=None, pag_scale: Optional[float] = None,
+                 pag_adaptive_scale: float = 0.0, **kwargs):
         """Keyword arguments and defaults of pipelines/sdxl_instantir.py:1067-1115.  Two additions for
         bit-reproducible parity runs: `init_noise` (the randn of init_latents) and
         `step_noises` (list of per-step DDPM / Euler-ancestral / DPM++ SDE noises) replace draws from `generator` when given.
         With a sigma scheduler (Euler, Euler-ancestral, DPM++) `eta` is ignored, as diffusers drops it for those `step()`s.
-        `image` must be the LQ *latent* (B,4,h,w) here unless a VAE is attached (`image.shape[1] == 4` branch of :1369-1382)."""
+        `image` must be the LQ *latent* (B,4,h,w) here unless a VAE is attached (`image.shape[1] == 4` branch of :1369-1382).
+        `pag_scale` / `pag_adaptive_scale` (an addition, after diffusers' PAG pipelines): need `enable_pag`; `pag_scale` None
+        means 3.0, and PAG runs when it is > 0 (s_t = max(pag_scale - pag_adaptive_scale * (1000 - t), 0) per step)."""
         # :1531-1535 merges the caller's dict over {"temb": emb} and hands it to both UNet passes.  What a key can do there:
         # "scale" is popped by diffusers' UNet forward and scales every LoRA layer for that pass (it also sets the text-encoder
         # LoRA scale, :1324-1326 -- no text-encoder LoRA exists on this path); "temb" / "external_kv" are the processors' own
@@ -595,6 +631,13 @@ class InstantIRPipeline:
                 raise ValueError(f"cross_attention_kwargs keys {sorted(extra)} are not accepted: the TA-IP attention processors take "
                                  "`temb` (set by the loop) and nothing a caller may override; only 'scale' (LoRA scale) is honoured")
             lora_mult = float(cross_attention_kwargs["scale"])
+        if self._pag_layers is None:
+            if pag_scale is not None or pag_adaptive_scale:
+                raise ValueError("pag_scale / pag_adaptive_scale need perturbed-attention guidance: call pipe.enable_pag(...) first")
+            pag_on = False
+        else:
+            pag_scale = pag.DEFAULT_PAG_SCALE if pag_scale is None else float(pag_scale)
+            pag_on = pag_scale > 0
         if multistep_restore:
             raise NotImplementedError("multistep_restore passes kwargs the shipped DDPM scheduler does not accept "
                                       "(SURVEY.md Appendix C Q5)")
@@ -655,7 +698,12 @@ class InstantIRPipeline:
         else:
             ctx, pooled = prompt_embeds, pooled_prompt_embeds
         rep = 2 if do_cfg else 1
-        R = rep * B
+        R = rep * B                   # rows of the previewer and the Aggregator
+        groups = rep + int(pag_on)    # row groups of the main UNet: [uncond;] cond [; perturbed]
+        if pag_on:
+            self._unet.set_pag(self._pag_paths, R)          # (refuses an fp8 engine)
+        else:
+            self._unet.set_pag(None, 0)
         original_size = original_size or (height, width)
         target_size = target_size or (height, width)
         ids = list(original_size) + list(crops_coords_top_left) + list(target_size)     # :965-981
@@ -717,11 +765,11 @@ class InstantIRPipeline:
             ts = [t for t in ts if t >= cutoff]
 
         # -- step-invariant device state
-        st = self._unet.prepare(ctx, pooled, time_ids, self._unet.resampler(img), Hl, Wl)
+        st = self._main_state(ctx, pooled, time_ids, img, Hl, Wl, B, rep, pag_on)
         st_prev = None
         if self._unet_prev is not None:
             st_prev = self._unet_prev.prepare(ctx, pooled, time_ids, self._unet_prev.resampler(img), Hl, Wl)
-        st_agg = self._agg.prepare(pooled, time_ids, Hl, Wl)
+        st_agg = self._agg.prepare(pooled, time_ids, Hl, Wl, out_rows=groups * B if pag_on else None)
 
         # -- initial latents (:1388-1403)
         if init_latents_with_lq:
@@ -736,7 +784,8 @@ class InstantIRPipeline:
             x = latents.to(dev, torch.float32) * self.scheduler.init_noise_sigma
         x = x.contiguous()
 
-        loop = self._loop_for(B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale)
+        loop = self._loop_for(B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale,
+                              pag_on)
         preview_row = []
         preview_factor = torch.ones(B)
         compound = None            # per-image scale the Aggregator's (persistent, raw) outputs currently carry
@@ -764,8 +813,9 @@ class InstantIRPipeline:
             noise = None
             if step_noises is not None:
                 noise = step_noises[i]
-            x0 = loop.step(mode, t, x, (compound if mode != "unet" else scale_rows).repeat(rep), guidance_scale, eta, noise,
-                           generator, want_x0=adastep_restore, want_preview=save_preview_row or adastep_restore, i=i)
+            x0 = loop.step(mode, t, x, (compound if mode != "unet" else scale_rows).repeat(groups), guidance_scale, eta, noise,
+                           generator, want_x0=adastep_restore, want_preview=save_preview_row or adastep_restore, i=i,
+                           pag_s=pag.scale_at(pag_scale, pag_adaptive_scale, t) if pag_on else 0.0)
             if mode == "preview":
                 pv = loop.preview_f32[B * (rep - 1):]
                 if save_preview_row:
@@ -795,12 +845,12 @@ class InstantIRPipeline:
                     if tuple(new_ctx.shape) != tuple(ctx.shape):
                         raise ValueError(f"callback_on_step_end returned prompt_embeds of shape {tuple(new_ctx.shape)}, expected {tuple(ctx.shape)}")
                     ctx = new_ctx
-                    st = self._unet.prepare(ctx, pooled, time_ids, self._unet.resampler(img), Hl, Wl)
+                    st = self._main_state(ctx, pooled, time_ids, img, Hl, Wl, B, rep, pag_on)
                     if self._unet_prev is not None:
                         st_prev = self._unet_prev.prepare(ctx, pooled, time_ids, self._unet_prev.resampler(img), Hl, Wl)
                     mean_keep, hist_keep = loop.previewer_mean, loop.hist
                     loop = _DenoiseLoop(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler,
-                                        guidance_rescale=guidance_rescale)
+                                        guidance_rescale=guidance_rescale, pag_on=pag_on)
                     loop.previewer_mean = mean_keep
                     if hist_keep is not None:                # a multistep solver's x0 history continues across the rebuild
                         loop.hist.copy_(hist_keep)
@@ -853,17 +903,25 @@ def _copy_state(dst, src):
 class _DenoiseLoop:
     """Device buffers + (optionally hipGraph-captured) launch sequences of one denoising step.
     Three phases exist (pipelines/sdxl_instantir.py:1542-1616): "preview" (UNet+LoRA -> LCM preview
-    -> Aggregator -> UNet), "agg" (Aggregator on the LQ / reference latent -> UNet), "unet"."""
+    -> Aggregator -> UNet), "agg" (Aggregator on the LQ / reference latent -> UNet), "unet".
+    Rows: the previewer and the Aggregator run `rep` groups of B rows ([uncond;] cond), the main UNet `groups` of them --
+    one more with perturbed-attention guidance (`pag_on`), whose rows copy the cond rows' inputs and residuals."""
 
-    def __init__(self, pipe, B, rep, H, W, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale=0.0):
+    def __init__(self, pipe, B, rep, H, W, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale=0.0,
+                 pag_on=False):
         dev = pipe.device
         self.guidance_rescale = float(guidance_rescale or 0.0)
         self.cfg_factor = torch.ones(B, dtype=torch.float32, device=dev)
         self.p, self.B, self.rep, self.H, self.W = pipe, B, rep, H, W
+        self.pag_on = bool(pag_on)
+        self.groups = rep + int(self.pag_on)
         self.st, self.st_prev, self.st_agg = st, st_prev, st_agg
         self.prev_sched = previewer_scheduler
         R, HW = B * rep, H * W
-        self.lat16 = torch.zeros(R * HW, CPAD, dtype=F16, device=dev)
+        Rm = B * self.groups                                               # main UNet rows
+        self.R_agg = R
+        self.lat16 = torch.zeros(Rm * HW, CPAD, dtype=F16, device=dev)
+        self.lat_prev = self.lat16[:R * HW]                                # the previewer's rows of it
         self.prev16 = torch.zeros(R * HW, CPAD, dtype=F16, device=dev)
         self.lq16 = torch.zeros(R * HW, CPAD, dtype=F16, device=dev)
         ops.pack_latent(lq, self.lq16, rep=rep)
@@ -880,8 +938,9 @@ class _DenoiseLoop:
         self.form = _sched_form(pipe.scheduler)
         # the x0 history of a multistep solver, read and rewritten in place by every step's iir_sched_step_hist
         self.hist = torch.zeros_like(self.x_in) if self.form == "hist" else None
-        # per-step scalars: [t x R | lcm coef x4 | sched coef x8 (k_h in [7]) | res scale x R | c_in]
-        self.n_sc = R + 4 + 8 + R + 1
+        # per-step scalars: [t x Rm | lcm coef x4 | sched coef x8 (k_h in [7]) | res scale x Rm | c_in | PAG s_t]
+        R = Rm
+        self.n_sc = R + 4 + 8 + R + 1 + 1
         # ring of pinned staging rows: a row is rewritten only after the H2D copy that read it has completed
         self.sc_ring = [torch.zeros(self.n_sc, dtype=torch.float32).pin_memory() for _ in range(8)]
         self.sc_events = [None] * 8
@@ -891,7 +950,19 @@ class _DenoiseLoop:
         self.lcm_coef = self.sc_dev[R:R + 4]
         self.sched_coef = self.sc_dev[R + 4:R + 12]
         self.res_scale = self.sc_dev[R + 12:2 * R + 12]
-        self.c_in = self.sc_dev[2 * R + 12:]
+        self.c_in = self.sc_dev[2 * R + 12:2 * R + 13]
+        self.pag_s = self.sc_dev[2 * R + 13:]
+        self.t_agg = self.t_dev[:self.R_agg]                                # the previewer's and the Aggregator's rows
+        self.seg_jobs = None
+        if self.pag_on:
+            # one launch per Aggregator pass gives the perturbed rows of every residual the cond rows' values
+            c0, c1, n = (rep - 1) * B, rep * B, self.groups * B
+            outs = list(pipe._agg._out) + [pipe._agg._out_mid]
+            jobs = []
+            for o in outs:
+                hw = o.shape[0] // n
+                jobs.append((o[c0 * hw:c1 * hw], o[c1 * hw:n * hw]))
+            self.seg_jobs = ops.segment_job_table(jobs, dev)
         self.graphs = {}
         self.side = None
 
@@ -915,9 +986,9 @@ class _DenoiseLoop:
     def _launch(self, mode, use_noise, want_x0, want_preview):
         p, B, rep = self.p, self.B, self.rep
         if self.form == "hist":                                              # scale_model_input(cat([latents]*2), t), :1503-1504
-            ops.pack_latent_dscale(self.x_in, self.lat16, self.c_in, rep=rep)
+            ops.pack_latent_dscale(self.x_in, self.lat16, self.c_in, rep=self.groups)
         else:
-            ops.pack_latent(self.x_in, self.lat16, rep=rep)                  # cat([latents]*2), :1503
+            ops.pack_latent(self.x_in, self.lat16, rep=self.groups)          # cat([latents]*2), :1503
         down = mid = None
         if mode == "unet_res":       # stale residuals of the last Aggregator pass, re-scaled (see __call__)
             eps = p._unet.forward(self.lat16, self.t_dev, self.st, p._agg._out, p._agg._out_mid, self.res_scale)
@@ -936,16 +1007,19 @@ class _DenoiseLoop:
                 enc = p._unet.encode(self.lat16, self.t_dev, self.st)
                 join.record(self.side)
             if mode == "preview":
-                eps1 = p._unet_prev.forward(self.lat16, self.t_dev, self.st_prev)
+                eps1 = p._unet_prev.forward(self.lat_prev, self.t_agg, self.st_prev)
                 ops.lcm_step(eps1, B, rep, self.lcm_coef, self.x_in, self.prev16, self.preview_f32 if want_preview else None)
                 cond = self.prev16
             else:
                 cond = self.ref16 if self.ref16 is not None else self.lq16
-            p._agg.defer_shallow = p.overlap_sft
-            down, mid = p._agg.forward(self.lq16, cond, self.t_dev, self.st_agg)
+            # (PAG: the perturbed rows' residuals are copied once every head has run, so no head is deferred)
+            p._agg.defer_shallow = p.overlap_sft and not self.pag_on
+            down, mid = p._agg.forward(self.lq16, cond, self.t_agg, self.st_agg)
+            if self.pag_on:
+                ops.copy_segments(*self.seg_jobs)
             main.wait_event(join)
             late = None
-            if p.overlap_sft:
+            if p._agg.defer_shallow:
                 # the SFT heads of the shallow skips (consumed by the last up blocks) run on the side stream beside the
                 # decoder's first up block
                 f2, late = torch.cuda.Event(), torch.cuda.Event()
@@ -959,33 +1033,38 @@ class _DenoiseLoop:
             return
         if mode != "unet":
             if mode == "preview":
-                eps1 = p._unet_prev.forward(self.lat16, self.t_dev, self.st_prev)          # :1545-1554
+                eps1 = p._unet_prev.forward(self.lat_prev, self.t_agg, self.st_prev)          # :1545-1554
                 ops.lcm_step(eps1, B, rep, self.lcm_coef, self.x_in, self.prev16,
                              self.preview_f32 if want_preview else None)                 # :1555-1561
                 cond = self.prev16
             else:
                 cond = self.ref16 if self.ref16 is not None else self.lq16               # :1579-1582
             p._agg.defer_shallow = False
-            down, mid = p._agg.forward(self.lq16, cond, self.t_dev, self.st_agg)           # :1591-1599
+            down, mid = p._agg.forward(self.lq16, cond, self.t_agg, self.st_agg)           # :1591-1599
+            if self.pag_on:
+                ops.copy_segments(*self.seg_jobs)
         eps = p._unet.forward(self.lat16, self.t_dev, self.st, down, mid, self.res_scale if down is not None else None)
         self._sched(eps, use_noise, want_x0)
 
     def _sched(self, eps, use_noise, want_x0):
         """CFG (+ rescale_noise_cfg when guidance_rescale > 0, :181-192) + scheduler step, :1619-1633."""
         B, rep = self.B, self.rep
+        ps = self.pag_s if self.pag_on else None          # PAG forms: + s_t * (c - p), s_t read from the step's scalar row
         fac = None
         if rep == 2 and self.guidance_rescale > 0.0:
-            fac = ops.cfg_rescale_factor(eps, B, self.sched_coef, self.x_in, self.guidance_rescale, self.cfg_factor)
+            fac = ops.cfg_rescale_factor(eps, B, self.sched_coef, self.x_in, self.guidance_rescale, self.cfg_factor, pag_scale=ps)
         if self.form == "hist":
             ops.sched_step_hist(eps, B, self.sched_coef, self.x_in, self.hist, self.x_out, noise=self.noise if use_noise else None,
-                                cfg=rep == 2, x0_out=self.x0 if want_x0 else None, eps_factor=fac)
+                                cfg=rep == 2, x0_out=self.x0 if want_x0 else None, eps_factor=fac, pag_scale=ps)
             return
         ops.sched_step(eps, B, self.sched_coef, self.x_in, self.x_out, noise=self.noise if use_noise else None,
-                       cfg=rep == 2, x0_out=self.x0 if want_x0 else None, eps_factor=fac)
+                       cfg=rep == 2, x0_out=self.x0 if want_x0 else None, eps_factor=fac, pag_scale=ps)
 
-    def step(self, mode, t, x, res_scale_rows, guidance, eta, noise, generator, want_x0=False, want_preview=False, i=None):
-        """`i`: the step's index in the scheduler's timetable (the sigma schedulers' coefficients are per index)."""
-        p, R = self.p, self.B * self.rep
+    def step(self, mode, t, x, res_scale_rows, guidance, eta, noise, generator, want_x0=False, want_preview=False, i=None,
+             pag_s=0.0):
+        """`i`: the step's index in the scheduler's timetable (the sigma schedulers' coefficients are per index).  `res_scale_rows`:
+        one scale per main-UNet row.  `pag_s`: the step's PAG scale s_t."""
+        p, R = self.p, self.B * self.groups
         slot = self.sc_idx % len(self.sc_ring)
         self.sc_idx += 1
         if self.sc_events[slot] is not None:
@@ -1010,6 +1089,7 @@ class _DenoiseLoop:
         coef[0] = float(guidance)
         sc[R + 4:R + 12] = torch.tensor(coef)
         sc[R + 12:2 * R + 12] = res_scale_rows.float()
+        sc[2 * R + 13] = float(pag_s)
         use_noise = coef[6] != 0.0
         if use_noise:
             if noise is None:

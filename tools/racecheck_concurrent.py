@@ -126,6 +126,13 @@ for (fH, fW, fcx, fcs) in [(32, 32, 1280, 1280), (64, 64, 640, 320)]:
     ops.freeu_stats(fsk, fparts, fH, fW, add=fadd, add_scale=fsc)
     screen(f"freeu_concat 2x{fH}x{fW} {fcx}+{fcs}", lambda o: ops.freeu_concat(fx, fsk, o, fparts, fH, fW, 1.3, 0.9, mid_add=fmid, add=fadd,
                                                                               add_scale=fsc), [(frows, fcx + fcs)])
+# perturbed-attention guidance (PAG): self-attention with identity rows at the step's shapes (q|k|v as the fused GEMM leaves it)
+for (pT, ph, pb, pf) in [(4096, 10, 3, 2), (1024, 20, 3, 2), (4096, 10, 2, 1), (1024, 20, 2, 1)]:
+    pC = ph * 64
+    pqk, pvt = rnd(pb * pT, 2 * pC), rnd(pC, pb * pT)
+    screen(f"pag identity attention T={pT} heads={ph} batch={pb} ident_from={pf}",
+           lambda o: ops.attention(pqk[:, :pC], o, [(pqk[:, pC:], pT, pvt, pT, pT)], pb, ph, pT, q_prescaled=True, ident_from=pf),
+           [(pb * pT, pC)])
 sil = rnd(2, 1280)
 screen("silu", lambda o: ops.silu(sil, o), [(2, 1280)])
 # the small launches of a step (few workgroups: the occupancy of the finalize kernel that failed)
