@@ -58,7 +58,10 @@ typedef struct iir_gemm_desc {
     const void* res; int64_t ldr;  /* residual / SFT `h` input, or NULL                            */
     int32_t epi, act;
     float out_scale;               /* 0 means 1                                                    */
-    int32_t tile;                  /* 0 auto, 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 128x160, 5 = 64x160 */
+    int32_t tile;                  /* 0 auto; base shape 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 128x160, 5 = 64x160, 6 = 256x128 (8 waves), */
+                                   /*   ring depth and loader waves chosen by the library; or one build by id: base + 10 x stages           */
+                                   /*   (21-26, 31, 34-36), loader waves 54 (128x160) / 55, 65, 75 (64x160, 3 / 4 / 2 stages), 90 = 256x320 */
+                                   /*   (paired epilogues), 91 / 92 = the 8-wave kernel at BN 320 / 256.  Any other value: IIR_EINVAL.      */
     const void* prefetch;          /* optional: range the workgroups touch (at most 1024 128-byte lines each) */
     int64_t prefetch_bytes;        /*   so it is in the Infinity Cache for a LATER launch (next layers' weights) */
     void* splitk_ws;               /* optional split-K workspace (iir_gemm_splitk_workspace_bytes), ZEROED once by the  */

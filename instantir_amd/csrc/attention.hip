@@ -17,7 +17,6 @@
 // global_load_lds_dwordx4 into double-buffered XOR-swizzled LDS images.
 #include "common.h"
 #include "../../include/instantir_hip.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -39,201 +38,7 @@ struct AGeo {
 
 constexpr int KT = 64;   // keys per tile
 
-__global__ __launch_bounds__(256) void attn_kernel(const AGeo g) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * 2 * KT * 128];
-    char* Ks = smem;                    // [2][64 keys][128 B]
-    char* Vs = smem + 2 * KT * 128;     // [2][64 d][128 B]
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int qi = lane & 31, hh = lane >> 5;
-    // XCD-aware placement: workgroups b, b+8, ... share an XCD (one L2).  Give each XCD a contiguous run of
-    // the (batch, head)-major tile order so a pair's K / V^T is pulled over the fabric by 1-2 L2s, not all 8.
-    // (bijective chunked remap: XCD x gets the contiguous run [start_x, start_x + len_x) of the pair-major order)
-    int lin;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = blockIdx.x & 7;
-        lin = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (blockIdx.x >> 3);
-    }
-    const int pair = lin / g.qtiles;
-    const int h = pair % g.heads, b = pair / g.heads;
-    const int q0 = (lin % g.qtiles) * 128 + wave * 32;
-
-    // Q fragments: B operand of S^T = K.Q^T -- lane (q, hh) holds d = 16*ks + 8*hh + [0,8)
-    f16x8 qf[4];
-    {
-        int q = q0 + qi;
-        if (q >= g.Tq) q = g.Tq - 1;
-        const f16* qp = g.Q + (long)b * g.qbs + (long)q * g.ldq + h * 64 + hh * 8;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const f16x8*)(qp + ks * 16);
-    }
-
-    f32x16 oout[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oout[i][r] = 0.f;
-
-    const int srow = lane >> 3, spos = lane & 7;
-
-    for (int sg = 0; sg < g.nseg; ++sg) {
-        const Seg s = g.seg[sg];
-        const f16* kbase = s.K + (long)b * s.kbs + h * 64;
-        const f16* vbase = s.Vt + (long)(h * 64) * s.ldvt + (long)b * s.vbs;
-        const int ntiles = (s.Tkv + KT - 1) / KT;
-        const int tpad = (s.Tkv + 7) & ~7;   // contract: Vt rows readable and finite on [0, tpad)
-
-        auto stage = [&](int t, int buf) {
-            // K tile: 8 glds instructions (8 key rows each); V^T tile: 8 (8 d rows each); 2+2 per wave
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int r0 = (i * 4 + wave) * 8;
-                int key = t * KT + r0 + srow;
-                if (key >= s.Tkv) key = s.Tkv - 1;
-                const int kc = spos ^ srow;                        // swz(key) = key & 7
-                glds16(kbase + (long)key * s.ldk + kc * 8, Ks + buf * KT * 128 + r0 * 128);
-                const int d = r0 + srow;
-                const int vc = spos ^ ((d >> 1) & 7);              // swz(d) = (d >> 1) & 7
-                int kcol = t * KT + vc * 8;                        // 8 keys per 16-byte chunk
-                if (kcol >= tpad) kcol = 0;                        // chunk fully past the end: all its keys are masked
-                glds16(vbase + (long)d * s.ldvt + kcol, Vs + buf * KT * 128 + r0 * 128);
-            }
-        };
-
-        float m = -INFINITY, l = 0.f;
-        f32x16 o[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
-
-        stage(0, 0);
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-        __syncthreads();
-
-        for (int t = 0; t < ntiles; ++t) {
-            const int buf = t & 1;
-            if (t + 1 < ntiles) stage(t + 1, buf ^ 1);
-            const char* kt = Ks + buf * KT * 128;
-            const char* vt = Vs + buf * KT * 128;
-
-            // ---- S^T = K . Q^T  (2 blocks of 32 keys); first k-step accumulates onto the inline constant 0
-            f32x16 sacc[2];
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-                const char* krow = kt + (kb * 32 + qi) * 128;
-                const int sw = qi & 7;
-                f16x8 kf = *(const f16x8*)(krow + ((hh ^ sw) * 16));
-                sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[0], (f32x16){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, 0, 0, 0);
-#pragma unroll
-                for (int ks = 1; ks < 4; ++ks) {
-                    kf = *(const f16x8*)(krow + (((2 * ks + hh) ^ sw) * 16));
-                    sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], sacc[kb], 0, 0, 0);
-                }
-            }
-            // ---- causal mask (CLIP text): key index > query index
-            if (g.causal && (t + 1) * KT > q0) {
-                const int qq = q0 + qi;
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int key = t * KT + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                        if (key > qq) sacc[kb][r] = -INFINITY;
-                    }
-            }
-            // ---- tail mask (last tile only; wave-uniform branch)
-            if ((t + 1) * KT > s.Tkv) {
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int key = t * KT + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                        if (key >= s.Tkv) sacc[kb][r] = -INFINITY;
-                    }
-            }
-            // ---- online softmax (base 2).  The O / l rescale runs only when some row's running max grew
-            //      (alpha == 1 exactly otherwise), which after the first tiles is rare.
-            float mx = sacc[0][0];
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[kb][r]);
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m, mx * g.c);
-            if (__any(m_new > m)) {
-                const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-                l *= alpha;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
-                m = m_new;
-            }
-            float lsum = 0.f;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float p = __builtin_amdgcn_exp2f(fmaf(sacc[kb][r], g.c, -m));
-                    sacc[kb][r] = p;
-                    lsum += p;
-                }
-            l += lsum;
-
-            // ---- O^T += V^T . P^T : k-step (kb, sp) covers keys 32kb+16sp+[0,16) in the permuted order
-            //      element j of lane half hh <-> key 16*sp' + 8*(j>>2) + 4*hh + (j&3)
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int sp = 0; sp < 2; ++sp) {
-                    f16x8 pf;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) pf[j] = (f16)sacc[kb][8 * sp + j];
-                    const int key_lo = kb * 32 + sp * 16 + 4 * hh;           // 4 keys, then 4 more at +8
-#pragma unroll
-                    for (int db = 0; db < 2; ++db) {
-                        const int d = db * 32 + qi;
-                        const int sw = (d >> 1) & 7;
-                        const char* row = vt + d * 128;
-                        const f16x4 lo = *(const f16x4*)(row + (((key_lo >> 3) ^ sw) * 16) + (key_lo & 7) * 2);
-                        const f16x4 hi = *(const f16x4*)(row + ((((key_lo + 8) >> 3) ^ sw) * 16) + (key_lo & 7) * 2);
-                        const f16x8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                        o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, o[db], 0, 0, 0);
-                    }
-                }
-            __builtin_amdgcn_s_waitcnt(0x0F70);
-            __syncthreads();
-        }
-        const float ltot = l + __shfl_xor(l, 32, 64);
-        const float inv = 1.0f / ltot;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) oout[i][r] += o[i][r] * inv;
-    }
-
-    // ---- store: lane (q, hh) holds d = 32*db + 8*gq + 4*hh + [0,4) in regs 4*gq..4*gq+3
-    const int q = q0 + qi;
-    if (q < g.Tq) {
-        f16* op = g.O + (long)b * g.obs + (long)q * g.ldo + h * 64;
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                f16x4 v;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = (f16)oout[db][4 * gq + j];
-                *(f16x4*)(op + db * 32 + gq * 8 + hh * 4) = v;
-            }
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Second-generation kernel (round 2).  Same tiling and operand layout as above; what changed is the per-tile VECTOR work,
-// which (not the MFMAs) set the pace at head_dim 64 -- 32 exponentials per 16 MFMAs and lane:
+// The per-tile VECTOR work (not the MFMAs) sets the pace at head_dim 64 -- 32 exponentials per 16 MFMAs and lane -- so:
 //   * the softmax scale (x log2 e) is folded into the Q fragments once per workgroup, and the running maximum enters the
 //     score MFMA as its C operand (a 16-register vector holding -m of the lane's query), so the accumulator leaves the
 //     MFMA chain as  s*c - m  and the exponential is applied to it directly: no multiply-add per score;
@@ -243,7 +48,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AGeo g) {
 //     being tested and applied per tile;
 //   * the first tile of a KV segment (accumulators empty, no maximum yet) and the masked tiles (ragged tail, causal) are
 //     separate instantiations, so the steady-state tile body is one branch-free basic block the scheduler can interleave
-//     (the first-generation loop carried 66 s_nop hazard pads per tile between its cvt_pk and MFMA instructions).
+//     (a loop with the masks inside carried 66 s_nop hazard pads per tile between its cvt_pk and MFMA instructions).
 // Cross-half row maximum by v_permlane32_swap (VALU) instead of ds_bpermute.
 
 constexpr float THR = 5.0f;
@@ -252,11 +57,7 @@ constexpr float THR = 5.0f;
 // share a 256-byte bank row and a ds_read_b128 lane group (16 lanes = 16 different rows, same logical chunk) is conflict-free
 // only if (rho & 1, chunk) differs for all 16: (rho >> 1) & 7 does that for the 32-row fragment reads of this kernel (lane
 // groups {0-3, 12-15, 20-27}, ...); the first form, rho & 7, left every K fragment read two-way conflicted.
-#ifndef IIR_ATTN_KSWZ_OLD
 #define KSWZ(rho) (((rho) >> 1) & 7)
-#else
-#define KSWZ(rho) ((rho) & 7)
-#endif
 
 // One 64-key tile as TWO online-softmax steps of 32 keys (third form, round 2 late).  The 16 MFMAs of a tile used to sit in two
 // groups either side of the whole tile's vector work (row maximum over all 64 keys before the first exponential): a serial
@@ -679,6 +480,46 @@ __global__ __launch_bounds__(256, WPS) void attn_kernel2(const AGeo g) {
     }
 }
 
+// Geometry and launch shared by the two entry points (which check their arguments first).  Rows [0, attn_batch) attend; the
+// identity form copies V for the rest.  Three builds: short KV (<= 4 tiles in all: the text + IP cross-attention) has every
+// tile requested at entry, one wait, no ring (see attn_kernel2<.., PRE>); otherwise the two-buffer ring, built for 2 waves per
+// SIMD (no spills) when the attending grid cannot put more than two workgroups on a CU anyway, else for 3 (measured: T = 1024
+// x 40 pairs 24.8 vs 27.2 us; T = 8192 462 vs 453 us).  (Ring depths 3 and 4 were built and measured: no change on any of the
+// step's shapes, `profiles/r02_attn_ring_depth.log`.)
+template <bool IDENT>
+int launch_attn(const iir_attn_desc* a, int attn_batch, hipStream_t stream) {
+    AGeo g{};
+    g.Q = (const f16*)a->Q; g.ldq = a->ldq; g.qbs = a->q_batch_stride;
+    g.O = (f16*)a->O; g.ldo = a->ldo; g.obs = a->o_batch_stride; g.o_fp8 = a->o_fp8 != 0;
+    g.Tq = a->Tq; g.nseg = a->nseg;
+    g.c = a->scale * 1.4426950408889634f;
+    g.qpre = a->q_prescaled;
+    int total_tiles = 0;
+    for (int i = 0; i < a->nseg; ++i) {
+        const iir_attn_kv* s = &a->kv[i];
+        g.seg[i] = Seg{(const f16*)s->K, s->ldk, s->k_batch_stride, (const f16*)s->Vt, s->ldvt, s->vt_batch_stride, s->Tkv};
+        total_tiles += (s->Tkv + KT - 1) / KT;
+    }
+    g.qtiles = (a->Tq + 127) / 128;
+    g.heads = a->heads;
+    g.npairs = a->heads * attn_batch;
+    g.causal = a->causal;
+    const int n_attn = g.npairs * g.qtiles;
+    if (IDENT) { g.n_attn = n_attn; g.ident_from = attn_batch; }
+    const dim3 grid(n_attn + (a->batch - attn_batch) * a->heads * g.qtiles);
+    if (!g.causal && total_tiles <= 4) {
+        constexpr size_t lds = 4 * 2 * KT * 128;
+        static unsigned long long lds_set = 0;
+        if (!iir_ensure_dynamic_lds((const void*)attn_kernel2<2, 4, true, IDENT>, lds, lds_set)) return IIR_ELAUNCH;
+        iir_launch(attn_kernel2<2, 4, true, IDENT>, grid, dim3(256), lds, stream, g);
+    } else {
+        constexpr size_t lds = 2 * 2 * KT * 128;     // (32 KB: below the 64 KB that needs the function attribute)
+        if (n_attn <= 512) iir_launch(attn_kernel2<2, 2, false, IDENT>, grid, dim3(256), lds, stream, g);
+        else iir_launch(attn_kernel2<3, 2, false, IDENT>, grid, dim3(256), lds, stream, g);
+    }
+    return iir_launch_status();
+}
+
 }  // namespace
 
 extern "C" int iir_attention_d64_f16(const iir_attn_desc* a, void* stream) {
@@ -686,55 +527,11 @@ extern "C" int iir_attention_d64_f16(const iir_attn_desc* a, void* stream) {
     if (!a || !a->Q || !a->O || a->nseg < 1 || a->nseg > 2) return IIR_EINVAL;
     if (a->Tq <= 0 || a->heads <= 0 || a->batch <= 0) return IIR_EINVAL;
     if (a->ldq % 8 || a->ldo % 4) return IIR_EINVAL;
-    AGeo g{};
-    g.Q = (const f16*)a->Q; g.ldq = a->ldq; g.qbs = a->q_batch_stride;
-    g.O = (f16*)a->O; g.ldo = a->ldo; g.obs = a->o_batch_stride; g.o_fp8 = a->o_fp8 != 0;
-    g.Tq = a->Tq; g.nseg = a->nseg;
-    g.c = a->scale * 1.4426950408889634f;
-    g.qpre = a->q_prescaled;
     for (int i = 0; i < a->nseg; ++i) {
         const iir_attn_kv* s = &a->kv[i];
         if (!s->K || !s->Vt || s->Tkv <= 0 || s->ldk % 8 || s->ldvt % 8 || s->vt_batch_stride % 8) return IIR_EINVAL;
-        g.seg[i] = Seg{(const f16*)s->K, s->ldk, s->k_batch_stride, (const f16*)s->Vt, s->ldvt, s->vt_batch_stride, s->Tkv};
     }
-    g.qtiles = (a->Tq + 127) / 128;
-    g.npairs = a->heads * a->batch;
-    g.heads = a->heads;
-    g.causal = a->causal;
-    const dim3 grid(g.npairs * g.qtiles);
-    // IIR_ATTN_V (A/B switch): 1 = first-generation kernel, 2 = second generation built for 3 waves per SIMD, 3 = built for 2
-    // waves per SIMD (no spills); default 0 = second generation, the 2-wave build when the grid cannot put more than two
-    // workgroups on a CU anyway (measured: T = 1024 x 40 pairs 24.8 vs 27.2 us; T = 8192 462 vs 453 us).
-    static const int version = getenv("IIR_ATTN_V") ? atoi(getenv("IIR_ATTN_V")) : 0;
-    if (g.o_fp8 && version == 1) return IIR_EINVAL;          // the first-generation kernel has no fp8 store
-    // (ring depths 3 and 4 were built and measured: no change on any of the step's shapes, `profiles/r02_attn_ring_depth.log`;
-    //  only the two-buffer instantiations are compiled)
-    auto launch2 = [&](auto kern, int nb) {
-        const size_t lds = (size_t)nb * 2 * KT * 128;
-        // (32 KB of dynamic LDS: below the 64 KB that needs hipFuncAttributeMaxDynamicSharedMemorySize)
-        iir_launch(kern, grid, dim3(256), lds, (hipStream_t)stream, g);
-    };
-    int total_tiles = 0;
-    for (int i = 0; i < a->nseg; ++i) total_tiles += (a->kv[i].Tkv + KT - 1) / KT;
-    static const bool pre_on = !(getenv("IIR_ATTN_PRE") && atoi(getenv("IIR_ATTN_PRE")) == 0);
-    if (version != 1 && pre_on && !g.causal && total_tiles <= 4) {
-        // short KV (text + IP cross-attention): every tile requested at entry, one wait, no ring (see attn_kernel2<.., PRE>)
-        static int attr_dev = -1;
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (attr_dev != dev) {
-            if (hipFuncSetAttribute((const void*)attn_kernel2<2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * KT * 128) != hipSuccess) return IIR_ELAUNCH;
-            attr_dev = dev;
-        }
-        launch2(attn_kernel2<2, 4, true>, 4);
-        return iir_launch_status();
-    }
-    if (version == 1) {
-        if (g.qpre) g.c = 1.0f;
-        iir_launch(attn_kernel, grid, dim3(256), 0, (hipStream_t)stream, g);
-    } else if (version == 3 || (version == 0 && grid.x <= 512)) launch2(attn_kernel2<2, 2>, 2);
-    else launch2(attn_kernel2<3, 2>, 2);
-    return iir_launch_status();
+    return launch_attn<false>(a, a->batch, (hipStream_t)stream);
 }
 
 extern "C" int iir_attention_d64_ident_f16(const iir_attn_desc* a, int32_t ident_from, void* stream) {
@@ -745,36 +542,5 @@ extern "C" int iir_attention_d64_ident_f16(const iir_attn_desc* a, int32_t ident
     const iir_attn_kv* s = &a->kv[0];
     if (!s->K || !s->Vt || s->Tkv != a->Tq || s->ldk % 8 || s->ldvt % 8 || s->vt_batch_stride % 8) return IIR_EINVAL;
     (void)hipGetLastError();
-    AGeo g{};
-    g.Q = (const f16*)a->Q; g.ldq = a->ldq; g.qbs = a->q_batch_stride;
-    g.O = (f16*)a->O; g.ldo = a->ldo; g.obs = a->o_batch_stride;
-    g.Tq = a->Tq; g.nseg = 1;
-    g.c = a->scale * 1.4426950408889634f;
-    g.qpre = a->q_prescaled;
-    g.seg[0] = Seg{(const f16*)s->K, s->ldk, s->k_batch_stride, (const f16*)s->Vt, s->ldvt, s->vt_batch_stride, s->Tkv};
-    g.qtiles = (a->Tq + 127) / 128;
-    g.heads = a->heads;
-    g.npairs = a->heads * ident_from;
-    g.n_attn = g.npairs * g.qtiles;
-    g.ident_from = ident_from;
-    const dim3 grid(g.n_attn + (a->batch - ident_from) * a->heads * g.qtiles);
-    // the same instantiation choice as iir_attention_d64_f16 for the attending rows (IIR_ATTN_V = 1, the first-generation
-    // kernel, has no identity form: the default choice is used then)
-    static const int version = getenv("IIR_ATTN_V") ? atoi(getenv("IIR_ATTN_V")) : 0;
-    static const bool pre_on = !(getenv("IIR_ATTN_PRE") && atoi(getenv("IIR_ATTN_PRE")) == 0);
-    if (pre_on && (s->Tkv + KT - 1) / KT <= 4) {
-        static int attr_dev = -1;
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (attr_dev != dev) {
-            if (hipFuncSetAttribute((const void*)attn_kernel2<2, 4, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * KT * 128) != hipSuccess) return IIR_ELAUNCH;
-            attr_dev = dev;
-        }
-        iir_launch(attn_kernel2<2, 4, true, true>, grid, dim3(256), (size_t)4 * 2 * KT * 128, (hipStream_t)stream, g);
-    } else if (version == 3 || (version != 2 && g.n_attn <= 512)) {
-        iir_launch(attn_kernel2<2, 2, false, true>, grid, dim3(256), (size_t)2 * 2 * KT * 128, (hipStream_t)stream, g);
-    } else {
-        iir_launch(attn_kernel2<3, 2, false, true>, grid, dim3(256), (size_t)2 * 2 * KT * 128, (hipStream_t)stream, g);
-    }
-    return iir_launch_status();
+    return launch_attn<true>(a, ident_from, (hipStream_t)stream);
 }

@@ -65,15 +65,11 @@ __device__ __forceinline__ int iir_fp8x4(f16x4 v) {
 // asm before any read of a staged buffer -- so nothing relied on the compiler knowing about it.  M0 (the LDS destination base)
 // is written and restored inside the statement (cdna_hip_programming.md 5.7: M0 is compiler-reserved).
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-#ifdef IIR_GLDS_BUILTIN
-    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)gsrc, (LDS_AS void*)lds_wave_base, 16, 0, 0);
-#else
     // (the low 32 bits of a generic pointer into LDS are the LDS byte address: no address-space cast with its null check)
     const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_wave_base);
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-#endif
 }
 
 // x * sigmoid(x) with one v_exp and one v_rcp (1 ulp) instead of the IEEE division sequence: the GroupNorm + SiLU pass
@@ -120,6 +116,17 @@ static inline void iir_launch(K kernel, dim3 grid, dim3 block, size_t lds, hipSt
     } else {
         hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
     }
+}
+
+// Dynamic LDS above 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize ON THE DEVICE THE LAUNCH GOES TO.  `done` is the
+// caller's static for this kernel: one bit per device that already has the attribute.
+static inline bool iir_ensure_dynamic_lds(const void* kernel, size_t lds, unsigned long long& done) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+    if (done & (1ull << dev)) return true;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+    done |= 1ull << dev;
+    return true;
 }
 
 static inline int iir_launch_status() {

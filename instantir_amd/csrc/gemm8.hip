@@ -20,7 +20,6 @@
 #include "common.h"
 #include "gemm_geo.h"
 #include "../../include/instantir_hip.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -29,13 +28,9 @@ using iir::Geo;
 constexpr int BK = 64;
 constexpr int PF_TOUCHES = 2;
 
-// V (schedule variant, A/B switch IIR_G8V): 0 = activation pieces requested in one block at the start of the tile; 1 = one
-// piece per sub-phase (activations in sub-phases 0..3, weights behind them); 2 = as 1, and waves 4-7 (the second wave of every
-// SIMD) issue a sub-phase's piece AFTER its MFMAs instead of before them, so the two waves of a SIMD do not sit in the
-// (~70-125 cycle) LDS-DMA issue at the same moment with the matrix pipe idle behind them
 // F8: both operands fp8-E4M3 (gemm_conv.hip, same scheme: K counted in 2-byte units by the host, two fp8 MFMAs per 16-byte fragment pair,
 // wscale[n] * a_scale in the epilogue)
-template <int BN, int V, bool F8 = false>
+template <int BN, bool F8 = false>
 __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
     using E = f16;
     using E4 = f16x4;
@@ -142,30 +137,22 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
     if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(B_PIECES) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
 
-    auto stage_a1 = [&](int t, int buf, int q) {
-        glds16(a_base + q * a_pstride + t * 128 + a_voff, smem + buf * STAGE + (q * 8 + wave) * 1024);
-    };
-    const bool late = V == 2 && wave >= 4;
     int cur = 0;
     for (int t = 0; t < nk; ++t) {
         const char* st = smem + cur * STAGE;
         read_b(st);
         read_a(st, 0, a0);
         const bool more_a = t + 1 < nk, more_b = t + 2 < nk;
-        if (V == 0 && more_a) stage_a(t + 1, cur ^ 1);      // the other stage's activation half: last read in tile t-1
-        // piece of sub-phase i (V >= 1): activation pieces first (all of them are issued before the first weight piece, which
-        // is what the counted vmcnt at X relies on), the weight pieces only after Y (i >= 1)
-        auto piece = [&](int i) {
-            if (V == 0) { if (i >= 1 && i <= B_PIECES && more_b) stage_b1(t + 2, cur, i - 1); return; }
-            if (i < A_PIECES) { if (more_a) stage_a1(t + 1, cur ^ 1, i); }
-            if (i >= MI - B_PIECES && more_b) stage_b1(t + 2, cur, i - (MI - B_PIECES));
-        };
+        if (more_a) stage_a(t + 1, cur ^ 1);      // the other stage's activation half: last read in tile t-1
+        // tile t+2's weight pieces, one per sub-phase and only after Y.  (Kept as a lambda: with the same condition written inline in
+        // the loop hipcc allocates registers and orders the scalar set-up differently.)
+        auto piece = [&](int i) { if (i >= 1 && i <= B_PIECES && more_b) stage_b1(t + 2, cur, i - 1); };
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             E8(&ac)[2] = (i & 1) ? a1 : a0;
             E8(&an)[2] = (i & 1) ? a0 : a1;
             if (i + 1 < MI) read_a(st, i + 1, an);
-            if (!late) piece(i);
+            piece(i);
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int s = 0; s < 2; ++s)
@@ -182,7 +169,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
                 }
             __builtin_amdgcn_s_setprio(0);
             if (i == 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // Y(t): every wave holds its weight fragments
-            if (late) piece(i);
         }
         // X(t+1): tile t+1 landed (activations requested a tile ago, weights two tiles ago; the weights of tile t+2 may still
         // be in flight), and every wave is done with tile t's stage
@@ -297,8 +283,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the LDS-DMA touches must land before the LDS is released
 }
 
-template <int BN, int V, bool F8 = false>
-int launch8v(const Geo& g0, hipStream_t stream) {
+template <int BN, bool F8 = false>
+int launch8(const Geo& g0, hipStream_t stream) {
     constexpr int BM = 256;
     Geo g = g0;
     g.tiles_m = g.M / BM;
@@ -314,22 +300,10 @@ int launch8v(const Geo& g0, hipStream_t stream) {
         if (best < 0. || cost < best) { best = cost; g.xm = xm; g.rm = rm; g.rn = rn; }
     }
     const size_t lds = 2 * (BM * 128 + BN * 128) + 2048 + BM * 8;
-    static int attr_dev = -1;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (attr_dev != dev) {
-        if (hipFuncSetAttribute((const void*)gemm8_kernel<BN, V, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return IIR_ELAUNCH;
-        attr_dev = dev;
-    }
-    iir_launch(gemm8_kernel<BN, V, F8>, dim3(8 * g.rm * g.rn), dim3(512), lds, stream, g);
+    static unsigned long long lds_set = 0;
+    if (!iir_ensure_dynamic_lds((const void*)gemm8_kernel<BN, F8>, lds, lds_set)) return IIR_ELAUNCH;
+    iir_launch(gemm8_kernel<BN, F8>, dim3(8 * g.rm * g.rn), dim3(512), lds, stream, g);
     return iir_launch_status();
-}
-
-template <int BN>
-int launch8(const Geo& g, hipStream_t stream) {
-    if (g.f8) return launch8v<BN, 0, true>(g, stream);
-    static const int v = getenv("IIR_G8V") ? atoi(getenv("IIR_G8V")) : 0;
-    return v == 2 ? launch8v<BN, 2>(g, stream) : v == 1 ? launch8v<BN, 1>(g, stream) : launch8v<BN, 0>(g, stream);
 }
 
 }  // namespace
@@ -354,6 +328,7 @@ bool gemm8_covers(const Geo& g, int bn) {
 
 int gemm8_launch(const Geo& g, int bn, hipStream_t stream) {
     if (!gemm8_covers(g, bn)) return IIR_EINVAL;
+    if (g.f8) return launch8<320, true>(g, stream);      // (gemm8_covers: the all-fp8 form exists at BN = 320 only)
     return bn == 320 ? launch8<320>(g, stream) : launch8<256>(g, stream);
 }
 

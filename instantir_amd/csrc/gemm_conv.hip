@@ -32,20 +32,8 @@ constexpr int BK = 64;   // halfs per K tile = one 128-byte LDS row
 // so that the LDS latency runs under the matrix instructions.  hipcc's scheduler sank the reads below the MFMAs and then waited
 // `lgkmcnt(0)` right behind them -- one exposed LDS round trip (~200 cycles with four waves reading and the LDS-DMA writing) per
 // half step, with one wave per SIMD nothing else to cover it.  A scheduling barrier after each read group keeps the source order.
-#ifndef IIR_NO_PIN
 #define IIR_PIN() __builtin_amdgcn_sched_barrier(0)
-#else
-#define IIR_PIN() ((void)0)
-#endif
 constexpr int PF_TOUCHES = 4;   // prefetch touches per lane per launch (x 128 B x threads = up to 128-256 KiB per workgroup)
-#define IIR_DEFAULT_STAGES 2
-#ifndef IIR_T1_MIN
-#define IIR_T1_MIN 384
-#endif
-#ifndef IIR_T2_MIN
-#define IIR_T2_MIN 256
-#endif
-
 
 // Chan's pairwise update of (count, mean, M2) -- the same form norm.hip uses for GroupNorm
 __device__ __forceinline__ void ln_merge(float& n, float& mean, float& m2, float nb, float mb, float m2b) {
@@ -72,20 +60,12 @@ constexpr bool gn_out_fits(int bm, int bn, int st, int nt, bool lw, bool w8 = fa
 // One asm statement with a memory clobber: no LDS access may be scheduled across it.
 template <int N>
 __device__ __forceinline__ void wait_vm_lgkm_and_barrier() {
-#ifdef IIR_DBG_NO_BARRIER
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-#else
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-#endif
 }
 
 template <int N>
 __device__ __forceinline__ void wait_vm_and_barrier() {
-#ifdef IIR_DBG_NO_BARRIER      // (timing experiment of DESIGN.md 5.10, results wrong: the K loop's barrier removed)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-#else
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-#endif
 }
 
 // W8 (BASELINE configs[4]: "fp8 MFMA weights"): the weight operand is fp8-E4M3 with one fp32 scale per output channel.  Its
@@ -114,6 +94,7 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     static_assert(!(F8 && (W8 || CONV)), "the all-fp8 build covers the linear layers; W8 is the fp16-activation form");
     static_assert(!(W8 && CONV), "the fp8-weight build covers the linear layers only");
     static_assert(!(LW && W8), "loader waves: fp16 / bf16 operands only");
+    static_assert(ST >= 2 && ST <= 4, "ring depths the counted waits below cover");
     using E4 = typename ET<E>::x4;
     using E8 = typename ET<E>::x8;     // (pointers stay f16-typed: both element types are 2 bytes; only conversions differ)
     constexpr int NW = WAVES_M * 2;                 // compute waves, laid out WAVES_M x 2 over the tile (= staging waves)
@@ -122,6 +103,7 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     constexpr int MI = WM / 16, NI = WN / 16;    // 16x16 MFMA tiles per wave
     constexpr int B_GROUPS = W8 ? BN / 16 : BN / 8;                   // LDS-DMA instructions that cover the weight tile
     constexpr int A_INST = BM / 8 / NW, B_INST = (B_GROUPS + NW - 1) / NW;   // glds instructions per wave per K tile
+    static_assert(W8 || B_GROUPS % NW == 0, "fp16 weight tile: every wave issues the same number of row groups");
     constexpr int B_STAGE_BYTES = W8 ? BN * 64 : BN * 128;
     constexpr int RING_BYTES = ST * (BM * 128 + B_STAGE_BYTES);
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -230,30 +212,17 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
         for (int i = 0; i < (CONV ? A_INST : 0); ++i) cv_ptr[i] += cv_inc[i] ? cv_c0 : 0;
     };
 
-    // (timing experiments of DESIGN.md 5.10, results wrong: -DIIR_DBG_THIN_A / _B stage 4 bytes per lane instead of 16 for the
-    // activation / weight pieces after the first tile -- same instruction count and waits, a quarter of the bytes)
-#ifdef IIR_DBG_THIN_A
-#define GLDS_A(src, dst) do { if (kt > kt0_dbg) __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(src), (LDS_AS void*)(dst), 4, 0, 0); else glds16(src, dst); } while (0)
-#else
-#define GLDS_A(src, dst) glds16(src, dst)
-#endif
-#ifdef IIR_DBG_THIN_B
-#define GLDS_B(src, dst) do { if (kt > kt0_dbg) __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(src), (LDS_AS void*)(dst), 4, 0, 0); else glds16(src, dst); } while (0)
-#else
-#define GLDS_B(src, dst) glds16(src, dst)
-#endif
-    const int kt0_dbg = 2;
     auto stage = [&](int kt, int buf) {
         f16* as = As + buf * BM * BK;
         f16* bs = Bs + buf * BN * BK;
         const int k0 = kt * BK;
         if (!CONV) {
 #pragma unroll
-            for (int i = 0; i < A_INST; ++i) GLDS_A(a_src[i] + k0, as + (i * NW + wave) * 8 * BK);
+            for (int i = 0; i < A_INST; ++i) glds16(a_src[i] + k0, as + (i * NW + wave) * 8 * BK);
         } else {
 #pragma unroll
             for (int i = 0; i < A_INST; ++i) {
-                GLDS_A(cv_ptr[i], as + (i * NW + wave) * 8 * BK);
+                glds16(cv_ptr[i], as + (i * NW + wave) * 8 * BK);
                 cv_ptr[i] += cv_inc[i];
             }
             cv_c0 += BK;
@@ -264,11 +233,7 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
         }
         if (!W8) {
 #pragma unroll
-            for (int i = 0; i < B_INST; ++i) {
-                if (B_GROUPS % NW == 0 || i * NW + wave < B_GROUPS) GLDS_B(b_src[i] + k0, bs + (i * NW + wave) * 8 * BK);
-                else     // (8-wave builds of the 160-wide tiles: 20 row groups over 8 waves) one 4-byte touch keeps the counted waits uniform
-                    __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)g.W, (LDS_AS void*)(smem + RING_BYTES + wave * 256), 4, 0, 0);
-            }
+            for (int i = 0; i < B_INST; ++i) glds16(b_src[i] + k0, bs + (i * NW + wave) * 8 * BK);
         } else {
             char* bs8 = (char*)Bs + buf * B_STAGE_BYTES;
 #pragma unroll
@@ -350,23 +315,12 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     auto frags = [&](int buf, int s, E8 (&af)[MI], BF (&bf)[NI]) {
         const char* as = (const char*)(As + buf * BM * BK);
         const char* bs = (const char*)Bs + buf * B_STAGE_BYTES;
-#ifdef IIR_DBG_THIN_READS      // (timing experiment of DESIGN.md 5.10, results wrong: two fragment reads per half step instead of MI + NI)
-        af[0] = *(const E8*)(as + a_off[s]);
-        bf[0] = *(const BF*)(bs + b_off[s]);
-        for (int i = 1; i < MI; ++i) af[i] = af[0];
-        for (int j = 1; j < NI; ++j) bf[j] = bf[0];
-        return;
-#endif
 #pragma unroll
         for (int i = 0; i < MI; ++i) af[i] = *(const E8*)(as + a_off[s] + i * 16 * 128);
 #pragma unroll
         for (int j = 0; j < NI; ++j) bf[j] = *(const BF*)(bs + b_off[s] + j * 16 * (W8 ? 64 : 128));
     };
     auto mma = [&](const E8 (&af)[MI], const BF (&bf)[NI]) {
-#ifdef IIR_DBG_NO_MFMA       // (trigger bisection of DESIGN.md 5.8: same loads, barriers and LDS reads, no matrix instructions; results are wrong)
-        for (int i = 0; i < MI; ++i) for (int j = 0; j < NI; ++j) asm volatile("" :: "v"(af[i]), "v"(bf[j]));
-        return;
-#endif
         if constexpr (F8) {
             typedef long l2 __attribute__((ext_vector_type(2)));
 #pragma unroll
@@ -405,8 +359,7 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
         }
     };
     auto admit = [&](int tiles_after) {     // wait until only `tiles_after` later tiles are still in flight, all LDS reads done, barrier
-        if (ST >= 5 && tiles_after >= 3) wait_vm_lgkm_and_barrier<(ST >= 5 ? 3 * LOADS : 0)>();
-        else if (ST >= 4 && tiles_after >= 2) wait_vm_lgkm_and_barrier<(ST >= 4 ? 2 * LOADS : 0)>();
+        if (ST >= 4 && tiles_after >= 2) wait_vm_lgkm_and_barrier<(ST >= 4 ? 2 * LOADS : 0)>();
         else if (ST >= 3 && tiles_after >= 1) wait_vm_lgkm_and_barrier<(ST >= 3 ? LOADS : 0)>();
         else wait_vm_lgkm_and_barrier<0>();
     };
@@ -433,8 +386,7 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     // the loop head the same reads get counted waits (`lgkmcnt(7)`): the prefetched group stays in flight under the MFMAs.
     auto admit2 = [&](int tiles_after) {
         __builtin_amdgcn_s_waitcnt(0xC07F);                     // lgkmcnt(0): every fragment read of the finished tile has returned
-        if (ST >= 5 && tiles_after >= 3) wait_vm_and_barrier<(ST >= 5 ? 3 * LOADS : 0)>();
-        else if (ST >= 4 && tiles_after >= 2) wait_vm_and_barrier<(ST >= 4 ? 2 * LOADS : 0)>();
+        if (ST >= 4 && tiles_after >= 2) wait_vm_and_barrier<(ST >= 4 ? 2 * LOADS : 0)>();
         else if (ST >= 3 && tiles_after >= 1) wait_vm_and_barrier<(ST >= 3 ? LOADS : 0)>();
         else wait_vm_and_barrier<0>();
     };
@@ -522,7 +474,6 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
         char* vl = smem + 2 * KIMG;
         const int tk0 = g.xa_tk[0], tk1 = g.xa_tk[1];
         const int vch0 = (tk0 + 7) >> 3, vch1 = (tk1 + 7) >> 3;               // readable 16-byte chunks of a V^T row
-#ifndef IIR_DBG_XA_NOSTAGE      // (timing experiments, results wrong: -DIIR_DBG_XA_NOSTAGE / _NOCOMPUTE / _NOSOFTMAX price the parts of this tail)
 #pragma unroll
         for (int it = 0; it < 9; ++it) {          // K rows: [0, 80) text keys, [80, 144) IP keys; rows past Tkv repeat the last key (masked below)
             const int s = (it * 4 + wave) * 64 + lane, hh = s >= 1152 ? 1 : 0, sl = s - hh * 1152;
@@ -544,7 +495,6 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
                                  : g.xa_vt[0] + rowv * g.xa_ldvt[0] + (long)img * g.xa_vb[0]) + cc * 8;
             glds16(src, vl + (it * 4 + wave) * 1024);
         }
-#endif
         // q = what the plain epilogue would have stored (LayerNorm fold, bias, fp16 rounding), as MFMA operands
         typedef E E4v __attribute__((ext_vector_type(4)));
         E8 qf[MI][2];
@@ -558,7 +508,6 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
                     qf[i][j >> 1][(j & 1) * 4 + t] = (E)fmaf(acc[i][j][t], rs.x, fmaf(rs.y, pre_c1[j][t], (float)pre_c0[j][t]));
         }
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");         // K / V images complete (waiting for K alone here and for V^T before P V measured no better)
-#ifndef IIR_DBG_XA_NOCOMPUTE
         // S = q K^T: 9 key blocks of 16 (5 text, 4 IP), contraction over d in the accumulator's order
         f32x4 sa[MI][9];
         const char* kh = kl + wn * KIMG;
@@ -582,9 +531,6 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
         }
         // softmax per segment (q carries scale x log2 e: p = exp2(s - max)), normalised, as the P operand of P V
         E8 pf[MI][5];
-#ifdef IIR_DBG_XA_NOSOFTMAX
-        for (int i = 0; i < MI; ++i) for (int kp = 0; kp < 5; ++kp) for (int t = 0; t < 4; ++t) { pf[i][kp][t] = (E)sa[i][2 * kp][t]; pf[i][kp][4 + t] = (E)sa[i][kp < 4 ? 2 * kp + 1 : 8][t]; }
-#else
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             float mx[2] = {-INFINITY, -INFINITY};
@@ -626,7 +572,6 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
                     pf[i][kp][4 + t] = kb2 < 9 ? (E)(sa[i][kb2 < 9 ? kb2 : 8][t] * sm[kb2 < 5 ? 0 : 1]) : (E)0.f;
                 }
         }
-#endif
         // O = P V: contraction over keys in the order P holds them (key column 16 kb + 4 fq + t: IP keys start at column 80)
         const char* vh = vl + wn * VIMG;
 #pragma unroll
@@ -644,7 +589,6 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
                 for (int i = 0; i < MI; ++i) acc[i][j] = ET<E>::mfma16(vf, pf[i][kp], acc[i][j]);
             }
         }
-#endif
 #pragma unroll
         for (int j = 0; j < NI; ++j) {            // the tile now holds finished values: phase 1 adds nothing
             pre_c1[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -800,9 +744,6 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     // for the launches that follow (see iir_gemm_desc.prefetch: 4-byte LDS-DMA touches, clamped into the range; no VGPR
     // destination, the data lands in a scratch KiB behind the ring and is never read), then the stores.
     auto touch_next_weights = [&]() {
-#ifdef IIR_DBG_NO_TOUCH      // (trigger bisection of DESIGN.md 5.8: build without the prefetch touches)
-        return;
-#endif
         const int per = (g.pf_lines + (int)gridDim.x - 1) / (int)gridDim.x;
         const long l0 = (long)blockIdx.x * per, last = g.pf_lines - 1;
         char* scratch = smem + RING_BYTES + wave_all * 256;
@@ -1009,27 +950,29 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the LDS-DMA touches must land before the LDS is released
 }
 
-template <typename E, int BM, int BN, int ST, int WAVES_M = 2, bool W8 = false, bool LW = false, bool F8 = false>
-int launch_t(const Geo& g0, bool conv, hipStream_t stream) {
+// One kernel instantiation: tile grid, the launch-time refusals of the statistics / fp8 outputs, XCD partition, launch.
+template <typename E, int BM, int BN, int ST, bool CONV, int WAVES_M = 2, bool W8 = false, bool LW = false, bool F8 = false>
+int launch_k(const Geo& g0, hipStream_t stream) {
+    constexpr int NT = 128 * WAVES_M * (LW ? 2 : 1);
+    constexpr int RING_BYTES = ST * (BM * 128 + (W8 ? BN * 64 : BN * 128));
+    constexpr size_t lds = RING_BYTES + 256 * WAVES_M * 2 * (LW ? 2 : 1) + BM * 8;   // ring (reused as the output tile) + prefetch scratch (256 B per wave) + LayerNorm row statistics
     Geo g = g0;
     g.tiles_m = (g.M + BM - 1) / BM;
     g.tiles_n = (g.N + BN - 1) / BN;
-    static const size_t dbg_pad = getenv("IIR_DBG_LDS_PAD") ? (size_t)atoi(getenv("IIR_DBG_LDS_PAD")) : 0;     // (5.8 bisection: force one workgroup per CU)
-    const size_t lds = ST * (BM * 128 + (W8 ? BN * 64 : BN * 128)) + 256 * WAVES_M * 2 * (LW ? 2 : 1) + BM * 8 + dbg_pad;   // ring (reused as the output tile) + prefetch scratch (256 B per wave) + LayerNorm row statistics
     if (g.c_fp8) {          // fp8 output: stored by the straight-line write-out only (whole tiles, 8-byte addressable rows)
-        if (conv || g.M % BM || g.N % BN || g.ldc % 8 || (uintptr_t)g.C % 8 || g.Ct || g.c_f32 || g.ln_out || g.gn_out || g.res_img_rows || g.y_img_rows ||
+        if (CONV || g.M % BM || g.N % BN || g.ldc % 8 || (uintptr_t)g.C % 8 || g.Ct || g.c_f32 || g.ln_out || g.gn_out || g.res_img_rows || g.y_img_rows ||
             (g.res && !g.r_vec) || g.dtype != IIR_DT_F16) return IIR_EINVAL;
         g.c_vec = 1; g.st_wt = 0;
     }
     if (g.gn_out) {         // producer of GroupNorm partials: whole tiles, 16-byte rows, plain epilogue, rows of an image tile-aligned (caller)
-        constexpr bool fits = gn_out_fits(BM, BN, ST, 128 * WAVES_M * (LW ? 2 : 1), LW, W8);
+        constexpr bool fits = gn_out_fits(BM, BN, ST, NT, LW, W8);
         if (!fits || g.epi != IIR_EPI_PLAIN || g.c_f32 || g.Ct || g.splitk == 2 || g.ln_out || g.M % BM || g.N % BN || !g.c_vec || (g.res && !g.r_vec) ||
-            (conv && (g.y_img_rows | g.res_img_rows)))
+            (CONV && (g.y_img_rows | g.res_img_rows)))
             return IIR_EINVAL;
     }
     if (g.ln_out) {         // producer of LayerNorm partials: whole tiles, 16-byte rows, plain epilogue (see the kernel's fast write-out path)
-        constexpr bool fits = (BM * (2 * BN + 32) + 15) / 16 * 16 + BM * (BN / 8) * 8 <= ST * (BM * 128 + (W8 ? BN * 64 : BN * 128));
-        if (!fits || conv || g.epi != IIR_EPI_PLAIN || g.c_f32 || g.Ct || g.splitk == 2 || g.M % BM || g.N % BN || !g.c_vec || (g.res && !g.r_vec))
+        constexpr bool fits = (BM * (2 * BN + 32) + 15) / 16 * 16 + BM * (BN / 8) * 8 <= RING_BYTES;
+        if (!fits || CONV || g.epi != IIR_EPI_PLAIN || g.c_f32 || g.Ct || g.splitk == 2 || g.M % BM || g.N % BN || !g.c_vec || (g.res && !g.r_vec))
             return IIR_EINVAL;
     }
     // pick the XCD partition (xm x 8/xm rectangles of the tile grid) with the least bytes each 4 MiB L2 pulls over the
@@ -1037,10 +980,8 @@ int launch_t(const Geo& g0, bool conv, hipStream_t stream) {
     // re-used by successive groups of N-tile columns: if they fit the L2 they are read once, otherwise once per group.
     // (PMC: the 128x160 GEMM class read 137 MB per launch against 52 MB of operands; kbench 16384x5120x640: 615 -> 679 TFLOP/s)
     double best = -1.;
-    static const int force_xm = getenv("IIR_XM") ? atoi(getenv("IIR_XM")) : 0;   // tuning knob: 1,2,4,8 forces the split
     const double row_bytes = (double)g.K * 2.;
     for (int xm = 1; xm <= 8; xm *= 2) {
-        if (force_xm && xm != force_xm) continue;
         const int xn = 8 / xm;
         const int rm = (g.tiles_m + xm - 1) / xm, rn = (g.tiles_n + xn - 1) / xn;
         const double a_bytes = (double)rm * BM * row_bytes, w_bytes = (double)rn * BN * row_bytes;
@@ -1050,84 +991,46 @@ int launch_t(const Geo& g0, bool conv, hipStream_t stream) {
         cost += ((double)rm * rn * 8 - (double)g.tiles_m * g.tiles_n) * 8. * BK * (BM + BN);     // padding workgroups of ragged rectangles
         if (best < 0. || cost < best) { best = cost; g.xm = xm; g.rm = rm; g.rn = rn; }
     }
-    const dim3 grid(8 * g.rm * g.rn * (g.splitk == 2 ? 2 : 1)), block(128 * WAVES_M * (LW ? 2 : 1));
-    // dynamic LDS above 64 KB needs the function attribute ON THE DEVICE THE LAUNCH GOES TO: tracked per device and kernel
-    // instantiation (a function-local static used to run it once, for whichever device was current at the first launch)
-    auto ensure_lds = [&](const void* fn) -> bool {
-        static unsigned long long done[64] = {};           // one bit per device, per instantiation of this launcher x {gemm, conv}
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-        const int slot = conv ? 1 : 0;
-        if (done[dev] & (1ull << slot)) return true;
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-        done[dev] |= 1ull << slot;
-        return true;
-    };
-    if constexpr (F8) {
-        if (conv || g.splitk == 2) return IIR_EINVAL;
-        if (!ensure_lds((const void*)gemm_kernel<E, BM, BN, ST, false, WAVES_M, false, LW, true>)) return IIR_ELAUNCH;
-        iir_launch(gemm_kernel<E, BM, BN, ST, false, WAVES_M, false, LW, true>, grid, block, lds, stream, g);
-        return iir_launch_status();
-    } else if constexpr (W8) {
-        if (!ensure_lds((const void*)gemm_kernel<E, BM, BN, ST, false, WAVES_M, true>)) return IIR_ELAUNCH;
-        iir_launch(gemm_kernel<E, BM, BN, ST, false, WAVES_M, true>, grid, block, lds, stream, g);
-        return iir_launch_status();
-    } else if constexpr (LW) {
-        if (g.splitk == 2) return IIR_EINVAL;
-        if (conv) {
-            if (!ensure_lds((const void*)gemm_kernel<E, BM, BN, ST, true, WAVES_M, false, true>)) return IIR_ELAUNCH;
-            iir_launch(gemm_kernel<E, BM, BN, ST, true, WAVES_M, false, true>, grid, block, lds, stream, g);
-        } else {
-            if (!ensure_lds((const void*)gemm_kernel<E, BM, BN, ST, false, WAVES_M, false, true>)) return IIR_ELAUNCH;
-            iir_launch(gemm_kernel<E, BM, BN, ST, false, WAVES_M, false, true>, grid, block, lds, stream, g);
-        }
-        return iir_launch_status();
-    } else
-    if (conv) {
-        if (!ensure_lds((const void*)gemm_kernel<E, BM, BN, ST, true, WAVES_M>)) return IIR_ELAUNCH;
-        iir_launch(gemm_kernel<E, BM, BN, ST, true, WAVES_M>, grid, block, lds, stream, g);
-    } else {
-        if (!ensure_lds((const void*)gemm_kernel<E, BM, BN, ST, false, WAVES_M>)) return IIR_ELAUNCH;
-        iir_launch(gemm_kernel<E, BM, BN, ST, false, WAVES_M>, grid, block, lds, stream, g);
-    }
+    const dim3 grid(8 * g.rm * g.rn * (g.splitk == 2 ? 2 : 1)), block(NT);
+    const auto kern = gemm_kernel<E, BM, BN, ST, CONV, WAVES_M, W8, LW, F8>;
+    static unsigned long long lds_set = 0;
+    if (!iir_ensure_dynamic_lds((const void*)kern, lds, lds_set)) return IIR_ELAUNCH;
+    iir_launch(kern, grid, block, lds, stream, g);
     return iir_launch_status();
 }
 
-// fp16 build of every tile / ring depth; bf16 build (the VAE) of the two-stage tiles the chooser picks for it
-template <int BM, int BN, int ST, int WAVES_M = 2>
+// The kernels that are built, per tile x ring depth x waves (x loader waves); anything else is refused here.
+//   fp16        : GEMM and conv of every shape dispatch() names; with loader waves the conv only with the 3-deep ring
+//   bf16 (VAE)  : GEMM and conv of the 4-wave two-stage tiles the chooser picks for it
+//   fp8 weights (fp16 activations) and all-fp8: the linear layers on the 4-wave two-stage tiles and on 64x160x3; with loader
+//                 waves the all-fp8 form of 64x160x3 only
+// Split-K exists in the fp16 form without loader waves.
+template <int BM, int BN, int ST, int WAVES_M = 2, bool LW = false>
 int launch(const Geo& g, bool conv, hipStream_t stream) {
-    if (g.f8) {               // all-fp8 build: the 4-wave tiles the chooser picks for the transformer linears
-        if constexpr (WAVES_M == 2 && (ST == 2 || (ST == 3 && BM == 64 && BN == 160))) {
-            if (conv || g.dtype != IIR_DT_F16) return IIR_EINVAL;
-            return launch_t<f16, BM, BN, ST, WAVES_M, false, false, true>(g, false, stream);
-        } else return IIR_EINVAL;
-    }
-    if (g.wscale) {           // fp8-weight build: fp16 activations, linear layers, the 4-wave tiles
-        if constexpr (WAVES_M == 2 && (ST == 2 || (ST == 3 && BM == 64 && BN == 160))) {
-            if (conv || g.dtype != IIR_DT_F16 || g.splitk == 2) return IIR_EINVAL;
-            return launch_t<f16, BM, BN, ST, WAVES_M, true>(g, false, stream);
-        } else return IIR_EINVAL;
+    constexpr bool T5_3 = BM == 64 && BN == 160 && ST == 3 && WAVES_M == 2;
+    constexpr bool FP8_TILE = T5_3 || (ST == 2 && WAVES_M == 2 && !LW);
+    if (g.f8 || g.wscale) {
+        if (conv || g.dtype != IIR_DT_F16 || g.splitk == 2) return IIR_EINVAL;
+        if constexpr (FP8_TILE) {
+            if (g.f8) return launch_k<f16, BM, BN, ST, false, WAVES_M, false, LW, true>(g, stream);
+            if constexpr (!LW) return launch_k<f16, BM, BN, ST, false, WAVES_M, true>(g, stream);
+        }
+        return IIR_EINVAL;
     }
     if (g.dtype == IIR_DT_BF16) {
-        if constexpr (ST == 2 && WAVES_M == 2) return launch_t<bf16, BM, BN, ST, WAVES_M>(g, conv, stream);
-        else return IIR_EINVAL;
+        if constexpr (ST == 2 && WAVES_M == 2 && !LW)
+            return conv ? launch_k<bf16, BM, BN, ST, true>(g, stream) : launch_k<bf16, BM, BN, ST, false>(g, stream);
+        return IIR_EINVAL;
     }
-    return launch_t<f16, BM, BN, ST, WAVES_M>(g, conv, stream);
-}
-
-template <int BM, int BN, int ST>
-int lw_launch(const Geo& g, bool conv, hipStream_t stream) {
-    if (g.f8) {
-        if constexpr (ST == 3 && BM == 64 && BN == 160) { if (conv) return IIR_EINVAL; return launch_t<f16, BM, BN, ST, 2, false, true, true>(g, false, stream); }
-        else return IIR_EINVAL;
-    }
-    if (g.wscale || g.dtype != IIR_DT_F16 || g.splitk == 2) return IIR_EINVAL;
-    if constexpr (ST == 3) return launch_t<f16, BM, BN, ST, 2, false, true>(g, conv, stream);
-    else { if (conv) return IIR_EINVAL; return launch_t<f16, BM, BN, ST, 2, false, true>(g, false, stream); }
+    if (LW && g.splitk == 2) return IIR_EINVAL;
+    if (!conv) return launch_k<f16, BM, BN, ST, false, WAVES_M, false, LW>(g, stream);
+    if constexpr (!LW || ST == 3) return launch_k<f16, BM, BN, ST, true, WAVES_M, false, LW>(g, stream);
+    return IIR_EINVAL;
 }
 
 struct TileShape { int bm, bn; };
-constexpr TileShape kTiles[] = {{0, 0}, {128, 128}, {128, 64}, {64, 64}, {128, 160}, {64, 160}, {256, 128}, {128, 320}, {256, 256}, {32, 160}};
+constexpr TileShape kTiles[] = {{0, 0}, {128, 128}, {128, 64}, {64, 64}, {128, 160}, {64, 160}, {256, 128}};
+constexpr int N_TILES = sizeof(kTiles) / sizeof(kTiles[0]) - 1;       // base shapes 1..6
 
 // Tile choice: the per-CU operand fill rate (L2 -> LDS, ~50-70 GB/s) bounds these launches, so pick the
 // shape that minimises the bytes the busiest CU has to pull.  Two workgroups per CU overlap each other's
@@ -1137,13 +1040,11 @@ constexpr TileShape kTiles[] = {{0, 0}, {128, 128}, {128, 64}, {64, 64}, {128, 1
 // Cold-weight sweep (tools/tilebench.py, us): 2048x1280x1280  128x64/2 21.9 | 64x160/3 16.7 | /4 16.3;  2048x1280x5120
 // 128x64/2 67.0 | 64x160/3 47.3 | /4 46.1.  In the loop: K >= 2560 only 72.8 ms/step, K >= 1280 71.8 (3 stages), 72.7
 // (4 stages) -- same call.  (With the first-generation epilogue the K = 1280 extension had measured as a loss.)
-// IIR_T5_MINK / IIR_T5_STAGES override for experiments.
-int one_per_cu_min_k() { static const int v = [] { const char* e = getenv("IIR_T5_MINK"); return e ? atoi(e) : 1280; }(); return v; }
-int one_per_cu_stages() { static const int v = [] { const char* e = getenv("IIR_T5_STAGES"); return e ? atoi(e) : 3; }(); return v; }
+constexpr int ONE_PER_CU_MIN_K = 1280;
 
 int pick_tile(int M, int N, bool paired, int K = 0) {
     // problems that fit one 64x160 workgroup per CU: that tile with a deep ring (see dispatch())
-    if (K >= one_per_cu_min_k() && (long)((M + 63) / 64) * ((N + 159) / 160) <= 256) return 5;
+    if (K >= ONE_PER_CU_MIN_K && (long)((M + 63) / 64) * ((N + 159) / 160) <= 256) return 5;
     long best = -1;
     int pick = 1;
     for (int t = 1; t <= 5; ++t) {
@@ -1163,18 +1064,20 @@ struct Resolved { int id, bm, bn, st, nt; bool lw; };
 
 // The one tile resolver.  Every question about what a launch will run -- dispatch() itself, iir_gemm_resolve_tile,
 // iir_gemm_gn_supported, iir_gemm_ln_parts, iir_gemm_fp8_out_supported -- is answered here, so a pre-check taken while a step is
-// planned and the launch it guards cannot disagree.  `tile`: 0 = automatic, 1..9 = a forced base shape (its ring depth and
-// loader waves still chosen here).  K counts 2-byte units of the operand row (all-fp8: the K of the fp8 bytes).  The cross-attention
-// epilogue, split-K and the 8-wave kernel of gemm8.hip are decided ahead of this by dispatch().
+// planned and the launch it guards cannot disagree.  `tile`: 0 = automatic, 1..6 = a forced base shape (its ring depth and
+// loader waves still chosen here); anything else resolves to id -1, which dispatch() refuses.  K counts 2-byte units of the
+// operand row (all-fp8: the K of the fp8 bytes).  The cross-attention epilogue, split-K and the 8-wave kernel of gemm8.hip are
+// decided ahead of this by dispatch().
 Resolved resolve_tile(int M, int N, int K, bool conv, int dtype, bool wscale, bool f8, int tile) {
     const bool f16 = dtype == IIR_DT_F16;
+    if (tile < 0 || tile > N_TILES) return {-1, 0, 0, 0, 0, false};
     if (tile == 0) {
-        // (round 4) problems of 257-512 64x160 tiles (M x N = 4096 x 1280, 8192 x 640) with a long K: one 128x160 loader-wave
+        // problems of 257-512 64x160 tiles (M x N = 4096 x 1280, 8192 x 640) with a long K: one 128x160 loader-wave
         // workgroup per CU (id 54) instead of two 64x160 ones (id 25).  Per CU and K tile that is 288 128-byte line requests
         // against 448 for the same outputs, and these launches are paced by line requests.  fp16 activations
-        // and weights only.  IIR_T4_LW=0 restores the round-3 choice (A/B switch).
+        // and weights only.  IIR_T4_LW=0 restores the two-per-CU choice: the bit-identity reference of the tests of id 54.
         static const bool t4_lw = !(getenv("IIR_T4_LW") && atoi(getenv("IIR_T4_LW")) == 0);
-        if (t4_lw && f16 && !wscale && !f8 && K >= one_per_cu_min_k() && M % 128 == 0 && N % 160 == 0 &&
+        if (t4_lw && f16 && !wscale && !f8 && K >= ONE_PER_CU_MIN_K && M % 128 == 0 && N % 160 == 0 &&
             (long)(M / 128) * (N / 160) <= 256 && (long)(M / 64) * (N / 160) > 256 && pick_tile(M, N, false, K) == 5)
             return {54, 128, 160, 3, 512, true};
         tile = pick_tile(M, N, false, K);
@@ -1183,17 +1086,13 @@ Resolved resolve_tile(int M, int N, int K, bool conv, int dtype, bool wscale, bo
     // ring depth: with at most one workgroup per CU nothing else hides the tile latency, and a long K loop
     // amortises the deeper prologue -> 3 stages for the 64x160 tile (measured +17..40 % on K >= 2560, M*N = 2048x1280)
     const long blocks = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-    const bool one_per_cu = tile == 5 && blocks <= 256 && K >= one_per_cu_min_k() && f16;
-    const int stages = one_per_cu ? one_per_cu_stages() : IIR_DEFAULT_STAGES;
-    // one workgroup per CU and a plain GEMM: the loader-wave build (kbench, warm: 2048x1280x1280 456 -> 535 TFLOP/s,
-    // K = 5120 645 -> 707; the per-tile slope stays at the ~70 GB/s per-CU L2 -> LDS fill rate, the fixed part drops)
-    static const bool lw_on = !(getenv("IIR_T5_LW") && atoi(getenv("IIR_T5_LW")) == 0);
-    static const bool lw_conv = !(getenv("IIR_T5_LWCONV") && atoi(getenv("IIR_T5_LWCONV")) == 0);
-    static const bool lw2 = getenv("IIR_T5_LW2") && atoi(getenv("IIR_T5_LW2")) == 1;     // experiment: 2-stage loader-wave build (58 KB of LDS: two kernels can share a CU)
-    if (one_per_cu && lw2 && !conv && !wscale) return {75, bm, bn, 2, 512, true};
-    if (one_per_cu && lw_on && (!conv || (lw_conv && stages == 3)) && (!wscale || (f8 && stages == 3)) && stages >= 3 && stages <= 5)
-        return {stages == 3 ? 55 : stages == 4 ? 65 : 85, bm, bn, stages, 512, true};
-    return {tile + 10 * stages, bm, bn, stages, tile >= 6 && tile <= 8 ? 512 : 256, false};     // (6, 7, 8: the 8-wave builds)
+    const bool one_per_cu = tile == 5 && blocks <= 256 && K >= ONE_PER_CU_MIN_K && f16;
+    // one workgroup per CU: the loader-wave build, for GEMM and conv (kbench, warm: 2048x1280x1280 456 -> 535 TFLOP/s,
+    // K = 5120 645 -> 707; the per-tile slope stays at the ~70 GB/s per-CU L2 -> LDS fill rate, the fixed part drops).
+    // With fp8 weights it exists in the all-fp8 form only.
+    if (one_per_cu && (!wscale || f8)) return {55, bm, bn, 3, 512, true};
+    const int stages = one_per_cu ? 3 : 2;
+    return {tile + 10 * stages, bm, bn, stages, tile == 6 ? 512 : 256, false};     // (6: the 8-wave build)
 }
 
 constexpr long SK_CNT_BYTES = 4096;     // 1024 per-tile arrival counters ahead of the slabs
@@ -1204,12 +1103,11 @@ long splitk_ws_bytes(int M, int N) {
 
 bool uses_splitk(int M, int N, int K, long ws_bytes) {
     const long need = splitk_ws_bytes(M, N);
-    return K >= one_per_cu_min_k() && (K / BK) % 2 == 0 && need > 0 && ws_bytes >= need;
+    return K >= ONE_PER_CU_MIN_K && (K / BK) % 2 == 0 && need > 0 && ws_bytes >= need;
 }
 
 bool gemm8_auto(const Geo& g, bool conv) {
-    static const bool g8_on = !(getenv("IIR_G8") && atoi(getenv("IIR_G8")) == 0);
-    return g8_on && !conv && (g.f8 ? 2 * g.K : g.K) >= 640 && (long)(g.M / 256) * (g.N / 320) >= 256 && iir::gemm8_covers(g, 320);
+    return !conv && (g.f8 ? 2 * g.K : g.K) >= 640 && (long)(g.M / 256) * (g.N / 320) >= 256 && iir::gemm8_covers(g, 320);
 }
 
 int dispatch(const Geo& g, bool conv, int tile, hipStream_t stream) {
@@ -1225,9 +1123,9 @@ int dispatch(const Geo& g, bool conv, int tile, hipStream_t stream) {
         g2.splitk = 2;
         return launch<128, 160, 3>(g2, conv, stream);
     }
-    // tile: 0 = auto; t in {1: 128x128, 2: 128x64, 3: 64x64, 4: 128x160, 5: 64x160}; t + 10*stages selects the ring depth.
+    // tile: 0 = auto; t in {1: 128x128, 2: 128x64, 3: 64x64, 4: 128x160, 5: 64x160, 6: 256x128}; t + 10*stages selects the ring depth.
     // large-N linears whose 256 x 320 tiles fill the chip (the GEGLU projections): the 8-wave two-tile-deep kernel of
-    // gemm8.hip (142 FLOP per staged byte against 71 for two 128x160 workgroups per CU).  IIR_G8=0 switches it off (A/B).
+    // gemm8.hip (142 FLOP per staged byte against 71 for two 128x160 workgroups per CU).
     if (tile == 0 && gemm8_auto(g, conv)) return iir::gemm8_launch(g, 320, stream);
     if (tile == 91 || tile == 92) return conv ? IIR_EINVAL : iir::gemm8_launch(g, tile == 91 ? 320 : 256, stream);
     if (tile < 10) tile = resolve_tile(g.M, g.N, g.f8 ? 2 * g.K : g.K, conv, g.dtype, g.wscale != nullptr, g.f8 != 0, tile).id;     // (all-fp8: g.K counts 2-byte units)
@@ -1235,42 +1133,27 @@ int dispatch(const Geo& g, bool conv, int tile, hipStream_t stream) {
         case 21: return launch<128, 128, 2>(g, conv, stream);
         case 31: return launch<128, 128, 3>(g, conv, stream);
         case 22: return launch<128, 64, 2>(g, conv, stream);
-        case 32: return launch<128, 64, 3>(g, conv, stream);
         case 23: return launch<64, 64, 2>(g, conv, stream);
-        case 33: return launch<64, 64, 3>(g, conv, stream);
         case 24: return launch<128, 160, 2>(g, conv, stream);
+        case 34: return launch<128, 160, 3>(g, conv, stream);
         case 25: return launch<64, 160, 2>(g, conv, stream);
         case 35: return launch<64, 160, 3>(g, conv, stream);
-        case 45: return launch<64, 160, 4>(g, conv, stream);
-        case 54: return lw_launch<128, 160, 3>(g, conv, stream);    // 4 compute + 4 loader waves, one workgroup per CU (fp16)
-        case 55: return lw_launch<64, 160, 3>(g, conv, stream);     // 4 compute + 4 loader waves (fp16)
-        case 65: return lw_launch<64, 160, 4>(g, conv, stream);
-        case 75: return lw_launch<64, 160, 2>(g, conv, stream);
-        case 85: return lw_launch<64, 160, 5>(g, conv, stream);
-        case 34: return launch<128, 160, 3>(g, conv, stream);
-        case 56: return launch<64, 160, 3, 4>(g, conv, stream);    // 8 waves (4 x 2): two waves per SIMD on the one-per-CU tile
-        case 66: return launch<64, 160, 4, 4>(g, conv, stream);
-        case 57: return launch<128, 160, 3, 4>(g, conv, stream);
-        case 47: return launch<128, 160, 2, 4>(g, conv, stream);
-        case 42: return launch<128, 64, 4>(g, conv, stream);
+        case 54: return launch<128, 160, 3, 2, true>(g, conv, stream);    // 4 compute + 4 loader waves, one workgroup per CU
+        case 55: return launch<64, 160, 3, 2, true>(g, conv, stream);
+        case 65: return launch<64, 160, 4, 2, true>(g, conv, stream);
+        case 75: return launch<64, 160, 2, 2, true>(g, conv, stream);     // (58 KB of LDS: two workgroups can share a CU)
         case 26: return launch<256, 128, 2, 4>(g, conv, stream);   // 8 waves, 1 workgroup per CU
         case 36: return launch<256, 128, 3, 4>(g, conv, stream);
-        case 29: return launch<32, 160, 2>(g, conv, stream);       // 512 workgroups on a 2048 x 1280 problem: two per CU, 24 KB per K tile each
-        case 27: return launch<128, 320, 2, 4>(g, conv, stream);   // 8 waves (4 x 2), 56 KB of operands per K tile: 91 FLOP per staged byte
         case 90:                                                   // 256x320, 8 waves, 72 KB per K tile: 142 FLOP per staged byte; paired
             if (g.epi == IIR_EPI_PLAIN) return IIR_EINVAL;         //   epilogues only (the half-width output tile is what fits the ring)
             return launch<256, 320, 2, 4>(g, conv, stream);
-        case 28:                                                   // 8 waves, 64 KB per K tile: 128 FLOP per staged byte; the output tile
-            if (g.epi == IIR_EPI_PLAIN && !g.c_f32) return IIR_EINVAL;   //   only fits the ring in its paired (half-width) form
-            return launch<256, 256, 2, 4>(g, conv, stream);
         default: return IIR_EINVAL;
     }
 }
 
 // no prefetch requested: the (unconditional) touches re-read the first line of this launch's own weights
 void finish_geo(Geo& g) {
-    static const int wt = getenv("IIR_ST_WT") ? atoi(getenv("IIR_ST_WT")) : 1;      // A/B switch; default on (step 60.39 -> 60.22 ms, same box)
-    g.st_wt = wt && ((long)g.M * g.ldc * 2 < (1L << 31));      // 32-bit buffer offsets
+    g.st_wt = (long)g.M * g.ldc * 2 < (1L << 31);      // write-through stores (step 60.39 -> 60.22 ms); 32-bit buffer offsets
     if (g.pf_lines <= 0) { g.pf = (const char*)g.W; g.pf_lines = 1; }
     g.c_vec = (g.ldc % 8 == 0) && ((uintptr_t)g.C % 16 == 0);
     g.r_vec = g.res && (g.ldr % 8 == 0) && ((uintptr_t)g.res % 16 == 0);
@@ -1278,7 +1161,7 @@ void finish_geo(Geo& g) {
 
 }  // namespace
 
-extern "C" int iir_gemm_tile_bn(int32_t tile) { tile %= 10; return (tile >= 1 && tile <= 9) ? kTiles[tile].bn : -1; }
+extern "C" int iir_gemm_tile_bn(int32_t tile) { tile %= 10; return (tile >= 1 && tile <= N_TILES) ? kTiles[tile].bn : -1; }
 
 extern "C" int64_t iir_gemm_splitk_workspace_bytes(int32_t M, int32_t N) { return splitk_ws_bytes(M, N); }
 extern "C" int iir_gemm_uses_splitk(int32_t M, int32_t N, int32_t K, int64_t ws_bytes) { return uses_splitk(M, N, K, ws_bytes) ? 1 : 0; }

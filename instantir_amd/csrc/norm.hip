@@ -7,12 +7,12 @@
 // and AdaLayerNorm (module/ip_adapter/attention_processor.py:18-25: LN without affine, eps 1e-6,
 // x * (1 + scale) + shift).
 #include "common.h"
-#include <stdlib.h>
 #include "../../include/instantir_hip.h"
 
 namespace {
 
 constexpr int GN_MAXC = 2560;
+constexpr int GN_MIN_PIX = 8;   // fewest pixels a statistics slab / an apply block walks (see iir_groupnorm_nhwc)
 
 // Statistics are carried as (count, mean, M2 = sum of squared deviations) and merged with Chan's pairwise update in a FIXED
 // order: no E[x^2] - mean^2 cancellation (real SDXL activations have group means far above their spread), and bitwise
@@ -463,8 +463,7 @@ extern "C" int iir_groupnorm_nhwc(const void* X, int64_t ldx, void* Y, int64_t l
     if (R <= 0 || HW <= 0 || (dtype != IIR_DT_F16 && dtype != IIR_DT_BF16)) return IIR_EINVAL;
     // slabs: enough blocks to fill the chip, at least 8 pixels each (a 32x32 map of 1280-2560 channels took 14.6 us with
     // 64 workgroups walking 32 pixels each, 8 us with 256 walking 8)
-    static const int min_pix = getenv("IIR_GN_MINPIX") ? atoi(getenv("IIR_GN_MINPIX")) : 8;
-    int nslab = (HW + min_pix - 1) / min_pix;
+    int nslab = (HW + GN_MIN_PIX - 1) / GN_MIN_PIX;
     const int want = (1024 + R - 1) / R;
     if (nslab > want) nslab = want;
     if (nslab > 256) nslab = 256;
@@ -478,8 +477,7 @@ extern "C" int iir_groupnorm_nhwc(const void* X, int64_t ldx, void* Y, int64_t l
     const hipStream_t st = (hipStream_t)stream;
     // apply: ~1024 blocks over the batch
     int nblk = (1024 + R - 1) / R;
-    static const int min_ppb = getenv("IIR_GN_APPLY_MINPIX") ? atoi(getenv("IIR_GN_APPLY_MINPIX")) : 8;
-    int ppb = (HW + nblk - 1) / nblk; if (ppb < min_ppb) ppb = min_ppb;
+    int ppb = (HW + nblk - 1) / nblk; if (ppb < GN_MIN_PIX) ppb = GN_MIN_PIX;
     nblk = (HW + ppb - 1) / ppb;
     if (dtype == IIR_DT_BF16) hipLaunchKernelGGL(gn_stats_kernel<bf16>, dim3(nslab, R), dim3(256), 0, st, (const f16*)X, (long)ldx, HW, C, groups, pps, part);
     else hipLaunchKernelGGL(gn_stats_kernel<f16>, dim3(nslab, R), dim3(256), 0, st, (const f16*)X, (long)ldx, HW, C, groups, pps, part);
@@ -504,8 +502,7 @@ extern "C" int iir_groupnorm_from_partials(const void* partials, int64_t ldp, co
     const hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(gn_finalize_cols_kernel, dim3(R * groups), dim3(256), 0, st, (const float2*)partials, (long)ldp, slabs, groups, cpg, eps, stat);
     int nblk = (1024 + R - 1) / R;
-    static const int min_ppb = getenv("IIR_GN_APPLY_MINPIX") ? atoi(getenv("IIR_GN_APPLY_MINPIX")) : 8;
-    int ppb = (HW + nblk - 1) / nblk; if (ppb < min_ppb) ppb = min_ppb;
+    int ppb = (HW + nblk - 1) / nblk; if (ppb < GN_MIN_PIX) ppb = GN_MIN_PIX;
     nblk = (HW + ppb - 1) / ppb;
     if (dtype == IIR_DT_BF16) hipLaunchKernelGGL(gn_apply_kernel<bf16>, dim3(nblk, R), dim3(256), 0, st, (const f16*)X, (long)ldx, (f16*)Y, (long)ldy, HW, C, groups, ppb, (const float*)stat, (const f16*)gamma, (const f16*)beta, silu);
     else hipLaunchKernelGGL(gn_apply_kernel<f16>, dim3(nblk, R), dim3(256), 0, st, (const f16*)X, (long)ldx, (f16*)Y, (long)ldy, HW, C, groups, ppb, (const float*)stat, (const f16*)gamma, (const f16*)beta, silu);

@@ -1,5 +1,4 @@
 """Attention microbenchmark: iir_attention_d64_f16 on the step's shapes, random data, warm; us per launch and TFLOP/s.
-IIR_ATTN_V selects the kernel generation (read once by the library): run once per value on the same box to compare.
 Also checks every shape against F.scaled_dot_product_attention in fp32 (max abs error / output range)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -12,7 +11,6 @@ SHAPES = [("unet L1 self", 2, 10, 4096, [4096]), ("unet L2 self", 2, 20, 1024, [
           ("agg L2 self", 2, 20, 2048, [2048]), ("unet L1 cross", 2, 10, 4096, [77, 64]), ("unet L2 cross", 2, 20, 1024, [77, 64]),
           ("2048^2 agg L1", 2, 10, 32768, [32768])]
 REP = int(os.environ.get("REP", "30"))
-print("IIR_ATTN_V =", os.environ.get("IIR_ATTN_V", "(default)"))
 for name, B, h, T, kvs in SHAPES:
     if T > 8192 and os.environ.get("BIG", "0") != "1":
         continue

@@ -5,7 +5,7 @@ import torch
 from instantir_amd import ops
 dev = torch.device("cuda:0")
 T = int(os.environ.get("T", "4096"))
-print("IIR_ATTN_V =", os.environ.get("IIR_ATTN_V", "(default)"), "T =", T)
+print("T =", T)
 for h in (4, 6, 8, 10, 12, 14, 16, 20, 24, 28, 32, 40, 48):
     B, C = 1, h * 64
     q, k, vt = (torch.randn(B * T, C, device=dev).half() for _ in range(2)) .__iter__().__next__(), None, None

@@ -23,7 +23,7 @@ def run(M, N, K, tile, pf, iters=150):
     e0.record(); go(iters); e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / iters * 1e3
 
-TILES = [int(t) for t in os.environ.get("TILES", "22,32,25,35,45,23").split(",")]
+TILES = [int(t) for t in os.environ.get("TILES", "22,25,35,23").split(",")]
 print("shape".ljust(22) + "".join(f"{('t%d' % t):>14s}" for t in TILES))
 for M, N, K in [(2048, 1280, 1280), (2048, 1280, 5120), (2048, 2560, 1280), (4096, 1280, 1280), (8192, 640, 640)]:
     row = f"{M:6d}x{N:5d}x{K:5d}".ljust(22)

@@ -1,4 +1,4 @@
-"""A few attention launches per shape for rocprofv3 --pmc passes (kernel generation chosen by IIR_ATTN_V)."""
+"""A few attention launches per shape for rocprofv3 --pmc passes."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

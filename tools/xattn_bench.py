@@ -1,5 +1,4 @@
-"""Text + IP cross-attention launch (Tkv = 77 + 64) on the step's shapes: time per launch and error against fp32 SDPA.
-Run twice (IIR_ATTN_PRE=0 / default) to compare the ring form with the pre-staged form."""
+"""Text + IP cross-attention launch (Tkv = 77 + 64) on the step's shapes: time per launch and error against fp32 SDPA."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
