@@ -343,6 +343,25 @@ int iir_prefetch(const void* p, int64_t bytes, int32_t blocks, void* stream);
 int iir_blend_tiles_f32(const float* a, float* b, int32_t planes, int32_t Ha, int32_t Wa, int32_t Hb, int32_t Wb,
                         int32_t extent, int32_t vertical, void* stream);
 
+/* LQ-guided colour correction of the decoded image (no reference counterpart: the definitions are the ones StableSR's
+ * `wavelet_color_fix` / `adain_color_fix` made standard; contract in DESIGN.md section 7 "Colour fix").  content, style, out:
+ * fp32 planar (B, C, H, W) in [0, 1], any H, W >= 1 (<= 32768), B * C <= 32767; `out` may equal `content`.
+ *   wavelet: blur_r(x) = replicate-pad by r, depthwise 3x3 [[1,2,1],[2,4,2],[1,2,1]] / 16 at dilation r;
+ *            decompose(x): for r in 1, 2, 4, 8, 16: low = blur_r(x), high += x - low, x = low;
+ *            out = clamp(decompose(content).high + decompose(style).low, 0, 1), computed as
+ *            clamp(content + blur_16(blur_8(blur_4(blur_2(blur_1(style - content)))))), rows then columns (2 launches).
+ *   adain:   per (image, channel) over H*W: mean, std = sqrt(unbiased var + 1e-5);
+ *            out = clamp((content - mean_c) / std_c * std_s + mean_s, 0, 1); H*W >= 2.  A statistics launch leaves
+ *            (n, mean, M2) per slab, float [2][B*C][IIR_COLORFIX_SLABS][3]; the apply launch merges them in slab order.
+ * `ws`: iir_colorfix_workspace_bytes(B, C, H, W) bytes (one fp32 plane set for wavelet, the slab table for adain, whichever
+ * is larger; -1 for a geometry outside the limits).  No atomics: equal inputs give equal bits. */
+#define IIR_COLORFIX_SLABS 64
+int64_t iir_colorfix_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int iir_colorfix_wavelet_f32(const float* content, const float* style, float* out, int32_t B, int32_t C, int32_t H, int32_t W,
+                             void* ws, int64_t ws_bytes, void* stream);
+int iir_colorfix_adain_f32(const float* content, const float* style, float* out, int32_t B, int32_t C, int32_t H, int32_t W,
+                           void* ws, int64_t ws_bytes, void* stream);
+
 int iir_transpose_f16(const void* in, int64_t ldi, int32_t rows, int32_t cols, void* out, int64_t ldo, int32_t rows_pad,
                       void* stream);
 /* Measurement hook (bench.py roofline leg; no reference counterpart): arm a start/stop event pair and the NEXT

@@ -45,9 +45,9 @@ def demo_resize(image: Image.Image, size=None, max_side=1280, base_pixel_number=
 
 @torch.no_grad()
 def instantir_restore(pipe, lcm_scheduler, lq, prompt="", steps=30, cfg_scale=7.0, guidance_end=1.0, creative_restoration=False,
-                      seed=3407, height=1024, width=1024, preview_start=0.0, **pipe_kwargs):
+                      seed=3407, height=1024, width=1024, preview_start=0.0, color_fix=None, **pipe_kwargs):
     """gradio_demo/app.py:110-156.  Returns (restored image, preview row) like the demo's handler; every preview entry gets
-    its gallery caption appended (`preview_{i}`, :154-155)."""
+    its gallery caption appended (`preview_{i}`, :154-155).  `color_fix` (an addition): passed through to the pipeline."""
     want = "lcm" if creative_restoration else "previewer"                     # :114-120
     if want not in pipe.unet.active_adapters():
         pipe.unet.set_adapter(want)
@@ -63,6 +63,8 @@ def instantir_restore(pipe, lcm_scheduler, lq, prompt="", steps=30, cfg_scale=7.
     if "prompt_embeds" not in pipe_kwargs:
         n = len(lq) if isinstance(lq, (list, tuple)) else lq.shape[0]
         kw.update(prompt=[DEFAULT_PROMPT if len(prompt) == 0 else prompt] * n, negative_prompt=[DEFAULT_NEG_PROMPT] * n)
+    if color_fix is not None:
+        kw["color_fix"] = color_fix
     kw.update(pipe_kwargs)
     out = pipe(**kw)
     for i, preview_img in enumerate(out[1]):

@@ -138,6 +138,9 @@ def build_parser():
                    help="PAG adaptive scale: s_t = max(pag_scale - pag_adaptive_scale * (1000 - t), 0)")
     p.add_argument("--pag_layers", type=str, default="mid",
                    help="comma-separated PAG layer expressions over the UNet's self-attention names (default mid), e.g. mid,up_blocks.0")
+    p.add_argument("--color_fix", choices=["none", "wavelet", "adain"], default="none",
+                   help="transfer the colour of the LQ input onto the restored image after the VAE decode (pipe(..., color_fix=...)); "
+                        "default none")
     return p
 
 
@@ -222,11 +225,21 @@ def apply_pag(pipe, args):
     return {"pag_scale": scale, "pag_adaptive_scale": adaptive}
 
 
+def apply_color_fix(args):
+    """`--color_fix {none,wavelet,adain}` -> the call's `color_fix` keyword argument (an addition: the reference has no colour
+    fix).  `none`, the default, adds nothing to the call."""
+    mode = getattr(args, "color_fix", "none") or "none"
+    if mode not in ("none", "wavelet", "adain"):
+        raise SystemExit(f"--color_fix must be none, wavelet or adain, got {mode}")
+    return {} if mode == "none" else {"color_fix": mode}
+
+
 def main(args, device, rank=0, world=1):
     pipe, lcm_scheduler = build_pipeline(args, device)
     apply_freeu(pipe, args)
     apply_scheduler(pipe, args)
     pag_kw = apply_pag(pipe, args)
+    pag_kw.update(apply_color_fix(args))
     post_fix = f"_{args.post_fix}" if args.post_fix else ""
     out_dir = f"{args.out_path}/{post_fix}"
     os.makedirs(out_dir, exist_ok=True)

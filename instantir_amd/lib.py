@@ -143,6 +143,9 @@ SIGNATURES = {
     "iir_sched_step_hist_f32": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "iir_prefetch": (C.c_int, [_P, _I64, _I32, _P]),
     "iir_blend_tiles_f32": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    "iir_colorfix_workspace_bytes": (C.c_int64, [_I32, _I32, _I32, _I32]),
+    "iir_colorfix_wavelet_f32": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P]),
+    "iir_colorfix_adain_f32": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P]),
     "iir_transpose_f16": (C.c_int, [_P, _I64, _I32, _I32, _P, _I64, _I32, _P]),
     "iir_timing_event_create": (C.c_void_p, []),
     "iir_timing_event_destroy": (None, [_P]),

@@ -753,3 +753,38 @@ def blend_tiles(a, b, extent, vertical):
     L.check(L.load().iir_blend_tiles_f32(a.data_ptr(), b.data_ptr(), a.shape[0] * a.shape[1], a.shape[2], a.shape[3], b.shape[2],
                                          b.shape[3], extent, int(vertical), _stream()), "iir_blend_tiles_f32")
     return b
+
+
+COLOR_FIX_MODES = ("wavelet", "adain")
+
+
+def colorfix(content, style, mode, out=None, ws=None):
+    """LQ-guided colour correction (DESIGN.md section 7 "Colour fix"): content, style fp32 (B, C, H, W) in [0, 1], contiguous,
+    on the same device; mode "wavelet" or "adain".  `out` may be `content` (in place); `ws` a byte workspace of at least
+    iir_colorfix_workspace_bytes (allocated here when absent)."""
+    if mode not in COLOR_FIX_MODES:
+        raise ValueError(f"colorfix: mode must be one of {COLOR_FIX_MODES}, got {mode!r}")
+    for name, t in (("content", content), ("style", style)):
+        if t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"colorfix: {name} must be a contiguous 4-D fp32 CUDA tensor, got {t.dtype} {tuple(t.shape)} {t.stride()}")
+    if style.shape != content.shape or style.device != content.device:
+        raise ValueError(f"colorfix: style {tuple(style.shape)} on {style.device} does not match content {tuple(content.shape)} on {content.device}")
+    if out is None:
+        out = torch.empty_like(content)
+    elif out.dtype != torch.float32 or out.shape != content.shape or not out.is_contiguous() or out.device != content.device:
+        raise ValueError("colorfix: out must be a contiguous fp32 tensor of content's shape on its device")
+    B, Cc, H, W = content.shape
+    if mode == "adain" and H * W < 2:
+        raise ValueError("colorfix: adain needs at least 2 pixels per plane (unbiased variance)")
+    h = L.load()
+    need = h.iir_colorfix_workspace_bytes(B, Cc, H, W)
+    if need < 0:
+        raise ValueError(f"colorfix: unsupported geometry B={B} C={Cc} H={H} W={W}")
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=content.device)
+    elif not ws.is_cuda or not ws.is_contiguous() or ws.numel() * ws.element_size() < need:
+        raise ValueError(f"colorfix: workspace needs {need} contiguous bytes on the device")
+    fn = h.iir_colorfix_wavelet_f32 if mode == "wavelet" else h.iir_colorfix_adain_f32
+    L.check(fn(content.data_ptr(), style.data_ptr(), out.data_ptr(), B, Cc, H, W, ws.data_ptr(), ws.numel() * ws.element_size(),
+               _stream()), f"iir_colorfix_{mode}_f32")
+    return out

@@ -36,6 +36,7 @@ from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepSchedul
                          EulerDiscreteScheduler, LCMSingleStepScheduler)
 from .weights import LCM_LORA_MODULES, PREVIEWER_LORA_MODULES, lora_target
 
+COLOR_FIX_MODES = (None,) + ops.COLOR_FIX_MODES          # `color_fix=` of __call__ / restore_single_step
 
 class StableDiffusionXLPipelineOutput(SimpleNamespace):
     """`.images` like diffusers' output class (pipelines/sdxl_instantir.py:1739)."""
@@ -538,18 +539,69 @@ class InstantIRPipeline:
             raise ValueError(f"image size {tuple(x.shape[2:])} must be a multiple of 8 (infer.py:31-66 resizes to multiples of 64)")
         return x * 2.0 - 1.0
 
+    # ---- LQ-guided colour fix of the final images (an addition; DESIGN.md section 7 "Colour fix") -----------------
+    @staticmethod
+    def _check_color_fix(color_fix, output_type):
+        if color_fix not in COLOR_FIX_MODES:
+            raise ValueError(f"color_fix must be None, 'wavelet' or 'adain', got {color_fix!r}")
+        if color_fix is not None and output_type == "latent":
+            raise ValueError("color_fix corrects decoded pixels: output_type='latent' leaves none to fix")
+
+    def _color_fix_reference(self, color_fix_reference, image, B, nipp):
+        """The colour reference of a call as fp32 (B,3,H,W) in [0,1] on the device.  `image` is what `_prepare_image` returned
+        (before the VAE encode): pixels in [-1,1] serve as the default reference, an LQ latent cannot.  Expanded over the batch
+        exactly as `lq` is (prepare_image :919-925)."""
+        if image.shape[1] == 4:
+            height, width = image.shape[2] * self.vae_scale_factor, image.shape[3] * self.vae_scale_factor
+        else:
+            height, width = image.shape[2], image.shape[3]
+        if color_fix_reference is None:
+            if image.shape[1] == 4:
+                raise ValueError("color_fix needs the LQ pixels: `image` is an LQ latent (B,4,h,w), so pass `color_fix_reference` "
+                                 "(a [0,1] tensor or PIL image(s) of the output size)")
+            ref = image.to(self.device, torch.float32) / 2 + 0.5
+        elif torch.is_tensor(color_fix_reference):
+            ref = color_fix_reference.to(self.device, torch.float32)
+            if ref.dim() == 3:
+                ref = ref.unsqueeze(0)
+        else:
+            import numpy as np
+            ims = color_fix_reference if isinstance(color_fix_reference, (list, tuple)) else [color_fix_reference]
+            arrs = [np.asarray(im.convert("RGB") if hasattr(im, "convert") else im, dtype=np.float32) / 255.0 for im in ims]
+            if len({a.shape for a in arrs}) != 1:
+                raise ValueError("color_fix_reference images must share one size")
+            ref = torch.from_numpy(np.stack(arrs)).permute(0, 3, 1, 2).to(self.device)
+        if ref.dim() != 4 or ref.shape[1] != 3 or tuple(ref.shape[2:]) != (height, width):
+            raise ValueError(f"color_fix reference has shape {tuple(ref.shape)}, expected (n, 3, {height}, {width}): the output's "
+                             "size (no resampling is done here)")
+        ref = ref.repeat(B, 1, 1, 1) if ref.shape[0] == 1 else ref.repeat_interleave(nipp, 0)
+        if ref.shape[0] != B:
+            raise ValueError(f"color_fix reference gives {ref.shape[0]} images, the batch has {B}")
+        return ref.clamp(0, 1).contiguous()
+
+    def _decode_output(self, latents, output_type, color_fix=None, reference=None):
+        """VAE decode of the final latents; with `color_fix` the decoded [0,1] image is corrected in place on the device
+        (ops.colorfix) before it becomes 'np' / 'pil'."""
+        if color_fix is None:
+            return self.vae.decode_latent(latents, output_type)          # tiles when `vae.enable_tiling()` is on
+        img = self.vae.decode_latent(latents, "pt").contiguous()
+        return self.vae.to_output(ops.colorfix(img, reference, color_fix, out=img), output_type)
+
     # ---- single-step previewer restoration (BASELINE configs[4]; spec train_previewer_lora.py:118-145) ------------
     @torch.no_grad()
     def restore_single_step(self, image, prompt_embeds, pooled_prompt_embeds, ip_adapter_image_embeds=None,
                             ip_adapter_image=None, timestep: int = 999, previewer_scheduler=None, generator=None,
-                            init_noise=None, output_type: str = "pil", fp8: bool = False, **kwargs):
+                            init_noise=None, output_type: str = "pil", fp8: bool = False, color_fix: Optional[str] = None,
+                            color_fix_reference=None, **kwargs):
         """LCM one-step restoration with the previewer LoRA, no CFG (guidance 1.0): noise the LQ latent to `timestep`
         (`prepare_latents` there = scheduler.add_noise), ONE UNet pass with the LoRA enabled, `LCMSingleStepScheduler.step`
         (schedulers/lcm_single_step_scheduler.py:421-489), VAE decode.  `fp8=True` (BASELINE configs[4]): the transformer
         blocks' linear layers of that pass run on fp8-E4M3 weights (per-output-channel scales) AND fp8 activations, stored as
         such by the LayerNorm / attention / GEGLU launch that produces them (`ops.gemm_fp8`, `v_mfma_f32_16x16x32_fp8_fp8`; round 3) --
-        a third weight set, built on first use; its tolerance is its own (45.8 dB against the fp32 oracle at SDXL shapes)."""
+        a third weight set, built on first use; its tolerance is its own (45.8 dB against the fp32 oracle at SDXL shapes).
+        `color_fix` / `color_fix_reference`: as for `__call__`."""
         from .engine import CPAD, F16
+        self._check_color_fix(color_fix, output_type)
         if self._lora is None:
             raise RuntimeError("restore_single_step needs the previewer LoRA: call prepare_previewers(...)")
         if fp8:
@@ -565,6 +617,7 @@ class InstantIRPipeline:
         sched = previewer_scheduler if previewer_scheduler is not None else LCMSingleStepScheduler.from_config(self.scheduler.config)
         dev, cfg = self.device, self.cfg
         image = self._prepare_image(image)
+        cf_ref = self._color_fix_reference(color_fix_reference, image, image.shape[0], 1) if color_fix is not None else None
         if image.shape[1] != 4:
             if self.vae is None:
                 raise NotImplementedError("pixel-space `image` needs a VAE; pass the LQ latent (B,4,h,w)")
@@ -592,7 +645,7 @@ class InstantIRPipeline:
             return StableDiffusionXLPipelineOutput(images=out)
         if self.vae is None:
             raise NotImplementedError("output_type other than 'latent' needs a VAE attached to the pipeline")
-        return StableDiffusionXLPipelineOutput(images=self.vae.decode_latent(out, output_type))
+        return StableDiffusionXLPipelineOutput(images=self._decode_output(out, output_type, color_fix, cf_ref))
 
     # ---- the call ---------------------------------------------------------------------------------
     @torch.no_grad()
@@ -610,14 +663,18 @@ class InstantIRPipeline:
                  clip_skip=None, callback_on_step_end: Optional[Callable] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"], previewer_scheduler=None,
                  reference_latents=None, init_noise=None, step_noises=None, pag_scale: Optional[float] = None,
-                 pag_adaptive_scale: float = 0.0, **kwargs):
+                 pag_adaptive_scale: float = 0.0, color_fix: Optional[str] = None, color_fix_reference=None, **kwargs):
         """Keyword arguments and defaults of pipelines/sdxl_instantir.py:1067-1115.  Two additions for
         bit-reproducible parity runs: `init_noise` (the randn of init_latents) and
         `step_noises` (list of per-step DDPM / Euler-ancestral / DPM++ SDE noises) replace draws from `generator` when given.
         With a sigma scheduler (Euler, Euler-ancestral, DPM++) `eta` is ignored, as diffusers drops it for those `step()`s.
         `image` must be the LQ *latent* (B,4,h,w) here unless a VAE is attached (`image.shape[1] == 4` branch of :1369-1382).
         `pag_scale` / `pag_adaptive_scale` (an addition, after diffusers' PAG pipelines): need `enable_pag`; `pag_scale` None
-        means 3.0, and PAG runs when it is > 0 (s_t = max(pag_scale - pag_adaptive_scale * (1000 - t), 0) per step)."""
+        means 3.0, and PAG runs when it is > 0 (s_t = max(pag_scale - pag_adaptive_scale * (1000 - t), 0) per step).
+        `color_fix` (an addition, after StableSR's colour fixes): None, "wavelet" or "adain" transfers the colour of the LQ image
+        onto the final images (never the preview row) after the VAE decode.  The reference is the pixel `image` mapped to
+        [0, 1] unless `color_fix_reference` (a [0, 1] tensor or PIL image(s) of the output size) is given."""
+        self._check_color_fix(color_fix, output_type)
         # :1531-1535 merges the caller's dict over {"temb": emb} and hands it to both UNet passes.  What a key can do there:
         # "scale" is popped by diffusers' UNet forward and scales every LoRA layer for that pass (it also sets the text-encoder
         # LoRA scale, :1324-1326 -- no text-encoder LoRA exists on this path); "temb" / "external_kv" are the processors' own
@@ -677,6 +734,7 @@ class InstantIRPipeline:
                 negative_pooled_prompt_embeds = negative_pooled_prompt_embeds.repeat_interleave(nipp, 0)
         B = pb * nipp
         image = self._prepare_image(image)
+        cf_ref = self._color_fix_reference(color_fix_reference, image, B, nipp) if color_fix is not None else None
         if image.shape[1] != 4:                                                        # :1369-1379
             if self.vae is None:
                 raise NotImplementedError("pixel-space `image` needs a VAE; pass the LQ latent (B,4,h,w)")
@@ -860,7 +918,7 @@ class InstantIRPipeline:
         else:
             if self.vae is None:
                 raise NotImplementedError("output_type other than 'latent' needs a VAE attached to the pipeline")
-            image_out = self.vae.decode_latent(latents_out, output_type)          # tiles when `vae.enable_tiling()` is on
+            image_out = self._decode_output(latents_out, output_type, color_fix, cf_ref)
         if save_preview_row and self.vae is not None and output_type != "latent":     # :1706-1729 (decoded independently, Q4)
             preview_row = [self.vae.decode_latent(pl, output_type) for pl in preview_row]
         if not return_dict:

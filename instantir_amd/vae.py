@@ -245,7 +245,12 @@ class HipVAE:
         if not torch.isfinite(img).all():
             raise FloatingPointError("VAE decode produced non-finite pixels (activation overflow): this build stores VAE "
                                      f"activations as {self.dtype_name}; see DESIGN.md section 7")
-        img = (img / 2 + 0.5).clamp(0, 1)
+        return self.to_output((img / 2 + 0.5).clamp(0, 1), output_type)
+
+    @staticmethod
+    def to_output(img: torch.Tensor, output_type: str):
+        """The tail of `decode_latent`: a (B,3,H,W) image in [0,1] as the 'pt' tensor itself, an 'np' NHWC array or 'pil' images
+        (the pipeline decodes to 'pt', applies `color_fix`, then converts here)."""
         if output_type == "pt":
             return img
         arr = img.permute(0, 2, 3, 1).cpu().numpy()

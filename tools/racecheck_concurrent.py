@@ -207,4 +207,12 @@ screen("lcm_step (rep 2, with fp32 preview)", lambda o, p32: ops.lcm_step(eps2, 
 fac = torch.ones(1, device=dev)
 screen("cfg_rescale_factor", lambda o: (ops.cfg_rescale_factor(eps2, 1, coef, xl, 0.7, fac), o.copy_(fac)), [(1,)], dtype=torch.float32)
 screen("unpack_latent", lambda o: ops.unpack_latent(eps2, o), [(2, 4, 128, 128)], dtype=torch.float32)
+# colour fix of the decoded image (round 8): both modes at the output sizes, out of place and in place
+for (cB, cH, cW) in [(1, 1024, 1024), (2, 768, 1024), (1, 257, 131)]:
+    cf_c = torch.rand(cB, 3, cH, cW, generator=g).to(dev)
+    cf_s = (0.7 * F.avg_pool2d(cf_c, 5, 1, 2) + 0.1 + 0.05 * torch.rand(cB, 3, cH, cW, generator=g).to(dev)).clamp(0, 1)
+    for cf_mode in ("wavelet", "adain"):
+        screen(f"colorfix {cf_mode} {cB}x3x{cH}x{cW}", lambda o: ops.colorfix(cf_c, cf_s, cf_mode, out=o), [(cB, 3, cH, cW)], dtype=torch.float32)
+        screen(f"colorfix {cf_mode} {cB}x3x{cH}x{cW} in place", lambda o: (o.copy_(cf_c), ops.colorfix(o, cf_s, cf_mode, out=o)),
+               [(cB, 3, cH, cW)], dtype=torch.float32)
 print("kernels with run-to-run differences:", bad)
