@@ -145,24 +145,21 @@ class _Net:
         self.units: List[tuple] = []
         self._use_log: Optional[list] = None
         self._gnws = None
-        self._skws = None
         self._warena = None
-        self.inkernel_prefetch = True
         self.arena_gen = 0
-        self.fuse_qkv = os.environ.get("IIR_FUSE_QKV", "1") != "0"
         # LayerNorm folded into the GEMMs either side of it (ops.LnFold; iir_gemm_desc.ln_stats_out / ln_stats_in): not with fp8
         # operands (the activation would be rounded to 3 mantissa bits BEFORE its row mean is removed)
-        self.ln_fold = os.environ.get("IIR_LN_FOLD", "1") != "0" and not fp8_linear
-        # GroupNorm statistics from the launch that produces the GroupNorm's input (ops.gemm / conv2d `gn_out=`, round 3): the
-        # producer tags its output tensor with the partials, the GroupNorm that consumes it skips its statistics pass
-        self.gn_fuse = os.environ.get("IIR_GN_FUSE", "1") != "0"
-        self.xattn_fuse = os.environ.get("IIR_XATTN_FUSE", "1") != "0"      # attn2.to_q + cross-attention as one launch
+        self.ln_fold = not fp8_linear
         # perturbed-attention guidance: None, or (frozenset of selected `attn1` paths, ident_from) -- set on the main UNet only
         # (HipUNet.set_pag)
         self.pag = None
-        # fp8 build (BASELINE configs[4]): the activations of the transformer linears are STORED as fp8 by the launch that produces
-        # them (LayerNorm, attention, GEGLU) and both operands enter the MFMA as fp8 (`ops.gemm_fp8`): the same operand bytes the
-        # fp8-weight GEMM formed in registers from fp16 activations (identical results), half the 128-byte lines per FLOP
+        # The two launch-path options a caller may set (both are part of the pipeline's loop key).  `inkernel_prefetch`: GEMMs and
+        # convs pull the weights that follow their own towards the Infinity Cache (`_pf`).
+        # `fp8_act`, fp8 build (BASELINE configs[4]): the activations of the transformer linears are STORED as fp8 by the launch that
+        # produces them (LayerNorm, attention, GEGLU) and both operands enter the MFMA as fp8 (`ops.gemm_fp8`): the same operand bytes
+        # the fp8-weight GEMM formed in registers from fp16 activations (identical results), half the 128-byte lines per FLOP.
+        # IIR_FP8_ACT=0 builds the register-conversion form (the reference side of the full-size fp8 test).
+        self.inkernel_prefetch = True
         self.fp8_act = fp8_linear and os.environ.get("IIR_FP8_ACT", "1") != "0"
         self._pack_encoder(sd)
 
@@ -297,8 +294,6 @@ class _Net:
         plain = self.w
         first = not self.units
         self._gnws = ops.gn_workspace(self.device, 64, self.cfg.norm_groups)
-        if self._skws is None and os.environ.get("IIR_SPLITK", "0") == "1":     # split-K measured slower: opt-in only
-            self._skws = torch.zeros(4096 + 256 * 128 * 160 * 4, dtype=torch.uint8, device=self.device)
         if first:
             self._use_log = []
             self.w = _RecDict(plain, lambda k: self._use_log.append(k))
@@ -347,34 +342,34 @@ class _Net:
         if self._use_log is not None:
             self._use_log.append(("unit", name))
 
-    import os as _os
-    PF_MULT = float(_os.environ.get("IIR_PF_MULT", "1"))
-    PF_LOOKAHEAD = int(_os.environ.get("IIR_PF_MB", "0")) << 20      # bytes of weight arena between a launch's own weights and what it prefetches
-
     def _pf(self, wt):
         """(ptr, bytes) of the weight-arena range a launch using `wt` should pull towards the Infinity Cache:
-        as many bytes as it consumes itself, PF_LOOKAHEAD further along the (execution-ordered) arena."""
+        as many bytes as it consumes itself, starting right after its own weights in the (execution-ordered) arena."""
         if not self.inkernel_prefetch or self._warena is None or self.o is not ops:
             return None
         base, end = self._warena.data_ptr(), self._warena.data_ptr() + self._warena.numel() * 2
         n = wt.numel() * 2
-        lo = wt.data_ptr() + n + self.PF_LOOKAHEAD
+        lo = wt.data_ptr() + n
         if lo < base or lo >= end or n < (256 << 10):
             return None
-        return (lo, min(int(n * self.PF_MULT), end - lo))
+        return (lo, min(n, end - lo))
 
     def _begin(self):
         self.arena.reset()
 
-    def _gn_alloc(self, rows, hw, C, K, conv):
-        """Arena room for the GroupNorm partials of a (rows, C) tensor about to be produced by a (rows, C, K) launch -- fp32
-        (rows / 64, C, 2) -- or None when the fused path does not apply (images not made of whole 64-row slabs, tiles that cannot
-        emit them).  Allocation happens in the sizing dry run as well: static addresses."""
-        if not self.gn_fuse or hw % 64 or self.arena.dtype != F16 or not ops.gn_supported(rows, C, K, conv):
+    def _gn_tag(self, y, hw, K, conv):
+        """GroupNorm statistics from the launch that produces the GroupNorm's input (ops.gemm / conv2d `gn_out=`): arena room for
+        the partials of `y` (rows, C), about to be written by a (rows, C, K) launch -- fp32 (rows / 64, C, 2) -- tagged onto `y`
+        so that the GroupNorm which consumes it skips its statistics pass (`_gn_of`), and returned for the producer's `gn_out=`.
+        None, and the three-launch GroupNorm, when the fused path does not apply (images not made of whole 64-row slabs, tiles that
+        cannot emit the partials).  Allocation happens in the sizing dry run as well: static addresses."""
+        rows, C = y.shape
+        if hw % 64 or self.arena.dtype != F16 or not ops.gn_supported(rows, C, K, conv):
             return None
         if (hw // 64) * (C // self.cfg.norm_groups) > ops.GN_PARTIALS_MAX:         # iir_groupnorm_from_partials merges at most this many per (image, group)
             return None
-        return self.arena.alloc(rows // 64 * C, 4).view(torch.float32).view(rows // 64, C, 2)
+        y._gn_parts = self.arena.alloc(rows // 64 * C, 4).view(torch.float32).view(rows // 64, C, 2)
+        return y._gn_parts
 
     @staticmethod
     def _gn_of(x):
@@ -390,27 +385,25 @@ class _Net:
         cout = w[path + ".conv1.w"].shape[0]
         if out is None:
             out = A.alloc(R * HW, cout)
-        p_out = self._gn_alloc(R * HW, HW, cout, 9 * cout, True) if self._skws is None else None     # partials of this block's output
+        p_out = self._gn_tag(out, HW, 9 * cout, True)            # partials of this block's output
         m = A.mark()
         h = A.alloc(R * HW, cin)
         o.groupnorm(x, h, R, HW, w[path + ".norm1.g"], w[path + ".norm1.b"], eps, True, self.cfg.norm_groups, self._gnws,
                     partials=self._gn_of(x))
         h2 = A.alloc(R * HW, cout)
-        p2 = self._gn_alloc(R * HW, HW, cout, 9 * cin, True) if self._skws is None else None
         o.conv2d(h.view(R, H, W, cin), w[path + ".conv1.w"], h2, bias=w[path + ".conv1.b"],
                  rowbias=temb_all[:, self._temb_slices[path]], rows_per_rb=HW, prefetch=self._pf(w[path + ".conv1.w"]),
-                 splitk_ws=self._skws, gn_out=p2)
+                 gn_out=self._gn_tag(h2, HW, 9 * cin, True))
         h3 = A.alloc(R * HW, cout)
-        o.groupnorm(h2, h3, R, HW, w[path + ".norm2.g"], w[path + ".norm2.b"], eps, True, self.cfg.norm_groups, self._gnws, partials=p2)
+        o.groupnorm(h2, h3, R, HW, w[path + ".norm2.g"], w[path + ".norm2.b"], eps, True, self.cfg.norm_groups, self._gnws,
+                    partials=self._gn_of(h2))
         if (path + ".conv_shortcut.w") in w:
             sc = A.alloc(R * HW, cout)
             o.gemm(x, w[path + ".conv_shortcut.w"], sc, bias=w[path + ".conv_shortcut.b"])
         else:
             sc = x
         o.conv2d(h3.view(R, H, W, cout), w[path + ".conv2.w"], out, bias=w[path + ".conv2.b"], res=sc,
-                 prefetch=self._pf(w[path + ".conv2.w"]), splitk_ws=self._skws, gn_out=p_out)
-        if p_out is not None:
-            out._gn_parts = p_out
+                 prefetch=self._pf(w[path + ".conv2.w"]), gn_out=p_out)
         A.release(m)
         return out
 
@@ -441,11 +434,7 @@ class _Net:
         else:
             o.layernorm(h, n, w[p + ".norm1.g"], w[p + ".norm1.b"], 1e-5)
             wqkv = w[p + ".attn1.qkv.w"]
-            if self.fuse_qkv:
-                o.gemm(n, wqkv, qk, prefetch=self._pf(wqkv), out_t=(vt, 2 * C))             # q | k, and V^T from the same launch
-            else:
-                o.gemm(n, wqkv[:2 * C], qk, prefetch=self._pf(wqkv))
-                o.gemm(wqkv[2 * C:], n, vt)                                                   # V^T = Wv . X^T (operands swapped)
+            o.gemm(n, wqkv, qk, prefetch=self._pf(wqkv), out_t=(vt, 2 * C))                 # q | k, and V^T from the same launch
         a = A.alloc(M, C)
         # PAG: the perturbed rows [ident_from, R) of a selected attn1 get the identity attention map, a = v, in the same launch
         ident = self.pag[1] if self.pag is not None and (p + ".attn1") in self.pag[0] else 0
@@ -463,7 +452,7 @@ class _Net:
             wq = w[p + (".attn2.to_q.lnw" if fold else ".attn2.to_q.w")]
             # to_q and the text / IP cross-attention in ONE launch (IIR_EPI_XATTN): every workgroup finishes a 64-row x 2-head
             # tile of q and attends with it; q never goes to memory and 174 launches per step disappear
-            fuse = (self.xattn_fuse and cfg.head_dim == 64 and C % 128 == 0 and T % 64 == 0 and cfg.text_len <= 80 and nip <= 64 and h.dtype == F16
+            fuse = (cfg.head_dim == 64 and C % 128 == 0 and T % 64 == 0 and cfg.text_len <= 80 and nip <= 64 and h.dtype == F16
                     and not isinstance(wq, ops.Fp8Weight))
             if not fold:
                 o.layernorm(h, n, w[p + ".norm2.g"], w[p + ".norm2.b"], 1e-5)
@@ -484,8 +473,7 @@ class _Net:
         else:
             o.layernorm(h, n, w[p + ".norm3.g"], w[p + ".norm3.b"], 1e-5)
             o.gemm(n, w[p + ".ff1.w"], f, bias=w[p + ".ff1.b"], epi=ops.EPI_GEGLU, prefetch=self._pf(w[p + ".ff1.w"]))
-        o.gemm(f, w[p + ".ff2.w"], h, bias=w[p + ".ff2.b"], res=h, prefetch=self._pf(w[p + ".ff2.w"]),
-               splitk_ws=None if fold else self._skws, ln_out=None if last else lnst)
+        o.gemm(f, w[p + ".ff2.w"], h, bias=w[p + ".ff2.b"], res=h, prefetch=self._pf(w[p + ".ff2.w"]), ln_out=None if last else lnst)
         A.release(m)
 
     def _tblock_fp8(self, p, h, R, T, heads, st):
@@ -529,7 +517,8 @@ class _Net:
         T = H * W
         if out is None:
             out = A.alloc(R * T, C)
-        p_out = self._gn_alloc(R * T, T, C, C, False)            # partials of the block's output (proj_out + residual)
+        # partials of the block's output (proj_out + residual); an fp8-weight proj_out cannot leave them
+        p_out = None if self.fp8_linear else self._gn_tag(out, T, C, False)
         m = A.mark()
         g = A.alloc(R * T, C)
         o.groupnorm(x, g, R, T, w[path + ".norm.g"], w[path + ".norm.b"], 1e-6, False, self.cfg.norm_groups, self._gnws,
@@ -544,10 +533,7 @@ class _Net:
         o.gemm(g, w[path + ".proj_in.w"], h, bias=w[path + ".proj_in.b"], ln_out=lnst)
         for k in range(depth):
             self._tblock(f"{path}.transformer_blocks.{k}", h, R, T, C // self.cfg.head_dim, st, ada, lnst, last=k == depth - 1)
-        o.gemm(h, w[path + ".proj_out.w"], out, bias=w[path + ".proj_out.b"], res=x,
-               gn_out=p_out if not isinstance(w[path + ".proj_out.w"], ops.Fp8Weight) else None)
-        if p_out is not None and not isinstance(w[path + ".proj_out.w"], ops.Fp8Weight):
-            out._gn_parts = p_out
+        o.gemm(h, w[path + ".proj_out.w"], out, bias=w[path + ".proj_out.b"], res=x, gn_out=p_out)
         A.release(m)
         return out
 
@@ -605,10 +591,7 @@ class _Net:
                 p = f"down_blocks.{i}.downsamplers.0.conv"
                 H2, W2 = (H + 1) // 2, (W + 1) // 2
                 y = A.alloc(R * H2 * W2, c)
-                py = self._gn_alloc(R * H2 * W2, H2 * W2, c, 9 * c, True)
-                o.conv2d(x.view(R, H, W, c), w[p + ".w"], y, stride=2, bias=w[p + ".b"], gn_out=py)
-                if py is not None:
-                    y._gn_parts = py
+                o.conv2d(x.view(R, H, W, c), w[p + ".w"], y, stride=2, bias=w[p + ".b"], gn_out=self._gn_tag(y, H2 * W2, 9 * c, True))
                 x, H, W = y, H2, W2
                 skips.append((x, H, W))
         x = self._resnet("mid_block.resnets.0", x, R, H, W, temb_all)
@@ -796,16 +779,13 @@ class HipUNet(_Net):
         R, H, W = st["R"], st["H"], st["W"]
         temb_all, ada = self._embeddings(t_dev, st)
         x = A.alloc(R * H * W, cfg.block_out_channels[0])
-        px = self._gn_alloc(R * H * W, H * W, cfg.block_out_channels[0], 9 * CPAD, True)
-        o.conv2d(sample.view(R, H, W, CPAD), w["conv_in.w"], x, bias=w["conv_in.b"], gn_out=px)
-        if px is not None:
-            x._gn_parts = px
+        o.conv2d(sample.view(R, H, W, CPAD), w["conv_in.w"], x, bias=w["conv_in.b"], gn_out=self._gn_tag(x, H * W, 9 * CPAD, True))
         x, h, wd, skips = self._down_and_mid(x, R, H, W, temb_all, ada, st)
         return x, h, wd, skips, temb_all, ada
 
-    def _decode(self, enc, st, down_res, mid_res, res_scale, late_event=None, late_from_block=1):
+    def _decode(self, enc, st, down_res, mid_res, res_scale, late_event=None):
         """`late_event`: recorded on another stream once the residuals of the shallow skips are complete; the decoder waits
-        for it only before up block `late_from_block` (the deep residuals it consumes first are already there)."""
+        for it only before up block 1 (the deep residuals it consumes first are already there)."""
         cfg, o, w, A = self.cfg, self.o, self.w, self.arena
         R = st["R"]
         x, h, wd, skips, temb_all, ada = enc
@@ -815,7 +795,7 @@ class HipUNet(_Net):
         nb = len(rev)
         pending_mid = mid_res            # added to the mid output when it is copied into the first concat
         for i, c in enumerate(rev):
-            if late_event is not None and i == late_from_block:
+            if late_event is not None and i == 1:
                 torch.cuda.current_stream().wait_event(late_event)
             for j in range(cfg.layers_per_block + 1):
                 sk, sh, sw = skips.pop()

@@ -163,12 +163,8 @@ def gemm_fp8(a8, w8, out, a_scale=1.0, bias=None, res=None, epi=EPI_PLAIN, act=A
             raise ValueError(f"{n_}: fp16 expected")
     d = L.GemmDesc()
     d.c_fp8 = int(c_fp8)
-    if out_t is not None:                      # columns >= tr_from leave transposed (the V third of q|k|v), as in `gemm`
-        ct, tr_from = out_t
-        _chk2d(ct, "out_t", dt)
-        if c_fp8 or ct.shape[0] < N - tr_from or ct.shape[1] < M:
-            raise ValueError("out_t: fp16 (N - tr_from, M), with an fp16 `out`")
-        d.Ct, d.ldct, d.tr_from = ct.data_ptr(), ct.stride(0), tr_from
+    if out_t is not None:
+        _fill_out_t(d, out_t, dt, M, N, c_fp8, "out_t: fp16 (N - tr_from, M), with an fp16 `out`")
     d.A, d.lda = a8.data_ptr(), a8.stride(0)
     d.W, d.wscale = w8.q.data_ptr(), w8.scale.data_ptr()
     d.C, d.ldc = out.data_ptr(), out.stride(0)
@@ -243,6 +239,43 @@ def _chk_gn_out(gn_out, M, N):
         raise ValueError(f"gn_out: contiguous fp32 ({M} // 64, {N}, 2) with M % 64 == 0, got {tuple(gn_out.shape)} {gn_out.dtype}")
 
 
+def _fill_operands(d, dt, M, N, rowbias, rows_per_rb, res, prefetch, splitk_ws, gn_out):
+    """The optional operands `GemmDesc` and `ConvDesc` name alike: per-image row bias, residual, GroupNorm partials of the
+    (M, N) output, weight prefetch range, split-K workspace."""
+    if rowbias is not None:
+        _chk2d(rowbias, "rowbias", dt)
+        d.rowbias, d.ldrb, d.rows_per_rb = rowbias.data_ptr(), rowbias.stride(0), rows_per_rb
+    if res is not None:
+        _chk2d(res, "res", dt)
+        d.res, d.ldr = res.data_ptr(), res.stride(0)
+    if gn_out is not None:
+        _chk_gn_out(gn_out, M, N)
+        d.gn_stats_out = gn_out.data_ptr()
+    if prefetch is not None:
+        d.prefetch, d.prefetch_bytes = prefetch
+    if splitk_ws is not None:
+        d.splitk_ws, d.splitk_ws_bytes = splitk_ws.data_ptr(), splitk_ws.numel()
+
+
+def _fill_out_t(d, out_t, dt, M, N, refuse, msg):
+    """out_t = (Ct, tr_from): output columns >= tr_from leave transposed, to Ct[n - tr_from, m] (the V third of q|k|v)."""
+    ct, tr_from = out_t
+    _chk2d(ct, "out_t", dt)
+    if refuse or ct.shape[0] < N - tr_from or ct.shape[1] < M:
+        raise ValueError(msg)
+    d.Ct, d.ldct, d.tr_from = ct.data_ptr(), ct.stride(0), tr_from
+
+
+def _fill_kv(table, kv):
+    """The K / V^T segment table (`iir_attn_kv` entries) of `attention` and of `gemm(xattn=)`."""
+    for i, (k, k_rows, vt, vbs, tkv) in enumerate(kv):
+        _chk2d(k, "k"); _chk2d(vt, "vt")
+        e = table[i]
+        e.K, e.ldk, e.k_batch_stride = k.data_ptr(), k.stride(0), k_rows * k.stride(0)
+        e.Vt, e.ldvt, e.vt_batch_stride = vt.data_ptr(), vt.stride(0), vbs
+        e.Tkv = tkv
+
+
 def gemm(a, w, out, bias=None, rowbias=None, rows_per_rb=1, res=None, epi=EPI_PLAIN, act=ACT_NONE, out_scale=1.0,
          tile=0, prefetch=None, splitk_ws=None, out_t=None, wscale=None, ln_out=None, ln_in=None, gn_out=None, xattn=None):
     """out = epi(a @ w.T).  a (M,K) view, w (N,K) contiguous, out (M,N) view ((M,N/2) for paired epilogues).
@@ -284,12 +317,7 @@ def gemm(a, w, out, bias=None, rowbias=None, rows_per_rb=1, res=None, epi=EPI_PL
     d.C, d.ldc = out.data_ptr(), out.stride(0)
     d.M, d.N, d.K = M, N, K
     d.bias = _p(bias)
-    if rowbias is not None:
-        _chk2d(rowbias, "rowbias", dt)
-        d.rowbias, d.ldrb, d.rows_per_rb = rowbias.data_ptr(), rowbias.stride(0), rows_per_rb
-    if res is not None:
-        _chk2d(res, "res", dt)
-        d.res, d.ldr = res.data_ptr(), res.stride(0)
+    _fill_operands(d, dt, M, N, rowbias, rows_per_rb, res, prefetch, splitk_ws, gn_out)
     d.epi, d.act, d.out_scale, d.tile = epi, act, out_scale, tile
     d.dtype, d.c_f32 = _DT[dt], int(c_f32)
     if wscale is not None:
@@ -299,9 +327,6 @@ def gemm(a, w, out, bias=None, rowbias=None, rows_per_rb=1, res=None, epi=EPI_PL
                 or ln_out.shape[0] != ln_parts(M, N, K) or tile != 0:
             raise ValueError("ln_out: contiguous fp32 (ln_parts(M, N, K), M, 2), tile = 0")
         d.ln_stats_out = ln_out.data_ptr()
-    if gn_out is not None:
-        _chk_gn_out(gn_out, M, N)
-        d.gn_stats_out = gn_out.data_ptr()
     if ln_in is not None:
         part, colsum, eps = ln_in
         if part.dtype != torch.float32 or not part.is_contiguous() or part.dim() != 3 or part.shape[1:] != (M, 2) or K % part.shape[0]:
@@ -317,26 +342,14 @@ def gemm(a, w, out, bias=None, rowbias=None, rows_per_rb=1, res=None, epi=EPI_PL
         if len(kvs) != 2:
             raise ValueError("xattn: two K / V^T segments (text, IP tokens)")
         kv_keep = (L.AttnKV * 2)()
-        for i, (k, k_rows, vt, vbs, tkv) in enumerate(kvs):
-            _chk2d(k, "k"); _chk2d(vt, "vt")
-            kv_keep[i].K, kv_keep[i].ldk, kv_keep[i].k_batch_stride = k.data_ptr(), k.stride(0), k_rows * k.stride(0)
-            kv_keep[i].Vt, kv_keep[i].ldvt, kv_keep[i].vt_batch_stride = vt.data_ptr(), vt.stride(0), vbs
-            kv_keep[i].Tkv = tkv
+        _fill_kv(kv_keep, kvs)
         d.xattn_kv, d.xattn_tq = kv_keep, tq
     if xattn is not None:
         tile = 93
     elif tile == 0:       # the library decides; resolve the same choice here only to NAME the launch for the profiler
         tile = 4 if splitk_ws is not None and L.load().iir_gemm_uses_splitk(M, N, K, splitk_ws.numel()) else auto_tile(M, N, epi != EPI_PLAIN, K)
-    if prefetch is not None:
-        d.prefetch, d.prefetch_bytes = prefetch
-    if splitk_ws is not None:
-        d.splitk_ws, d.splitk_ws_bytes = splitk_ws.data_ptr(), splitk_ws.numel()
     if out_t is not None:
-        ct, tr_from = out_t
-        _chk2d(ct, "out_t", dt)
-        if ct.shape[0] < N - tr_from or ct.shape[1] < M:
-            raise ValueError("out_t must hold (N - tr_from, M)")
-        d.Ct, d.ldct, d.tr_from = ct.data_ptr(), ct.stride(0), tr_from
+        _fill_out_t(d, out_t, dt, M, N, False, "out_t must hold (N - tr_from, M)")
     No = N // 2 if epi not in (EPI_PLAIN, EPI_XATTN) else N
     if xattn is not None:
         cls = "gemm_kernel<64x128,gemm+xattn>"
@@ -374,28 +387,16 @@ def conv2d(x, w, out, ksize=3, stride=1, upsample=False, bias=None, rowbias=None
     d.Y, d.ldy = out.data_ptr(), out.stride(0)
     d.Cout, d.ksize, d.stride, d.upsample = Cout, ksize, stride, int(bool(upsample))
     d.bias = _p(bias)
-    if rowbias is not None:
-        _chk2d(rowbias, "rowbias", dt)
-        d.rowbias, d.ldrb, d.rows_per_rb = rowbias.data_ptr(), rowbias.stride(0), rows_per_rb
-    if res is not None:
-        _chk2d(res, "res", dt)
-        d.res, d.ldr = res.data_ptr(), res.stride(0)
     d.dtype = _DT[dt]
     Hi, Wi = (2 * H, 2 * Wd) if upsample else (H, Wd)
     pad2 = 1 if pad_mode == 1 else 2 * (ksize // 2)
     Mo = R * ((Hi + pad2 - ksize) // stride + 1) * ((Wi + pad2 - ksize) // stride + 1)
+    _fill_operands(d, dt, Mo, Cout, rowbias, rows_per_rb, res, prefetch, splitk_ws, gn_out)
     d.epi, d.act, d.out_scale, d.tile = epi, act, out_scale, tile
-    if gn_out is not None:
-        _chk_gn_out(gn_out, Mo, Cout)
-        d.gn_stats_out = gn_out.data_ptr()
     if tile == 0:       # as in gemm(): the library decides, this only names the launch
         Kc = ksize * ksize * Cin
         tile = 4 if splitk_ws is not None and L.load().iir_gemm_uses_splitk(Mo, Cout, Kc, splitk_ws.numel()) else auto_tile(Mo, Cout, epi != EPI_PLAIN, Kc)
     d.zero_page = zero_page(x.device).data_ptr()          # (all-zero bits are zero in fp16 and bf16 alike)
-    if prefetch is not None:
-        d.prefetch, d.prefetch_bytes = prefetch
-    if splitk_ws is not None:
-        d.splitk_ws, d.splitk_ws_bytes = splitk_ws.data_ptr(), splitk_ws.numel()
     d.x_img_stride, d.y_img_rows, d.res_img_rows, d.pad_mode = x.stride(0), y_img_rows, res_img_rows, pad_mode
     Co = Cout // 2 if epi != EPI_PLAIN else Cout
     with _Timed("gemm_kernel<%s,conv>" % _TILE_NAMES[tile % 10], 2.0 * Mo * Cout * ksize * ksize * Cin,
@@ -432,11 +433,7 @@ def attention(q, o, kv, batch, heads, Tq, scale=0.125, causal=False, q_prescaled
     d.batch, d.heads, d.Tq, d.nseg, d.scale = batch, heads, Tq, len(kv), scale
     d.causal = int(bool(causal))
     d.q_prescaled = int(bool(q_prescaled))
-    for i, (k, k_rows, vt, vbs, tkv) in enumerate(kv):
-        _chk2d(k, "k"); _chk2d(vt, "vt")
-        d.kv[i].K, d.kv[i].ldk, d.kv[i].k_batch_stride = k.data_ptr(), k.stride(0), k_rows * k.stride(0)
-        d.kv[i].Vt, d.kv[i].ldvt, d.kv[i].vt_batch_stride = vt.data_ptr(), vt.stride(0), vbs
-        d.kv[i].Tkv = tkv
+    _fill_kv(d.kv, kv)
     if ident_from:
         if head_dim != 64:
             raise ValueError("attention: identity rows need head_dim 64")

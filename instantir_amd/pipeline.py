@@ -23,6 +23,7 @@ Latents are carried in fp32 between steps (the reference carries fp16); UNet inp
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 from types import SimpleNamespace
 from typing import Callable, Dict, List, Optional, Union
@@ -34,9 +35,44 @@ from .config import UNetConfig, VAEConfig
 from .engine import CPAD, F16, HipAggregator, HipUNet
 from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,  # noqa: F401
                          EulerDiscreteScheduler, LCMSingleStepScheduler)
-from .weights import LCM_LORA_MODULES, PREVIEWER_LORA_MODULES, lora_target
+from .weights import LCM_LORA_MODULES, PREVIEWER_LORA_MODULES, aggregator_specs, lora_target
 
 COLOR_FIX_MODES = (None,) + ops.COLOR_FIX_MODES          # `color_fix=` of __call__ / restore_single_step
+
+
+def _tokenizer_fn(tk):
+    """A transformers tokenizer as the callable the pipeline holds: list[str] -> (B, 77) int64 ids, padded / truncated."""
+    return lambda texts: tk(texts, padding="max_length", max_length=tk.model_max_length, truncation=True, return_tensors="pt").input_ids
+
+
+def _clip_text(tensors, config, default_act, device):
+    """`encoders.HipCLIPText` from a text encoder's tensors and its config.json mapping (None / {}: the architecture's defaults)."""
+    from .encoders import HipCLIPText
+    c = config or {}
+    return HipCLIPText(tensors, device, hidden_act=c.get("hidden_act", default_act), eos_token_id=c.get("eos_token_id", 2),
+                       eps=c.get("layer_norm_eps", 1e-5))
+
+
+def _image_array(images, same_size=None):
+    """PIL / numpy image(s) -> fp32 NCHW tensor in [0, 1].  `same_size`: what to call the images when their sizes differ."""
+    import numpy as np
+    if not isinstance(images, (list, tuple)):
+        images = [images]
+    arrs = [np.asarray(im.convert("RGB") if hasattr(im, "convert") else im, dtype=np.float32) / 255.0 for im in images]
+    if same_size is not None and len({a.shape for a in arrs}) != 1:
+        raise ValueError(f"{same_size} images must share one size")
+    return torch.from_numpy(np.stack(arrs)).permute(0, 3, 1, 2)
+
+
+def _randn(shape, generator, device):
+    """fp32 normal draw on the generator's own device (a host generator draws on the host), on `device` without one."""
+    return torch.randn(tuple(shape), generator=generator, device=generator.device if generator is not None else device, dtype=torch.float32)
+
+
+def _time_ids(rows, n):
+    """`add_time_ids` rows (original size + crop offset + target size, :965-981), the block repeated `n` times."""
+    return torch.tensor(rows, dtype=torch.float32).repeat(n, 1)
+
 
 class StableDiffusionXLPipelineOutput(SimpleNamespace):
     """`.images` like diffusers' output class (pipelines/sdxl_instantir.py:1739)."""
@@ -49,10 +85,8 @@ class _AggregatorHandle:
         self._pipe = pipe
 
     def load_state_dict(self, sd, strict=True):
-        from .weights import aggregator_specs
         k = "controlnet_mid_block.0.mlp_shared.0.weight"            # SFT hidden width comes from the file (module/aggregator.py:60)
         if k in sd and sd[k].shape[0] != self._pipe.cfg.sft_hidden:
-            import dataclasses
             self._pipe.cfg = dataclasses.replace(self._pipe.cfg, sft_hidden=sd[k].shape[0])
         want = {n for n, _, _ in aggregator_specs(self._pipe.cfg)}
         missing, unexpected = sorted(want - set(sd)), sorted(set(sd) - want)
@@ -60,6 +94,7 @@ class _AggregatorHandle:
             raise RuntimeError(f"Error(s) in loading state_dict for Aggregator: missing {missing[:5]} unexpected {unexpected[:5]}")
         self._pipe._agg_sd = dict(sd)
         self._pipe._agg = None
+        self._pipe._loop_cache = None               # (the entry pins the released engine)
 
     def to(self, *a, **k):
         return self
@@ -71,7 +106,6 @@ class _AggregatorHandle:
         SFT heads freshly initialised behind zero 1x1 convolutions, so every residual it emits is exactly zero.  (The
         reference draws the SFT 3x3 weights from PyTorch's default init; behind the zero convs their values are unobservable,
         zeros are used.)"""
-        from .weights import aggregator_specs
         usd = self._pipe._unet_sd
         out = {}
         for name, shape, _ in aggregator_specs(self._pipe.cfg):
@@ -105,6 +139,8 @@ class _UNetHandle:
             raise ValueError(f"Adapter {name} not found. Available adapters: {list(self._pipe._adapters)}")
         self._pipe._active_adapter = name
         self._pipe._unet_prev = self._pipe._prev_nets.get((name, 1.0))
+        self._pipe._loop_cache = None               # its entry pins the previewer copy it was captured on, switched away from or
+        #                                             released by `prepare_previewers` (~5 GB at SDXL size)
 
     def enable_adapters(self):       # the loop itself decides which pass runs with the LoRA (:1543-1556)
         pass
@@ -142,12 +178,11 @@ class InstantIRPipeline:
         self.text_encoder, self.text_encoder_2 = text_encoder, text_encoder_2     # encoders.HipCLIPText
         self.tokenizer, self.tokenizer_2 = tokenizer, tokenizer_2               # callables: list[str] -> (B,77) int64 ids
         self._unet = self._unet_prev = self._agg = self._unet_prev8 = None
-        self._graphs = {}
         self._loop_cache = None                     # (key, _DenoiseLoop) of the last call: see _loop_for
         self._prompt_cache = {}                     # (token ids, encoders) -> (prompt_embeds, pooled): see encode_prompt
         self.use_graphs = True
         self.overlap_streams = True
-        self.overlap_sft = os.environ.get("IIR_OVERLAP_SFT", "1") != "0"     # shallow SFT heads beside the decoder's first up block
+        self.overlap_sft = True                     # shallow SFT heads beside the decoder's first up block
         self._guidance_scale = 7.0
         self._freeu = None                          # (s1, s2, b1, b2) or None: see enable_freeu
         self._pag_layers = None                     # perturbed-attention guidance: the layer list of enable_pag, or None
@@ -163,7 +198,6 @@ class InstantIRPipeline:
         (`loaders.load_adapter_to_pipe`, `prepare_previewers`, `aggregator.load_state_dict`).  Compute is fp16 with
         fp32 accumulation whatever `torch_dtype` says."""
         from . import loaders
-        from .encoders import HipCLIPText
         from .vae import HipVAE
         d = pretrained_model_name_or_path
         if not os.path.isdir(d):
@@ -177,13 +211,10 @@ class InstantIRPipeline:
             if os.path.isdir(os.path.join(d, sub)):
                 cj = os.path.join(d, sub, "config.json")
                 c = loaders._read_json(cj) if os.path.isfile(cj) else {}
-                e = HipCLIPText(loaders.load_component(d, sub), device, hidden_act=c.get("hidden_act", default_act),
-                                eos_token_id=c.get("eos_token_id", 2), eps=c.get("layer_norm_eps", 1e-5))
+                e = _clip_text(loaders.load_component(d, sub), c, default_act, device)
             if os.path.isdir(os.path.join(d, tsub)):
                 from transformers import CLIPTokenizer
-                tk = CLIPTokenizer.from_pretrained(os.path.join(d, tsub))
-                t = (lambda tk_: (lambda texts: tk_(texts, padding="max_length", max_length=tk_.model_max_length, truncation=True,
-                                                    return_tensors="pt").input_ids))(tk)
+                t = _tokenizer_fn(CLIPTokenizer.from_pretrained(os.path.join(d, tsub)))
             enc.append(e)
             tok.append(t)
         return cls(cfg, unet_sd, scheduler=kwargs.get("scheduler"), vae=vae, device=device, text_encoder=enc[0],
@@ -231,18 +262,10 @@ class InstantIRPipeline:
             hv = HipVAE(vc, tensors(vae), device)
         encs = []
         for m, default_act in ((text_encoder, "quick_gelu"), (text_encoder_2, "gelu")):
-            if m is None or isinstance(m, HipCLIPText):
-                encs.append(m)
-                continue
-            c = conf(m) or {}
-            encs.append(HipCLIPText(tensors(m), device, hidden_act=c.get("hidden_act", default_act), eos_token_id=c.get("eos_token_id", 2),
-                                    eps=c.get("layer_norm_eps", 1e-5)))
-        toks = []
-        for t in (tokenizer, tokenizer_2):
-            if t is not None and hasattr(t, "model_max_length"):          # a transformers tokenizer
-                t = (lambda tk_: (lambda texts: tk_(texts, padding="max_length", max_length=tk_.model_max_length, truncation=True,
-                                                    return_tensors="pt").input_ids))(t)
-            toks.append(t)
+            ready = m is None or isinstance(m, HipCLIPText)
+            encs.append(m if ready else _clip_text(tensors(m), conf(m), default_act, device))
+        # (a transformers tokenizer has `model_max_length`; anything else is taken as the ids callable itself)
+        toks = [_tokenizer_fn(t) if t is not None and hasattr(t, "model_max_length") else t for t in (tokenizer, tokenizer_2)]
         ie = image_encoder
         if ie is not None and not isinstance(ie, (HipDinov2, HipCLIPVision)):
             sd_ie = tensors(ie)
@@ -348,7 +371,6 @@ class InstantIRPipeline:
             lora_alpha = file_alpha if lora_alpha is None else lora_alpha
         ranks = {v.shape[0] for k, v in lora_state_dict.items() if k.endswith(".lora_A.weight")}
         if len(ranks) == 1 and next(iter(ranks)) != self.cfg.lora_rank:
-            import dataclasses
             self.cfg = dataclasses.replace(self.cfg, lora_rank=next(iter(ranks)))
         unexpected = []
         for k in lora_state_dict:
@@ -380,11 +402,12 @@ class InstantIRPipeline:
             self._unet = HipUNet(self.cfg, self._unet_sd, self.device)
         if self._active_adapter is not None:
             key = (self._active_adapter, float(lora_mult))
-            if key not in self._prev_nets and float(lora_mult) != 1.0:
-                # a merged copy is a whole UNet (~5 GB at SDXL size): keep ONE non-default scale per adapter, evict the previous
-                for k_old in [k for k in self._prev_nets if k[0] == self._active_adapter and k[1] != 1.0 and len(k) == 2]:
-                    del self._prev_nets[k_old]
             if key not in self._prev_nets:
+                self._loop_cache = None    # a new copy follows: the cached loop pins the one it replaces
+                if float(lora_mult) != 1.0:
+                    # a merged copy is a whole UNet (~5 GB at SDXL size): keep ONE non-default scale per adapter, evict the previous
+                    for k_old in [k for k in self._prev_nets if k[0] == self._active_adapter and k[1] != 1.0 and len(k) == 2]:
+                        del self._prev_nets[k_old]
                 if self._lora is None:
                     raise RuntimeError(f"LoRA adapter {self._active_adapter!r}: the host copy was released; call prepare_previewers again")
                 self._prev_nets[key] = HipUNet(self.cfg, self._unet_sd, self.device, lora=self._lora,
@@ -396,27 +419,31 @@ class InstantIRPipeline:
             self._agg = HipAggregator(self.cfg, self._agg_sd, self.device)
         self._apply_freeu(self._unet, self._unet_prev)
 
-    def _loop_for(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale, pag_on=False):
+    def _loop_for(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale, pag_on=False,
+                  fresh=False):
         """The step's buffers and captured hipGraphs are kept from one call to the next: a second image of the same geometry,
         through the same engines, re-uses them (its hoisted K / V, embeddings and LQ latent are copied into the captured
         tensors) instead of paying the warm-up step, the capture and the graph instantiation again (~0.1 s of a 1.9 s call
-        at 1024^2).  Anything the captured launches depend on is part of the key; `IIR_LOOP_CACHE=0` switches it off."""
+        at 1024^2).  Anything the captured launches depend on is part of the key; `IIR_LOOP_CACHE=0` switches it off.
+        `fresh` (a callback replaced the context in mid-call): a new loop beside the cached one, which stays as it is."""
         nets = (self._unet, self._unet_prev, self._agg)
         key = (B, rep, Hl, Wl, reference_latents is not None, float(guidance_rescale or 0.0), self.use_graphs, self.overlap_streams,
-               self.overlap_sft, tuple(None if n is None else (id(n), n.arena_gen, n.inkernel_prefetch, n.gn_fuse) for n in nets),
+               self.overlap_sft, tuple(None if n is None else (id(n), n.arena_gen, n.inkernel_prefetch) for n in nets),
                self._freeu,           # the FreeU factors are launch arguments of the captured concats
                _sched_form(self.scheduler),   # the sigma schedulers launch the device-scale pack and the history step
                self._pag_paths if pag_on else None)     # PAG: row count and the identity launches (its scale is a device scalar)
-        cached = self._loop_cache
-        if cached is not None and cached[0] == key and os.environ.get("IIR_LOOP_CACHE", "1") != "0":
-            if cached[1].adopt(st, st_prev, st_agg, lq, reference_latents, previewer_scheduler):
-                return cached[1]
-        self._loop_cache = None                      # drop the old graphs before building the new ones
+        if not fresh:
+            cached = self._loop_cache
+            if cached is not None and cached[0] == key and os.environ.get("IIR_LOOP_CACHE", "1") != "0":
+                if cached[1].adopt(st, st_prev, st_agg, lq, reference_latents, previewer_scheduler):
+                    return cached[1]
+            self._loop_cache = cached = None         # drop the old graphs before building the new ones
         loop = _DenoiseLoop(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler,
                             guidance_rescale=guidance_rescale, pag_on=pag_on)
         # the entry keeps the engines alive: `id()` in the key can then not be re-issued to a NEW engine (adapter switch, LoRA
         # scale change) while graphs captured on the old one's arena and weights are still cached
-        self._loop_cache = (key, loop, nets)
+        if not fresh:
+            self._loop_cache = (key, loop, nets)
         return loop
 
     # ---- input checks (pipelines/sdxl_instantir.py:749-864, the conditions that apply to tensor inputs) ----
@@ -444,13 +471,13 @@ class InstantIRPipeline:
                              "generate `pooled_prompt_embeds` from the same text encoder that was used to generate `prompt_embeds`.")
         if negative_prompt_embeds is not None and negative_pooled_prompt_embeds is None:
             raise ValueError("If `negative_prompt_embeds` are provided, `negative_pooled_prompt_embeds` also have to be passed.")
-        for s, e in [(control_guidance_start, control_guidance_end)]:
-            if s >= e:
-                raise ValueError(f"control guidance start: {s} cannot be larger or equal to control guidance end: {e}.")
-            if s < 0.0:
-                raise ValueError(f"control guidance start: {s} can't be smaller than 0.")
-            if e > 1.0:
-                raise ValueError(f"control guidance end: {e} can't be larger than 1.0.")
+        s, e = control_guidance_start, control_guidance_end
+        if s >= e:
+            raise ValueError(f"control guidance start: {s} cannot be larger or equal to control guidance end: {e}.")
+        if s < 0.0:
+            raise ValueError(f"control guidance start: {s} can't be smaller than 0.")
+        if e > 1.0:
+            raise ValueError(f"control guidance end: {e} can't be larger than 1.0.")
         if ip_adapter_image is not None and ip_adapter_image_embeds is not None:
             raise ValueError("Provide either `ip_adapter_image` or `ip_adapter_image_embeds`. Cannot leave both "
                              "`ip_adapter_image` and `ip_adapter_image_embeds` defined.")
@@ -516,10 +543,12 @@ class InstantIRPipeline:
         px = image if torch.is_tensor(image) else pre(image)
         return self.image_encoder.encode_image_pair(px)
 
-    def prepare_ip_adapter_image_embeds(self, ip_adapter_image, do_cfg):
-        """:672-707 for one IP adapter: [(2, B, S, E)] = cat([zero-image features, image features]) under CFG."""
-        f, z = self.encode_image(ip_adapter_image)
-        f, z = f.unsqueeze(0), z.unsqueeze(0)
+    def prepare_ip_adapter_image_embeds(self, ip_adapter_image, do_cfg, batch=None):
+        """:672-707 for one IP adapter: [(2 n, Bimg, S, E)] = cat([zero-image features, image features]) under CFG, each stacked
+        n = `batch` // Bimg times (:1350-1357: torch.stack([e] * (B // e.shape[0]), dim=0); once without `batch`)."""
+        f, z = self.encode_image(ip_adapter_image)                                 # (Bimg, S, E) features, zero-image features
+        reps = max((batch or 0) // f.shape[0], 1)
+        f, z = torch.stack([f] * reps, 0), torch.stack([z] * reps, 0)
         return [torch.cat([z, f]) if do_cfg else f]
 
     @staticmethod
@@ -530,11 +559,7 @@ class InstantIRPipeline:
             if image.shape[1] == 4 or image.min() < 0:
                 return image
             return image * 2.0 - 1.0
-        import numpy as np
-        if not isinstance(image, (list, tuple)):
-            image = [image]
-        arrs = [np.asarray(im.convert("RGB") if hasattr(im, "convert") else im, dtype=np.float32) / 255.0 for im in image]
-        x = torch.from_numpy(np.stack(arrs)).permute(0, 3, 1, 2)
+        x = _image_array(image)
         if x.shape[2] % 8 or x.shape[3] % 8:
             raise ValueError(f"image size {tuple(x.shape[2:])} must be a multiple of 8 (infer.py:31-66 resizes to multiples of 64)")
         return x * 2.0 - 1.0
@@ -551,10 +576,8 @@ class InstantIRPipeline:
         """The colour reference of a call as fp32 (B,3,H,W) in [0,1] on the device.  `image` is what `_prepare_image` returned
         (before the VAE encode): pixels in [-1,1] serve as the default reference, an LQ latent cannot.  Expanded over the batch
         exactly as `lq` is (prepare_image :919-925)."""
-        if image.shape[1] == 4:
-            height, width = image.shape[2] * self.vae_scale_factor, image.shape[3] * self.vae_scale_factor
-        else:
-            height, width = image.shape[2], image.shape[3]
+        up = self.vae_scale_factor if image.shape[1] == 4 else 1
+        height, width = image.shape[2] * up, image.shape[3] * up
         if color_fix_reference is None:
             if image.shape[1] == 4:
                 raise ValueError("color_fix needs the LQ pixels: `image` is an LQ latent (B,4,h,w), so pass `color_fix_reference` "
@@ -565,12 +588,7 @@ class InstantIRPipeline:
             if ref.dim() == 3:
                 ref = ref.unsqueeze(0)
         else:
-            import numpy as np
-            ims = color_fix_reference if isinstance(color_fix_reference, (list, tuple)) else [color_fix_reference]
-            arrs = [np.asarray(im.convert("RGB") if hasattr(im, "convert") else im, dtype=np.float32) / 255.0 for im in ims]
-            if len({a.shape for a in arrs}) != 1:
-                raise ValueError("color_fix_reference images must share one size")
-            ref = torch.from_numpy(np.stack(arrs)).permute(0, 3, 1, 2).to(self.device)
+            ref = _image_array(color_fix_reference, same_size="color_fix_reference").to(self.device)
         if ref.dim() != 4 or ref.shape[1] != 3 or tuple(ref.shape[2:]) != (height, width):
             raise ValueError(f"color_fix reference has shape {tuple(ref.shape)}, expected (n, 3, {height}, {width}): the output's "
                              "size (no resampling is done here)")
@@ -579,9 +597,22 @@ class InstantIRPipeline:
             raise ValueError(f"color_fix reference gives {ref.shape[0]} images, the batch has {B}")
         return ref.clamp(0, 1).contiguous()
 
+    def _lq_latent(self, image, vae_noise):
+        """The LQ latent, fp32 on the device, of what `_prepare_image` returned: a latent (B,4,h,w) as it stands, pixels through
+        the VAE encoder (:1369-1379; `vae_noise`: the posterior sample's noise, drawn when None)."""
+        if image.shape[1] != 4:
+            if self.vae is None:
+                raise NotImplementedError("pixel-space `image` needs a VAE; pass the LQ latent (B,4,h,w)")
+            image = self.vae.encode_to_latent(image, eps=vae_noise)
+        return image.to(self.device, torch.float32)
+
     def _decode_output(self, latents, output_type, color_fix=None, reference=None):
         """VAE decode of the final latents; with `color_fix` the decoded [0,1] image is corrected in place on the device
-        (ops.colorfix) before it becomes 'np' / 'pil'."""
+        (ops.colorfix) before it becomes 'np' / 'pil'.  :1706-1729: any `output_type` but 'latent' needs the VAE."""
+        if output_type == "latent":
+            return latents
+        if self.vae is None:
+            raise NotImplementedError("output_type other than 'latent' needs a VAE attached to the pipeline")
         if color_fix is None:
             return self.vae.decode_latent(latents, output_type)          # tiles when `vae.enable_tiling()` is on
         img = self.vae.decode_latent(latents, "pt").contiguous()
@@ -600,7 +631,6 @@ class InstantIRPipeline:
         such by the LayerNorm / attention / GEGLU launch that produces them (`ops.gemm_fp8`, `v_mfma_f32_16x16x32_fp8_fp8`; round 3) --
         a third weight set, built on first use; its tolerance is its own (45.8 dB against the fp32 oracle at SDXL shapes).
         `color_fix` / `color_fix_reference`: as for `__call__`."""
-        from .engine import CPAD, F16
         self._check_color_fix(color_fix, output_type)
         if self._lora is None:
             raise RuntimeError("restore_single_step needs the previewer LoRA: call prepare_previewers(...)")
@@ -618,21 +648,14 @@ class InstantIRPipeline:
         dev, cfg = self.device, self.cfg
         image = self._prepare_image(image)
         cf_ref = self._color_fix_reference(color_fix_reference, image, image.shape[0], 1) if color_fix is not None else None
-        if image.shape[1] != 4:
-            if self.vae is None:
-                raise NotImplementedError("pixel-space `image` needs a VAE; pass the LQ latent (B,4,h,w)")
-            image = self.vae.encode_to_latent(image, eps=kwargs.get("vae_noise"))
-        lq = image.to(dev, torch.float32).contiguous()
+        lq = self._lq_latent(image, kwargs.get("vae_noise")).contiguous()
         B, _, Hl, Wl = lq.shape
         if ip_adapter_image_embeds is None:
             ip_adapter_image_embeds = self.prepare_ip_adapter_image_embeds(ip_adapter_image, False)
         px = (Hl * self.vae_scale_factor, Wl * self.vae_scale_factor)
-        time_ids = torch.tensor([[px[0], px[1], 0, 0, px[0], px[1]]], dtype=torch.float32).repeat(B, 1)
+        time_ids = _time_ids([[px[0], px[1], 0, 0, px[0], px[1]]], B)
         st = net.prepare(prompt_embeds, pooled_prompt_embeds, time_ids, net.resampler(ip_adapter_image_embeds[0]), Hl, Wl)
-        if init_noise is None:
-            gdev = generator.device if generator is not None else dev
-            init_noise = torch.randn(lq.shape, generator=generator, device=gdev, dtype=torch.float32)
-        x = sched.add_noise(lq, init_noise.to(dev, torch.float32), torch.tensor([timestep] * B)).contiguous()
+        x = self._initial_latents(sched, lq, timestep, generator, init_noise)
         lat16 = torch.zeros(B * Hl * Wl, CPAD, dtype=F16, device=dev)
         ops.pack_latent(x, lat16)
         t_dev = torch.full((B, 1), float(timestep), dtype=torch.float32, device=dev)
@@ -641,13 +664,172 @@ class InstantIRPipeline:
         out = torch.empty(B, 4, Hl, Wl, dtype=torch.float32, device=dev)
         coef = torch.tensor(sched.preview_coefficients(timestep), dtype=torch.float32).to(dev)
         ops.lcm_step(eps, B, 1, coef, x, out16, out)
-        if output_type == "latent":
-            return StableDiffusionXLPipelineOutput(images=out)
-        if self.vae is None:
-            raise NotImplementedError("output_type other than 'latent' needs a VAE attached to the pipeline")
         return StableDiffusionXLPipelineOutput(images=self._decode_output(out, output_type, color_fix, cf_ref))
 
-    # ---- the call ---------------------------------------------------------------------------------
+    # ---- the call: its stages, in the reference's order -----------------------------------------------------------
+    def _check_call(self, color_fix, output_type, cross_attention_kwargs, pag_scale, pag_adaptive_scale, multistep_restore):
+        """Checks of the arguments `check_inputs` does not see -> (LoRA scale, `pag_scale` with its default, whether PAG runs)."""
+        self._check_color_fix(color_fix, output_type)
+        # :1531-1535 merges the caller's dict over {"temb": emb} and hands it to both UNet passes.  What a key can do there:
+        # "scale" is popped by diffusers' UNet forward and scales every LoRA layer for that pass (it also sets the text-encoder
+        # LoRA scale, :1324-1326 -- no text-encoder LoRA exists on this path); "temb" / "external_kv" are the processors' own
+        # arguments (module/ip_adapter/attention_processor.py:1093-1100): the loop owns `temb`, and no caller passes `external_kv`;
+        # any other key is a TypeError inside the reference's processors.  "scale" is honoured by building the previewer's
+        # merged copy with scale * alpha / r; the rest is refused with the reason.
+        lora_mult = 1.0
+        if cross_attention_kwargs:
+            extra = set(cross_attention_kwargs) - {"scale"}
+            if extra:
+                raise ValueError(f"cross_attention_kwargs keys {sorted(extra)} are not accepted: the TA-IP attention processors take "
+                                 "`temb` (set by the loop) and nothing a caller may override; only 'scale' (LoRA scale) is honoured")
+            lora_mult = float(cross_attention_kwargs["scale"])
+        if self._pag_layers is None and (pag_scale is not None or pag_adaptive_scale):
+            raise ValueError("pag_scale / pag_adaptive_scale need perturbed-attention guidance: call pipe.enable_pag(...) first")
+        if self._pag_layers is not None:
+            pag_scale = pag.DEFAULT_PAG_SCALE if pag_scale is None else float(pag_scale)
+        pag_on = self._pag_layers is not None and pag_scale > 0
+        if multistep_restore:
+            raise NotImplementedError("multistep_restore passes kwargs the shipped DDPM scheduler does not accept "
+                                      "(SURVEY.md Appendix C Q5)")
+        return lora_mult, pag_scale, pag_on
+
+    def _embedding_rows(self, prompt, prompt_2, negative_prompt, negative_prompt_2, ids, prompt_embeds, negative_prompt_embeds,
+                        pooled_prompt_embeds, negative_pooled_prompt_embeds, do_cfg, clip_skip, nipp):
+        """Prompt embeddings (:1325-1348; encoded unless given, `ids`: the call's extra keyword arguments), one row per image, as the
+        UNet's context and pooled rows in CFG order [negative; positive] (:1456-1464); and the negative ones, for the callback."""
+        if prompt_embeds is None:
+            prompt_embeds, ne, pooled_prompt_embeds, npool = self.encode_prompt(
+                prompt, prompt_2, negative_prompt, negative_prompt_2, ids.get("prompt_ids"), ids.get("prompt_ids_2"),
+                ids.get("negative_prompt_ids"), ids.get("negative_prompt_ids_2"), do_cfg, clip_skip)
+            if negative_prompt_embeds is None:
+                negative_prompt_embeds, negative_pooled_prompt_embeds = ne, npool
+        if nipp > 1:            # diffusers encode_prompt: embeds.repeat(1, n, 1).view(bs * n, ...) == repeat_interleave
+            prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds, negative_pooled_prompt_embeds = (
+                None if v is None else v.repeat_interleave(nipp, 0)
+                for v in (prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds, negative_pooled_prompt_embeds))
+        if not do_cfg:
+            return prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds
+        if negative_prompt_embeds is None:
+            negative_prompt_embeds = torch.zeros_like(prompt_embeds)               # force_zeros_for_empty_prompt
+            negative_pooled_prompt_embeds = torch.zeros_like(pooled_prompt_embeds)
+        return (torch.cat([negative_prompt_embeds, prompt_embeds], 0), torch.cat([negative_pooled_prompt_embeds, pooled_prompt_embeds], 0),
+                negative_prompt_embeds)
+
+    def _image_rows(self, ip_adapter_image, ip_adapter_image_embeds, do_cfg, pb, nipp):
+        """The image-embedding rows handed to the Resampler, (n, B, S, E) with CFG order [zero image; image]."""
+        B = pb * nipp
+        if ip_adapter_image_embeds is None:
+            img = self.prepare_ip_adapter_image_embeds(ip_adapter_image, do_cfg, B)[0]
+        else:
+            # :709-722: each CFG half ([negative; positive]) repeated per prompt copy
+            img = torch.cat([h.repeat(nipp, *([1] * (h.dim() - 1))) for h in ip_adapter_image_embeds[0].chunk(2 if do_cfg else 1)])
+        if img.dim() == 3:
+            img = img.unsqueeze(0)
+        n_rows, R = img.shape[0] * img.shape[1], (2 if do_cfg else 1) * B
+        if n_rows != R:
+            raise ValueError(f"image embeds give {n_rows} rows, the batch has {R} (prompts {pb} x images-per-prompt {nipp}"
+                             f"{' x 2 (CFG)' if do_cfg else ''})")
+        return img
+
+    def _timetable(self, timesteps, num_inference_steps, denoising_end, control_guidance_start, control_guidance_end, preview_start,
+                   preview_end, controlnet_conditioning_scale):
+        """Timetable and per-step gates (:1385, :1415-1425) -> (timesteps, `controlnet_keep`, previewing gate, conditioning scales)."""
+        sigma_form = _sched_form(self.scheduler) == "hist"
+        if timesteps is not None and sigma_form:
+            raise ValueError(f"timesteps= is not supported with {type(self.scheduler).__name__} (custom sigma timetables are out of "
+                             "scope); pass num_inference_steps, or use DDPMScheduler / DDIMScheduler for a hand-built timetable")
+        if timesteps is not None:                                                   # retrieve_timesteps, :195-237
+            self.scheduler.set_timesteps(timesteps=list(timesteps), device=None)
+        else:
+            self.scheduler.set_timesteps(num_inference_steps, device=None)
+        # sigma schedulers: the float timestep reaches the UNet and the Aggregator (Karras timetables are fractional)
+        ts = [float(t) if sigma_form else int(t) for t in self.scheduler.timesteps]
+        n = len(ts)
+        gate = lambda start, end: [1.0 - float(i / n < start or (i + 1) / n > end) for i in range(n)]      # noqa: E731
+        keep, previewing = gate(control_guidance_start, control_guidance_end), gate(preview_start, preview_end)
+        ccs = controlnet_conditioning_scale if isinstance(controlnet_conditioning_scale, list) else [controlnet_conditioning_scale] * n
+        assert len(ccs) == n, f"{len(ccs)} controlnet scales do not match number of sampling steps {n}"
+        if denoising_end is not None and isinstance(denoising_end, float) and 0 < denoising_end < 1:      # :1470-1483
+            cutoff = int(round(self.scheduler.config.num_train_timesteps - denoising_end * self.scheduler.config.num_train_timesteps))
+            ts = [t for t in ts if t >= cutoff]
+        return ts, keep, previewing, ccs
+
+    def _initial_latents(self, sched, lq, t0, generator, init_noise, init_latents_with_lq=True, latents=None):
+        """:1388-1403: the LQ latent noised to the first timestep `t0`, or `latents` / a draw scaled by `init_noise_sigma`."""
+        dev = self.device
+        if not init_latents_with_lq:
+            latents = _randn(lq.shape, generator, dev) if latents is None else latents
+            return (latents.to(dev, torch.float32) * sched.init_noise_sigma).contiguous()
+        init_noise = _randn(lq.shape, generator, dev) if init_noise is None else init_noise
+        return sched.add_noise(lq, init_noise.to(dev, torch.float32), torch.tensor([t0] * lq.shape[0])).contiguous()
+
+    def _denoise(self, x, ctx, loop_of, ts, keep, previewing, ccs, lq, reference_latents, previewer_scheduler, guidance_scale, eta,
+                 generator, step_noises, pag_scale, pag_adaptive_scale, adastep_restore, save_preview_row, callback_on_step_end,
+                 callback_on_step_end_tensor_inputs, negative_prompt_embeds):
+        """The denoising loop (:1497-1660) on the latents `x` -> (final latents, preview latents of each previewing step).
+        `loop_of(ctx, fresh)`: the hoisted states and the `_DenoiseLoop` of a context."""
+        loop = loop_of(ctx, False)
+        B, rep, groups, pag_on, dev = loop.B, loop.rep, loop.groups, loop.pag_on, self.device
+        preview_row = []
+        preview_factor = torch.ones(B)
+        compound = None            # per-image scale the Aggregator's (persistent, raw) outputs currently carry
+        pv = None                  # positive half of `preview_latent`: what conditioned the Aggregator last (:1545-1582)
+        if adastep_restore and rep == 1:
+            raise ValueError("adastep_restore slices preview_latent[B:], which is empty without classifier-free guidance "
+                             "(pipelines/sdxl_instantir.py:1638; SURVEY.md Appendix C Q6)")
+        for i, t in enumerate(ts):
+            have_previewer = loop.st_prev is not None and previewer_scheduler is not None
+            scale_rows = torch.clamp(preview_factor, 0.0, ccs[i]) * keep[i]            # :1538-1540
+            use_agg = bool((scale_rows > 0.1).sum().item() > 0)                      # :1542
+            if use_agg:
+                mode = "preview" if (previewing[i] > 0 and have_previewer) else "agg"
+                if previewing[i] > 0 and not have_previewer:
+                    raise RuntimeError("previewing requested but no previewer: call prepare_previewers(...) and pass "
+                                       "previewer_scheduler=LCMSingleStepScheduler")
+                compound = scale_rows.clone()
+            elif compound is None:
+                raise RuntimeError("control_guidance_start > 0 leaves no aggregator residuals for step 0 "
+                                   "(the reference fails with NameError here, SURVEY.md Appendix C Q2)")
+            else:
+                # :1602-1603 run unconditionally: the PREVIOUS step's already scaled residuals are scaled again (Q2).
+                # Zero everywhere (the creative phase, keep = 0) -> the adds are skipped, which is the same result.
+                compound = compound * scale_rows
+                mode = "unet_res" if bool((compound != 0).any()) else "unet"
+            x0 = loop.step(mode, t, x, (compound if mode != "unet" else scale_rows).repeat(groups), guidance_scale, eta,
+                           None if step_noises is None else step_noises[i], generator, want_x0=adastep_restore, want_preview=save_preview_row or adastep_restore, i=i,
+                           pag_s=pag.scale_at(pag_scale, pag_adaptive_scale, t) if pag_on else 0.0)
+            if mode == "preview":
+                pv = loop.preview_f32[B * (rep - 1):]
+                if save_preview_row:
+                    preview_row.append(pv.clone().cpu())
+            elif mode == "agg":
+                pv = reference_latents.to(dev, torch.float32) if reference_latents is not None else lq     # :1579-1582
+            if adastep_restore:                                                    # :1636-1644
+                pv = pv.float().clone()
+                pred_x0_l2 = (pv - x0).pow(2).sum(dim=(1, 2, 3))
+                prev_l2 = (pv - loop.previewer_mean).pow(2).sum(dim=(1, 2, 3))
+                loop.previewer_mean = pv
+                preview_factor = (pred_x0_l2 / prev_l2).cpu()
+            if callback_on_step_end is not None:                                   # :1646-1659
+                named = {"latents": x, "prompt_embeds": ctx, "negative_prompt_embeds": negative_prompt_embeds}      # (the CFG-concatenated context)
+                cb_in = {"latents": x, **{k: named[k] for k in (callback_on_step_end_tensor_inputs or [])}}
+                cb = callback_on_step_end(self, i, t, cb_in)
+                x = cb.pop("latents", x)
+                new_ctx = cb.pop("prompt_embeds", None)
+                cb.pop("negative_prompt_embeds", None)       # the reference rebinds a name it never reads again (:1465, :1655): no effect
+                if new_ctx is not None and new_ctx is not ctx:
+                    # the text K / V^T of all 70 cross-attention blocks are hoisted per call: a replaced context means hoisting
+                    # again (and a new captured step), after which the loop continues on the same latents
+                    if tuple(new_ctx.shape) != tuple(ctx.shape):
+                        raise ValueError(f"callback_on_step_end returned prompt_embeds of shape {tuple(new_ctx.shape)}, expected {tuple(ctx.shape)}")
+                    ctx = new_ctx
+                    mean_keep, hist_keep = loop.previewer_mean, loop.hist
+                    loop = loop_of(ctx, True)
+                    loop.previewer_mean = mean_keep
+                    if hist_keep is not None:                # a multistep solver's x0 history continues across the rebuild
+                        loop.hist.copy_(hist_keep)
+        return x, preview_row
+
     @torch.no_grad()
     def __call__(self, prompt=None, prompt_2=None, image=None, height=None, width=None, num_inference_steps: int = 30,
                  timesteps: List[int] = None, denoising_end: Optional[float] = None, guidance_scale: float = 7.0,
@@ -674,51 +856,25 @@ class InstantIRPipeline:
         `color_fix` (an addition, after StableSR's colour fixes): None, "wavelet" or "adain" transfers the colour of the LQ image
         onto the final images (never the preview row) after the VAE decode.  The reference is the pixel `image` mapped to
         [0, 1] unless `color_fix_reference` (a [0, 1] tensor or PIL image(s) of the output size) is given."""
-        self._check_color_fix(color_fix, output_type)
-        # :1531-1535 merges the caller's dict over {"temb": emb} and hands it to both UNet passes.  What a key can do there:
-        # "scale" is popped by diffusers' UNet forward and scales every LoRA layer for that pass (it also sets the text-encoder
-        # LoRA scale, :1324-1326 -- no text-encoder LoRA exists on this path); "temb" / "external_kv" are the processors' own
-        # arguments (module/ip_adapter/attention_processor.py:1093-1100): the loop owns `temb`, and no caller passes `external_kv`;
-        # any other key is a TypeError inside the reference's processors.  "scale" is honoured by building the previewer's
-        # merged copy with scale * alpha / r; the rest is refused with the reason.
-        lora_mult = 1.0
-        if cross_attention_kwargs:
-            extra = set(cross_attention_kwargs) - {"scale"}
-            if extra:
-                raise ValueError(f"cross_attention_kwargs keys {sorted(extra)} are not accepted: the TA-IP attention processors take "
-                                 "`temb` (set by the loop) and nothing a caller may override; only 'scale' (LoRA scale) is honoured")
-            lora_mult = float(cross_attention_kwargs["scale"])
-        if self._pag_layers is None:
-            if pag_scale is not None or pag_adaptive_scale:
-                raise ValueError("pag_scale / pag_adaptive_scale need perturbed-attention guidance: call pipe.enable_pag(...) first")
-            pag_on = False
-        else:
-            pag_scale = pag.DEFAULT_PAG_SCALE if pag_scale is None else float(pag_scale)
-            pag_on = pag_scale > 0
-        if multistep_restore:
-            raise NotImplementedError("multistep_restore passes kwargs the shipped DDPM scheduler does not accept "
-                                      "(SURVEY.md Appendix C Q5)")
-        if prompt is None and prompt_embeds is None and kwargs.get("prompt_ids") is not None and self.text_encoder is not None:
-            prompt_embeds_chk = kwargs["prompt_ids"]          # ids stand in for the prompt in the exclusivity checks
-        else:
-            prompt_embeds_chk = prompt_embeds
+        lora_mult, pag_scale, pag_on = self._check_call(color_fix, output_type, cross_attention_kwargs, pag_scale, pag_adaptive_scale,
+                                                        multistep_restore)
+        ids_given = prompt is None and prompt_embeds is None and kwargs.get("prompt_ids") is not None and self.text_encoder is not None
+        prompt_embeds_chk = kwargs["prompt_ids"] if ids_given else prompt_embeds      # ids stand in for the prompt in the exclusivity checks
         self.check_inputs(prompt, prompt_embeds_chk, negative_prompt_embeds,
                           pooled_prompt_embeds if prompt_embeds_chk is prompt_embeds else torch.zeros(1), negative_pooled_prompt_embeds,
                           ip_adapter_image, ip_adapter_image_embeds, control_guidance_start, control_guidance_end,
                           callback_on_step_end_tensor_inputs)
         self._guidance_scale = guidance_scale
-        cfg, dev = self.cfg, self.device
         do_cfg = self.do_classifier_free_guidance
         self._build(lora_mult)
 
-        if prompt_embeds is None:                                                   # :1325-1348
-            prompt_embeds, ne, pooled_prompt_embeds, npool = self.encode_prompt(
-                prompt, prompt_2, negative_prompt, negative_prompt_2, kwargs.get("prompt_ids"), kwargs.get("prompt_ids_2"),
-                kwargs.get("negative_prompt_ids"), kwargs.get("negative_prompt_ids_2"), do_cfg, clip_skip)
-            if negative_prompt_embeds is None:
-                negative_prompt_embeds, negative_pooled_prompt_embeds = ne, npool
         nipp = int(num_images_per_prompt or 1)
-        pb = prompt_embeds.shape[0]                                                # `batch_size` of :1304-1315
+        rep = 2 if do_cfg else 1      # row groups of the previewer and the Aggregator; the main UNet: [uncond;] cond [; perturbed]
+        ctx, pooled, negative_prompt_embeds = self._embedding_rows(
+            prompt, prompt_2, negative_prompt, negative_prompt_2, kwargs, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
+            negative_pooled_prompt_embeds, do_cfg, clip_skip, nipp)
+        B = ctx.shape[0] // rep
+        pb = B // nipp                                                             # `batch_size` of :1304-1315
         n_img = 1 if hasattr(image, "size") and not torch.is_tensor(image) and not isinstance(image, (list, tuple)) else len(image)
         assert pb == n_img or n_img == 1                                          # :1310-1315
         if ip_adapter_image is None and ip_adapter_image_embeds is None:           # :1278-1279 (see Q15 in the header)
@@ -726,199 +882,48 @@ class InstantIRPipeline:
                 raise ValueError("`image` is an LQ latent (B,4,h,w): it cannot stand in for `ip_adapter_image` (the image encoder takes "
                                  "pixels); pass `ip_adapter_image` or `ip_adapter_image_embeds`")
             ip_adapter_image = image
-        if nipp > 1:            # diffusers encode_prompt: embeds.repeat(1, n, 1).view(bs * n, ...) == repeat_interleave
-            prompt_embeds = prompt_embeds.repeat_interleave(nipp, 0)
-            pooled_prompt_embeds = pooled_prompt_embeds.repeat_interleave(nipp, 0)
-            if negative_prompt_embeds is not None:
-                negative_prompt_embeds = negative_prompt_embeds.repeat_interleave(nipp, 0)
-                negative_pooled_prompt_embeds = negative_pooled_prompt_embeds.repeat_interleave(nipp, 0)
-        B = pb * nipp
+
+        # -- the LQ latent (:1369-1379)
         image = self._prepare_image(image)
         cf_ref = self._color_fix_reference(color_fix_reference, image, B, nipp) if color_fix is not None else None
-        if image.shape[1] != 4:                                                        # :1369-1379
-            if self.vae is None:
-                raise NotImplementedError("pixel-space `image` needs a VAE; pass the LQ latent (B,4,h,w)")
-            image = self.vae.encode_to_latent(image, eps=kwargs.get("vae_noise"), generator=None)
-        lq = image.to(dev, torch.float32)
+        lq = self._lq_latent(image, kwargs.get("vae_noise"))
         # prepare_image :919-925: one image serves the whole batch, otherwise each image is repeated per prompt copy
-        lq = lq.repeat(B, 1, 1, 1) if lq.shape[0] == 1 else lq.repeat_interleave(nipp, 0)
-        lq = lq.contiguous()
+        lq = (lq.repeat(B, 1, 1, 1) if lq.shape[0] == 1 else lq.repeat_interleave(nipp, 0)).contiguous()
         Hl, Wl = lq.shape[2], lq.shape[3]
         height, width = Hl * self.vae_scale_factor, Wl * self.vae_scale_factor
 
-        # -- embeddings, CFG order [negative; positive] (:1456-1464)
-        if do_cfg:
-            if negative_prompt_embeds is None:
-                negative_prompt_embeds = torch.zeros_like(prompt_embeds)           # force_zeros_for_empty_prompt
-                negative_pooled_prompt_embeds = torch.zeros_like(pooled_prompt_embeds)
-            ctx = torch.cat([negative_prompt_embeds, prompt_embeds], 0)
-            pooled = torch.cat([negative_pooled_prompt_embeds, pooled_prompt_embeds], 0)
-        else:
-            ctx, pooled = prompt_embeds, pooled_prompt_embeds
-        rep = 2 if do_cfg else 1
-        R = rep * B                   # rows of the previewer and the Aggregator
-        groups = rep + int(pag_on)    # row groups of the main UNet: [uncond;] cond [; perturbed]
-        if pag_on:
-            self._unet.set_pag(self._pag_paths, R)          # (refuses an fp8 engine)
-        else:
-            self._unet.set_pag(None, 0)
-        original_size = original_size or (height, width)
-        target_size = target_size or (height, width)
-        ids = list(original_size) + list(crops_coords_top_left) + list(target_size)     # :965-981
-        if cfg.addition_time_embed_dim * len(ids) + cfg.pooled_dim != cfg.add_embed_in:
-            raise ValueError("Model expects an added time embedding vector of length "
-                             f"{cfg.add_embed_in}, but a vector of {cfg.addition_time_embed_dim * len(ids) + cfg.pooled_dim} was created.")
+        self._unet.set_pag(self._pag_paths if pag_on else None, rep * B)          # (refuses an fp8 engine)
+        ids = list(original_size or (height, width)) + list(crops_coords_top_left) + list(target_size or (height, width))     # :965-981
         neg_ids = ids
         if negative_original_size is not None and negative_target_size is not None:   # :1445-1454
             neg_ids = list(negative_original_size) + list(negative_crops_coords_top_left) + list(negative_target_size)
-        if do_cfg:
-            # :1459,:1464 verbatim: cat([neg, pos]) then .repeat(B, 1) -- for B > 1 the rows alternate neg, pos, neg, ... while
-            # the prompt rows are [neg x B; pos x B]; only observable when negative sizes differ from the positive ones
-            time_ids = torch.tensor([neg_ids, ids], dtype=torch.float32).repeat(B, 1)
-        else:
-            time_ids = torch.tensor([ids], dtype=torch.float32).repeat(R, 1)
-        if ip_adapter_image_embeds is None:                                         # :1350-1357, :672-707
-            f, z = self.encode_image(ip_adapter_image)                             # (Bimg, S, E) features, zero-image features
-            reps = max(B // f.shape[0], 1)                                         # torch.stack([e] * (B // e.shape[0]), dim=0)
-            f, z = torch.stack([f] * reps, 0), torch.stack([z] * reps, 0)
-            img = torch.cat([z, f]) if do_cfg else f
-        else:
-            img = ip_adapter_image_embeds[0]
-            if do_cfg:                                                              # :709-722
-                neg, pos = img.chunk(2)
-                img = torch.cat([neg.repeat(nipp, *([1] * (neg.dim() - 1))), pos.repeat(nipp, *([1] * (pos.dim() - 1)))])
-            else:
-                img = img.repeat(nipp, *([1] * (img.dim() - 1)))
-        if img.dim() == 3:
-            img = img.unsqueeze(0)
-        n_rows = img.shape[0] * img.shape[1]
-        if n_rows != R:
-            raise ValueError(f"image embeds give {n_rows} rows, the batch has {R} (prompts {pb} x images-per-prompt {nipp}"
-                             f"{' x 2 (CFG)' if do_cfg else ''})")
+        if self.cfg.addition_time_embed_dim * len(ids) + self.cfg.pooled_dim != self.cfg.add_embed_in:
+            raise ValueError(f"Model expects an added time embedding vector of length {self.cfg.add_embed_in}, but a vector of "
+                             f"{self.cfg.addition_time_embed_dim * len(ids) + self.cfg.pooled_dim} was created.")
+        # :1459,:1464 verbatim: cat([neg, pos]) then .repeat(B, 1) -- for B > 1 the rows alternate neg, pos, neg, ... while
+        # the prompt rows are [neg x B; pos x B]; only observable when negative sizes differ from the positive ones
+        time_ids = _time_ids([neg_ids, ids] if do_cfg else [ids], B)
+        img = self._image_rows(ip_adapter_image, ip_adapter_image_embeds, do_cfg, pb, nipp)
 
-        # -- timetable and gates (:1385, :1415-1425)
-        sigma_form = _sched_form(self.scheduler) == "hist"
-        if timesteps is not None and sigma_form:
-            raise ValueError(f"timesteps= is not supported with {type(self.scheduler).__name__} (custom sigma timetables are out of "
-                             "scope); pass num_inference_steps, or use DDPMScheduler / DDIMScheduler for a hand-built timetable")
-        if timesteps is not None:                                                   # retrieve_timesteps, :195-237
-            self.scheduler.set_timesteps(timesteps=list(timesteps), device=None)
-        else:
-            self.scheduler.set_timesteps(num_inference_steps, device=None)
-        # sigma schedulers: the float timestep reaches the UNet and the Aggregator (Karras timetables are fractional)
-        ts = [float(t) if sigma_form else int(t) for t in self.scheduler.timesteps]
-        n = len(ts)
-        keep, previewing = [], []
-        for i in range(n):
-            keep.append(1.0 - float(i / n < control_guidance_start or (i + 1) / n > control_guidance_end))
-            previewing.append(1.0 - float(i / n < preview_start or (i + 1) / n > preview_end))
-        if isinstance(controlnet_conditioning_scale, list):
-            assert len(controlnet_conditioning_scale) == n, \
-                f"{len(controlnet_conditioning_scale)} controlnet scales do not match number of sampling steps {n}"
-            ccs = controlnet_conditioning_scale
-        else:
-            ccs = [controlnet_conditioning_scale] * n
-        if denoising_end is not None and isinstance(denoising_end, float) and 0 < denoising_end < 1:      # :1470-1483
-            cutoff = int(round(self.scheduler.config.num_train_timesteps - denoising_end * self.scheduler.config.num_train_timesteps))
-            ts = [t for t in ts if t >= cutoff]
+        ts, keep, previewing, ccs = self._timetable(timesteps, num_inference_steps, denoising_end, control_guidance_start,
+                                                    control_guidance_end, preview_start, preview_end, controlnet_conditioning_scale)
 
-        # -- step-invariant device state
-        st = self._main_state(ctx, pooled, time_ids, img, Hl, Wl, B, rep, pag_on)
-        st_prev = None
-        if self._unet_prev is not None:
-            st_prev = self._unet_prev.prepare(ctx, pooled, time_ids, self._unet_prev.resampler(img), Hl, Wl)
-        st_agg = self._agg.prepare(pooled, time_ids, Hl, Wl, out_rows=groups * B if pag_on else None)
+        # -- step-invariant device state: the Aggregator's here, the UNets' per context
+        st_agg = self._agg.prepare(pooled, time_ids, Hl, Wl, out_rows=(rep + 1) * B if pag_on else None)
 
-        # -- initial latents (:1388-1403)
-        if init_latents_with_lq:
-            if init_noise is None:
-                gdev = generator.device if generator is not None else dev
-                init_noise = torch.randn(lq.shape, generator=generator, device=gdev, dtype=torch.float32)
-            x = self.scheduler.add_noise(lq, init_noise.to(dev, torch.float32), torch.tensor([ts[0]] * B))
-        else:
-            if latents is None:
-                gdev = generator.device if generator is not None else dev
-                latents = torch.randn(lq.shape, generator=generator, device=gdev, dtype=torch.float32)
-            x = latents.to(dev, torch.float32) * self.scheduler.init_noise_sigma
-        x = x.contiguous()
+        def loop_of(ctx_, fresh):
+            st = self._main_state(ctx_, pooled, time_ids, img, Hl, Wl, B, rep, pag_on)
+            prev = self._unet_prev
+            st_prev = None if prev is None else prev.prepare(ctx_, pooled, time_ids, prev.resampler(img), Hl, Wl)
+            return self._loop_for(B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale,
+                                  pag_on, fresh=fresh)
 
-        loop = self._loop_for(B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale,
-                              pag_on)
-        preview_row = []
-        preview_factor = torch.ones(B)
-        compound = None            # per-image scale the Aggregator's (persistent, raw) outputs currently carry
-        pv = None                  # positive half of `preview_latent`: what conditioned the Aggregator last (:1545-1582)
-        if adastep_restore and not do_cfg:
-            raise ValueError("adastep_restore slices preview_latent[B:], which is empty without classifier-free guidance "
-                             "(pipelines/sdxl_instantir.py:1638; SURVEY.md Appendix C Q6)")
-        for i, t in enumerate(ts):
-            scale_rows = torch.clamp(preview_factor, 0.0, ccs[i]) * keep[i]            # :1538-1540
-            use_agg = bool((scale_rows > 0.1).sum().item() > 0)                      # :1542
-            if use_agg:
-                mode = "preview" if (previewing[i] > 0 and st_prev is not None and previewer_scheduler is not None) else "agg"
-                if previewing[i] > 0 and (st_prev is None or previewer_scheduler is None):
-                    raise RuntimeError("previewing requested but no previewer: call prepare_previewers(...) and pass "
-                                       "previewer_scheduler=LCMSingleStepScheduler")
-                compound = scale_rows.clone()
-            elif compound is None:
-                raise RuntimeError("control_guidance_start > 0 leaves no aggregator residuals for step 0 "
-                                   "(the reference fails with NameError here, SURVEY.md Appendix C Q2)")
-            else:
-                # :1602-1603 run unconditionally: the PREVIOUS step's already scaled residuals are scaled again (Q2).
-                # Zero everywhere (the creative phase, keep = 0) -> the adds are skipped, which is the same result.
-                compound = compound * scale_rows
-                mode = "unet_res" if bool((compound != 0).any()) else "unet"
-            noise = None
-            if step_noises is not None:
-                noise = step_noises[i]
-            x0 = loop.step(mode, t, x, (compound if mode != "unet" else scale_rows).repeat(groups), guidance_scale, eta, noise,
-                           generator, want_x0=adastep_restore, want_preview=save_preview_row or adastep_restore, i=i,
-                           pag_s=pag.scale_at(pag_scale, pag_adaptive_scale, t) if pag_on else 0.0)
-            if mode == "preview":
-                pv = loop.preview_f32[B * (rep - 1):]
-                if save_preview_row:
-                    preview_row.append(pv.clone().cpu())
-            elif mode == "agg":
-                pv = reference_latents.to(dev, torch.float32) if reference_latents is not None else lq     # :1579-1582
-            if adastep_restore:                                                    # :1636-1644
-                pv = pv.float().clone()
-                pred_x0_l2 = (pv - x0).pow(2).sum(dim=(1, 2, 3))
-                prev_l2 = (pv - loop.previewer_mean).pow(2).sum(dim=(1, 2, 3))
-                loop.previewer_mean = pv
-                preview_factor = (pred_x0_l2 / prev_l2).cpu()
-            if callback_on_step_end is not None:                                   # :1646-1659
-                cb_in = {"latents": x}
-                for name in (callback_on_step_end_tensor_inputs or []):            # (`prompt_embeds` here is the CFG-concatenated context)
-                    if name == "prompt_embeds":
-                        cb_in[name] = ctx
-                    elif name == "negative_prompt_embeds":
-                        cb_in[name] = negative_prompt_embeds
-                cb = callback_on_step_end(self, i, t, cb_in)
-                x = cb.pop("latents", x)
-                new_ctx = cb.pop("prompt_embeds", None)
-                cb.pop("negative_prompt_embeds", None)       # the reference rebinds a name it never reads again (:1465, :1655): no effect
-                if new_ctx is not None and new_ctx is not ctx:
-                    # the text K / V^T of all 70 cross-attention blocks are hoisted per call: a replaced context means hoisting
-                    # again (and a new captured step), after which the loop continues on the same latents
-                    if tuple(new_ctx.shape) != tuple(ctx.shape):
-                        raise ValueError(f"callback_on_step_end returned prompt_embeds of shape {tuple(new_ctx.shape)}, expected {tuple(ctx.shape)}")
-                    ctx = new_ctx
-                    st = self._main_state(ctx, pooled, time_ids, img, Hl, Wl, B, rep, pag_on)
-                    if self._unet_prev is not None:
-                        st_prev = self._unet_prev.prepare(ctx, pooled, time_ids, self._unet_prev.resampler(img), Hl, Wl)
-                    mean_keep, hist_keep = loop.previewer_mean, loop.hist
-                    loop = _DenoiseLoop(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler,
-                                        guidance_rescale=guidance_rescale, pag_on=pag_on)
-                    loop.previewer_mean = mean_keep
-                    if hist_keep is not None:                # a multistep solver's x0 history continues across the rebuild
-                        loop.hist.copy_(hist_keep)
-        latents_out = x
-        if output_type == "latent":
-            image_out = latents_out
-        else:
-            if self.vae is None:
-                raise NotImplementedError("output_type other than 'latent' needs a VAE attached to the pipeline")
-            image_out = self._decode_output(latents_out, output_type, color_fix, cf_ref)
+        x = self._initial_latents(self.scheduler, lq, ts[0], generator, init_noise, init_latents_with_lq, latents)
+        x, preview_row = self._denoise(x, ctx, loop_of, ts, keep, previewing, ccs, lq, reference_latents, previewer_scheduler,
+                                       guidance_scale, eta, generator, step_noises, pag_scale, pag_adaptive_scale, adastep_restore,
+                                       save_preview_row, callback_on_step_end, callback_on_step_end_tensor_inputs,
+                                       negative_prompt_embeds)
+        image_out = self._decode_output(x, output_type, color_fix, cf_ref)
         if save_preview_row and self.vae is not None and output_type != "latent":     # :1706-1729 (decoded independently, Q4)
             preview_row = [self.vae.decode_latent(pl, output_type) for pl in preview_row]
         if not return_dict:
@@ -932,17 +937,26 @@ def _sched_form(scheduler):
     return "hist" if hasattr(scheduler, "loop_coefficients") else "linear"
 
 
+def _scalar_row(rows):
+    """Layout of a loop's per-step scalar row when its main UNet runs `rows` rows: ({name: slice}, length) of
+    [t x rows | lcm coef x4 | sched coef x8 | res scale x rows | c_in | PAG s_t].  `sched` is the (8,) coefficient vector the
+    iir_sched_step* and PAG kernels index themselves: guidance in [0], the history term k_h in [7]."""
+    lay, off = {}, 0
+    for name, n in (("t", rows), ("lcm", 4), ("sched", 8), ("res_scale", rows), ("c_in", 1), ("pag_s", 1)):
+        lay[name] = slice(off, off + n)
+        off += n
+    return lay, off
+
+
 def _copy_state(dst, src):
     """Refresh a `prepare()` state in place (same structure, shapes and dtypes) so that launch sequences captured on `dst`'s
     tensors see `src`'s values.  `ada_jobs` is a device table of pointers into `dst`'s own tensors and stays.  False = the
     two states differ in structure: the caller builds a new loop."""
     if dst is None or src is None:
         return dst is None and src is None
-    if len(dst) != len(src):
+    if dst.keys() != src.keys():
         return False
     for k, v in src.items():
-        if k not in dst:
-            return False
         d = dst[k]
         if k == "ada_jobs":
             continue
@@ -977,15 +991,13 @@ class _DenoiseLoop:
         self.prev_sched = previewer_scheduler
         R, HW = B * rep, H * W
         Rm = B * self.groups                                               # main UNet rows
-        self.R_agg = R
         self.lat16 = torch.zeros(Rm * HW, CPAD, dtype=F16, device=dev)
         self.lat_prev = self.lat16[:R * HW]                                # the previewer's rows of it
         self.prev16 = torch.zeros(R * HW, CPAD, dtype=F16, device=dev)
         self.lq16 = torch.zeros(R * HW, CPAD, dtype=F16, device=dev)
+        self.ref16 = torch.zeros(R * HW, CPAD, dtype=F16, device=dev) if reference_latents is not None else None
         ops.pack_latent(lq, self.lq16, rep=rep)
-        self.ref16 = None
-        if reference_latents is not None:
-            self.ref16 = torch.zeros(R * HW, CPAD, dtype=F16, device=dev)
+        if self.ref16 is not None:
             ops.pack_latent(reference_latents.to(dev, torch.float32).contiguous(), self.ref16, rep=rep)
         self.x_in = torch.empty(B, 4, H, W, dtype=torch.float32, device=dev)
         self.x_out = torch.empty_like(self.x_in)
@@ -996,21 +1008,16 @@ class _DenoiseLoop:
         self.form = _sched_form(pipe.scheduler)
         # the x0 history of a multistep solver, read and rewritten in place by every step's iir_sched_step_hist
         self.hist = torch.zeros_like(self.x_in) if self.form == "hist" else None
-        # per-step scalars: [t x Rm | lcm coef x4 | sched coef x8 (k_h in [7]) | res scale x Rm | c_in | PAG s_t]
-        R = Rm
-        self.n_sc = R + 4 + 8 + R + 1 + 1
+        lay, n_sc = _scalar_row(Rm)                              # per-step scalars
         # ring of pinned staging rows: a row is rewritten only after the H2D copy that read it has completed
-        self.sc_ring = [torch.zeros(self.n_sc, dtype=torch.float32).pin_memory() for _ in range(8)]
+        self.sc_ring = [torch.zeros(n_sc, dtype=torch.float32).pin_memory() for _ in range(8)]
         self.sc_events = [None] * 8
         self.sc_idx = 0
-        self.sc_dev = torch.zeros(self.n_sc, dtype=torch.float32, device=dev)
-        self.t_dev = self.sc_dev[:R].view(R, 1)
-        self.lcm_coef = self.sc_dev[R:R + 4]
-        self.sched_coef = self.sc_dev[R + 4:R + 12]
-        self.res_scale = self.sc_dev[R + 12:2 * R + 12]
-        self.c_in = self.sc_dev[2 * R + 12:2 * R + 13]
-        self.pag_s = self.sc_dev[2 * R + 13:]
-        self.t_agg = self.t_dev[:self.R_agg]                                # the previewer's and the Aggregator's rows
+        self.sc_dev, self.sc_lay = torch.zeros(n_sc, dtype=torch.float32, device=dev), lay
+        self.t_dev = self.sc_dev[lay["t"]].view(Rm, 1)
+        self.lcm_coef, self.sched_coef, self.res_scale, self.c_in, self.pag_s = (
+            self.sc_dev[lay[k]] for k in ("lcm", "sched", "res_scale", "c_in", "pag_s"))
+        self.t_agg = self.t_dev[:R]                                         # the previewer's and the Aggregator's rows
         self.seg_jobs = None
         if self.pag_on:
             # one launch per Aggregator pass gives the perturbed rows of every residual the cond rows' values
@@ -1041,67 +1048,62 @@ class _DenoiseLoop:
             self.hist.zero_()
         return True
 
+    def _on_side(self, fn):
+        """Run `fn` on the side stream, between a fork event recorded on the current stream now and a join event recorded behind
+        it: (what `fn` returned, the join event)."""
+        if self.side is None:
+            self.side = torch.cuda.Stream(device=self.x_in.device)
+        fork, join = torch.cuda.Event(), torch.cuda.Event()
+        fork.record(torch.cuda.current_stream())
+        self.side.wait_event(fork)
+        with torch.cuda.stream(self.side):
+            out = fn()
+            join.record(self.side)
+        return out, join
+
+    def _condition(self, mode, want_preview, defer_shallow):
+        """Previewer forward + LCM step (or the LQ / reference latent), Aggregator forward, PAG segment copy -> the residuals."""
+        p = self.p
+        if mode == "preview":
+            eps1 = p._unet_prev.forward(self.lat_prev, self.t_agg, self.st_prev)          # :1545-1554
+            ops.lcm_step(eps1, self.B, self.rep, self.lcm_coef, self.x_in, self.prev16,
+                         self.preview_f32 if want_preview else None)                     # :1555-1561
+            cond = self.prev16
+        else:
+            cond = self.ref16 if self.ref16 is not None else self.lq16               # :1579-1582
+        p._agg.defer_shallow = defer_shallow
+        down, mid = p._agg.forward(self.lq16, cond, self.t_agg, self.st_agg)           # :1591-1599
+        if self.pag_on:
+            ops.copy_segments(*self.seg_jobs)
+        return down, mid
+
     def _launch(self, mode, use_noise, want_x0, want_preview):
-        p, B, rep = self.p, self.B, self.rep
+        p = self.p
         if self.form == "hist":                                              # scale_model_input(cat([latents]*2), t), :1503-1504
             ops.pack_latent_dscale(self.x_in, self.lat16, self.c_in, rep=self.groups)
         else:
             ops.pack_latent(self.x_in, self.lat16, rep=self.groups)          # cat([latents]*2), :1503
-        down = mid = None
-        if mode == "unet_res":       # stale residuals of the last Aggregator pass, re-scaled (see __call__)
+        if mode == "unet":
+            eps = p._unet.forward(self.lat16, self.t_dev, self.st)
+        elif mode == "unet_res":     # stale residuals of the last Aggregator pass, re-scaled (see __call__)
             eps = p._unet.forward(self.lat16, self.t_dev, self.st, p._agg._out, p._agg._out_mid, self.res_scale)
-            self._sched(eps, use_noise, want_x0)
-            return
-        if mode != "unet" and p.overlap_streams:
+        elif p.overlap_streams:
             # The main UNet's encoder half does not depend on the previewer / Aggregator: run it on a side
             # stream so its (CU-underfilling) launches overlap theirs; join before the residual adds.
-            main = torch.cuda.current_stream()
-            if self.side is None:
-                self.side = torch.cuda.Stream(device=self.x_in.device)
-            fork, join = torch.cuda.Event(), torch.cuda.Event()
-            fork.record(main)
-            self.side.wait_event(fork)
-            with torch.cuda.stream(self.side):
-                enc = p._unet.encode(self.lat16, self.t_dev, self.st)
-                join.record(self.side)
-            if mode == "preview":
-                eps1 = p._unet_prev.forward(self.lat_prev, self.t_agg, self.st_prev)
-                ops.lcm_step(eps1, B, rep, self.lcm_coef, self.x_in, self.prev16, self.preview_f32 if want_preview else None)
-                cond = self.prev16
-            else:
-                cond = self.ref16 if self.ref16 is not None else self.lq16
+            enc, join = self._on_side(lambda: p._unet.encode(self.lat16, self.t_dev, self.st))
             # (PAG: the perturbed rows' residuals are copied once every head has run, so no head is deferred)
-            p._agg.defer_shallow = p.overlap_sft and not self.pag_on
-            down, mid = p._agg.forward(self.lq16, cond, self.t_agg, self.st_agg)
-            if self.pag_on:
-                ops.copy_segments(*self.seg_jobs)
-            main.wait_event(join)
+            defer = p.overlap_sft and not self.pag_on
+            down, mid = self._condition(mode, want_preview, defer)
+            torch.cuda.current_stream().wait_event(join)
             late = None
-            if p._agg.defer_shallow:
+            if defer:
                 # the SFT heads of the shallow skips (consumed by the last up blocks) run on the side stream beside the
                 # decoder's first up block
-                f2, late = torch.cuda.Event(), torch.cuda.Event()
-                f2.record(main)
-                self.side.wait_event(f2)
-                with torch.cuda.stream(self.side):
-                    p._agg.late_heads()
-                    late.record(self.side)
+                _, late = self._on_side(p._agg.late_heads)
             eps = p._unet.decode(enc, self.st, down, mid, self.res_scale, late_event=late)
-            self._sched(eps, use_noise, want_x0)
-            return
-        if mode != "unet":
-            if mode == "preview":
-                eps1 = p._unet_prev.forward(self.lat_prev, self.t_agg, self.st_prev)          # :1545-1554
-                ops.lcm_step(eps1, B, rep, self.lcm_coef, self.x_in, self.prev16,
-                             self.preview_f32 if want_preview else None)                 # :1555-1561
-                cond = self.prev16
-            else:
-                cond = self.ref16 if self.ref16 is not None else self.lq16               # :1579-1582
-            p._agg.defer_shallow = False
-            down, mid = p._agg.forward(self.lq16, cond, self.t_agg, self.st_agg)           # :1591-1599
-            if self.pag_on:
-                ops.copy_segments(*self.seg_jobs)
-        eps = p._unet.forward(self.lat16, self.t_dev, self.st, down, mid, self.res_scale if down is not None else None)
+        else:
+            down, mid = self._condition(mode, want_preview, False)
+            eps = p._unet.forward(self.lat16, self.t_dev, self.st, down, mid, self.res_scale)
         self._sched(eps, use_noise, want_x0)
 
     def _sched(self, eps, use_noise, want_x0):
@@ -1111,48 +1113,43 @@ class _DenoiseLoop:
         fac = None
         if rep == 2 and self.guidance_rescale > 0.0:
             fac = ops.cfg_rescale_factor(eps, B, self.sched_coef, self.x_in, self.guidance_rescale, self.cfg_factor, pag_scale=ps)
+        kw = dict(noise=self.noise if use_noise else None, cfg=rep == 2, x0_out=self.x0 if want_x0 else None, eps_factor=fac, pag_scale=ps)
         if self.form == "hist":
-            ops.sched_step_hist(eps, B, self.sched_coef, self.x_in, self.hist, self.x_out, noise=self.noise if use_noise else None,
-                                cfg=rep == 2, x0_out=self.x0 if want_x0 else None, eps_factor=fac, pag_scale=ps)
-            return
-        ops.sched_step(eps, B, self.sched_coef, self.x_in, self.x_out, noise=self.noise if use_noise else None,
-                       cfg=rep == 2, x0_out=self.x0 if want_x0 else None, eps_factor=fac, pag_scale=ps)
+            ops.sched_step_hist(eps, B, self.sched_coef, self.x_in, self.hist, self.x_out, **kw)
+        else:
+            ops.sched_step(eps, B, self.sched_coef, self.x_in, self.x_out, **kw)
 
     def step(self, mode, t, x, res_scale_rows, guidance, eta, noise, generator, want_x0=False, want_preview=False, i=None,
              pag_s=0.0):
         """`i`: the step's index in the scheduler's timetable (the sigma schedulers' coefficients are per index).  `res_scale_rows`:
         one scale per main-UNet row.  `pag_s`: the step's PAG scale s_t."""
-        p, R = self.p, self.B * self.groups
+        p, lay = self.p, self.sc_lay
         slot = self.sc_idx % len(self.sc_ring)
         self.sc_idx += 1
         if self.sc_events[slot] is not None:
             self.sc_events[slot].synchronize()
         sc = self.sc_ring[slot]
-        sc[:R] = float(t)
+        sc[lay["t"]] = float(t)
+        c_in, t_lcm = 1.0, t
         if self.form == "hist":
             # eta is not an argument of these schedulers' step() (diffusers drops it): ignored
             lc = p.scheduler.loop_coefficients(i)
-            c_in = lc["c_in"]
-            if mode == "preview":
-                # the LCM previewer gets the scaled input c_in * x (:1555-1561) and t.to(int64) (:1557): fold c_in into its
-                # coefficients so that iir_lcm_step reads the unscaled latent
-                sb, sa, c_out, c_skip = self.prev_sched.preview_coefficients(lc["t_lcm"])
-                sc[R:R + 4] = torch.tensor([sb / c_in, sa / c_in, c_out, c_skip * c_in])
-            coef = list(lc["coef"])
-            sc[2 * R + 12] = c_in
+            c_in, t_lcm, coef = lc["c_in"], lc["t_lcm"], list(lc["coef"])
+            sc[lay["c_in"]] = c_in
         else:
-            if mode == "preview":
-                sc[R:R + 4] = torch.tensor(self.prev_sched.preview_coefficients(t))
             coef = p.scheduler.step_coefficients(t, eta=eta)
+        if mode == "preview":
+            # a sigma scheduler's LCM previewer gets the scaled input c_in * x (:1555-1561) and t.to(int64) (:1557): fold c_in into
+            # its coefficients so that iir_lcm_step reads the unscaled latent (c_in = 1 otherwise: / 1 and * 1 are exact)
+            sb, sa, c_out, c_skip = self.prev_sched.preview_coefficients(t_lcm)
+            sc[lay["lcm"]] = torch.tensor([sb / c_in, sa / c_in, c_out, c_skip * c_in])
         coef[0] = float(guidance)
-        sc[R + 4:R + 12] = torch.tensor(coef)
-        sc[R + 12:2 * R + 12] = res_scale_rows.float()
-        sc[2 * R + 13] = float(pag_s)
+        sc[lay["sched"]] = torch.tensor(coef)
+        sc[lay["res_scale"]] = res_scale_rows.float()
+        sc[lay["pag_s"]] = float(pag_s)
         use_noise = coef[6] != 0.0
         if use_noise:
-            if noise is None:
-                gdev = generator.device if generator is not None else self.x_in.device
-                noise = torch.randn(self.x_in.shape, generator=generator, device=gdev, dtype=torch.float32)
+            noise = _randn(self.x_in.shape, generator, self.x_in.device) if noise is None else noise
             self.noise.copy_(noise.to(self.noise.device, torch.float32), non_blocking=True)
         self.sc_dev.copy_(sc, non_blocking=True)
         ev = torch.cuda.Event()

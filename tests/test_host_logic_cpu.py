@@ -269,3 +269,34 @@ def test_oracle_chain_resumed_in_sittings_equals_one_chain():
     assert torch.equal(OP.denoise(P, PA, L, cfg, lq, pe, po, im, resume=(st["x"], 3, 6), **kw), full)
     with pytest.raises(ValueError):
         OP.denoise(P, PA, L, cfg, lq, pe, po, im, resume=(st["x"], 3, 6), adastep_restore=True, **kw)
+
+
+@pytest.mark.parametrize("rows", [1, 2, 3, 6])       # B=1 without CFG, with CFG, with CFG + PAG; B=2 with CFG + PAG
+def test_loop_scalar_row_layout(rows):
+    """`pipeline._scalar_row`: the one layout of the per-step scalar row [t | lcm | sched | res scale | c_in | pag s] that
+    `_DenoiseLoop` takes its device views from and writes its staging row through."""
+    from instantir_amd.pipeline import _scalar_row
+    from instantir_amd.schedulers import DPMSolverMultistepScheduler, EulerDiscreteScheduler
+    lay, total = _scalar_row(rows)
+    assert list(lay) == ["t", "lcm", "sched", "res_scale", "c_in", "pag_s"]                     # the documented order ...
+    assert all(s.step in (None, 1) for s in lay.values())
+    starts = [s.start for s in lay.values()]
+    assert starts == sorted(starts) and starts[0] == 0
+    sizes = {k: s.stop - s.start for k, s in lay.items()}
+    assert sizes == {"t": rows, "lcm": 4, "sched": 8, "res_scale": rows, "c_in": 1, "pag_s": 1}
+    cover = [i for s in lay.values() for i in range(s.start, s.stop)]
+    assert cover == list(range(total))             # ... pairwise disjoint, contiguous, covering the row exactly
+    # iir_sched_step* and the PAG kernels index `sched_coef` themselves: 8 contiguous floats, guidance slot [0], k_noise [6]
+    # (the loop's `use_noise`), k_h [7] -- the vectors the schedulers hand the loop have exactly that shape
+    assert lay["sched"] == slice(rows + 4, rows + 12)
+    ddpm, dpm, euler = DDPMScheduler(), DPMSolverMultistepScheduler(), EulerDiscreteScheduler()
+    for s in (ddpm, dpm, euler):
+        s.set_timesteps(4)
+    c_ddpm = ddpm.step_coefficients(int(ddpm.timesteps[0]), eta=0.0)
+    c_dpm, c_euler = dpm.loop_coefficients(1)["coef"], euler.loop_coefficients(1)["coef"]
+    assert len(c_ddpm) == len(c_dpm) == len(c_euler) == 8
+    assert c_dpm[7] != 0.0 and c_euler[7] == 0.0 and c_ddpm[7] == 0.0          # only the second-order step has a history term
+    assert c_ddpm[6] != 0.0 and c_dpm[6] == 0.0                                 # DDPM draws noise, DPM++ 2M does not
+    row = torch.zeros(total)
+    row[lay["sched"]] = torch.tensor(c_dpm)
+    assert row[lay["sched"].start + 7].item() == np.float32(c_dpm[7]) and row[lay["res_scale"]].abs().sum() == 0

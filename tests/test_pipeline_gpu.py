@@ -397,6 +397,31 @@ def test_adapter_switching_and_lora_scale(env):
     with pytest.raises(ValueError):
         pipe.unet.set_adapter("nope")
 
+    # Replacing or releasing an engine drops the cached loop (its entry pins the engines it was captured on), and the next call
+    # is bit-identical to a freshly built pipeline given the same adapters and inputs.
+    def fresh(active):
+        ref = _pipe(cfg, sd, sda, lora, DDIMScheduler())
+        ref.prepare_previewers(lcm_lora, use_lcm=True, lora_alpha=8)
+        ref.unet.set_adapter(active)
+        return _call(ref, inp, **kw3)
+
+    kw3 = dict(num_inference_steps=3, guidance_scale=5.0)
+    want = {name: fresh(name) for name in ("lcm", "previewer")}
+    assert not torch.equal(want["lcm"], want["previewer"])
+    _call(pipe, inp, **kw3)                                        # (`previewer` is active)
+    assert pipe._loop_cache is not None
+    pipe.unet.set_adapter("lcm")
+    assert pipe._loop_cache is None
+    assert torch.equal(_call(pipe, inp, **kw3), want["lcm"])
+    assert pipe._loop_cache is not None
+    pipe.prepare_previewers(lora, lora_alpha=16)                   # a second time: releases the merged `previewer` copies
+    assert pipe._loop_cache is None and pipe.unet.active_adapters() == ["previewer"]
+    assert torch.equal(_call(pipe, inp, **kw3), want["previewer"])
+    assert pipe._loop_cache is not None
+    pipe.aggregator.load_state_dict(sda)
+    assert pipe._loop_cache is None
+    assert torch.equal(_call(pipe, inp, **kw3), want["previewer"])
+
 
 def test_step_graphs_are_reused_across_calls(env, monkeypatch):
     """A second image of the same geometry runs on the first call's buffers and captured graphs (its hoisted state is copied
