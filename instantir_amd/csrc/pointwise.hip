@@ -59,11 +59,15 @@ __global__ void copy_add_kernel(const f16* src, long lds_, f16* dst, long ldd, l
     *(f16x8*)(dst + m * ldd + dst_off + ch * 8) = v;
 }
 
-// fp32 NCHW (B, C, H, W) -> f16 NHWC rows (rep*B, H*W, ldo), channels [0,C) written, repeated `rep` times
+// fp32 NCHW (B, C, H, W) -> f16 NHWC rows (rep*B, H*W, ldo), channels [0,C) written, repeated `rep` times.  The scale is the
+// host float, or read from `scale_dev` when given (sigma schedulers: the UNet input c_in * x changes every step, and a host
+// float would be baked into a captured graph).  One product expression, so equal scales give equal bits.
 template <typename E>
-__global__ void pack_latent_kernel(const float* x, int B, int C, int HW, E* out, long ldo, int rep, float scale) {
+__global__ void pack_latent_kernel(const float* x, int B, int C, int HW, E* out, long ldo, int rep, float scale,
+                                   const float* scale_dev) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)B * HW) return;
+    if (scale_dev) scale = *scale_dev;
     const int b = (int)(i / HW), p = (int)(i % HW);
     for (int c = 0; c < C; ++c) {
         const E v = (E)(x[((long)b * C + c) * HW + p] * scale);
@@ -83,26 +87,26 @@ __global__ void unpack_latent_kernel(const E* in, long ldi, int R, int C, int HW
 // Main scheduler step with classifier-free guidance, fp32.
 //   eps  = cfg ? u + g * (c - u) : c         (u = rows [0,B), c = rows [B,2B) of the UNet output)
 //   x0   = (x - sqrt_beta_t * eps) / sqrt_alpha_t
-//   prev = k_x0 * x0 + k_x * x + k_eps * eps + k_noise * noise
-// coef (device, fp32[8]) = {g, sqrt_beta_t, sqrt_alpha_t, k_x0, k_x, k_eps, k_noise, unused}
+//   prev = k_x0 * x0 + k_x * x + k_eps * eps + k_h * m_prev + k_noise * noise
+// coef (device, fp32[8]) = {g, sqrt_beta_t, sqrt_alpha_t, k_x0, k_x, k_eps, k_noise, k_h}
 // rescale_noise_cfg (pipelines/sdxl_instantir.py:181-192): per image, over (C, H, W),
 //   factor = phi * std(eps_text) / std(eps_cfg) + (1 - phi),  eps_cfg = u + g * (text - u)   (torch.std: unbiased; the
 // N-1 cancels in the ratio).  One workgroup per image, fp32 element math, fp64 accumulation.
-// PAG: eps_cfg gains the perturbed-attention term + s * (text - perturbed) (rows [2B, 3B)), s = *pag_s, before the ratio.
-template <bool PAG>
+// PAG (pag_s given): eps_cfg gains the perturbed-attention term + s * (text - perturbed) (rows [2B, 3B)), s = *pag_s, before
+// the ratio.
 __global__ __launch_bounds__(1024) void cfg_rescale_kernel(const f16* eps_nhwc, long lde, int B, int C, int HW, const float* coef,
                                                            const float* pag_s, float phi, float* factor) {
     __shared__ double red[4][16];
     const int b = blockIdx.x;
     const float g = coef[0];
-    const float ps = PAG ? *pag_s : 0.f;
+    const float ps = pag_s ? *pag_s : 0.f;
     double st = 0., st2 = 0., sc = 0., sc2 = 0.;
     for (int p = threadIdx.x; p < HW; p += blockDim.x)
         for (int c = 0; c < C; ++c) {
             const float u = (float)eps_nhwc[((long)b * HW + p) * lde + c];
             const float t = (float)eps_nhwc[((long)(B + b) * HW + p) * lde + c];
             float e = u + g * (t - u);
-            if (PAG && ps != 0.f) e = e + ps * (t - (float)eps_nhwc[((long)(2 * B + b) * HW + p) * lde + c]);
+            if (ps != 0.f) e = e + ps * (t - (float)eps_nhwc[((long)(2 * B + b) * HW + p) * lde + c]);
             st += t; st2 += (double)t * t; sc += e; sc2 += (double)e * e;
         }
     double v[4] = {st, st2, sc, sc2};
@@ -125,8 +129,8 @@ __global__ __launch_bounds__(1024) void cfg_rescale_kernel(const f16* eps_nhwc, 
 
 // Perturbed-attention guidance (PAG) form: the UNet output has one more group of B rows, the perturbed prediction p
 // (rows [2B, 3B) with CFG, [B, 2B) without), and  eps = u + g * (c - u) + s * (c - p)  (CFG) or  c + s * (c - p),  s = *pag_s
-// (device: the per-step s_t of the adaptive scale).  The term is skipped when s == 0, so s = 0 gives the plain kernel's bits.
-template <bool PAG>
+// (device: the per-step s_t of the adaptive scale).  The term is skipped when s == 0 (ps = 0 without PAG), so s = 0 gives
+// the plain bits and the perturbed rows are never read.
 __device__ __forceinline__ float guided_eps(const f16* eps_nhwc, long lde, int B, int HW, int cfg, float g, float ps,
                                             const float* eps_factor, int b, int p, int c) {
     float e;
@@ -135,34 +139,48 @@ __device__ __forceinline__ float guided_eps(const f16* eps_nhwc, long lde, int B
         const float u = (float)eps_nhwc[((long)b * HW + p) * lde + c];
         const float t = (float)eps_nhwc[((long)(B + b) * HW + p) * lde + c];
         e = u + g * (t - u);
-        if (PAG && ps != 0.f) e = e + ps * (t - (float)eps_nhwc[((long)(2 * B + b) * HW + p) * lde + c]);
+        if (ps != 0.f) e = e + ps * (t - (float)eps_nhwc[((long)(2 * B + b) * HW + p) * lde + c]);
         if (eps_factor) e *= eps_factor[b];
     } else {
         e = (float)eps_nhwc[((long)b * HW + p) * lde + c];
-        if (PAG && ps != 0.f) e = e + ps * (e - (float)eps_nhwc[((long)(B + b) * HW + p) * lde + c]);
+        if (ps != 0.f) e = e + ps * (e - (float)eps_nhwc[((long)(B + b) * HW + p) * lde + c]);
     }
     return e;
 }
 
-template <bool PAG>
+// The update of element o, written once for the NHWC and the fp32 step.  k = {sb, sa, k_x0, k_x, k_eps, k_noise, k_h}; a term
+// whose coefficient is 0 is skipped.  hist (optional, multistep solvers such as DPM++ 2M) holds m_prev on entry and this
+// step's x0 on exit: each element is read, then overwritten by the thread that owns it, so one captured launch serves every
+// step.  With k_h == 0 the plane is never loaded (it is uninitialised or stale on a solver's first step, and 0 * NaN would
+// leak into prev).
+__device__ __forceinline__ void sched_update(float e, long o, const float (&k)[7], const float* x, const float* noise, float* hist,
+                                             float* prev, float* x0_out) {
+    const float xv = x[o];
+    const float x0 = (xv - k[0] * e) / k[1];
+    float pv = k[2] * x0 + k[3] * xv;
+    if (k[4] != 0.f) pv = pv + k[4] * e;
+    if (hist && k[6] != 0.f) pv = pv + k[6] * hist[o];
+    if (noise && k[5] != 0.f) pv = pv + k[5] * noise[o];
+    prev[o] = pv;
+    if (hist) hist[o] = x0;
+    if (x0_out) x0_out[o] = x0;
+}
+
+// One thread per latent pixel; pag_s, noise, hist, x0_out, eps_out and eps_factor are optional (every branch on them is
+// wave-uniform).  coef is read once, before the channel loop: prev may alias it as far as the compiler knows.
 __global__ void sched_step_kernel(const f16* eps_nhwc, long lde, int B, int C, int HW, int cfg, const float* coef,
-                                  const float* pag_s, const float* x, const float* noise, float* prev, float* x0_out,
-                                  float* eps_out, const float* eps_factor) {
+                                  const float* pag_s, const float* x, const float* noise, float* hist, float* prev,
+                                  float* x0_out, float* eps_out, const float* eps_factor) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)B * HW) return;
     const int b = (int)(i / HW), p = (int)(i % HW);
-    const float g = coef[0], sb = coef[1], sa = coef[2], k0 = coef[3], k1 = coef[4], k2 = coef[5], k3 = coef[6];
-    const float ps = PAG ? *pag_s : 0.f;
+    const float g = coef[0];
+    const float k[7] = {coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7]};
+    const float ps = pag_s ? *pag_s : 0.f;
     for (int c = 0; c < C; ++c) {
         const long o = ((long)b * C + c) * HW + p;
-        const float e = guided_eps<PAG>(eps_nhwc, lde, B, HW, cfg, g, ps, eps_factor, b, p, c);
-        const float xv = x[o];
-        const float x0 = (xv - sb * e) / sa;
-        float pv = k0 * x0 + k1 * xv;
-        if (k2 != 0.f) pv = pv + k2 * e;
-        if (noise && k3 != 0.f) pv = pv + k3 * noise[o];
-        prev[o] = pv;
-        if (x0_out) x0_out[o] = x0;
+        const float e = guided_eps(eps_nhwc, lde, B, HW, cfg, g, ps, eps_factor, b, p, c);
+        sched_update(e, o, k, x, noise, hist, prev, x0_out);
         if (eps_out) eps_out[o] = e;
     }
 }
@@ -206,49 +224,6 @@ __global__ void transpose_kernel(const f16* in, long ldi, int rows, int cols, f1
     }
 }
 
-// The same pack with the scale read from device memory (sigma schedulers: the UNet input c_in * x changes every step, and
-// a host float would be baked into a captured graph).  Same expression as pack_latent_kernel, so equal scales give equal bits.
-template <typename E>
-__global__ void pack_latent_dscale_kernel(const float* x, int B, int C, int HW, E* out, long ldo, int rep, const float* scale_dev) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)B * HW) return;
-    const float scale = *scale_dev;
-    const int b = (int)(i / HW), p = (int)(i % HW);
-    for (int c = 0; c < C; ++c) {
-        const E v = (E)(x[((long)b * C + c) * HW + p] * scale);
-        for (int k = 0; k < rep; ++k) out[((long)(k * B + b) * HW + p) * ldo + c] = v;
-    }
-}
-
-// sched_step_kernel plus one history term (multistep solvers, DPM++ 2M):
-//   prev = k_x0 * x0 + k_x * x + k_eps * eps + k_h * m_prev + k_noise * noise ,  coef[7] = k_h
-// hist (fp32 NCHW, B rows) holds m_prev on entry and this step's x0 on exit: each element is read, then overwritten by the
-// thread that owns it, so one captured launch serves every step.  With k_h == 0 the plane is never loaded (it is
-// uninitialised or stale on a solver's first step, and 0 * NaN would leak into prev).
-template <bool PAG>
-__global__ void sched_step_hist_kernel(const f16* eps_nhwc, long lde, int B, int C, int HW, int cfg, const float* coef,
-                                       const float* pag_s, const float* x, const float* noise, float* hist, float* prev,
-                                       float* x0_out, const float* eps_factor) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)B * HW) return;
-    const int b = (int)(i / HW), p = (int)(i % HW);
-    const float g = coef[0], sb = coef[1], sa = coef[2], k0 = coef[3], k1 = coef[4], k2 = coef[5], k3 = coef[6], kh = coef[7];
-    const float ps = PAG ? *pag_s : 0.f;
-    for (int c = 0; c < C; ++c) {
-        const long o = ((long)b * C + c) * HW + p;
-        const float e = guided_eps<PAG>(eps_nhwc, lde, B, HW, cfg, g, ps, eps_factor, b, p, c);
-        const float xv = x[o];
-        const float x0 = (xv - sb * e) / sa;
-        float pv = k0 * x0 + k1 * xv;
-        if (k2 != 0.f) pv = pv + k2 * e;
-        if (kh != 0.f) pv = pv + kh * hist[o];
-        if (noise && k3 != 0.f) pv = pv + k3 * noise[o];
-        prev[o] = pv;
-        hist[o] = x0;
-        if (x0_out) x0_out[o] = x0;
-    }
-}
-
 // Batched 16-byte copies: job j of the device table {src, dst, units} copies `units` x 16 bytes (blockIdx.y = job).
 __global__ void copy_segments_kernel(const long long* jobs) {
     const long long* jb = jobs + 3 * blockIdx.y;
@@ -259,6 +234,54 @@ __global__ void copy_segments_kernel(const long long* jobs) {
 }
 
 inline int nblk(long n, int t) { return (int)((n + t - 1) / t); }
+
+// One launcher per family: the validation the exported entries share is here, what an entry refuses on its own (a missing
+// pag_scale / hist / device scale) is in its forwarder below.
+template <typename... A>
+int launch_1d(void (*kern)(A...), long n, void* stream, A... args) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(kern, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, args...);
+    return iir_launch_status();
+}
+
+int launch_pack(const float* x, int B, int C, int HW, void* out, long ldo, int rep, float scale, const float* scale_dev, int dtype,
+                void* stream) {
+    if (!x || !out || B <= 0 || C <= 0 || HW <= 0 || rep <= 0 || ldo < C) return IIR_EINVAL;
+    if (dtype == IIR_DT_BF16) return launch_1d(pack_latent_kernel<bf16>, (long)B * HW, stream, x, B, C, HW, (bf16*)out, ldo, rep, scale, scale_dev);
+    if (dtype == IIR_DT_F16) return launch_1d(pack_latent_kernel<f16>, (long)B * HW, stream, x, B, C, HW, (f16*)out, ldo, rep, scale, scale_dev);
+    return IIR_EINVAL;
+}
+
+int launch_unpack(const void* in, long ldi, int R, int C, int HW, float* out, int dtype, void* stream) {
+    if (!in || !out || R <= 0 || C <= 0 || HW <= 0 || ldi < C) return IIR_EINVAL;
+    if (dtype == IIR_DT_BF16) return launch_1d(unpack_latent_kernel<bf16>, (long)R * HW, stream, (const bf16*)in, ldi, R, C, HW, out);
+    if (dtype == IIR_DT_F16) return launch_1d(unpack_latent_kernel<f16>, (long)R * HW, stream, (const f16*)in, ldi, R, C, HW, out);
+    return IIR_EINVAL;
+}
+
+int launch_cfg_rescale(const void* eps_nhwc, long lde, int B, int C, int HW, const float* coef, const float* pag_s, float phi,
+                       float* factor, void* stream) {
+    if (!eps_nhwc || !coef || !factor || B <= 0 || C <= 0 || HW <= 0 || lde < C || (long)C * HW < 2) return IIR_EINVAL;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(cfg_rescale_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, (const f16*)eps_nhwc, lde, B, C, HW, coef,
+                       pag_s, phi, factor);
+    return iir_launch_status();
+}
+
+// hist, when given, is read and rewritten per element: it may not be one of the other planes
+inline bool hist_aliases(const float* hist, const float* x, const float* prev, const float* x0_out) {
+    return hist && (hist == x || hist == prev || hist == x0_out);
+}
+
+int launch_sched_step(const void* eps_nhwc, long lde, int B, int C, int HW, int cfg, const float* coef, const float* pag_s,
+                      const float* x, const float* noise, float* hist, float* prev, float* x0_out, float* eps_out,
+                      const float* eps_factor, void* stream) {
+    if (!eps_nhwc || !coef || !x || !prev || B <= 0 || C <= 0 || HW <= 0 || lde < C) return IIR_EINVAL;
+    if (eps_factor && !cfg) return IIR_EINVAL;
+    if (hist_aliases(hist, x, prev, x0_out)) return IIR_EINVAL;
+    return launch_1d(sched_step_kernel, (long)B * HW, stream, (const f16*)eps_nhwc, lde, B, C, HW, cfg, coef, pag_s, x, noise, hist,
+                     prev, x0_out, eps_out, eps_factor);
+}
 
 }  // namespace
 
@@ -293,107 +316,69 @@ extern "C" int iir_copy_add_f16(const void* src, int64_t lds, void* dst, int64_t
 
 extern "C" int iir_pack_latent_t(const float* x, int32_t B, int32_t C, int32_t HW, void* out, int64_t ldo, int32_t rep,
                                  float scale, int32_t dtype, void* stream) {
-    (void)hipGetLastError();
-    if (!x || !out || B <= 0 || C <= 0 || HW <= 0 || rep <= 0 || ldo < C) return IIR_EINVAL;
-    if (dtype == IIR_DT_BF16) hipLaunchKernelGGL(pack_latent_kernel<bf16>, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream, x, B, C, HW, (bf16*)out, (long)ldo, rep, scale);
-    else if (dtype == IIR_DT_F16) hipLaunchKernelGGL(pack_latent_kernel<f16>, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream, x, B, C, HW, (f16*)out, (long)ldo, rep, scale);
-    else return IIR_EINVAL;
-    return iir_launch_status();
+    return launch_pack(x, B, C, HW, out, (long)ldo, rep, scale, nullptr, dtype, stream);
 }
 
 extern "C" int iir_pack_latent(const float* x, int32_t B, int32_t C, int32_t HW, void* out, int64_t ldo, int32_t rep,
                                float scale, void* stream) {
-    return iir_pack_latent_t(x, B, C, HW, out, ldo, rep, scale, IIR_DT_F16, stream);
+    return launch_pack(x, B, C, HW, out, (long)ldo, rep, scale, nullptr, IIR_DT_F16, stream);
 }
 
 extern "C" int iir_pack_latent_dscale(const float* x, int32_t B, int32_t C, int32_t HW, void* out, int64_t ldo, int32_t rep,
                                       const float* scale, int32_t dtype, void* stream) {
-    (void)hipGetLastError();
-    if (!x || !out || !scale || B <= 0 || C <= 0 || HW <= 0 || rep <= 0 || ldo < C) return IIR_EINVAL;
-    if (dtype != IIR_DT_F16 && dtype != IIR_DT_BF16) return IIR_EINVAL;
-    if (dtype == IIR_DT_BF16) hipLaunchKernelGGL(pack_latent_dscale_kernel<bf16>, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream, x, B, C, HW, (bf16*)out, (long)ldo, rep, scale);
-    else hipLaunchKernelGGL(pack_latent_dscale_kernel<f16>, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream, x, B, C, HW, (f16*)out, (long)ldo, rep, scale);
-    return iir_launch_status();
+    if (!scale) return IIR_EINVAL;
+    return launch_pack(x, B, C, HW, out, (long)ldo, rep, 1.0f, scale, dtype, stream);
 }
 
 extern "C" int iir_unpack_latent_t(const void* in, int64_t ldi, int32_t R, int32_t C, int32_t HW, float* out, int32_t dtype,
                                    void* stream) {
-    (void)hipGetLastError();
-    if (!in || !out || R <= 0 || C <= 0 || HW <= 0 || ldi < C) return IIR_EINVAL;
-    if (dtype == IIR_DT_BF16) hipLaunchKernelGGL(unpack_latent_kernel<bf16>, dim3(nblk((long)R * HW, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)in, (long)ldi, R, C, HW, out);
-    else if (dtype == IIR_DT_F16) hipLaunchKernelGGL(unpack_latent_kernel<f16>, dim3(nblk((long)R * HW, 256)), dim3(256), 0, (hipStream_t)stream, (const f16*)in, (long)ldi, R, C, HW, out);
-    else return IIR_EINVAL;
-    return iir_launch_status();
+    return launch_unpack(in, (long)ldi, R, C, HW, out, dtype, stream);
 }
 
 extern "C" int iir_unpack_latent(const void* in, int64_t ldi, int32_t R, int32_t C, int32_t HW, float* out, void* stream) {
-    return iir_unpack_latent_t(in, ldi, R, C, HW, out, IIR_DT_F16, stream);
+    return launch_unpack(in, (long)ldi, R, C, HW, out, IIR_DT_F16, stream);
 }
 
 extern "C" int iir_cfg_rescale_factor(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, const float* coef,
                                       float guidance_rescale, float* factor, void* stream) {
-    (void)hipGetLastError();
-    if (!eps_nhwc || !coef || !factor || B <= 0 || C <= 0 || HW <= 0 || lde < C || (long)C * HW < 2) return IIR_EINVAL;
-    hipLaunchKernelGGL(cfg_rescale_kernel<false>, dim3(B), dim3(1024), 0, (hipStream_t)stream, (const f16*)eps_nhwc, (long)lde, B, C,
-                       HW, coef, (const float*)nullptr, guidance_rescale, factor);
-    return iir_launch_status();
+    return launch_cfg_rescale(eps_nhwc, (long)lde, B, C, HW, coef, nullptr, guidance_rescale, factor, stream);
 }
 
 extern "C" int iir_cfg_rescale_factor_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, const float* coef,
                                           const float* pag_scale, float guidance_rescale, float* factor, void* stream) {
-    if (!eps_nhwc || !coef || !pag_scale || !factor || B <= 0 || C <= 0 || HW <= 0 || lde < C || (long)C * HW < 2) return IIR_EINVAL;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(cfg_rescale_kernel<true>, dim3(B), dim3(1024), 0, (hipStream_t)stream, (const f16*)eps_nhwc, (long)lde, B, C,
-                       HW, coef, pag_scale, guidance_rescale, factor);
-    return iir_launch_status();
+    if (!pag_scale) return IIR_EINVAL;
+    return launch_cfg_rescale(eps_nhwc, (long)lde, B, C, HW, coef, pag_scale, guidance_rescale, factor, stream);
 }
 
 extern "C" int iir_sched_step(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
                               const float* coef, const float* x, const float* noise, float* prev, float* x0_out,
                               float* eps_out, const float* eps_factor, void* stream) {
-    (void)hipGetLastError();
-    if (!eps_nhwc || !coef || !x || !prev || B <= 0 || C <= 0 || HW <= 0 || lde < C) return IIR_EINVAL;
-    if (eps_factor && !cfg) return IIR_EINVAL;
-    hipLaunchKernelGGL(sched_step_kernel<false>, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const f16*)eps_nhwc, (long)lde, B, C, HW, cfg, coef, (const float*)nullptr, x, noise, prev, x0_out, eps_out,
-                       eps_factor);
-    return iir_launch_status();
+    return launch_sched_step(eps_nhwc, (long)lde, B, C, HW, cfg, coef, nullptr, x, noise, nullptr, prev, x0_out, eps_out, eps_factor,
+                             stream);
 }
 
 extern "C" int iir_sched_step_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
                                   const float* coef, const float* pag_scale, const float* x, const float* noise, float* prev,
                                   float* x0_out, float* eps_out, const float* eps_factor, void* stream) {
-    if (!eps_nhwc || !coef || !pag_scale || !x || !prev || B <= 0 || C <= 0 || HW <= 0 || lde < C) return IIR_EINVAL;
-    if (eps_factor && !cfg) return IIR_EINVAL;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(sched_step_kernel<true>, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const f16*)eps_nhwc, (long)lde, B, C, HW, cfg, coef, pag_scale, x, noise, prev, x0_out, eps_out, eps_factor);
-    return iir_launch_status();
+    if (!pag_scale) return IIR_EINVAL;
+    return launch_sched_step(eps_nhwc, (long)lde, B, C, HW, cfg, coef, pag_scale, x, noise, nullptr, prev, x0_out, eps_out,
+                             eps_factor, stream);
 }
 
 extern "C" int iir_sched_step_hist(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
                                    const float* coef, const float* x, const float* noise, float* hist, float* prev, float* x0_out,
                                    const float* eps_factor, void* stream) {
-    (void)hipGetLastError();
-    if (!eps_nhwc || !coef || !x || !hist || !prev || B <= 0 || C <= 0 || HW <= 0 || lde < C) return IIR_EINVAL;
-    if (eps_factor && !cfg) return IIR_EINVAL;
-    if (hist == x || hist == prev || (x0_out && hist == x0_out)) return IIR_EINVAL;
-    hipLaunchKernelGGL(sched_step_hist_kernel<false>, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const f16*)eps_nhwc, (long)lde, B, C, HW, cfg, coef, (const float*)nullptr, x, noise, hist, prev, x0_out,
-                       eps_factor);
-    return iir_launch_status();
+    if (!hist) return IIR_EINVAL;
+    return launch_sched_step(eps_nhwc, (long)lde, B, C, HW, cfg, coef, nullptr, x, noise, hist, prev, x0_out, nullptr, eps_factor,
+                             stream);
 }
 
 extern "C" int iir_sched_step_hist_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
                                        const float* coef, const float* pag_scale, const float* x, const float* noise, float* hist,
                                        float* prev, float* x0_out, const float* eps_factor, void* stream) {
-    if (!eps_nhwc || !coef || !pag_scale || !x || !hist || !prev || B <= 0 || C <= 0 || HW <= 0 || lde < C) return IIR_EINVAL;
-    if (eps_factor && !cfg) return IIR_EINVAL;
-    if (hist == x || hist == prev || (x0_out && hist == x0_out)) return IIR_EINVAL;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(sched_step_hist_kernel<true>, dim3(nblk((long)B * HW, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const f16*)eps_nhwc, (long)lde, B, C, HW, cfg, coef, pag_scale, x, noise, hist, prev, x0_out, eps_factor);
-    return iir_launch_status();
+    if (!pag_scale || !hist) return IIR_EINVAL;
+    return launch_sched_step(eps_nhwc, (long)lde, B, C, HW, cfg, coef, pag_scale, x, noise, hist, prev, x0_out, nullptr, eps_factor,
+                             stream);
 }
 
 extern "C" int iir_copy_segments(const void* jobs, int32_t njobs, int64_t max_units, void* stream) {
@@ -448,37 +433,14 @@ extern "C" int iir_timing_elapsed_us(void* start, void* stop, float* us) {
 extern "C" int iir_abi_version(void) { return IIR_ABI_VERSION; }
 
 namespace {
-// Scheduler update on fp32 NCHW tensors (the scheduler objects' .step() API):
-//   x0 = (x - sb * eps) / sa ; prev = k0*x0 + k1*x + k2*eps + k3*noise ; coef = {_, sb, sa, k0, k1, k2, k3, _}
-__global__ void sched_step_f32_kernel(const float* eps, const float* x, const float* noise, const float* coef, long n,
+// Scheduler update on fp32 NCHW tensors (the scheduler objects' .step() API): sched_update on eps given in fp32, no guidance;
+// coef = {_, sb, sa, k_x0, k_x, k_eps, k_noise, k_h}, hist optional
+__global__ void sched_step_f32_kernel(const float* eps, const float* x, const float* noise, const float* coef, float* hist, long n,
                                       float* prev, float* x0_out) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float sb = coef[1], sa = coef[2], k0 = coef[3], k1 = coef[4], k2 = coef[5], k3 = coef[6];
-    const float e = eps[i], xv = x[i];
-    const float x0 = (xv - sb * e) / sa;
-    float pv = k0 * x0 + k1 * xv;
-    if (k2 != 0.f) pv = pv + k2 * e;
-    if (noise && k3 != 0.f) pv = pv + k3 * noise[i];
-    prev[i] = pv;
-    if (x0_out) x0_out[i] = x0;
-}
-// sched_step_f32_kernel plus the history term of sched_step_hist_kernel (coef[7] = k_h; hist read only when k_h != 0,
-// then overwritten with x0)
-__global__ void sched_step_hist_f32_kernel(const float* eps, const float* x, const float* noise, const float* coef, float* hist,
-                                           long n, float* prev, float* x0_out) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float sb = coef[1], sa = coef[2], k0 = coef[3], k1 = coef[4], k2 = coef[5], k3 = coef[6], kh = coef[7];
-    const float e = eps[i], xv = x[i];
-    const float x0 = (xv - sb * e) / sa;
-    float pv = k0 * x0 + k1 * xv;
-    if (k2 != 0.f) pv = pv + k2 * e;
-    if (kh != 0.f) pv = pv + kh * hist[i];
-    if (noise && k3 != 0.f) pv = pv + k3 * noise[i];
-    prev[i] = pv;
-    hist[i] = x0;
-    if (x0_out) x0_out[i] = x0;
+    const float k[7] = {coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7]};
+    sched_update(eps[i], i, k, x, noise, hist, prev, x0_out);
 }
 // a*x + b*y elementwise fp32 (add_noise: sqrt(abar)*x + sqrt(1-abar)*noise), coef = device {a, b}
 __global__ void axpby_f32_kernel(const float* x, const float* y, const float* coef, long n, float* out) {
@@ -486,25 +448,24 @@ __global__ void axpby_f32_kernel(const float* x, const float* y, const float* co
     if (i >= n) return;
     out[i] = coef[0] * x[i] + coef[1] * y[i];
 }
+
+int launch_sched_step_f32(const float* eps, const float* x, const float* noise, const float* coef, float* hist, long n, float* prev,
+                          float* x0_out, void* stream) {
+    if (!eps || !x || !coef || !prev || n <= 0) return IIR_EINVAL;
+    if (hist_aliases(hist, x, prev, x0_out) || (hist && hist == eps)) return IIR_EINVAL;
+    return launch_1d(sched_step_f32_kernel, n, stream, eps, x, noise, coef, hist, n, prev, x0_out);
+}
 }  // namespace
 
 extern "C" int iir_sched_step_f32(const float* eps, const float* x, const float* noise, const float* coef, int64_t n,
                                   float* prev, float* x0_out, void* stream) {
-    (void)hipGetLastError();
-    if (!eps || !x || !coef || !prev || n <= 0) return IIR_EINVAL;
-    hipLaunchKernelGGL(sched_step_f32_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, noise, coef,
-                       (long)n, prev, x0_out);
-    return iir_launch_status();
+    return launch_sched_step_f32(eps, x, noise, coef, nullptr, (long)n, prev, x0_out, stream);
 }
 
 extern "C" int iir_sched_step_hist_f32(const float* eps, const float* x, const float* noise, const float* coef, float* hist,
                                        int64_t n, float* prev, float* x0_out, void* stream) {
-    (void)hipGetLastError();
-    if (!eps || !x || !coef || !hist || !prev || n <= 0) return IIR_EINVAL;
-    if (hist == x || hist == eps || hist == prev || (x0_out && hist == x0_out)) return IIR_EINVAL;
-    hipLaunchKernelGGL(sched_step_hist_f32_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, eps, x, noise, coef, hist,
-                       (long)n, prev, x0_out);
-    return iir_launch_status();
+    if (!hist) return IIR_EINVAL;
+    return launch_sched_step_f32(eps, x, noise, coef, hist, (long)n, prev, x0_out, stream);
 }
 
 extern "C" int iir_axpby_f32(const float* x, const float* y, const float* coef, int64_t n, float* out, void* stream) {

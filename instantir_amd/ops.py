@@ -591,21 +591,16 @@ def freeu_concat(x, skip, dst, partials, H, W, b, s, dst_off=0, mid_add=None, ad
 
 
 def pack_latent(x, out, rep=1, scale=1.0):
-    """x fp32 (B,C,H,W) contiguous -> out 2-D fp16 view (rep*B*H*W, ld>=C)."""
+    """x fp32 (B,C,H,W) contiguous -> out 2-D fp16 view (rep*B*H*W, ld>=C).  `scale`: a float, or an fp32 CUDA tensor (one
+    element) read at launch time (iir_pack_latent_dscale)."""
     B, Cc, H, Wd = x.shape
     assert x.dtype == torch.float32 and x.is_contiguous() and out.dtype in _DT
-    L.check(L.load().iir_pack_latent_t(x.data_ptr(), B, Cc, H * Wd, out.data_ptr(), out.stride(0), rep, scale, _DT[out.dtype],
-                                       _stream()), "iir_pack_latent_t")
-    return out
-
-
-def pack_latent_dscale(x, out, scale, rep=1):
-    """pack_latent with the scale read from `scale` (fp32 CUDA tensor, one element) at launch time."""
-    B, Cc, H, Wd = x.shape
-    assert x.dtype == torch.float32 and x.is_contiguous() and out.dtype in _DT
-    assert scale.dtype == torch.float32 and scale.is_cuda and scale.numel() >= 1
-    L.check(L.load().iir_pack_latent_dscale(x.data_ptr(), B, Cc, H * Wd, out.data_ptr(), out.stride(0), rep, scale.data_ptr(),
-                                            _DT[out.dtype], _stream()), "iir_pack_latent_dscale")
+    h, args = L.load(), (x.data_ptr(), B, Cc, H * Wd, out.data_ptr(), out.stride(0), rep)
+    if torch.is_tensor(scale):
+        assert scale.dtype == torch.float32 and scale.is_cuda and scale.numel() >= 1
+        L.check(h.iir_pack_latent_dscale(*args, scale.data_ptr(), _DT[out.dtype], _stream()), "iir_pack_latent_dscale")
+    else:
+        L.check(h.iir_pack_latent_t(*args, scale, _DT[out.dtype], _stream()), "iir_pack_latent_t")
     return out
 
 
@@ -623,34 +618,27 @@ def _chk_pag(pag_scale):
         raise ValueError("pag_scale must be a CUDA fp32 tensor (the step's s_t, read at launch time)")
 
 
-def sched_step(eps2d, B, coef, x, prev, noise=None, cfg=True, x0_out=None, eps_out=None, eps_factor=None, pag_scale=None):
-    """`pag_scale` (device fp32[1]): the PAG form -- eps2d holds the perturbed rows after the cond rows (iir_sched_step_pag)."""
-    _, Cc, H, Wd = x.shape
-    if pag_scale is not None:
-        _chk_pag(pag_scale)
-        L.check(L.load().iir_sched_step_pag(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(),
-                                            pag_scale.data_ptr(), x.data_ptr(), _p(noise), prev.data_ptr(), _p(x0_out), _p(eps_out),
-                                            _p(eps_factor), _stream()), "iir_sched_step_pag")
-        return prev
-    L.check(L.load().iir_sched_step(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(),
-                                    x.data_ptr(), _p(noise), prev.data_ptr(), _p(x0_out), _p(eps_out), _p(eps_factor),
-                                    _stream()), "iir_sched_step")
-    return prev
+def _pag_entry(name, pag_scale):
+    """(exported entry, its name, the pag_scale argument list) of `name` or its PAG form."""
+    if pag_scale is None:
+        return getattr(L.load(), name), name, []
+    _chk_pag(pag_scale)
+    return getattr(L.load(), name + "_pag"), name + "_pag", [pag_scale.data_ptr()]
 
 
-def sched_step_hist(eps2d, B, coef, x, hist, prev, noise=None, cfg=True, x0_out=None, eps_factor=None, pag_scale=None):
-    """sched_step with the history term coef[7] * hist; `hist` (shape of x, fp32) then holds this step's x0."""
+def sched_step(eps2d, B, coef, x, prev, noise=None, cfg=True, x0_out=None, eps_out=None, eps_factor=None, pag_scale=None, hist=None):
+    """`pag_scale` (device fp32[1]): the PAG form -- eps2d holds the perturbed rows after the cond rows (iir_sched_step*_pag).
+    `hist` (shape of x, fp32): adds the history term coef[7] * hist and then holds this step's x0 (iir_sched_step_hist*)."""
     _, Cc, H, Wd = x.shape
-    assert hist.shape == x.shape and hist.dtype == torch.float32 and hist.is_contiguous()
-    if pag_scale is not None:
-        _chk_pag(pag_scale)
-        L.check(L.load().iir_sched_step_hist_pag(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(),
-                                                 pag_scale.data_ptr(), x.data_ptr(), _p(noise), hist.data_ptr(), prev.data_ptr(),
-                                                 _p(x0_out), _p(eps_factor), _stream()), "iir_sched_step_hist_pag")
-        return prev
-    L.check(L.load().iir_sched_step_hist(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(),
-                                         x.data_ptr(), _p(noise), hist.data_ptr(), prev.data_ptr(), _p(x0_out), _p(eps_factor),
-                                         _stream()), "iir_sched_step_hist")
+    outs = [prev.data_ptr(), _p(x0_out), _p(eps_out)]
+    if hist is not None:
+        assert hist.shape == x.shape and hist.dtype == torch.float32 and hist.is_contiguous()
+        if eps_out is not None:
+            raise ValueError("sched_step: eps_out is not available together with hist")
+        outs = [hist.data_ptr(), prev.data_ptr(), _p(x0_out)]
+    fn, name, ps = _pag_entry("iir_sched_step_hist" if hist is not None else "iir_sched_step", pag_scale)
+    L.check(fn(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(), *ps, x.data_ptr(), _p(noise), *outs,
+               _p(eps_factor), _stream()), name)
     return prev
 
 
@@ -658,14 +646,9 @@ def cfg_rescale_factor(eps2d, B, coef, x, guidance_rescale, factor, pag_scale=No
     """factor (B,) fp32 device: the per-image multiplier `rescale_noise_cfg` applies to the guided eps (with `pag_scale`: the
     guided eps includes the PAG term of rows [2B, 3B))."""
     _, Cc, H, Wd = x.shape
-    if pag_scale is not None:
-        _chk_pag(pag_scale)
-        L.check(L.load().iir_cfg_rescale_factor_pag(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, coef.data_ptr(),
-                                                    pag_scale.data_ptr(), float(guidance_rescale), factor.data_ptr(), _stream()),
-                "iir_cfg_rescale_factor_pag")
-        return factor
-    L.check(L.load().iir_cfg_rescale_factor(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, coef.data_ptr(),
-                                            float(guidance_rescale), factor.data_ptr(), _stream()), "iir_cfg_rescale_factor")
+    fn, name, ps = _pag_entry("iir_cfg_rescale_factor", pag_scale)
+    L.check(fn(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, coef.data_ptr(), *ps, float(guidance_rescale), factor.data_ptr(),
+               _stream()), name)
     return factor
 
 
@@ -703,18 +686,25 @@ def transpose(x, out, rows_pad):
     return out
 
 
-def sched_step_f32(eps, x, coef, prev, noise=None, x0_out=None):
-    """fp32 contiguous tensors of equal shape; coef fp32 device (8,)."""
-    L.check(L.load().iir_sched_step_f32(eps.data_ptr(), x.data_ptr(), _p(noise), coef.data_ptr(), x.numel(), prev.data_ptr(),
-                                        _p(x0_out), _stream()), "iir_sched_step_f32")
+def sched_step_f32(eps, x, coef, prev, noise=None, x0_out=None, hist=None):
+    """fp32 contiguous tensors of equal shape; coef fp32 device (8,).  `hist`: the history term, k_h in coef[7], as in sched_step."""
+    name, hp = ("iir_sched_step_f32", []) if hist is None else ("iir_sched_step_hist_f32", [hist.data_ptr()])
+    L.check(getattr(L.load(), name)(eps.data_ptr(), x.data_ptr(), _p(noise), coef.data_ptr(), *hp, x.numel(), prev.data_ptr(),
+                                    _p(x0_out), _stream()), name)
     return prev
 
 
-def sched_step_hist_f32(eps, x, coef, hist, prev, noise=None, x0_out=None):
-    """sched_step_f32 with the history term: fp32 contiguous tensors of equal shape, coef fp32 device (8,) with k_h in [7]."""
-    L.check(L.load().iir_sched_step_hist_f32(eps.data_ptr(), x.data_ptr(), _p(noise), coef.data_ptr(), hist.data_ptr(), x.numel(),
-                                             prev.data_ptr(), _p(x0_out), _stream()), "iir_sched_step_hist_f32")
-    return prev
+# The earlier spellings of the hist / device-scale forms: the GPU tests call them, and so may code outside the package.
+def sched_step_hist(eps2d, B, coef, x, hist, prev, **kw):
+    return sched_step(eps2d, B, coef, x, prev, hist=hist, **kw)
+
+
+def sched_step_hist_f32(eps, x, coef, hist, prev, **kw):
+    return sched_step_f32(eps, x, coef, prev, hist=hist, **kw)
+
+
+def pack_latent_dscale(x, out, scale, rep=1):
+    return pack_latent(x, out, rep=rep, scale=scale)
 
 
 def axpby_f32(x, y, coef, out):

@@ -1079,10 +1079,8 @@ class _DenoiseLoop:
 
     def _launch(self, mode, use_noise, want_x0, want_preview):
         p = self.p
-        if self.form == "hist":                                              # scale_model_input(cat([latents]*2), t), :1503-1504
-            ops.pack_latent_dscale(self.x_in, self.lat16, self.c_in, rep=self.groups)
-        else:
-            ops.pack_latent(self.x_in, self.lat16, rep=self.groups)          # cat([latents]*2), :1503
+        # scale_model_input(cat([latents]*2), t), :1503-1504: c_in from the step's scalar row (1 for DDPM / DDIM: x * 1 is exact)
+        ops.pack_latent(self.x_in, self.lat16, rep=self.groups, scale=self.c_in)
         if mode == "unet":
             eps = p._unet.forward(self.lat16, self.t_dev, self.st)
         elif mode == "unet_res":     # stale residuals of the last Aggregator pass, re-scaled (see __call__)
@@ -1113,11 +1111,8 @@ class _DenoiseLoop:
         fac = None
         if rep == 2 and self.guidance_rescale > 0.0:
             fac = ops.cfg_rescale_factor(eps, B, self.sched_coef, self.x_in, self.guidance_rescale, self.cfg_factor, pag_scale=ps)
-        kw = dict(noise=self.noise if use_noise else None, cfg=rep == 2, x0_out=self.x0 if want_x0 else None, eps_factor=fac, pag_scale=ps)
-        if self.form == "hist":
-            ops.sched_step_hist(eps, B, self.sched_coef, self.x_in, self.hist, self.x_out, **kw)
-        else:
-            ops.sched_step(eps, B, self.sched_coef, self.x_in, self.x_out, **kw)
+        ops.sched_step(eps, B, self.sched_coef, self.x_in, self.x_out, noise=self.noise if use_noise else None, cfg=rep == 2,
+                       x0_out=self.x0 if want_x0 else None, eps_factor=fac, pag_scale=ps, hist=self.hist)
 
     def step(self, mode, t, x, res_scale_rows, guidance, eta, noise, generator, want_x0=False, want_preview=False, i=None,
              pag_s=0.0):
@@ -1135,9 +1130,9 @@ class _DenoiseLoop:
             # eta is not an argument of these schedulers' step() (diffusers drops it): ignored
             lc = p.scheduler.loop_coefficients(i)
             c_in, t_lcm, coef = lc["c_in"], lc["t_lcm"], list(lc["coef"])
-            sc[lay["c_in"]] = c_in
         else:
             coef = p.scheduler.step_coefficients(t, eta=eta)
+        sc[lay["c_in"]] = c_in
         if mode == "preview":
             # a sigma scheduler's LCM previewer gets the scaled input c_in * x (:1555-1561) and t.to(int64) (:1557): fold c_in into
             # its coefficients so that iir_lcm_step reads the unscaled latent (c_in = 1 otherwise: / 1 and * 1 are exact)

@@ -58,6 +58,52 @@ def _dev_coef(vals, device):
     return torch.tensor(vals, dtype=torch.float32).to(device)
 
 
+def _custom_timetable(num_inference_steps, timesteps, T):
+    """A caller's own descending `timesteps` as int64, checked; None when `num_inference_steps` sets the timetable."""
+    if num_inference_steps is not None and timesteps is not None:
+        raise ValueError("Can only pass one of `num_inference_steps` or `custom_timesteps`.")
+    if timesteps is None:
+        return None
+    for i in range(1, len(timesteps)):
+        if timesteps[i] >= timesteps[i - 1]:
+            raise ValueError("`custom_timesteps` must be in descending order.")
+    if timesteps[0] >= T:
+        raise ValueError(f"`timesteps` must start before `self.config.train_timesteps`: {T}.")
+    return np.array(timesteps, dtype=np.int64)
+
+
+def _add_noise(original_samples, noise, pairs):
+    """sa * x + sb * noise with one (sa, sb) pair per batch row.  CUDA fp32 tensors with one pair for every row go through
+    the HIP kernel; anything else is computed with the same formula on its own device (host plumbing)."""
+    if original_samples.is_cuda and original_samples.dtype == torch.float32 and all(p == pairs[0] for p in pairs):
+        from . import ops
+        out = torch.empty_like(original_samples)
+        ops.axpby_f32(original_samples.contiguous(), noise.contiguous().float(), _dev_coef(list(pairs[0]), original_samples.device), out)
+        return out
+    shape = (-1,) + (1,) * (original_samples.dim() - 1)
+    sa = torch.tensor([p[0] for p in pairs], dtype=original_samples.dtype, device=original_samples.device).reshape(shape)
+    sb = torch.tensor([p[1] for p in pairs], dtype=original_samples.dtype, device=original_samples.device).reshape(shape)
+    return sa * original_samples + sb * noise
+
+
+def _run_step(model_output, sample, coef, generator=None, variance_noise=None, hist=None):
+    """One `.step()` update on the GPU (iir_sched_step_f32 / iir_sched_step_hist_f32 with `hist`): (prev, x0) in the sample's
+    dtype.  The noise is drawn here, fp32 on the generator's device, only when k_noise != 0 and none was given."""
+    from . import ops
+    noise = None
+    if coef[6] != 0.0:
+        if variance_noise is None:
+            variance_noise = torch.randn(model_output.shape, generator=generator,
+                                         device=generator.device if generator is not None else model_output.device,
+                                         dtype=torch.float32)
+        noise = variance_noise.float().contiguous().to(sample.device)
+    x = sample.float().contiguous()
+    e = model_output.float().contiguous()
+    prev, x0 = torch.empty_like(x), torch.empty_like(x)
+    ops.sched_step_f32(e, x, _dev_coef(coef, x.device), prev, noise=noise, x0_out=x0, hist=hist)
+    return prev.to(sample.dtype), x0.to(sample.dtype)
+
+
 class _Base:
     order = 1
     init_noise_sigma = 1.0
@@ -87,8 +133,12 @@ class _Base:
 
     @classmethod
     def from_config(cls, config, **kw):
+        """As diffusers: a config of any scheduler class; keys this class does not take are ignored, `kw` overrides."""
         import inspect
-        names = set(_SDXL_DEFAULTS) | (set(inspect.signature(cls.__init__).parameters) - {"self", "kw"})
+        names = set(_SDXL_DEFAULTS)
+        for k in cls.__mro__:
+            if "__init__" in vars(k):
+                names |= set(inspect.signature(k.__init__).parameters) - {"self", "kw"}
         args = {k: v for k, v in dict(config).items() if k in names}
         args.update(kw)
         return cls(**args)
@@ -98,15 +148,8 @@ class _Base:
 
     def set_timesteps(self, num_inference_steps=None, device=None, timesteps: Optional[List[int]] = None):
         T = self.config.num_train_timesteps
-        if num_inference_steps is not None and timesteps is not None:
-            raise ValueError("Can only pass one of `num_inference_steps` or `custom_timesteps`.")
-        if timesteps is not None:
-            for i in range(1, len(timesteps)):
-                if timesteps[i] >= timesteps[i - 1]:
-                    raise ValueError("`custom_timesteps` must be in descending order.")
-            if timesteps[0] >= T:
-                raise ValueError(f"`timesteps` must start before `self.config.train_timesteps`: {T}.")
-            ts = np.array(timesteps, dtype=np.int64)
+        ts = _custom_timetable(num_inference_steps, timesteps, T)
+        if ts is not None:
             self.custom_timesteps = True
             self.num_inference_steps = len(ts)
         else:
@@ -131,42 +174,21 @@ class _Base:
         return t - self.config.num_train_timesteps // n
 
     def add_noise(self, original_samples, noise, timesteps):
-        """sqrt(abar_t) x + sqrt(1-abar_t) noise, one t per batch row.  CUDA fp32 tensors go through the HIP
-        kernel; anything else is computed with the same fp32 formula on its own device (host plumbing)."""
+        """sqrt(abar_t) x + sqrt(1-abar_t) noise (the fp32 table's values), one t per batch row."""
         acp = self.alphas_cumprod
         t = torch.as_tensor(timesteps).reshape(-1).cpu().long()
         sa, sb = acp[t] ** 0.5, (1 - acp[t]) ** 0.5
-        if original_samples.is_cuda and original_samples.dtype == torch.float32 and bool((t == t[0]).all()):
-            from . import ops
-            out = torch.empty_like(original_samples)
-            ops.axpby_f32(original_samples.contiguous(), noise.contiguous().float(),
-                          _dev_coef([float(sa[0]), float(sb[0])], original_samples.device), out)
-            return out
-        shape = (-1,) + (1,) * (original_samples.dim() - 1)
-        sa = sa.to(original_samples.device, original_samples.dtype).reshape(shape)
-        sb = sb.to(original_samples.device, original_samples.dtype).reshape(shape)
-        return sa * original_samples + sb * noise
+        return _add_noise(original_samples, noise, list(zip(sa.tolist(), sb.tolist())))
 
     # coefficients of prev = k_x0*x0 + k_x*x + k_eps*eps + k_noise*noise, x0 = (x - sb*eps)/sa
     def step_coefficients(self, t, **kw):
         raise NotImplementedError
 
     def step(self, model_output, timestep, sample, eta=None, generator=None, variance_noise=None, return_dict=True, **kw):
-        from . import ops
-        t = int(timestep)
-        c = self.step_coefficients(t, eta=eta if eta is not None else 0.0)
-        need_noise = c[6] != 0.0
-        if need_noise and variance_noise is None:
-            variance_noise = torch.randn(model_output.shape, generator=generator,
-                                         device=generator.device if generator is not None else model_output.device,
-                                         dtype=torch.float32).to(model_output.device)
         if not sample.is_cuda:
             raise RuntimeError("scheduler.step: tensors must live on the GPU (the update runs in the HIP library)")
-        x = sample.float().contiguous()
-        e = model_output.float().contiguous()
-        prev, x0 = torch.empty_like(x), torch.empty_like(x)
-        ops.sched_step_f32(e, x, _dev_coef(c, x.device), prev, noise=variance_noise if need_noise else None, x0_out=x0)
-        prev, x0 = prev.to(sample.dtype), x0.to(sample.dtype)
+        c = self.step_coefficients(int(timestep), eta=eta if eta is not None else 0.0)
+        prev, x0 = _run_step(model_output, sample, c, generator, variance_noise)
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
@@ -222,16 +244,8 @@ class LCMSingleStepScheduler(_Base):
     def set_timesteps(self, num_inference_steps=None, device=None, original_inference_steps=None, strength=1.0,
                       timesteps=None):
         T = self.config.num_train_timesteps
-        if num_inference_steps is not None and timesteps is not None:
-            raise ValueError("Can only pass one of `num_inference_steps` or `custom_timesteps`.")
-        if timesteps is not None:
-            for i in range(1, len(timesteps)):
-                if timesteps[i] >= timesteps[i - 1]:
-                    raise ValueError("`custom_timesteps` must be in descending order.")
-            if timesteps[0] >= T:
-                raise ValueError(f"`timesteps` must start before `self.config.train_timesteps`: {T}.")
-            ts = np.array(timesteps, dtype=np.int64)
-        else:
+        ts = _custom_timetable(num_inference_steps, timesteps, T)
+        if ts is None:
             if num_inference_steps > T:
                 raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than {T}")
             self.num_inference_steps = num_inference_steps
@@ -263,14 +277,10 @@ class LCMSingleStepScheduler(_Base):
     def step(self, model_output, timestep, sample, generator=None, return_dict=True):
         """denoised = c_out * x0 + c_skip * sample, on the GPU via the scheduler kernel:
         prev = k_x0*x0 + k_x*x with k_x0 = c_out, k_x = c_skip."""
-        from . import ops
         if not sample.is_cuda:
             raise RuntimeError("LCMSingleStepScheduler.step: tensors must live on the GPU")
         sb, sa, c_out, c_skip = self.preview_coefficients(int(timestep))
-        x, e = sample.float().contiguous(), model_output.float().contiguous()
-        out = torch.empty_like(x)
-        ops.sched_step_f32(e, x, _dev_coef([0.0, sb, sa, c_out, c_skip, 0.0, 0.0, 0.0], x.device), out)
-        out = out.to(sample.dtype)
+        out, _ = _run_step(model_output, sample, [0.0, sb, sa, c_out, c_skip, 0.0, 0.0, 0.0])
         if not return_dict:
             return (out,)
         return SchedulerOutput(denoised=out)
@@ -329,18 +339,6 @@ class _SigmaBase(_Base):
         self.sigmas = torch.from_numpy(np.concatenate([self._sig_train[::-1], [0.0]]).astype(np.float32))
         self._reset()
 
-    @classmethod
-    def from_config(cls, config, **kw):
-        """As diffusers: a config of any scheduler class; keys this class does not take are ignored, `kw` overrides."""
-        import inspect
-        names = set(_SDXL_DEFAULTS)
-        for k in cls.__mro__:
-            if "__init__" in vars(k):
-                names |= set(inspect.signature(k.__init__).parameters) - {"self", "kw"}
-        args = {k: v for k, v in dict(config).items() if k in names}
-        args.update(kw)
-        return cls(**args)
-
     def _reset(self):
         self._step_index = None
         self._hist = None
@@ -361,6 +359,16 @@ class _SigmaBase(_Base):
     def _index(self, timestep):
         return self._step_index if self._step_index is not None else self.index_for_timestep(timestep)
 
+    def _begin_timesteps(self, num_inference_steps, timesteps, sigmas):
+        """Shared opening of the sigma schedulers' set_timesteps: (num_train_timesteps, N, timestep_spacing)."""
+        if timesteps is not None or sigmas is not None:
+            raise ValueError(f"{type(self).__name__}: custom `timesteps` / `sigmas` are not supported; pass num_inference_steps")
+        T, N = self.config.num_train_timesteps, int(num_inference_steps)
+        if N > T or N < 1:
+            raise ValueError(f"`num_inference_steps`: {N} must be in [1, {T}]")
+        self.num_inference_steps = N
+        return T, N, self.config.timestep_spacing
+
     def _set(self, timesteps, sigmas, device):
         self.timesteps = torch.from_numpy(np.asarray(timesteps)).to(device=device)
         self.sigmas = torch.from_numpy(np.asarray(sigmas, dtype=np.float32))
@@ -372,16 +380,7 @@ class _SigmaBase(_Base):
     def add_noise(self, original_samples, noise, timesteps):
         """sa_i * x0 + sb_i * noise with the noise-level pair of each row's timestep (`_noise_pair`)."""
         ts = torch.as_tensor(timesteps).reshape(-1)
-        pairs = [self._noise_pair(self.index_for_timestep(t)) for t in ts]
-        if original_samples.is_cuda and original_samples.dtype == torch.float32 and all(p == pairs[0] for p in pairs):
-            from . import ops
-            out = torch.empty_like(original_samples)
-            ops.axpby_f32(original_samples.contiguous(), noise.contiguous().float(), _dev_coef(list(pairs[0]), original_samples.device), out)
-            return out
-        shape = (-1,) + (1,) * (original_samples.dim() - 1)
-        sa = torch.tensor([p[0] for p in pairs], dtype=original_samples.dtype, device=original_samples.device).reshape(shape)
-        sb = torch.tensor([p[1] for p in pairs], dtype=original_samples.dtype, device=original_samples.device).reshape(shape)
-        return sa * original_samples + sb * noise
+        return _add_noise(original_samples, noise, [self._noise_pair(self.index_for_timestep(t)) for t in ts])
 
     def loop_coefficients(self, i):
         """Step i of the denoising loop, run from step 0: c_in (UNet input scale), the UNet / Aggregator timestep (float),
@@ -395,7 +394,6 @@ class _SigmaBase(_Base):
         return 1
 
     def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict=True, s_churn=0.0, **kw):
-        from . import ops
         if s_churn and s_churn > 0:
             _refuse("s_churn", s_churn, "stochastic churn is not implemented")
         if self.num_inference_steps is None:
@@ -406,21 +404,12 @@ class _SigmaBase(_Base):
             self._step_index = self.index_for_timestep(timestep)
         i = self._step_index
         c = [float(np.float32(v)) for v in self._coefficients64(i, self._order_at(i, self._lower_order_nums))]
-        need_noise = c[6] != 0.0
-        if need_noise and variance_noise is None:
-            variance_noise = torch.randn(model_output.shape, generator=generator,
-                                         device=generator.device if generator is not None else model_output.device,
-                                         dtype=torch.float32).to(model_output.device)
-        x = sample.float().contiguous()
-        e = model_output.float().contiguous()
-        if self._hist is None or self._hist.shape != x.shape or self._hist.device != x.device:
-            self._hist = torch.empty_like(x)              # never read on a first-order step (k_h == 0)
-        prev, x0 = torch.empty_like(x), torch.empty_like(x)
-        ops.sched_step_hist_f32(e, x, _dev_coef(c, x.device), self._hist, prev,
-                                noise=variance_noise.float().contiguous().to(x.device) if need_noise else None, x0_out=x0)
+        if self._hist is None or self._hist.shape != sample.shape or self._hist.device != sample.device:
+            # never read on a first-order step (k_h == 0)
+            self._hist = torch.empty(sample.shape, dtype=torch.float32, device=sample.device)
+        prev, x0 = _run_step(model_output, sample, c, generator, variance_noise, hist=self._hist)
         self._step_index += 1
         self._lower_order_nums = min(self._lower_order_nums + 1, self.config.get("solver_order", 1))
-        prev, x0 = prev.to(sample.dtype), x0.to(sample.dtype)
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev, pred_original_sample=x0)
@@ -446,13 +435,7 @@ class _EulerBase(_SigmaBase):
         return m if self.config.timestep_spacing in ("linspace", "trailing") else (m ** 2 + 1) ** 0.5
 
     def set_timesteps(self, num_inference_steps=None, device=None, timesteps=None, sigmas=None):
-        if timesteps is not None or sigmas is not None:
-            raise ValueError(f"{type(self).__name__}: custom `timesteps` / `sigmas` are not supported; pass num_inference_steps")
-        T, N = self.config.num_train_timesteps, int(num_inference_steps)
-        if N > T or N < 1:
-            raise ValueError(f"`num_inference_steps`: {N} must be in [1, {T}]")
-        self.num_inference_steps = N
-        sp = self.config.timestep_spacing
+        T, N, sp = self._begin_timesteps(num_inference_steps, timesteps, sigmas)
         if sp == "linspace":
             ts = np.linspace(0, T - 1, N, dtype=np.float32)[::-1].copy()
         elif sp == "leading":
@@ -535,13 +518,7 @@ class DPMSolverMultistepScheduler(_SigmaBase):
         return self.config.solver_order
 
     def set_timesteps(self, num_inference_steps=None, device=None, timesteps=None, sigmas=None):
-        if timesteps is not None or sigmas is not None:
-            raise ValueError(f"{type(self).__name__}: custom `timesteps` / `sigmas` are not supported; pass num_inference_steps")
-        T, N = self.config.num_train_timesteps, int(num_inference_steps)
-        if N > T or N < 1:
-            raise ValueError(f"`num_inference_steps`: {N} must be in [1, {T}]")
-        self.num_inference_steps = N
-        sp = self.config.timestep_spacing
+        T, N, sp = self._begin_timesteps(num_inference_steps, timesteps, sigmas)
         if sp == "linspace":
             ts = np.linspace(0, T - 1, N + 1).round()[::-1][:-1].copy().astype(np.int64)
         elif sp == "leading":

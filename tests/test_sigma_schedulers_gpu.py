@@ -111,6 +111,18 @@ def test_sched_step_hist_never_reads_history_when_kh_is_zero(dev):
     assert torch.equal(prev, ref) and torch.equal(hist, x0) and torch.isfinite(hf).all()
 
 
+def test_update_bits_match_the_recorded_library(dev, golden_dir):
+    """Every output buffer of the exported pack / CFG-rescale / scheduler-step entries, replayed on seeded inputs, against the
+    bits recorded in tests/golden/sched_update_bits.npz (tests/golden/make_sched_update_bits.py) before the kernels behind
+    those entries were folded into one per family."""
+    from golden.make_sched_update_bits import replay
+    want = np.load(os.path.join(golden_dir, "sched_update_bits.npz"))
+    got = replay()
+    assert sorted(got) == sorted(want.files)
+    bad = [k for k in want.files if not np.array_equal(got[k], want[k])]
+    assert not bad, bad
+
+
 @pytest.mark.parametrize("B,H,W,rep", [(1, 128, 128, 2), (2, 5, 7, 1), (2, 16, 16, 2)])
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 def test_device_scale_pack_bit_identical_to_host_scale(dev, B, H, W, rep, dtype):
