@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the InstantIR denoising step on MI355X (BASELINE.json metric: denoising steps/sec).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]     (e.g. DIR = bench_outputs/, git-ignored)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]     (e.g. DIR = bench_outputs/, git-ignored)
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Workload (BASELINE.json configs[1], the configuration the metric is quoted on): one 1024x1024 image
@@ -14,7 +14,11 @@ weights are broadcast once from rank 0 over RCCL before the timed region.
 
 Timed region: K steps replayed from the captured hipGraph of the step, inputs resident in HBM,
 bracketed by barrier + synchronize; max over ranks; value = N*K / time.
-roofline: a separate, eager pass of 2 steps (queued behind a spin kernel so launches run back to back) where every
+A plain run stops there: set-up, warm-up, the timed steps, --dump-outputs, the JSON line (its "roofline", "cpu_baseline", "vae"
+and "end_to_end" fields are null).  --full adds the legs below, each after the timed region and each with a switch of its own
+(--no-vae, --no-e2e, --no-roofline, --no-cpu-baseline) that leaves it out of a --full run.
+vae, end_to_end (--full): the SDXL VAE's decode and encode of one image, and one whole `pipe(...)` call (see end_to_end_leg).
+roofline (--full): a separate, eager pass of 2 steps (queued behind a spin kernel so launches run back to back) where every
 MFMA-kernel launch carries a HIP start/stop event pair stamped with the kernel's own begin / end timestamps on its stream
 (hipExtLaunchKernelGGL inside the library); the kernel class with the largest total time is reported against the dense
 fp16 MFMA peak (2.5 PFLOP/s, MI355X_MICROARCH.md).  Algorithmic FLOPs per launch = 2*M*N*K (GEMM /
@@ -22,7 +26,7 @@ implicit-GEMM conv) or 4*B*h*Tq*Tkv*64 (attention).
 --dump-outputs DIR: after the timed steps, what the timed path returned in its last step (the latents it wrote back) is saved
 as DIR/<name>.npy in float32 (ranks > 0 add _rank<r>); inputs and weights are seeded, so two builds run with the same arguments
 can be compared output for output.
-cpu_baseline: the CPU fp32 oracle (oracle/, kind "port") timed on the host cores for a bounded sample
+cpu_baseline (--full): the CPU fp32 oracle (oracle/, kind "port") timed on the host cores for a bounded sample
 (one UNet forward of one row at the same resolution), converted with SURVEY.md section 8d's FLOP model.
 """
 import argparse
@@ -149,11 +153,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--size", type=int, default=1024, help="image side (pixels)")
     ap.add_argument("--tiny", action="store_true", help="tiny geometry (debug only, not a valid bench)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the VAE, end-to-end, roofline and CPU-baseline legs (off by default: a plain "
+                         "run measures the headline figure only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="leave the CPU-baseline leg out of a --full run")
+    ap.add_argument("--no-roofline", action="store_true", help="leave the roofline leg out of a --full run")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-vae", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end pipe(...) call (images/s measured)")
+    ap.add_argument("--no-vae", action="store_true", help="leave the VAE legs (and the end-to-end call, which needs the VAE) out of a --full run")
+    ap.add_argument("--no-e2e", action="store_true", help="leave the end-to-end pipe(...) call (images/s measured) out of a --full run")
     ap.add_argument("--no-inkernel-prefetch", action="store_true")
     ap.add_argument("--no-overlap", action="store_true", help="single stream (no encoder/previewer overlap)")
     ap.add_argument("--rows", type=int, default=2, choices=[1, 2],
@@ -169,6 +176,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:      # a plain run: the headline figure only, none of the legs that follow the timed region
+        args.no_cpu_baseline = args.no_roofline = args.no_vae = args.no_e2e = True
 
     # ---- launch contract: `--gpus N` must mean N ranks.  Under torch.distributed.run WORLD_SIZE says how many there are;
     # a bare `python bench.py --gpus N` (N > 1) starts the N ranks itself as a CHILD process group (torchrun on

@@ -27,7 +27,7 @@ def leg(pipe, cfg, hv, dev, px, lcm, seed):
     r = orig_leg(pipe, cfg, hv, dev, px, lcm, seed)
     return r
 B.end_to_end_leg = leg
-sys.argv = ["bench.py", "--no-cpu-baseline", "--no-roofline", "--steps", "5"]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--no-roofline", "--steps", "5"]
 import runpy
 try:
     B.main() if hasattr(B, "main") else runpy.run_module("bench", run_name="__main__")

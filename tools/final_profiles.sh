@@ -8,8 +8,8 @@ R=$PWD
 O=$R/gpurun_out/final
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $R
-echo "[1/5] bench"; python bench.py 2> $O/bench.stderr | tail -1 > $O/bench.json
-echo "[2/5] kernel trace"; rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --no-cpu-baseline > $O/bench_under_rocprof.log 2>&1
+echo "[1/5] bench"; python bench.py --full 2> $O/bench.stderr | tail -1 > $O/bench.json
+echo "[2/5] kernel trace"; rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --full --no-cpu-baseline > $O/bench_under_rocprof.log 2>&1
 grep -a '^{"metric' $O/bench_under_rocprof.log | tail -1 > $O/bench_under_rocprof.json || true
 cp $(find $O/trace -name '*kernel_stats.csv' | head -1) $O/kernel_stats.csv
 python tools/trace_by_shape.py $O/trace 0.25 > $O/kernel_time_by_shape.txt
