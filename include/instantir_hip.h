@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define IIR_ABI_VERSION 1
+#define IIR_ABI_VERSION 2
 
 /* epilogue selectors */
 #define IIR_EPI_PLAIN 0 /* C = act(acc + bias + rowbias) + res                                    */
@@ -64,8 +64,6 @@ typedef struct iir_gemm_desc {
                                    /*   (paired epilogues), 91 / 92 = the 8-wave kernel at BN 320 / 256.  Any other value: IIR_EINVAL.      */
     const void* prefetch;          /* optional: range the workgroups touch (at most 1024 128-byte lines each) */
     int64_t prefetch_bytes;        /*   so it is in the Infinity Cache for a LATER launch (next layers' weights) */
-    void* splitk_ws;               /* optional split-K workspace (iir_gemm_splitk_workspace_bytes), ZEROED once by the  */
-    int64_t splitk_ws_bytes;       /*   caller and private to one stream; lets tile = 0 pick the 2-slice form for long K  */
     void* Ct; int64_t ldct;        /* optional (PLAIN epilogue, no residual on those columns): output columns n >= tr_from */
     int32_t tr_from;               /*   are stored TRANSPOSED, Ct[(n - tr_from) * ldct + m] -- the V third of a fused       */
                                    /*   q|k|v projection lands as the V^T image iir_attention_d64_f16 consumes              */
@@ -92,7 +90,7 @@ typedef struct iir_gemm_desc {
     /* softmax scale x log2(e) folded into W / bias by the caller; every workgroup finishes a 64-row x 2-head tile of q and runs the    */
     /* two SDPA calls + add of :1165,:1185,:1192 on it, so C receives `hidden_states + ip_hidden_states` (before to_out) and q never     */
     /* goes to memory.  Needs: fp16, N % 128 == 0 (head dimension 64), M % 64 == 0, xattn_tq % 64 == 0, 1 <= Tkv[0] <= 80,             */
-    /* 1 <= Tkv[1] <= 64, ldk / ldvt / batch strides % 8 == 0, no res / rowbias / act / Ct / c_f32 / wscale / *_stats_out / split-K.      */
+    /* 1 <= Tkv[1] <= 64, ldk / ldvt / batch strides % 8 == 0, no res / rowbias / act / Ct / c_f32 / wscale / *_stats_out.                */
     const iir_attn_kv* xattn_kv;   /* [2]: text K / V^T, IP-token K / V^T (layouts as for iir_attention_d64_f16)                       */
     int32_t xattn_tq;              /* query rows per image (row m belongs to image m / xattn_tq)                                      */
     /* BASELINE configs[4], both operands in fp8: with `wscale` set and a_fp8 != 0, A holds fp8-E4M3 (OCP) BYTES [M][K] too (lda in    */
@@ -119,10 +117,6 @@ int iir_gemm_resolve_tile(const iir_gemm_desc* d);
 int iir_gemm_gn_supported(int32_t M, int32_t N, int32_t K, int32_t is_conv);
 /* 1 when the tile = 0 all-fp8 launch (a_fp8) of (M, N, K) can store its result as fp8 bytes (c_fp8): whole tiles */
 int iir_gemm_fp8_out_supported(int32_t M, int32_t N, int32_t K, int32_t paired);
-/* bytes of split-K workspace an (M, N) problem can use (0: the split form does not apply to it) */
-int64_t iir_gemm_splitk_workspace_bytes(int32_t M, int32_t N);
-/* 1 if a tile = 0 launch of this problem with a workspace of ws_bytes takes the two-slice split-K form (128x160 tile) */
-int iir_gemm_uses_splitk(int32_t M, int32_t N, int32_t K, int64_t ws_bytes);
 /* output-tile width BN of tile id `tile` (1..6) */
 int iir_gemm_tile_bn(int32_t tile);
 
@@ -146,8 +140,6 @@ typedef struct iir_conv_desc {
                                    /*    Downsample2D(padding=0) + F.pad(0,1,0,1), vae.py:110)      */
     const void* prefetch;          /* as in iir_gemm_desc                                          */
     int64_t prefetch_bytes;
-    void* splitk_ws;               /* as in iir_gemm_desc (M = R*Ho*Wo, N = Cout)                  */
-    int64_t splitk_ws_bytes;
     int32_t dtype;                 /* IIR_DT_F16 / IIR_DT_BF16, as in iir_gemm_desc                */
     void* gn_stats_out;            /* as in iir_gemm_desc: float2 [R * Ho * Wo / 64][Cout] (rows of one image must fill whole 64-row slabs) */
 } iir_conv_desc;

@@ -312,7 +312,7 @@ namespace iir {
 
 bool gemm8_covers(const Geo& g, int bn) {
     if (bn != 320 && bn != 256) return false;
-    if (g.dtype != IIR_DT_F16 || g.c_f32 || g.ln_out || g.gn_out || g.splitk == 2 || (g.wscale && !g.f8) || g.rowbias || g.xa_on) return false;
+    if (g.dtype != IIR_DT_F16 || g.c_f32 || g.ln_out || g.gn_out || (g.wscale && !g.f8) || g.rowbias || g.xa_on) return false;
     if (g.f8 && (g.ln_in || g.Ct || bn != 320)) return false;            // all-fp8 form: the GEGLU / plain projections of the fp8 build
     if (g.c_fp8 && (g.ldc % 8 || (uintptr_t)g.C % 8)) return false;
     if (g.Ct && (g.epi != IIR_EPI_PLAIN || g.res || g.tr_from % bn || !g.ct_vec)) return false;      // transposed column range: whole tiles only

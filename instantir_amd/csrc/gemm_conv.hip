@@ -16,7 +16,7 @@
 // stays lane-linear), fragments by ds_read_b128 double-buffered across the barrier, XCD-aware tile order.
 // The weight fragment is the MFMA "A" operand so each lane ends up with 4 consecutive output columns of one row;
 // the finished tile is staged through the (then idle) ring and written out in whole rows (or, for a column range,
-// transposed).  Optional: two-slice split-K with an in-launch reduction, LayerNorm of the A rows folded in.
+// transposed).  Optional: LayerNorm of the A rows folded in.
 #include "common.h"
 #include "gemm_geo.h"
 #include "../../include/instantir_hip.h"
@@ -50,10 +50,16 @@ constexpr int vmcnt_imm(int n) { return (n & 15) | 0x0F70 | ((n >> 4) << 14); } 
 // once on 256 threads each: the thread layout of the two-per-CU 64x160 tile (id 25) it stands in for, so the partials are
 // bit-identical to that tile's (the finalize kernel merges them in a fixed order).
 constexpr int gn_par(int bm, bool lw) { return lw && bm == 128 ? 2 : 1; }
+// LDS layout, one definition for the kernel and its launcher: the ST-deep operand ring (reused as the output tile), 256 B of
+// scratch per wave (prefetch touches, dummy loads), the LayerNorm row statistics; statistics partials sit behind the output tile.
+constexpr int ring_bytes(int bm, int bn, int st, bool w8) { return st * (bm * 128 + (w8 ? bn * 64 : bn * 128)); }
+constexpr int scratch_bytes(int waves_m, bool lw) { return 256 * waves_m * 2 * (lw ? 2 : 1); }
+constexpr int lds_bytes(int bm, int bn, int st, int waves_m, bool w8, bool lw) { return ring_bytes(bm, bn, st, w8) + scratch_bytes(waves_m, lw) + bm * 8; }
+constexpr int lnp_off(int bm, int bn) { return (bm * (2 * bn + 32) + 15) / 16 * 16; }
+constexpr bool ln_out_fits(int bm, int bn, int st, bool w8) { return lnp_off(bm, bn) + bm * (bn / 8) * 8 <= ring_bytes(bm, bn, st, w8); }
 constexpr bool gn_out_fits(int bm, int bn, int st, int nt, bool lw, bool w8 = false) {
     const int gnt = nt / gn_par(bm, lw);
-    const long ring = (long)st * (bm * 128 + (w8 ? bn * 64 : bn * 128));
-    return bm % 64 == 0 && bn <= gnt && ((long)bm * (2 * bn + 32) + 15) / 16 * 16 + (long)gn_par(bm, lw) * (gnt / (bn / 8)) * bn * 8 <= ring;
+    return bm % 64 == 0 && bn <= gnt && (long)lnp_off(bm, bn) + (long)gn_par(bm, lw) * (gnt / (bn / 8)) * bn * 8 <= ring_bytes(bm, bn, st, w8);
 }
 
 // wait until at most N of this wave's vector-memory ops (the LDS-DMA loads) are outstanding, then barrier.
@@ -105,15 +111,15 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     constexpr int A_INST = BM / 8 / NW, B_INST = (B_GROUPS + NW - 1) / NW;   // glds instructions per wave per K tile
     static_assert(W8 || B_GROUPS % NW == 0, "fp16 weight tile: every wave issues the same number of row groups");
     constexpr int B_STAGE_BYTES = W8 ? BN * 64 : BN * 128;
-    constexpr int RING_BYTES = ST * (BM * 128 + B_STAGE_BYTES);
+    constexpr int RING_BYTES = ring_bytes(BM, BN, ST, W8);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f16* As = (f16*)smem;                       // [ST][BM][64]
     f16* Bs = As + ST * BM * BK;                // [ST][BN][64]  (W8: [ST][BN][64 bytes])
     constexpr int LOADS = A_INST + B_INST;      // LDS-DMA instructions per wave per stage (every wave issues exactly this many)
-    constexpr int SCRATCH_BYTES = 256 * NW * (LW ? 2 : 1);        // 256 B per wave (prefetch touches, dummy loads)
+    constexpr int SCRATCH_BYTES = scratch_bytes(WAVES_M, LW);     // 256 B per wave (prefetch touches, dummy loads)
     float2* rowstat = (float2*)(smem + RING_BYTES + SCRATCH_BYTES);          // [BM] (rstd, -rstd * mean) of this tile's rows (ln_in)
-    constexpr int LNP_OFF = (BM * (2 * BN + 32) + 15) / 16 * 16;              // producer partials sit behind the finished output tile
-    constexpr bool LN_OUT_FITS = LNP_OFF + BM * (BN / 8) * 8 <= RING_BYTES;
+    constexpr int LNP_OFF = lnp_off(BM, BN);                                  // producer partials sit behind the finished output tile
+    constexpr bool LN_OUT_FITS = ln_out_fits(BM, BN, ST, W8);
     // GroupNorm partials (round 3): per-thread column statistics of a 64-row slab meet in [row groups][BN] float2 behind the tile
     constexpr int GN_PAR = gn_par(BM, LW), GN_NT = NT / GN_PAR;              // slabs written side by side, threads per slab
     constexpr int GN_RG = GN_NT / (BN / 8);                                  // row groups of the column-fixed write-out mapping
@@ -130,12 +136,9 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     // cut into 8 rectangles (xm x 8/xm), one per XCD, chosen on the host to minimise the operand bytes each
     // L2 has to pull over the fabric; inside a rectangle tiles walk M fastest so co-resident workgroups
     // share a weight panel.  Placement only affects speed, never results.
-    // split-K: the grid holds every tile twice; the second half of the grid (kz = 1) works on the upper half of K.
-    // Both workgroups of a tile keep the same index mod 8, i.e. the same XCD / L2.
-    const int kz = (g.splitk == 2 && blockIdx.x >= (gridDim.x >> 1)) ? 1 : 0;
     int tm, tn;
     {
-        const int bid = kz ? (int)blockIdx.x - (int)(gridDim.x >> 1) : (int)blockIdx.x, xcd = bid & 7, local = bid >> 3;
+        const int bid = (int)blockIdx.x, xcd = bid & 7, local = bid >> 3;
         const int rx = xcd % g.xm, ry = xcd / g.xm;
         tm = rx * g.rm + local % g.rm;
         tn = ry * g.rn + local / g.rm;
@@ -268,8 +271,8 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     // ---- main loop: ST-deep LDS ring, tiles kt+1 .. kt+ST-2 stay in flight across the barrier ---------
     // (one barrier per K tile; the buffer refilled after the barrier is the one every wave finished
     //  reading before it arrived there)
-    const int nk_all = g.K / BK;
-    const int kt0 = kz ? nk_all / 2 : 0, nk = g.splitk == 2 ? (kz ? nk_all : nk_all / 2) : nk_all;   // this workgroup's K tiles [kt0, nk)
+    constexpr int kt0 = 0;
+    const int nk = g.K / BK;                                             // this workgroup's K tiles [kt0, nk): all of K
     if (!LW || loader) {
         if (CONV) conv_seek(kt0);
 #pragma unroll
@@ -606,40 +609,6 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     // the Linear / Conv output is an fp16 tensor before `+ residual`.)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // every wave is done reading the ring
 
-    // ---- split-K: whichever of a tile's two workgroups finishes LAST adds the other's fp32 partial and runs the epilogue
-    // (a + b = b + a in fp32, so the result does not depend on which one that is).  Hand-off: all stores of the slab
-    // drained by every wave -> workgroup barrier -> one agent-scope release -> relaxed agent-scope ticket; the reducer
-    // does one agent-scope acquire, then plain loads (cdna_hip_programming.md, in-launch split-K reduction recipe).
-    if (!LW && g.splitk == 2) {
-        const int tile_id = tn * g.tiles_m + tm;
-        float* mine = g.sk_slabs + ((long)tile_id * 2 + kz) * (BM * BN);
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NI; ++j) *(f32x4*)(mine + ((i * NI + j) * NT + tid) * 4) = acc[i][j];
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int* flag = (int*)(smem + RING_BYTES);     // first word of the prefetch scratch (unused until phase 2)
-        if (tid == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            *flag = __hip_atomic_fetch_add(g.sk_cnt + tile_id, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        if (*flag == 0) return;                                              // first to arrive: the partner finishes the tile
-        if (tid == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            g.sk_cnt[tile_id] = 0;                                            // ready for the next launch on this stream
-        }
-        __syncthreads();
-        const float* other = g.sk_slabs + ((long)tile_id * 2 + (1 - kz)) * (BM * BN);
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NI; ++j) acc[i][j] += *(const f32x4*)(other + ((i * NI + j) * NT + tid) * 4);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    }
     if (g.c_f32) {      // fp32 output straight from the accumulators (a lane holds 4 consecutive columns of one row)
         float* c32 = (float*)g.C;
         if (loader) return;
@@ -954,8 +923,7 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
 template <typename E, int BM, int BN, int ST, bool CONV, int WAVES_M = 2, bool W8 = false, bool LW = false, bool F8 = false>
 int launch_k(const Geo& g0, hipStream_t stream) {
     constexpr int NT = 128 * WAVES_M * (LW ? 2 : 1);
-    constexpr int RING_BYTES = ST * (BM * 128 + (W8 ? BN * 64 : BN * 128));
-    constexpr size_t lds = RING_BYTES + 256 * WAVES_M * 2 * (LW ? 2 : 1) + BM * 8;   // ring (reused as the output tile) + prefetch scratch (256 B per wave) + LayerNorm row statistics
+    constexpr size_t lds = lds_bytes(BM, BN, ST, WAVES_M, W8, LW);
     Geo g = g0;
     g.tiles_m = (g.M + BM - 1) / BM;
     g.tiles_n = (g.N + BN - 1) / BN;
@@ -966,13 +934,13 @@ int launch_k(const Geo& g0, hipStream_t stream) {
     }
     if (g.gn_out) {         // producer of GroupNorm partials: whole tiles, 16-byte rows, plain epilogue, rows of an image tile-aligned (caller)
         constexpr bool fits = gn_out_fits(BM, BN, ST, NT, LW, W8);
-        if (!fits || g.epi != IIR_EPI_PLAIN || g.c_f32 || g.Ct || g.splitk == 2 || g.ln_out || g.M % BM || g.N % BN || !g.c_vec || (g.res && !g.r_vec) ||
+        if (!fits || g.epi != IIR_EPI_PLAIN || g.c_f32 || g.Ct || g.ln_out || g.M % BM || g.N % BN || !g.c_vec || (g.res && !g.r_vec) ||
             (CONV && (g.y_img_rows | g.res_img_rows)))
             return IIR_EINVAL;
     }
     if (g.ln_out) {         // producer of LayerNorm partials: whole tiles, 16-byte rows, plain epilogue (see the kernel's fast write-out path)
-        constexpr bool fits = (BM * (2 * BN + 32) + 15) / 16 * 16 + BM * (BN / 8) * 8 <= RING_BYTES;
-        if (!fits || CONV || g.epi != IIR_EPI_PLAIN || g.c_f32 || g.Ct || g.splitk == 2 || g.M % BM || g.N % BN || !g.c_vec || (g.res && !g.r_vec))
+        constexpr bool fits = ln_out_fits(BM, BN, ST, W8);
+        if (!fits || CONV || g.epi != IIR_EPI_PLAIN || g.c_f32 || g.Ct || g.M % BM || g.N % BN || !g.c_vec || (g.res && !g.r_vec))
             return IIR_EINVAL;
     }
     // pick the XCD partition (xm x 8/xm rectangles of the tile grid) with the least bytes each 4 MiB L2 pulls over the
@@ -991,7 +959,7 @@ int launch_k(const Geo& g0, hipStream_t stream) {
         cost += ((double)rm * rn * 8 - (double)g.tiles_m * g.tiles_n) * 8. * BK * (BM + BN);     // padding workgroups of ragged rectangles
         if (best < 0. || cost < best) { best = cost; g.xm = xm; g.rm = rm; g.rn = rn; }
     }
-    const dim3 grid(8 * g.rm * g.rn * (g.splitk == 2 ? 2 : 1)), block(NT);
+    const dim3 grid(8 * g.rm * g.rn), block(NT);
     const auto kern = gemm_kernel<E, BM, BN, ST, CONV, WAVES_M, W8, LW, F8>;
     static unsigned long long lds_set = 0;
     if (!iir_ensure_dynamic_lds((const void*)kern, lds, lds_set)) return IIR_ELAUNCH;
@@ -1004,13 +972,12 @@ int launch_k(const Geo& g0, hipStream_t stream) {
 //   bf16 (VAE)  : GEMM and conv of the 4-wave two-stage tiles the chooser picks for it
 //   fp8 weights (fp16 activations) and all-fp8: the linear layers on the 4-wave two-stage tiles and on 64x160x3; with loader
 //                 waves the all-fp8 form of 64x160x3 only
-// Split-K exists in the fp16 form without loader waves.
 template <int BM, int BN, int ST, int WAVES_M = 2, bool LW = false>
 int launch(const Geo& g, bool conv, hipStream_t stream) {
     constexpr bool T5_3 = BM == 64 && BN == 160 && ST == 3 && WAVES_M == 2;
     constexpr bool FP8_TILE = T5_3 || (ST == 2 && WAVES_M == 2 && !LW);
     if (g.f8 || g.wscale) {
-        if (conv || g.dtype != IIR_DT_F16 || g.splitk == 2) return IIR_EINVAL;
+        if (conv || g.dtype != IIR_DT_F16) return IIR_EINVAL;
         if constexpr (FP8_TILE) {
             if (g.f8) return launch_k<f16, BM, BN, ST, false, WAVES_M, false, LW, true>(g, stream);
             if constexpr (!LW) return launch_k<f16, BM, BN, ST, false, WAVES_M, true>(g, stream);
@@ -1022,7 +989,6 @@ int launch(const Geo& g, bool conv, hipStream_t stream) {
             return conv ? launch_k<bf16, BM, BN, ST, true>(g, stream) : launch_k<bf16, BM, BN, ST, false>(g, stream);
         return IIR_EINVAL;
     }
-    if (LW && g.splitk == 2) return IIR_EINVAL;
     if (!conv) return launch_k<f16, BM, BN, ST, false, WAVES_M, false, LW>(g, stream);
     if constexpr (!LW || ST == 3) return launch_k<f16, BM, BN, ST, true, WAVES_M, false, LW>(g, stream);
     return IIR_EINVAL;
@@ -1066,8 +1032,8 @@ struct Resolved { int id, bm, bn, st, nt; bool lw; };
 // iir_gemm_gn_supported, iir_gemm_ln_parts, iir_gemm_fp8_out_supported -- is answered here, so a pre-check taken while a step is
 // planned and the launch it guards cannot disagree.  `tile`: 0 = automatic, 1..6 = a forced base shape (its ring depth and
 // loader waves still chosen here); anything else resolves to id -1, which dispatch() refuses.  K counts 2-byte units of the
-// operand row (all-fp8: the K of the fp8 bytes).  The cross-attention epilogue, split-K and the 8-wave kernel of gemm8.hip are
-// decided ahead of this by dispatch().
+// operand row (all-fp8: the K of the fp8 bytes).  The cross-attention epilogue and the 8-wave kernel of gemm8.hip are decided
+// ahead of this by dispatch().
 Resolved resolve_tile(int M, int N, int K, bool conv, int dtype, bool wscale, bool f8, int tile) {
     const bool f16 = dtype == IIR_DT_F16;
     if (tile < 0 || tile > N_TILES) return {-1, 0, 0, 0, 0, false};
@@ -1095,34 +1061,12 @@ Resolved resolve_tile(int M, int N, int K, bool conv, int dtype, bool wscale, bo
     return {tile + 10 * stages, bm, bn, stages, tile == 6 ? 512 : 256, false};     // (6: the 8-wave build)
 }
 
-constexpr long SK_CNT_BYTES = 4096;     // 1024 per-tile arrival counters ahead of the slabs
-long splitk_ws_bytes(int M, int N) {
-    const long t = (long)((M + 127) / 128) * ((N + 159) / 160);
-    return t * 2 <= 256 ? SK_CNT_BYTES + t * 2 * 128 * 160 * (long)sizeof(float) : 0;
-}
-
-bool uses_splitk(int M, int N, int K, long ws_bytes) {
-    const long need = splitk_ws_bytes(M, N);
-    return K >= ONE_PER_CU_MIN_K && (K / BK) % 2 == 0 && need > 0 && ws_bytes >= need;
-}
-
 bool gemm8_auto(const Geo& g, bool conv) {
     return !conv && (g.f8 ? 2 * g.K : g.K) >= 640 && (long)(g.M / 256) * (g.N / 320) >= 256 && iir::gemm8_covers(g, 320);
 }
 
 int dispatch(const Geo& g, bool conv, int tile, hipStream_t stream) {
     if (g.xa_on) return conv ? IIR_EINVAL : launch<64, 128, 3>(g, false, stream);      // to_q + cross-attention: the head-aligned 64 x 128 tile, two workgroups per CU
-    // Two-slice split-K, taken only when the caller hands over a workspace: two 128x160 workgroups per tile each take half of
-    // K and the last one to finish reduces (see the kernel).  Meant for long-K problems too small to fill the chip with
-    // 128x160 tiles (M x N = 2048 x 1280 at K = 5120 / 11520); MEASURED SLOWER than one 64x160 workgroup per CU over all
-    // of K on exactly those (51.8 vs 44.8 us warm at K = 5120, equal at K = 11520, 73.9 vs 73.0 ms per step): the agent-scope
-    // release per workgroup and the fp32 slab round trip cost more than the smaller operand fill saves.  The engine does
-    // not pass a workspace unless IIR_SPLITK=1.
-    if (tile == 0 && g.sk_slabs && !g.ln_out && !g.ln_in && !g.gn_out && g.dtype == IIR_DT_F16 && uses_splitk(g.M, g.N, g.K, g.sk_bytes)) {
-        Geo g2 = g;
-        g2.splitk = 2;
-        return launch<128, 160, 3>(g2, conv, stream);
-    }
     // tile: 0 = auto; t in {1: 128x128, 2: 128x64, 3: 64x64, 4: 128x160, 5: 64x160, 6: 256x128}; t + 10*stages selects the ring depth.
     // large-N linears whose 256 x 320 tiles fill the chip (the GEGLU projections): the 8-wave two-tile-deep kernel of
     // gemm8.hip (142 FLOP per staged byte against 71 for two 128x160 workgroups per CU).
@@ -1162,9 +1106,6 @@ void finish_geo(Geo& g) {
 }  // namespace
 
 extern "C" int iir_gemm_tile_bn(int32_t tile) { tile %= 10; return (tile >= 1 && tile <= N_TILES) ? kTiles[tile].bn : -1; }
-
-extern "C" int64_t iir_gemm_splitk_workspace_bytes(int32_t M, int32_t N) { return splitk_ws_bytes(M, N); }
-extern "C" int iir_gemm_uses_splitk(int32_t M, int32_t N, int32_t K, int64_t ws_bytes) { return uses_splitk(M, N, K, ws_bytes) ? 1 : 0; }
 
 extern "C" int iir_gemm_pick_tile(int32_t M, int32_t N, int32_t K, int32_t paired) { return pick_tile(M, N, paired != 0, K); }
 
@@ -1227,7 +1168,7 @@ static int fill_gemm_geo(const iir_gemm_desc* d, Geo& g) {
     if (d->epi == IIR_EPI_XATTN) {
         const iir_attn_kv* kv = d->xattn_kv;
         if (!kv || d->dtype != IIR_DT_F16 || d->N % 128 || d->M % 64 || d->xattn_tq <= 0 || d->xattn_tq % 64 || d->M % d->xattn_tq) return IIR_EINVAL;
-        if (d->res || d->rowbias || d->act || d->Ct || d->c_f32 || d->wscale || d->ln_stats_out || d->gn_stats_out || d->splitk_ws) return IIR_EINVAL;
+        if (d->res || d->rowbias || d->act || d->Ct || d->c_f32 || d->wscale || d->ln_stats_out || d->gn_stats_out) return IIR_EINVAL;
         if (d->ldc % 8 || (uintptr_t)d->C % 16 || (d->tile != 0 && d->tile != 93)) return IIR_EINVAL;
         if (kv[0].Tkv < 1 || kv[0].Tkv > 80 || kv[1].Tkv < 1 || kv[1].Tkv > 64) return IIR_EINVAL;
         for (int sgm = 0; sgm < 2; ++sgm) {
@@ -1249,13 +1190,12 @@ static int fill_gemm_geo(const iir_gemm_desc* d, Geo& g) {
     if (d->dtype != IIR_DT_F16 && d->dtype != IIR_DT_BF16) return IIR_EINVAL;
     g.dtype = d->dtype;
     if (d->c_f32) {
-        if (d->epi != IIR_EPI_PLAIN || d->bias || d->rowbias || d->res || d->Ct || d->act || d->ldc % 4 || (uintptr_t)d->C % 16 || d->splitk_ws) return IIR_EINVAL;
+        if (d->epi != IIR_EPI_PLAIN || d->bias || d->rowbias || d->res || d->Ct || d->act || d->ldc % 4 || (uintptr_t)d->C % 16) return IIR_EINVAL;
         g.c_f32 = 1;
     }
     if (d->wscale) {          // W is fp8-E4M3 [N][K] bytes with one fp32 scale per row of W
         if (d->c_f32 || d->K % 64 || (uintptr_t)d->W % 16 || (uintptr_t)d->wscale % 16 || d->dtype != IIR_DT_F16) return IIR_EINVAL;
         g.wscale = (const float*)d->wscale;
-        g.sk_slabs = nullptr;
     }
     if (d->c_fp8) {
         if (d->epi == IIR_EPI_XATTN || d->epi == IIR_EPI_SFT || d->c_f32 || d->Ct || d->ln_stats_out || d->gn_stats_out || d->dtype != IIR_DT_F16) return IIR_EINVAL;
@@ -1263,7 +1203,7 @@ static int fill_gemm_geo(const iir_gemm_desc* d, Geo& g) {
     }
     g.a_scale = 1.f;
     if (d->a_fp8) {           // A is fp8-E4M3 [M][K] bytes as well (lda in bytes): both operands by 128-byte rows of 128 K values
-        if (!d->wscale || d->K % 128 || d->lda % 16 || (uintptr_t)d->A % 16 || d->ln_stats_in || d->epi == IIR_EPI_XATTN || d->splitk_ws) return IIR_EINVAL;
+        if (!d->wscale || d->K % 128 || d->lda % 16 || (uintptr_t)d->A % 16 || d->ln_stats_in || d->epi == IIR_EPI_XATTN) return IIR_EINVAL;
         g.f8 = 1;
         g.a_scale = d->a_scale == 0.f ? 1.f : d->a_scale;
         g.K = d->K / 2; g.lda = d->lda / 2;          // counted in 2-byte units from here on: the fp16 staging path unchanged
@@ -1272,9 +1212,6 @@ static int fill_gemm_geo(const iir_gemm_desc* d, Geo& g) {
         if (d->epi != IIR_EPI_PLAIN || d->tr_from < 0 || d->tr_from >= d->N || d->tr_from % 8 || d->ldct < d->M) return IIR_EINVAL;
         g.Ct = (f16*)d->Ct; g.ldct = d->ldct; g.tr_from = d->tr_from;
         g.ct_vec = (d->ldct % 8 == 0) && ((uintptr_t)d->Ct % 16 == 0);
-    }
-    if (d->splitk_ws && d->splitk_ws_bytes > SK_CNT_BYTES) {
-        g.sk_cnt = (int*)d->splitk_ws; g.sk_slabs = (float*)((char*)d->splitk_ws + SK_CNT_BYTES); g.sk_bytes = d->splitk_ws_bytes;
     }
     if (d->ln_stats_out) {
         if ((uintptr_t)d->ln_stats_out % 8 || d->c_f32 || d->Ct || d->epi != IIR_EPI_PLAIN) return IIR_EINVAL;
@@ -1325,9 +1262,6 @@ extern "C" int iir_conv2d_nhwc_f16(const iir_conv_desc* c, void* stream) {
     if (c->gn_stats_out) {
         if ((uintptr_t)c->gn_stats_out % 8 || (g.Ho * g.Wo) % 64 || c->epi != IIR_EPI_PLAIN || c->y_img_rows || c->res_img_rows) return IIR_EINVAL;
         g.gn_out = (float*)c->gn_stats_out;
-    }
-    if (c->splitk_ws && c->splitk_ws_bytes > SK_CNT_BYTES) {
-        g.sk_cnt = (int*)c->splitk_ws; g.sk_slabs = (float*)((char*)c->splitk_ws + SK_CNT_BYTES); g.sk_bytes = c->splitk_ws_bytes;
     }
     return dispatch(g, true, c->tile, (hipStream_t)stream);
 }

@@ -39,9 +39,6 @@ struct Geo {   // per-launch constants shared by GEMM and CONV paths
     int tiles_m, tiles_n;
     int xm, rm, rn;           // XCD partition: xm x (8/xm) rectangles of rm x rn tiles
     const char* pf; int pf_lines;   // weight prefetch: 128-byte lines to pull towards the Infinity Cache
-    int splitk;                     // 1 or 2 K slices per output tile (workgroups z = 0 / 1 of a tile share an XCD)
-    long sk_bytes;                  // host only: bytes of the caller's split-K workspace
-    float* sk_slabs; int* sk_cnt;   // split-K workspace: fp32 partial tiles [tile][z][BM*BN] and per-tile arrival counters
     f16* Ct; long ldct; int tr_from, ct_vec;   // columns n >= tr_from are stored transposed: Ct[(n - tr_from) * ldct + m]
     int c_vec, r_vec;               // C / res rows allow 16-byte accesses (ld % 8 == 0, base 16-byte aligned)
     int dtype;                      // IIR_DT_F16 / IIR_DT_BF16: element type of A, W, C, bias, rowbias, res

@@ -39,7 +39,6 @@ class GemmDesc(C.Structure):
         ("out_scale", C.c_float),
         ("tile", C.c_int32),
         ("prefetch", C.c_void_p), ("prefetch_bytes", C.c_int64),
-        ("splitk_ws", C.c_void_p), ("splitk_ws_bytes", C.c_int64),
         ("Ct", C.c_void_p), ("ldct", C.c_int64), ("tr_from", C.c_int32),
         ("dtype", C.c_int32), ("c_f32", C.c_int32),
         ("wscale", C.c_void_p),
@@ -67,7 +66,6 @@ class ConvDesc(C.Structure):
         ("zero_page", C.c_void_p),
         ("x_img_stride", C.c_int64), ("y_img_rows", C.c_int32), ("res_img_rows", C.c_int32), ("pad_mode", C.c_int32),
         ("prefetch", C.c_void_p), ("prefetch_bytes", C.c_int64),
-        ("splitk_ws", C.c_void_p), ("splitk_ws_bytes", C.c_int64),
         ("dtype", C.c_int32),
         ("gn_stats_out", C.c_void_p),
     ]
@@ -98,8 +96,6 @@ _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 # symbol -> (restype, argtypes); must list every function declared in include/instantir_hip.h
 SIGNATURES = {
     "iir_gemm_f16": (C.c_int, [C.POINTER(GemmDesc), _P]),
-    "iir_gemm_splitk_workspace_bytes": (C.c_int64, [_I32, _I32]),
-    "iir_gemm_uses_splitk": (C.c_int, [_I32, _I32, _I32, _I64]),
     "iir_gemm_pick_tile": (C.c_int, [_I32, _I32, _I32, _I32]),
     "iir_gemm_resolve_tile": (C.c_int, [_P]),
     "iir_gemm_gn_supported": (C.c_int, [_I32, _I32, _I32, _I32]),
@@ -189,7 +185,7 @@ def load():
         except AttributeError as e:
             raise HipLibraryError(f"{LIB_PATH} does not export {name}") from e
         fn.restype, fn.argtypes = SIGNATURES[name]
-    if lib.iir_abi_version() != 1:
+    if lib.iir_abi_version() != 2:
         raise HipLibraryError("ABI version mismatch")
     _lib = lib
     return lib

@@ -101,12 +101,6 @@ def zero_page(device):
     return z
 
 
-def splitk_workspace(M, N, device):
-    """Zeroed split-K workspace for (M, N) problems (None when the 2-slice form does not apply).  One per stream."""
-    n = L.load().iir_gemm_splitk_workspace_bytes(M, N)
-    return torch.zeros(n, dtype=torch.uint8, device=device) if n > 0 else None
-
-
 FP8_MAX = 448.0          # largest finite E4M3 (OCP) value
 
 
@@ -239,9 +233,9 @@ def _chk_gn_out(gn_out, M, N):
         raise ValueError(f"gn_out: contiguous fp32 ({M} // 64, {N}, 2) with M % 64 == 0, got {tuple(gn_out.shape)} {gn_out.dtype}")
 
 
-def _fill_operands(d, dt, M, N, rowbias, rows_per_rb, res, prefetch, splitk_ws, gn_out):
+def _fill_operands(d, dt, M, N, rowbias, rows_per_rb, res, prefetch, gn_out):
     """The optional operands `GemmDesc` and `ConvDesc` name alike: per-image row bias, residual, GroupNorm partials of the
-    (M, N) output, weight prefetch range, split-K workspace."""
+    (M, N) output, weight prefetch range."""
     if rowbias is not None:
         _chk2d(rowbias, "rowbias", dt)
         d.rowbias, d.ldrb, d.rows_per_rb = rowbias.data_ptr(), rowbias.stride(0), rows_per_rb
@@ -253,8 +247,6 @@ def _fill_operands(d, dt, M, N, rowbias, rows_per_rb, res, prefetch, splitk_ws, 
         d.gn_stats_out = gn_out.data_ptr()
     if prefetch is not None:
         d.prefetch, d.prefetch_bytes = prefetch
-    if splitk_ws is not None:
-        d.splitk_ws, d.splitk_ws_bytes = splitk_ws.data_ptr(), splitk_ws.numel()
 
 
 def _fill_out_t(d, out_t, dt, M, N, refuse, msg):
@@ -277,7 +269,7 @@ def _fill_kv(table, kv):
 
 
 def gemm(a, w, out, bias=None, rowbias=None, rows_per_rb=1, res=None, epi=EPI_PLAIN, act=ACT_NONE, out_scale=1.0,
-         tile=0, prefetch=None, splitk_ws=None, out_t=None, wscale=None, ln_out=None, ln_in=None, gn_out=None, xattn=None):
+         tile=0, prefetch=None, out_t=None, wscale=None, ln_out=None, ln_in=None, gn_out=None, xattn=None):
     """out = epi(a @ w.T).  a (M,K) view, w (N,K) contiguous, out (M,N) view ((M,N/2) for paired epilogues).
     out_t = (Ct, tr_from): output columns >= tr_from go, transposed, to Ct[n - tr_from, m]; `out` then is (M, tr_from).
     wscale (fp32 (N,)): `w` holds fp8-E4M3 bytes (torch.float8_e4m3fn / uint8) with that per-row scale (fp8 MFMA).
@@ -317,7 +309,7 @@ def gemm(a, w, out, bias=None, rowbias=None, rows_per_rb=1, res=None, epi=EPI_PL
     d.C, d.ldc = out.data_ptr(), out.stride(0)
     d.M, d.N, d.K = M, N, K
     d.bias = _p(bias)
-    _fill_operands(d, dt, M, N, rowbias, rows_per_rb, res, prefetch, splitk_ws, gn_out)
+    _fill_operands(d, dt, M, N, rowbias, rows_per_rb, res, prefetch, gn_out)
     d.epi, d.act, d.out_scale, d.tile = epi, act, out_scale, tile
     d.dtype, d.c_f32 = _DT[dt], int(c_f32)
     if wscale is not None:
@@ -347,7 +339,7 @@ def gemm(a, w, out, bias=None, rowbias=None, rows_per_rb=1, res=None, epi=EPI_PL
     if xattn is not None:
         tile = 93
     elif tile == 0:       # the library decides; resolve the same choice here only to NAME the launch for the profiler
-        tile = 4 if splitk_ws is not None and L.load().iir_gemm_uses_splitk(M, N, K, splitk_ws.numel()) else auto_tile(M, N, epi != EPI_PLAIN, K)
+        tile = auto_tile(M, N, epi != EPI_PLAIN, K)
     if out_t is not None:
         _fill_out_t(d, out_t, dt, M, N, False, "out_t must hold (N - tr_from, M)")
     No = N // 2 if epi not in (EPI_PLAIN, EPI_XATTN) else N
@@ -365,8 +357,7 @@ def gemm(a, w, out, bias=None, rowbias=None, rows_per_rb=1, res=None, epi=EPI_PL
 
 
 def conv2d(x, w, out, ksize=3, stride=1, upsample=False, bias=None, rowbias=None, rows_per_rb=1, res=None,
-           epi=EPI_PLAIN, act=ACT_NONE, out_scale=1.0, tile=0, y_img_rows=0, res_img_rows=0, pad_mode=0, prefetch=None,
-           splitk_ws=None, gn_out=None):
+           epi=EPI_PLAIN, act=ACT_NONE, out_scale=1.0, tile=0, y_img_rows=0, res_img_rows=0, pad_mode=0, prefetch=None, gn_out=None):
     """x (R,H,W,Cin) NHWC view (pixel stride x.stride(2), image stride x.stride(0) free), w (Cout,k,k,Cin) contiguous,
     out (rows, Cout[/2]) 2-D view; image i's pixels start at row i*y_img_rows (0 = dense)."""
     R, H, Wd, Cin = x.shape
@@ -391,11 +382,11 @@ def conv2d(x, w, out, ksize=3, stride=1, upsample=False, bias=None, rowbias=None
     Hi, Wi = (2 * H, 2 * Wd) if upsample else (H, Wd)
     pad2 = 1 if pad_mode == 1 else 2 * (ksize // 2)
     Mo = R * ((Hi + pad2 - ksize) // stride + 1) * ((Wi + pad2 - ksize) // stride + 1)
-    _fill_operands(d, dt, Mo, Cout, rowbias, rows_per_rb, res, prefetch, splitk_ws, gn_out)
+    _fill_operands(d, dt, Mo, Cout, rowbias, rows_per_rb, res, prefetch, gn_out)
     d.epi, d.act, d.out_scale, d.tile = epi, act, out_scale, tile
     if tile == 0:       # as in gemm(): the library decides, this only names the launch
         Kc = ksize * ksize * Cin
-        tile = 4 if splitk_ws is not None and L.load().iir_gemm_uses_splitk(Mo, Cout, Kc, splitk_ws.numel()) else auto_tile(Mo, Cout, epi != EPI_PLAIN, Kc)
+        tile = auto_tile(Mo, Cout, epi != EPI_PLAIN, Kc)
     d.zero_page = zero_page(x.device).data_ptr()          # (all-zero bits are zero in fp16 and bf16 alike)
     d.x_img_stride, d.y_img_rows, d.res_img_rows, d.pad_mode = x.stride(0), y_img_rows, res_img_rows, pad_mode
     Co = Cout // 2 if epi != EPI_PLAIN else Cout

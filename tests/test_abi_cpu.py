@@ -18,7 +18,16 @@ def test_library_exports_every_declared_symbol():
     for s in lib.declared_symbols():
         assert hasattr(h, s), s
     h.iir_abi_version.restype = ctypes.c_int
-    assert h.iir_abi_version() == 1
+    assert h.iir_abi_version() == 2
+
+
+def test_k_split_workspace_has_left_the_abi():
+    """The two-slice K split went out of the library with ABI version 2: no workspace field of it in either descriptor, neither
+    of its two query functions declared -- nothing in the header or its ctypes mirror names a split any more."""
+    for desc in (lib.GemmDesc, lib.ConvDesc):
+        assert not [name for name, _ in desc._fields_ if "split" in name]
+    assert not [s for s in list(lib.declared_symbols()) + list(lib.SIGNATURES) if "split" in s]
+    assert "split" not in open(lib.HEADER_PATH).read().lower()
 
 
 def test_descriptor_layouts_match_header():

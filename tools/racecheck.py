@@ -1,5 +1,5 @@
 """Race screen: every kernel here is deterministic, so repeated launches on the same inputs must be BIT-identical; any
-difference (or a mismatch against the fp32 reference) is reported with its location.  GEMM tiles x epilogues, split-K,
+difference (or a mismatch against the fp32 reference) is reported with its location.  GEMM tiles x epilogues,
 transposed column range, conv, attention."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -37,9 +37,6 @@ for (M, N, K) in [(2048, 1280, 1280), (1000, 640, 1280), (2048, 1280, 5120)]:
     want = (x.float() @ w.float().T + b.float() + res.float()).flatten()
     for tile in (0, 1, 2, 3, 4, 5, 35):
         screen(f"gemm {M}x{N}x{K} tile {tile} bias+res", lambda o: ops.gemm(xd, wd, o, bias=bd, res=rd, tile=tile), want, [(M, N)])
-    ws = ops.splitk_workspace(M, N, dev)
-    if ws is not None and K >= 2560:
-        screen(f"gemm {M}x{N}x{K} split-K", lambda o: ops.gemm(xd, wd, o, bias=bd, res=rd, splitk_ws=ws), want, [(M, N)])
     h = x.float() @ w.float().T + b.float()
     wantg = (h[:, :N // 2] * F.gelu(h[:, N // 2:])).flatten()
     wp, bp = pair_rows(w[:N // 2], w[N // 2:]).to(dev), pair_rows(b[:N // 2], b[N // 2:]).to(dev)
@@ -56,10 +53,8 @@ R, H, Cin, Cout = 2, 32, 1280, 1280
 x, w, b = rnd(R, Cin, H, H), rnd(Cout, Cin, 3, 3, scale=(9 * Cin) ** -0.5), rnd(Cout)
 want = F.conv2d(x.float(), w.float(), b.float(), padding=1).permute(0, 2, 3, 1).reshape(-1, Cout).flatten()
 xd, wd, bd = x.permute(0, 2, 3, 1).contiguous().to(dev), conv_weight_nhwc(w).to(dev), b.to(dev)
-ws = ops.splitk_workspace(R * H * H, Cout, dev)
-for tile, sk in ((0, None), (0, ws), (2, None), (5, None), (35, None)):
-    screen(f"conv3x3 {R}x{H}x{H} {Cin}->{Cout} tile {tile}{' split-K' if sk is not None else ''}",
-           lambda o: ops.conv2d(xd, wd, o, bias=bd, tile=tile, splitk_ws=sk), want, [(R * H * H, Cout)])
+for tile in (0, 2, 5, 35):
+    screen(f"conv3x3 {R}x{H}x{H} {Cin}->{Cout} tile {tile}", lambda o: ops.conv2d(xd, wd, o, bias=bd, tile=tile), want, [(R * H * H, Cout)])
 B, heads, T = 2, 20, 1024
 Cc = heads * 64
 qkv = rnd(B * T, 2 * Cc).to(dev); vt = rnd(Cc, B * T).to(dev)
