@@ -15,28 +15,14 @@
 // cross-half exchange, and the exponentiated accumulator registers are, after fp16 packing, directly
 // the B operand of O^T += V^T . P^T (no LDS round trip for P).  K and V^T tiles are staged by
 // global_load_lds_dwordx4 into double-buffered XOR-swizzled LDS images.
-#include "common.h"
-#include "../../include/instantir_hip.h"
-#include <type_traits>
+#include "attn_geo.h"
 
 namespace {
 
-struct Seg { const f16* K; long ldk, kbs; const f16* Vt; long ldvt, vbs; int Tkv; };
-struct AGeo {
-    const f16* Q; long ldq, qbs;
-    f16* O; long ldo, obs; int o_fp8;      // o_fp8: O is a byte matrix of fp8-E4M3 (ldo / obs in bytes)
-    int Tq, nseg;
-    int qtiles, npairs;   // query tiles per (batch, head); number of (batch, head) pairs; heads below
-    int heads;
-    int causal;            // mask keys with index > query index (CLIP text encoders)
-    int qpre;              // Q already multiplied by c
-    float c;   // softmax scale * log2(e)
-    Seg seg[2];
-    int n_attn;            // identity form: workgroups [0, n_attn) attend (batch rows below ident_from), the rest copy V
-    int ident_from;
-};
-
-constexpr int KT = 64;   // keys per tile
+using Seg = iir::AttnSeg;
+using AGeo = iir::AttnGeo;
+using iir::attn_vswz;
+constexpr int KT = iir::ATTN_KT;
 
 // The per-tile VECTOR work (not the MFMAs) sets the pace at head_dim 64 -- 32 exponentials per 16 MFMAs and lane -- so:
 //   * the softmax scale (x log2 e) is folded into the Q fragments once per workgroup, and the running maximum enters the
@@ -90,9 +76,7 @@ __device__ __forceinline__ void attn_tile(const char* kt, const char* vt, const 
             mx = fmaxf(fmaxf(mx, a[r]), a[r + 1]);
             mxb = fmaxf(fmaxf(mxb, a[r + 2]), a[r + 3]);
         }
-        mx = fmaxf(mx, mxb);
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-        return fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+        return iir::xhalf_max(fmaxf(mx, mxb));
     };
     // P = 2^S' of one half, its row sum, and O^T += V^T . P^T for the half's two k-steps.  The K rows of the tile were staged in
     // the order that makes accumulator register 8*sp + j of lane half hh the score of key 32*kb + 16*sp + 8*hh + j (see `stage`),
@@ -115,7 +99,7 @@ __device__ __forceinline__ void attn_tile(const char* kt, const char* vt, const 
 #pragma unroll
             for (int db = 0; db < 2; ++db) {
                 const int d = db * 32 + qi;
-                const f16x8 vf = *(const f16x8*)(vt + d * 128 + ((chunk ^ ((d >> 1) & 7)) * 16));
+                const f16x8 vf = *(const f16x8*)(vt + d * 128 + ((chunk ^ attn_vswz(d)) * 16));
                 if (zero_o && sp == 0) o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, (f32x16){0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, 0, 0, 0);
                 else o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, o[db], 0, 0, 0);
             }
@@ -214,7 +198,7 @@ __device__ __forceinline__ void attn_tile(const char* kt, const char* vt, const 
 #pragma unroll
             for (int db = 0; db < 2; ++db) {
                 const int d = db * 32 + qi, chunk = sp * 2 + hh;
-                vf[sp * 2 + db] = *(const f16x8*)(vt + d * 128 + ((chunk ^ ((d >> 1) & 7)) * 16));
+                vf[sp * 2 + db] = *(const f16x8*)(vt + d * 128 + ((chunk ^ attn_vswz(d)) * 16));
             }
         // (no sched_barrier: pure exp / MFMA intrinsics are not ordered by it)
 #pragma unroll
@@ -240,7 +224,7 @@ __device__ __forceinline__ void attn_tile(const char* kt, const char* vt, const 
 #pragma unroll
             for (int db = 0; db < 2; ++db) {
                 const int d = db * 32 + qi, chunk = 4 + sp * 2 + hh;
-                const f16x8 v2 = *(const f16x8*)(vt + d * 128 + ((chunk ^ ((d >> 1) & 7)) * 16));
+                const f16x8 v2 = *(const f16x8*)(vt + d * 128 + ((chunk ^ attn_vswz(d)) * 16));
                 o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v2, pb[sp], o[db], 0, 0, 0);
             }
     }
@@ -304,11 +288,7 @@ __global__ __launch_bounds__(256, WPS) void attn_kernel2(const AGeo g) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qi = lane & 31, hh = lane >> 5;
-    int lin;
-    {
-        const int nwg = IDENT ? g.n_attn : (int)gridDim.x, q = nwg >> 3, r = nwg & 7, x = blockIdx.x & 7;
-        lin = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (blockIdx.x >> 3);
-    }
+    const int lin = iir::attn_lin(IDENT ? g.n_attn : (int)gridDim.x);
     const int pair = lin / g.qtiles;
     const int h = pair % g.heads, b = pair / g.heads;
     const int q0 = (lin % g.qtiles) * 128 + wave * 32;
@@ -340,18 +320,10 @@ __global__ __launch_bounds__(256, WPS) void attn_kernel2(const AGeo g) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int r0 = (i * 4 + wave) * 8;
-            // LDS row rho holds key pi(rho) = rho with bits 2 and 3 swapped: accumulator row (r&3) + 8*(r>>2) + 4*hh of the
-            // score MFMA then is key 16*(r>>3) + 8*hh + (r&7) -- a lane's 8 scores of a k-step are 8 CONSECUTIVE keys
-            const int rho = r0 + srow;
-            int key = t * KT + ((rho & ~12) | ((rho & 4) << 1) | ((rho & 8) >> 1));
-            if (key >= s.Tkv) key = s.Tkv - 1;
+            const int rho = r0 + srow;                       // LDS row: of the K image (key order of attn_krow_key) and of V^T (d)
             const int kc = spos ^ KSWZ(rho);
-            glds16(kbase + (long)key * s.ldk + kc * 8, Ks + buf * KT * 128 + r0 * 128);
-            const int d = r0 + srow;
-            const int vc = spos ^ ((d >> 1) & 7);
-            int kcol = t * KT + vc * 8;
-            if (kcol >= tpad) kcol = 0;
-            glds16(vbase + (long)d * s.ldvt + kcol, Vs + buf * KT * 128 + r0 * 128);
+            glds16(kbase + (long)iir::attn_krow_key(t, rho, s.Tkv) * s.ldk + kc * 8, Ks + buf * KT * 128 + r0 * 128);
+            glds16(vbase + (long)rho * s.ldvt + iir::attn_vt_col(t, spos, rho, tpad), Vs + buf * KT * 128 + r0 * 128);
         }
     };
     int pre_slot = 0;                     // PRE: ring slot of the current segment's first tile
@@ -461,7 +433,7 @@ __global__ __launch_bounds__(256, WPS) void attn_kernel2(const AGeo g) {
 #pragma unroll
                     for (int r = 0; r < 8; ++r) { o[i][2 * r] += (float)ohold[i * 8 + r][0]; o[i][2 * r + 1] += (float)ohold[i * 8 + r][1]; }
             }
-            // ---- store: lane (q, hh) holds d = 32*db + 8*gq + 4*hh + [0,4) in regs 4*gq..4*gq+3
+            // ---- store (lane mapping: attn_o_col)
             if (qq < g.Tq) {
                 f16* op = g.O + (long)b * g.obs + (long)qq * g.ldo + h * 64;
                 char* op8 = (char*)g.O + (long)b * g.obs + (long)qq * g.ldo + h * 64;
@@ -469,11 +441,9 @@ __global__ __launch_bounds__(256, WPS) void attn_kernel2(const AGeo g) {
                 for (int db = 0; db < 2; ++db)
 #pragma unroll
                     for (int gq = 0; gq < 4; ++gq) {
-                        f16x4 v;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = (f16)o[db][4 * gq + j];
-                        if (g.o_fp8) *(int*)(op8 + db * 32 + gq * 8 + hh * 4) = iir_fp8x4(v);      // rounded to fp16 first, as the fp16 output would be
-                        else *(f16x4*)(op + db * 32 + gq * 8 + hh * 4) = v;
+                        const f16x4 v = iir::attn_o_quad(o[db], gq);
+                        if (g.o_fp8) *(int*)(op8 + iir::attn_o_col(db, gq, hh)) = iir_fp8x4(v);      // rounded to fp16 first, as the fp16 output would be
+                        else *(f16x4*)(op + iir::attn_o_col(db, gq, hh)) = v;
                     }
             }
         }
@@ -488,25 +458,10 @@ __global__ __launch_bounds__(256, WPS) void attn_kernel2(const AGeo g) {
 // step's shapes, `profiles/r02_attn_ring_depth.log`.)
 template <bool IDENT>
 int launch_attn(const iir_attn_desc* a, int attn_batch, hipStream_t stream) {
-    AGeo g{};
-    g.Q = (const f16*)a->Q; g.ldq = a->ldq; g.qbs = a->q_batch_stride;
-    g.O = (f16*)a->O; g.ldo = a->ldo; g.obs = a->o_batch_stride; g.o_fp8 = a->o_fp8 != 0;
-    g.Tq = a->Tq; g.nseg = a->nseg;
-    g.c = a->scale * 1.4426950408889634f;
-    g.qpre = a->q_prescaled;
+    const AGeo g = iir::attn_geo(a, attn_batch);
     int total_tiles = 0;
-    for (int i = 0; i < a->nseg; ++i) {
-        const iir_attn_kv* s = &a->kv[i];
-        g.seg[i] = Seg{(const f16*)s->K, s->ldk, s->k_batch_stride, (const f16*)s->Vt, s->ldvt, s->vt_batch_stride, s->Tkv};
-        total_tiles += (s->Tkv + KT - 1) / KT;
-    }
-    g.qtiles = (a->Tq + 127) / 128;
-    g.heads = a->heads;
-    g.npairs = a->heads * attn_batch;
-    g.causal = a->causal;
-    const int n_attn = g.npairs * g.qtiles;
-    if (IDENT) { g.n_attn = n_attn; g.ident_from = attn_batch; }
-    const dim3 grid(n_attn + (a->batch - attn_batch) * a->heads * g.qtiles);
+    for (int i = 0; i < g.nseg; ++i) total_tiles += (g.seg[i].Tkv + KT - 1) / KT;
+    const dim3 grid(g.n_attn + (a->batch - attn_batch) * a->heads * g.qtiles);
     if (!g.causal && total_tiles <= 4) {
         constexpr size_t lds = 4 * 2 * KT * 128;
         static unsigned long long lds_set = 0;
@@ -514,7 +469,7 @@ int launch_attn(const iir_attn_desc* a, int attn_batch, hipStream_t stream) {
         iir_launch(attn_kernel2<2, 4, true, IDENT>, grid, dim3(256), lds, stream, g);
     } else {
         constexpr size_t lds = 2 * 2 * KT * 128;     // (32 KB: below the 64 KB that needs the function attribute)
-        if (n_attn <= 512) iir_launch(attn_kernel2<2, 2, false, IDENT>, grid, dim3(256), lds, stream, g);
+        if (g.n_attn <= 512) iir_launch(attn_kernel2<2, 2, false, IDENT>, grid, dim3(256), lds, stream, g);
         else iir_launch(attn_kernel2<3, 2, false, IDENT>, grid, dim3(256), lds, stream, g);
     }
     return iir_launch_status();
@@ -523,24 +478,14 @@ int launch_attn(const iir_attn_desc* a, int attn_batch, hipStream_t stream) {
 }  // namespace
 
 extern "C" int iir_attention_d64_f16(const iir_attn_desc* a, void* stream) {
+    if (!iir::attn_desc_ok(a)) return IIR_EINVAL;       // (every argument is checked before the first HIP call)
     (void)hipGetLastError();
-    if (!a || !a->Q || !a->O || a->nseg < 1 || a->nseg > 2) return IIR_EINVAL;
-    if (a->Tq <= 0 || a->heads <= 0 || a->batch <= 0) return IIR_EINVAL;
-    if (a->ldq % 8 || a->ldo % 4) return IIR_EINVAL;
-    for (int i = 0; i < a->nseg; ++i) {
-        const iir_attn_kv* s = &a->kv[i];
-        if (!s->K || !s->Vt || s->Tkv <= 0 || s->ldk % 8 || s->ldvt % 8 || s->vt_batch_stride % 8) return IIR_EINVAL;
-    }
     return launch_attn<false>(a, a->batch, (hipStream_t)stream);
 }
 
 extern "C" int iir_attention_d64_ident_f16(const iir_attn_desc* a, int32_t ident_from, void* stream) {
-    // (every argument is checked before the first HIP call)
-    if (!a || !a->Q || !a->O || a->nseg != 1 || a->causal || a->o_fp8) return IIR_EINVAL;
-    if (a->Tq <= 0 || a->heads <= 0 || a->batch <= 1 || ident_from < 1 || ident_from >= a->batch) return IIR_EINVAL;
-    if (a->ldq % 8 || a->ldo % 4) return IIR_EINVAL;
-    const iir_attn_kv* s = &a->kv[0];
-    if (!s->K || !s->Vt || s->Tkv != a->Tq || s->ldk % 8 || s->ldvt % 8 || s->vt_batch_stride % 8) return IIR_EINVAL;
+    if (!iir::attn_desc_ok(a) || a->nseg != 1 || a->causal || a->o_fp8) return IIR_EINVAL;
+    if (ident_from < 1 || ident_from >= a->batch || a->kv[0].Tkv != a->Tq) return IIR_EINVAL;
     (void)hipGetLastError();
     return launch_attn<true>(a, ident_from, (hipStream_t)stream);
 }

@@ -15,9 +15,9 @@
 //     (Columns h*D + [D, DK) of a row belong to the next head or lie past the row, and 0 x Inf = NaN.)
 //   O^T += V^T . P^T with 32x32x16 MFMA, d on the accumulator rows in blocks of 32: 80 -> 3 blocks (96 rows), 104 -> 4 (128).
 //     V^T image rows [D, DV) are zeroed once per kernel and never staged; only d < D is stored.
-// The K rows of a tile are staged in the order of the d64 kernel's second generation (LDS row rho holds key rho with bits 2 and 3
-// swapped), so accumulator register 8*sp + j of lane half hh is the score of key 32*kb + 16*sp + 8*hh + j: the packed P registers
-// are the B operand as they stand and each V^T fragment is one 16-byte read.
+// The K rows of a tile are staged in the order both attention kernels use (attn_geo.h, attn_krow_key), so accumulator register
+// 8*sp + j of lane half hh is the score of key 32*kb + 16*sp + 8*hh + j: the packed P registers are the B operand as they stand
+// and each V^T fragment is one 16-byte read.
 //
 // LDS layouts (both conflict-free for the ds_read_b128 lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31} and their +32 twins):
 //   K image, CHUNK-MAJOR: [DK/8 planes][64 rows][16 B]; plane c holds halves d = 8c + [0, 8) of every row.  A fragment read is
@@ -26,27 +26,20 @@
 //     as they stand and under every rotation of the chunk index by a function of the row that was tried, and the d64 XOR
 //     (chunk ^ f(row), f < 8) leaves a 10-chunk row.  A glds16 instruction fills one plane of one tile
 //     (64 lanes = 64 rows), so each row stages exactly D/8 chunks and the pad plane (D = 104: plane 13) is never written by DMA.
-//   V^T image: [DV rows d][64 keys = 128 B], 16-byte chunk c of row d stored at chunk c ^ ((d >> 1) & 7): the d64 kernel's
-//     V layout (the row length is 64 keys at any D), conflict-free for its reads.
+//   V^T image: [DV rows d][64 keys = 128 B], chunk swizzle attn_vswz: the layout both kernels share (the row length is 64 keys
+//     at any D), conflict-free for its reads.
 // LDS: 2 x (DK/8 KiB + DV/8 KiB) = 44 KiB at D = 80, 60 KiB at D = 104 (static; below the 64 KiB that needs an attribute).
 //
 // DESIGN 5.8 rule: no cross-lane exchange downstream of a per-lane-guarded load.  Every load here is unconditional from a clamped
 // address (query row, key row, V^T column chunk, Q pad); the cross-half row maximum / row sum use v_permlane32_swap.
-#include "common.h"
-#include "../../include/instantir_hip.h"
+#include "attn_geo.h"
 
 namespace {
 
-struct HdSeg { const f16* K; long ldk, kbs; const f16* Vt; long ldvt, vbs; int Tkv; };
-struct HdGeo {
-    const f16* Q; long ldq, qbs;
-    f16* O; long ldo, obs;
-    int Tq, nseg, qtiles, heads, causal;
-    float c;          // log2(e) * scale, or 1 when Q is pre-scaled
-    HdSeg seg[2];
-};
-
-constexpr int KT = 64;   // keys per tile
+using HdSeg = iir::AttnSeg;
+using HdGeo = iir::AttnGeo;       // (c is 1 when Q is pre-scaled: see iir_attention_f16)
+using iir::attn_vswz;
+constexpr int KT = iir::ATTN_KT;
 
 template <int D> struct HdShape {
     static constexpr int KS = (D + 15) / 16;        // k-steps of S^T = K . Q^T
@@ -59,15 +52,6 @@ template <int D> struct HdShape {
     static_assert(D % 8 == 0 && DC <= KC, "head_dim must be a multiple of 8");
 };
 
-__device__ __forceinline__ float xhalf_max(float v) {
-    const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(s[0]), __uint_as_float(s[1]));
-}
-__device__ __forceinline__ float xhalf_sum(float v) {
-    const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(s[0]) + __uint_as_float(s[1]);
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void attn_hd_kernel(const HdGeo g) {
     using S = HdShape<D>;
@@ -78,12 +62,7 @@ __global__ __launch_bounds__(256) void attn_hd_kernel(const HdGeo g) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qi = lane & 31, hh = lane >> 5;
-    // XCD-aware placement as in the d64 kernel: XCD x gets a contiguous run of the (batch, head)-major tile order
-    int lin;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, x = blockIdx.x & 7;
-        lin = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (blockIdx.x >> 3);
-    }
+    const int lin = iir::attn_lin(gridDim.x);
     const int pair = lin / g.qtiles;
     const int h = pair % g.heads, b = pair / g.heads;
     const int q0 = (lin % g.qtiles) * 128 + wave * 32;
@@ -130,19 +109,13 @@ __global__ __launch_bounds__(256) void attn_hd_kernel(const HdGeo g) {
         // one tile: DC K planes (one glds16 each: lane = LDS row) and DC V^T row groups (8 rows each), spread over the 4 waves
         auto stage = [&](int t, int buf) {
             {
-                const int rho = lane;
-                int key = t * KT + ((rho & ~12) | ((rho & 4) << 1) | ((rho & 8) >> 1));
-                if (key >= s.Tkv) key = s.Tkv - 1;
-                const f16* src = kbase + (long)key * s.ldk;
+                const f16* src = kbase + (long)iir::attn_krow_key(t, lane, s.Tkv) * s.ldk;      // LDS row = lane
                 for (int c = wave; c < S::DC; c += 4) glds16(src + c * 8, Ks + buf * S::KBYTES + c * KT * 16);
             }
             const int srow = lane >> 3, spos = lane & 7;
             for (int i = wave; i < S::DC; i += 4) {
                 const int d = i * 8 + srow;
-                const int vc = spos ^ ((d >> 1) & 7);
-                int kcol = t * KT + vc * 8;                        // 8 keys per 16-byte chunk
-                if (kcol >= tpad) kcol = 0;                        // chunk fully past the end: all its keys are masked
-                glds16(vbase + (long)d * s.ldvt + kcol, Vs + buf * S::VBYTES + i * 8 * 128);
+                glds16(vbase + (long)d * s.ldvt + iir::attn_vt_col(t, spos, d, tpad), Vs + buf * S::VBYTES + i * 8 * 128);
             }
         };
 
@@ -192,7 +165,7 @@ __global__ __launch_bounds__(256) void attn_hd_kernel(const HdGeo g) {
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[kb][r]);
-            const float m_new = fmaxf(m, xhalf_max(mx) * g.c);
+            const float m_new = fmaxf(m, iir::xhalf_max(mx) * g.c);
             if (__any(m_new > m)) {
                 const float alpha = __builtin_amdgcn_exp2f(m - m_new);
                 l *= alpha;
@@ -225,21 +198,21 @@ __global__ __launch_bounds__(256) void attn_hd_kernel(const HdGeo g) {
 #pragma unroll
                     for (int db = 0; db < S::NDB; ++db) {
                         const int d = db * 32 + qi;
-                        const f16x8 vf = *(const f16x8*)(vt + d * 128 + ((chunk ^ ((d >> 1) & 7)) * 16));
+                        const f16x8 vf = *(const f16x8*)(vt + d * 128 + ((chunk ^ attn_vswz(d)) * 16));
                         o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, o[db], 0, 0, 0);
                     }
                 }
             __builtin_amdgcn_s_waitcnt(0x0F70);
             __syncthreads();
         }
-        const float inv = 1.0f / xhalf_sum(l);
+        const float inv = 1.0f / iir::xhalf_sum(l);
 #pragma unroll
         for (int i = 0; i < S::NDB; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) oout[i][r] += o[i][r] * inv;
     }
 
-    // ---- store d < D: lane (q, hh) holds d = 32*db + 8*gq + 4*hh + [0,4) in regs 4*gq..4*gq+3 (D % 8 == 0: whole groups)
+    // ---- store d < D (lane mapping: attn_o_col; D % 8 == 0: whole groups)
     if (qq < g.Tq) {
         f16* op = g.O + (long)b * g.obs + (long)qq * g.ldo + h * D;
 #pragma unroll
@@ -247,10 +220,7 @@ __global__ __launch_bounds__(256) void attn_hd_kernel(const HdGeo g) {
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
                 if (db * 32 + gq * 8 >= D) continue;
-                f16x4 v;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = (f16)oout[db][4 * gq + j];
-                *(f16x4*)(op + db * 32 + gq * 8 + hh * 4) = v;
+                *(f16x4*)(op + iir::attn_o_col(db, gq, hh)) = iir::attn_o_quad(oout[db], gq);
             }
     }
 }
@@ -258,29 +228,13 @@ __global__ __launch_bounds__(256) void attn_hd_kernel(const HdGeo g) {
 }  // namespace
 
 extern "C" int iir_attention_f16(const iir_attn_desc* a, int32_t head_dim, void* stream) {
-    if (!a || !a->Q || !a->O) return IIR_EINVAL;
-    if (head_dim != 64 && head_dim != 80 && head_dim != 104) return IIR_EINVAL;
-    if (a->nseg < 1 || a->nseg > 2) return IIR_EINVAL;
-    if (a->Tq <= 0 || a->heads <= 0 || a->batch <= 0) return IIR_EINVAL;
-    if (a->ldq % 8 || a->ldo % 4) return IIR_EINVAL;
-    for (int i = 0; i < a->nseg; ++i) {
-        const iir_attn_kv* s = &a->kv[i];
-        if (!s->K || !s->Vt || s->Tkv <= 0 || s->ldk % 8 || s->ldvt % 8 || s->vt_batch_stride % 8) return IIR_EINVAL;
-    }
-    if (head_dim == 64) return iir_attention_d64_f16(a, stream);
-    if (a->o_fp8) return IIR_EINVAL;
+    if (head_dim == 64) return iir_attention_d64_f16(a, stream);         // (which checks `a` itself)
+    if (head_dim != 80 && head_dim != 104) return IIR_EINVAL;
+    if (!iir::attn_desc_ok(a) || a->o_fp8) return IIR_EINVAL;
     (void)hipGetLastError();
-    HdGeo g{};
-    g.Q = (const f16*)a->Q; g.ldq = a->ldq; g.qbs = a->q_batch_stride;
-    g.O = (f16*)a->O; g.ldo = a->ldo; g.obs = a->o_batch_stride;
-    g.Tq = a->Tq; g.nseg = a->nseg; g.heads = a->heads; g.causal = a->causal;
-    g.c = a->q_prescaled ? 1.0f : a->scale * 1.4426950408889634f;
-    for (int i = 0; i < a->nseg; ++i) {
-        const iir_attn_kv* s = &a->kv[i];
-        g.seg[i] = HdSeg{(const f16*)s->K, s->ldk, s->k_batch_stride, (const f16*)s->Vt, s->ldvt, s->vt_batch_stride, s->Tkv};
-    }
-    g.qtiles = (a->Tq + 127) / 128;
-    const dim3 grid(a->heads * a->batch * g.qtiles);
+    HdGeo g = iir::attn_geo(a, a->batch);
+    if (g.qpre) g.c = 1.0f;            // this kernel scales the scores by c in the softmax: a pre-scaled Q is used as it stands
+    const dim3 grid(g.n_attn);
     if (head_dim == 80) iir_launch(attn_hd_kernel<80>, grid, dim3(256), 0, (hipStream_t)stream, g);
     else iir_launch(attn_hd_kernel<104>, grid, dim3(256), 0, (hipStream_t)stream, g);
     return iir_launch_status();

@@ -92,6 +92,11 @@ __device__ __forceinline__ float gelu_erf_f(float x) {
     return 0.5f * x * (1.0f + copysignf(erf_abs, z));
 }
 
+// x * sigmoid(1.702 x) (CLIP's quick-GELU), same two transcendental instructions as silu_f
+__device__ __forceinline__ float quick_gelu_f(float x) {
+    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * x));
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -20,7 +20,6 @@
 #include "common.h"
 #include "gemm_geo.h"
 #include "../../include/instantir_hip.h"
-#include <type_traits>
 
 namespace {
 
@@ -48,13 +47,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
     const int wm = wave >> 2, wn = wave & 3;
 
     int tm, tn;
-    {   // XCD-aware tile order (see gemm_conv.hip): workgroups b, b+8, ... share an L2
-        const int bid = (int)blockIdx.x, xcd = bid & 7, local = bid >> 3;
-        const int rx = xcd % g.xm, ry = xcd / g.xm;
-        tm = rx * g.rm + local % g.rm;
-        tn = ry * g.rn + local / g.rm;
-        if (tm >= g.tiles_m || tn >= g.tiles_n) return;
-    }
+    if (!iir::tile_of_block(g, tm, tn)) return;
     const int m0 = tm * BM, n0 = tn * BN;
 
     // ---- staging: piece p = q * 8 + wave covers rows 8p .. 8p+7; lane = (row in piece, swizzled 16-byte chunk)
@@ -98,28 +91,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
         for (int q = 0; q < B_PIECES; ++q) stage_b1(1, 1, q);
     }
 
-    // LayerNorm statistics of this tile's rows from the producer's partials (as gemm_conv.hip): one batch of clamped loads
-    if (g.ln_in && tid < BM) {
-        constexpr int MAXP = 8;
-        float2 lnp_in[MAXP];
-        const int m = min(m0 + tid, g.M - 1);
-#pragma unroll
-        for (int j = 0; j < MAXP; ++j) lnp_in[j] = ((const float2*)g.ln_in)[(long)min(j, g.ln_parts - 1) * g.M + m];
-        float sm = 0.f;
-#pragma unroll
-        for (int j = 0; j < MAXP; ++j) sm += j < g.ln_parts ? lnp_in[j].x : 0.f;
-        const float inv_p = 1.0f / (float)g.ln_parts, mean = sm * inv_p;
-        float m2 = 0.f, dev = 0.f;
-#pragma unroll
-        for (int j = 0; j < MAXP; ++j) {
-            const float d = lnp_in[j].x - mean;
-            m2 += j < g.ln_parts ? lnp_in[j].y : 0.f;
-            dev += j < g.ln_parts ? d * d : 0.f;
-        }
-        const float var = (m2 + (float)g.ln_part_cols * dev) * inv_p / (float)g.ln_part_cols;
-        const float rstd = rsqrtf(var + g.ln_eps);
-        rowstat[tid] = make_float2(rstd, -rstd * mean);
-    }
+    // LayerNorm statistics of this tile's rows from the producer's partials, parked in LDS until the epilogue
+    if (g.ln_in && tid < BM) rowstat[tid] = iir::ln_row_stat(g, min(m0 + tid, g.M - 1));
 
     E8 bfr[2][NI], a0[2], a1[2];
     auto read_b = [&](const char* st) {
@@ -158,14 +131,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
             for (int s = 0; s < 2; ++s)
 #pragma unroll
                 for (int j = 0; j < NI; ++j) {
-                    if constexpr (F8) {
-                        typedef long l2 __attribute__((ext_vector_type(2)));
-                        const l2 b2 = __builtin_bit_cast(l2, bfr[s][j]), a2 = __builtin_bit_cast(l2, ac[s]);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(b2[0], a2[0], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(b2[1], a2[1], acc[i][j], 0, 0, 0);
-                    } else {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bfr[s][j], ac[s], acc[i][j], 0, 0, 0);
-                    }
+                    if constexpr (F8) acc[i][j] = iir::mfma16_f8x2(bfr[s][j], ac[s], acc[i][j]);
+                    else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bfr[s][j], ac[s], acc[i][j], 0, 0, 0);
                 }
             __builtin_amdgcn_s_setprio(0);
             if (i == 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // Y(t): every wave holds its weight fragments
@@ -185,17 +152,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
     const bool paired = g.epi != IIR_EPI_PLAIN;
     const int cs = (paired ? BN : 2 * BN) + 32;          // staged row stride in bytes (odd multiple of 32 mod 256)
     constexpr int CHUNK_ROWS = 64, STAGE_STRIDE = CHUNK_ROWS * (2 * BN + 32);
-    auto touch_next_weights = [&]() {
-        const int per = (g.pf_lines + (int)gridDim.x - 1) / (int)gridDim.x;
-        const long l0 = (long)blockIdx.x * per, last = g.pf_lines - 1;
-        char* scratch = smem + RING_BYTES + wave * 256;
-#pragma unroll
-        for (int i = 0; i < PF_TOUCHES; ++i) {
-            long l = l0 + min(tid + i * NT, per - 1);
-            if (l > last) l = last;
-            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(g.pf + l * 128), (LDS_AS void*)scratch, 4, 0, 0);
-        }
-    };
     // column constants of this lane's NI column quads
     f32x4 c1v[NI], scv[F8 ? NI : 1];
     E4 c0v[NI];
@@ -211,7 +167,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
     const int no_tile = paired ? n0 / 2 : n0;
     const bool use_res = g.res && !paired;
     const int total = CHUNK_ROWS * cpr;                        // 16-byte pieces of one chunk (1280 or 2560)
-    touch_next_weights();
+    iir::touch_next_weights<NT, PF_TOUCHES>(g, tid, smem + RING_BYTES + wave * 256);
 #pragma unroll
     for (int c = 0; c < MI / 2; ++c) {
         char* ct = smem + (c & 1) * STAGE_STRIDE;
@@ -225,25 +181,16 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
             for (int j = 0; j < NI; ++j) {
                 float a[4];
 #pragma unroll
-                for (int t = 0; t < 4; ++t) a[t] = fmaf(F8 ? acc[i][j][t] * scv[F8 ? j : 0][t] : acc[i][j][t], rs.x, fmaf(rs.y, c1v[j][t], (float)c0v[j][t]));
+                for (int t = 0; t < 4; ++t) a[t] = iir::epi_affine(F8 ? acc[i][j][t] * scv[F8 ? j : 0][t] : acc[i][j][t], rs, c1v[j][t], (float)c0v[j][t]);
                 if (!paired) {
-                    if (g.act == IIR_ACT_SILU) for (int t = 0; t < 4; ++t) a[t] = silu_f(a[t]);
-                    else if (g.act == IIR_ACT_GELU) for (int t = 0; t < 4; ++t) a[t] = gelu_erf_f(a[t]);
-                    else if (g.act == IIR_ACT_QUICKGELU) for (int t = 0; t < 4; ++t) a[t] = a[t] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * a[t]));
+                    iir::epi_act(g.act, a);
                     E4 o;
                     for (int t = 0; t < 4; ++t) o[t] = (E)a[t];
                     *(E4*)(rowp + (wn * WN + j * 16 + fq * 4) * 2) = o;
                 } else {
-                    // GEGLU: value lanes (fq = 0,1) and their gate lanes (fq + 2) sit 32 lanes apart; the value lane finishes
-                    // columns 0,1 of the quad, its gate lane columns 2,3 (gemm_conv.hip)
-                    float b[4];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) b[t] = __shfl_xor(a[t], 32, 64);
-                    const bool gate = fq >= 2;
-                    const int lco = (wn * WN + j * 16) / 2 + (fq & 1) * 4 + (gate ? 2 : 0);
-                    const float v0 = gate ? b[2] : a[0], v1 = gate ? b[3] : a[1], g0 = gate ? a[2] : b[0], g1 = gate ? a[3] : b[1];
-                    f16x2 o2 = {(E)(v0 * gelu_erf_f(g0)), (E)(v1 * gelu_erf_f(g1))};
-                    *(f16x2*)(rowp + lco * 2) = o2;
+                    int col;
+                    const f16x2 o2 = iir::geglu_pair<E>(a, fq, col);
+                    *(f16x2*)(rowp + ((wn * WN + j * 16) / 2 + col) * 2) = o2;
                 }
             }
         }
@@ -287,18 +234,7 @@ template <int BN, bool F8 = false>
 int launch8(const Geo& g0, hipStream_t stream) {
     constexpr int BM = 256;
     Geo g = g0;
-    g.tiles_m = g.M / BM;
-    g.tiles_n = g.N / BN;
-    // XCD partition: the split whose per-XCD operand panels are smallest (same rule as gemm_conv.hip)
-    double best = -1.;
-    const double row_bytes = (double)g.K * 2.;
-    for (int xm = 1; xm <= 8; xm *= 2) {
-        const int xn = 8 / xm;
-        const int rm = (g.tiles_m + xm - 1) / xm, rn = (g.tiles_n + xn - 1) / xn;
-        double cost = (double)rm * BM * row_bytes + (double)rn * BN * row_bytes;
-        cost += ((double)rm * rn * 8 - (double)g.tiles_m * g.tiles_n) * 8. * BK * (BM + BN);
-        if (best < 0. || cost < best) { best = cost; g.xm = xm; g.rm = rm; g.rn = rn; }
-    }
+    iir::xcd_partition(g, BM, BN, HUGE_VAL);      // whole tiles (gemm8_covers); the split whose per-XCD operand panels are smallest
     const size_t lds = 2 * (BM * 128 + BN * 128) + 2048 + BM * 8;
     static unsigned long long lds_set = 0;
     if (!iir_ensure_dynamic_lds((const void*)gemm8_kernel<BN, F8>, lds, lds_set)) return IIR_ELAUNCH;

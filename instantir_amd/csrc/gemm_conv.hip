@@ -35,16 +35,6 @@ constexpr int BK = 64;   // halfs per K tile = one 128-byte LDS row
 #define IIR_PIN() __builtin_amdgcn_sched_barrier(0)
 constexpr int PF_TOUCHES = 4;   // prefetch touches per lane per launch (x 128 B x threads = up to 128-256 KiB per workgroup)
 
-// Chan's pairwise update of (count, mean, M2) -- the same form norm.hip uses for GroupNorm
-__device__ __forceinline__ void ln_merge(float& n, float& mean, float& m2, float nb, float mb, float m2b) {
-    const float tot = n + nb, d = mb - mean;
-    mean += d * (nb / tot);
-    m2 += m2b + d * d * (n * nb / tot);
-    n = tot;
-}
-
-constexpr int vmcnt_imm(int n) { return (n & 15) | 0x0F70 | ((n >> 4) << 14); }   // s_waitcnt vmcnt(n) only
-
 // GroupNorm-partial write-out (gn_out): 64-row slabs written side by side, and whether its LDS fits behind the staged output tile.
 // One definition for the kernel, its launcher and iir_gemm_gn_supported.  The 128-row loader-wave tile writes its two slabs at
 // once on 256 threads each: the thread layout of the two-per-CU 64x160 tile (id 25) it stands in for, so the partials are
@@ -132,18 +122,8 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     const int wave = loader ? wave_all - NW : wave_all;             // index among the waves of its role
     const int wm = wave >> 1, wn = wave & 1;
 
-    // XCD-aware tile order.  Workgroups b, b+8, b+16, ... share an XCD (= one private L2).  The tile grid is
-    // cut into 8 rectangles (xm x 8/xm), one per XCD, chosen on the host to minimise the operand bytes each
-    // L2 has to pull over the fabric; inside a rectangle tiles walk M fastest so co-resident workgroups
-    // share a weight panel.  Placement only affects speed, never results.
     int tm, tn;
-    {
-        const int bid = (int)blockIdx.x, xcd = bid & 7, local = bid >> 3;
-        const int rx = xcd % g.xm, ry = xcd / g.xm;
-        tm = rx * g.rm + local % g.rm;
-        tn = ry * g.rn + local / g.rm;
-        if (tm >= g.tiles_m || tn >= g.tiles_n) return;     // padding workgroup of a ragged rectangle
-    }
+    if (!iir::tile_of_block(g, tm, tn)) return;
     const int m0 = tm * BM, n0 = tn * BN;
 
     // ---- per-lane staging addresses -------------------------------------------------------------
@@ -271,14 +251,14 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     // ---- main loop: ST-deep LDS ring, tiles kt+1 .. kt+ST-2 stay in flight across the barrier ---------
     // (one barrier per K tile; the buffer refilled after the barrier is the one every wave finished
     //  reading before it arrived there)
-    constexpr int kt0 = 0;
-    const int nk = g.K / BK;                                             // this workgroup's K tiles [kt0, nk): all of K
+    const int nk = g.K / BK;
     if (!LW || loader) {
-        if (CONV) conv_seek(kt0);
+        if (CONV) conv_seek(0);
 #pragma unroll
         for (int s = 0; s < ST - 1; ++s)
-            if (kt0 + s < nk) stage(kt0 + s, s);
+            if (s < nk) stage(s, s);
     }
+    // (Twin of iir::ln_row_stat, gemm_geo.h, which gemm8.hip calls: as a call it grows the scratch of the two 256x320 builds.)
     // LayerNorm statistics of this tile's rows: the producer's per-column-tile partials are fetched here, behind the first K
     // tiles' LDS-DMA, as ONE batch of unconditional loads, merged without a division per group and parked in LDS until the
     // epilogue.  (Measured on the 2048 x 10240 x 1280 GEGLU projection: branchy loads + Chan merges with divisions up front
@@ -325,17 +305,11 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     };
     auto mma = [&](const E8 (&af)[MI], const BF (&bf)[NI]) {
         if constexpr (F8) {
-            typedef long l2 __attribute__((ext_vector_type(2)));
 #pragma unroll
-            for (int i = 0; i < MI; ++i) {
-                const l2 a2 = __builtin_bit_cast(l2, af[i]);
+            for (int i = 0; i < MI; ++i)
 #pragma unroll
-                for (int j = 0; j < NI; ++j) {
-                    const l2 b2 = __builtin_bit_cast(l2, bf[j]);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(b2[0], a2[0], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(b2[1], a2[1], acc[i][j], 0, 0, 0);
-                }
-            }
+                for (int j = 0; j < NI; ++j)
+                    acc[i][j] = iir::mfma16_f8x2(bf[j], af[i], acc[i][j]);
         } else if constexpr (!W8) {
 #pragma unroll
             for (int i = 0; i < MI; ++i)
@@ -345,15 +319,7 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
         } else {
             long a8[MI];
 #pragma unroll
-            for (int i = 0; i < MI; ++i) {          // 8 halves -> 8 fp8 (E4M3, round to nearest even, saturating), k order kept
-                typedef short s16x2 __attribute__((ext_vector_type(2)));
-                s16x2 lo = {0, 0}, hi = {0, 0};
-                lo = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(lo, (f16x2){af[i][0], af[i][1]}, 1.0f, false);
-                lo = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(lo, (f16x2){af[i][2], af[i][3]}, 1.0f, true);
-                hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(hi, (f16x2){af[i][4], af[i][5]}, 1.0f, false);
-                hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(hi, (f16x2){af[i][6], af[i][7]}, 1.0f, true);
-                a8[i] = (long)(unsigned)__builtin_bit_cast(int, lo) | ((long)__builtin_bit_cast(int, hi) << 32);
-            }
+            for (int i = 0; i < MI; ++i) a8[i] = iir_fp8x8(af[i]);      // the conversion producers of fp8 operands store with
 #pragma unroll
             for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -395,9 +361,9 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     };
     if constexpr (!LW) {
         {
-            const int rem = nk - 1 - kt0;
+            const int rem = nk - 1;
             admit(rem < ST - 2 ? rem : ST - 2);
-            if (kt0 + ST - 1 < nk) stage(kt0 + ST - 1, ST - 1);
+            if (ST - 1 < nk) stage(ST - 1, ST - 1);
             frags(0, 0, a0, b0);
             IIR_PIN();
             frags(0, 1, a1, b1);
@@ -405,7 +371,7 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
             mma(a0, b0);
         }
         int cur = 0;
-        for (int kt = kt0 + 1; kt < nk; ++kt) {                 // kt = the tile this iteration admits and starts
+        for (int kt = 1; kt < nk; ++kt) {                 // kt = the tile this iteration admits and starts
             const int rem = nk - 1 - kt;                        // tiles that exist after kt
             admit2(rem < ST - 2 ? rem : ST - 2);
             if (kt - 1 + ST < nk) stage(kt - 1 + ST, cur);      // tile kt-1's buffer is free: every wave finished reading it
@@ -422,12 +388,12 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     } else if (loader) {
         // loader waves: same barriers, same counted waits, no LDS reads and no MFMAs
         {
-            const int rem = nk - 1 - kt0;
+            const int rem = nk - 1;
             admit(rem < ST - 2 ? rem : ST - 2);
-            if (kt0 + ST - 1 < nk) stage(kt0 + ST - 1, ST - 1);
+            if (ST - 1 < nk) stage(ST - 1, ST - 1);
         }
         int cur = 0;
-        for (int kt = kt0; kt + 1 < nk; ++kt) {
+        for (int kt = 0; kt + 1 < nk; ++kt) {
             const int rem = nk - 2 - kt;
             admit(rem < ST - 2 ? rem : ST - 2);
             if (kt + ST < nk) stage(kt + ST, cur);
@@ -442,7 +408,7 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
         IIR_PIN();
         mma(a0, b0);
         int cur = 0;
-        for (int kt = kt0 + 1; kt < nk; ++kt) {
+        for (int kt = 1; kt < nk; ++kt) {
             admit2(0);
             cur = cur + 1 == ST ? 0 : cur + 1;
             frags(cur, 0, a0, b0);
@@ -508,7 +474,7 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
             for (int j = 0; j < NI; ++j)
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
-                    qf[i][j >> 1][(j & 1) * 4 + t] = (E)fmaf(acc[i][j][t], rs.x, fmaf(rs.y, pre_c1[j][t], (float)pre_c0[j][t]));
+                    qf[i][j >> 1][(j & 1) * 4 + t] = (E)iir::epi_affine(acc[i][j][t], rs, pre_c1[j][t], (float)pre_c0[j][t]);
         }
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");         // K / V images complete (waiting for K alone here and for V^T before P V measured no better)
         // S = q K^T: 9 key blocks of 16 (5 text, 4 IP), contraction over d in the accumulator's order
@@ -651,11 +617,12 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
                 const int lr = lrs[i];
                 float v[4];
                 for (int t = 0; t < 4; ++t) v[t] = (W8 || F8) ? acc[i][j][t] * sc[t] : acc[i][j][t];
-                for (int t = 0; t < 4; ++t) v[t] = fmaf(v[t], rss[i].x, fmaf(rss[i].y, c1[t], c0[t]));     // (1, 0) without ln_in
+                for (int t = 0; t < 4; ++t) v[t] = iir::epi_affine(v[t], rss[i], c1[t], c0[t]);
                 if (g.rowbias) { E4 b = *(const E4*)(g.rowbias + (long)(ms[i] / g.rows_per_rb) * g.ldrb + n); for (int t = 0; t < 4; ++t) v[t] += (float)b[t]; }
+                // (twin of iir::epi_act, gemm_geo.h: as a call it grows the scratch of the two 256x320 builds)
                 if (g.act == IIR_ACT_SILU) for (int t = 0; t < 4; ++t) v[t] = silu_f(v[t]);
                 else if (g.act == IIR_ACT_GELU) for (int t = 0; t < 4; ++t) v[t] = gelu_erf_f(v[t]);
-                else if (g.act == IIR_ACT_QUICKGELU) for (int t = 0; t < 4; ++t) v[t] = v[t] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * v[t]));
+                else if (g.act == IIR_ACT_QUICKGELU) for (int t = 0; t < 4; ++t) v[t] = quick_gelu_f(v[t]);
                 E4 o;
                 for (int t = 0; t < 4; ++t) o[t] = (E)v[t];
                 *(E4*)(ct + lr * cs + lc * 2) = o;
@@ -677,10 +644,11 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
                 const int lr = lrs[i];
                 float a[4];
                 for (int t = 0; t < 4; ++t) a[t] = (W8 || F8) ? acc[i][j][t] * sc[t] : acc[i][j][t];
-                for (int t = 0; t < 4; ++t) a[t] = fmaf(a[t], rss[i].x, fmaf(rss[i].y, c1[t], c0[t]));
+                for (int t = 0; t < 4; ++t) a[t] = iir::epi_affine(a[t], rss[i], c1[t], c0[t]);
                 float b[4];
                 for (int t = 0; t < 4; ++t) b[t] = __shfl_xor(a[t], 32, 64);     // all lanes take part in the exchange
                 if (g.epi == IIR_EPI_GEGLU) {
+                    // (Twin of iir::geglu_pair, gemm_geo.h, which gemm8.hip calls: as a call it costs the bf16 64x64 build a wave per SIMD.)
                     // value * gelu(gate): the erf evaluation (14 VALU + v_rcp + v_exp per element) is the cost of this epilogue
                     // -- kbench 2048x10240x1280: 865 TFLOP/s plain, 735 with value lanes alone doing all four columns -- so
                     // both lanes of a pair work: the value lane finishes columns 0,1 of the quad, its gate lane columns 2,3.
@@ -710,19 +678,8 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // tile complete
 
     // ---- phase 2: LDS -> memory, one 16-byte chunk of a row per lane: residual loads, add, then the weight prefetch
-    // for the launches that follow (see iir_gemm_desc.prefetch: 4-byte LDS-DMA touches, clamped into the range; no VGPR
-    // destination, the data lands in a scratch KiB behind the ring and is never read), then the stores.
-    auto touch_next_weights = [&]() {
-        const int per = (g.pf_lines + (int)gridDim.x - 1) / (int)gridDim.x;
-        const long l0 = (long)blockIdx.x * per, last = g.pf_lines - 1;
-        char* scratch = smem + RING_BYTES + wave_all * 256;
-#pragma unroll
-        for (int i = 0; i < PF_TOUCHES; ++i) {
-            long l = l0 + min(tid + i * NT, per - 1);
-            if (l > last) l = last;
-            __builtin_amdgcn_global_load_lds((const GLOBAL_AS void*)(g.pf + l * 128), (LDS_AS void*)scratch, 4, 0, 0);
-        }
-    };
+    // for the launches that follow, then the stores.
+    auto touch_next_weights = [&]() { iir::touch_next_weights<NT, PF_TOUCHES>(g, tid, smem + RING_BYTES + wave_all * 256); };
     auto write_out = [&](auto cpr_tag) {
         constexpr int CPR = decltype(cpr_tag)::value;                    // 16-byte chunks per tile row
         constexpr int TOTAL = BM * CPR, CH = (TOTAL + NT - 1) / NT;
@@ -925,8 +882,6 @@ int launch_k(const Geo& g0, hipStream_t stream) {
     constexpr int NT = 128 * WAVES_M * (LW ? 2 : 1);
     constexpr size_t lds = lds_bytes(BM, BN, ST, WAVES_M, W8, LW);
     Geo g = g0;
-    g.tiles_m = (g.M + BM - 1) / BM;
-    g.tiles_n = (g.N + BN - 1) / BN;
     if (g.c_fp8) {          // fp8 output: stored by the straight-line write-out only (whole tiles, 8-byte addressable rows)
         if (CONV || g.M % BM || g.N % BN || g.ldc % 8 || (uintptr_t)g.C % 8 || g.Ct || g.c_f32 || g.ln_out || g.gn_out || g.res_img_rows || g.y_img_rows ||
             (g.res && !g.r_vec) || g.dtype != IIR_DT_F16) return IIR_EINVAL;
@@ -943,22 +898,7 @@ int launch_k(const Geo& g0, hipStream_t stream) {
         if (!fits || CONV || g.epi != IIR_EPI_PLAIN || g.c_f32 || g.Ct || g.M % BM || g.N % BN || !g.c_vec || (g.res && !g.r_vec))
             return IIR_EINVAL;
     }
-    // pick the XCD partition (xm x 8/xm rectangles of the tile grid) with the least bytes each 4 MiB L2 pulls over the
-    // fabric.  Inside a rectangle tiles walk M fastest, ~64 workgroups are resident per XCD, so its rm x BM rows of A are
-    // re-used by successive groups of N-tile columns: if they fit the L2 they are read once, otherwise once per group.
-    // (PMC: the 128x160 GEMM class read 137 MB per launch against 52 MB of operands; kbench 16384x5120x640: 615 -> 679 TFLOP/s)
-    double best = -1.;
-    const double row_bytes = (double)g.K * 2.;
-    for (int xm = 1; xm <= 8; xm *= 2) {
-        const int xn = 8 / xm;
-        const int rm = (g.tiles_m + xm - 1) / xm, rn = (g.tiles_n + xn - 1) / xn;
-        const double a_bytes = (double)rm * BM * row_bytes, w_bytes = (double)rn * BN * row_bytes;
-        const int cols_per_group = rm >= 64 ? 1 : 64 / rm;
-        const double groups = (double)((rn + cols_per_group - 1) / cols_per_group);
-        double cost = (a_bytes <= 3.0 * 1048576. ? a_bytes : a_bytes * groups) + w_bytes;
-        cost += ((double)rm * rn * 8 - (double)g.tiles_m * g.tiles_n) * 8. * BK * (BM + BN);     // padding workgroups of ragged rectangles
-        if (best < 0. || cost < best) { best = cost; g.xm = xm; g.rm = rm; g.rn = rn; }
-    }
+    iir::xcd_partition(g, BM, BN, 3.0 * 1048576.);      // tile grid and its XCD partition
     const dim3 grid(8 * g.rm * g.rn), block(NT);
     const auto kern = gemm_kernel<E, BM, BN, ST, CONV, WAVES_M, W8, LW, F8>;
     static unsigned long long lds_set = 0;

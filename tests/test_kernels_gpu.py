@@ -879,3 +879,19 @@ def test_gemm_conv_bits_match_the_recorded_library(dev):
     assert len(got) == len(want) and sorted(got) == sorted(want), "the replayed cases are not the recorded ones"
     bad = [k for k in sorted(want) if not np.array_equal(got[k], want[k])]
     assert not bad, f"{len(bad)}/{len(want)} buffers differ from the library of commit {recorded_by}: {bad}"
+
+
+# ---- every build of the attention kernels, bit for bit against a recorded library ---------------------------------------------------
+def test_attention_bits_match_the_recorded_library(dev):
+    """tests/golden/attention_bits.npz holds the SHA-256 of every output buffer (margins included) of 22 small launches that
+    between them run the six builds of `attn_kernel2` (staged at entry, the ring for 2 and for 3 waves per SIMD, the identity form
+    of each) and both builds of `attn_hd_kernel`, with every masked path, written by the library as it stood before the two
+    attention files got one definition of their shared code (tests/golden/make_attention_bits.py).  The same launches on this
+    library must give the same bits, key for key, and write nothing outside their views."""
+    from golden import make_attention_bits as maker
+    want = dict(np.load(maker.PATH))
+    recorded_by = bytes(want.pop(maker.PARENT_KEY)).decode()
+    got = maker.replay()
+    assert len(got) == len(want) and sorted(got) == sorted(want), "the replayed cases are not the recorded ones"
+    bad = [k for k in sorted(want) if not np.array_equal(got[k], want[k])]
+    assert not bad, f"{len(bad)}/{len(want)} buffers differ from the library of commit {recorded_by}: {bad}"
