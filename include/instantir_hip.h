@@ -176,6 +176,18 @@ int iir_attention_d64_ident_f16(const iir_attn_desc* a, int32_t ident_from, void
  * head_dim 64 is routed to iir_attention_d64_f16. */
 int iir_attention_f16(const iir_attn_desc* a, int32_t head_dim, void* stream);
 
+/* Single-head attention of AutoencoderKL's mid block: `Attention(heads=1)` of module/unet/unet_2d_ZeroSFT_blocks.py:776-790,
+ * whose SDPA is module/ip_adapter/attention_processor.py:394, at head_dim = the block's channel count (128, 256 or 512).
+ * One flash-style launch for the whole batch, nothing of size Tq x Tkv in memory, any Tq >= 1 and Tkv >= 1.
+ * dtype: IIR_DT_F16 / IIR_DT_BF16, the element type of Q, K, Vt, O and o_bias (fp32 scores, softmax and accumulation).
+ * Layouts as iir_attention_d64_f16 with heads = 1 and 64 -> head_dim; Vt rows must be readable on [0, roundup8(Tkv)) but
+ * need not be finite at and past Tkv.  O = softmax(Q K^T * scale) V + o_bias (o_bias: [head_dim] or NULL; rows of the
+ * softmax sum to 1, so this is the V projection's bias added after the product).
+ * IIR_EINVAL for heads != 1, nseg != 1, causal, o_fp8, q_prescaled, another head_dim or dtype, a null Q / K / Vt / O, a row or
+ * batch stride that is not a multiple of 8 elements or a row stride below the row, Tq / Tkv / batch < 1, scale <= 0, and
+ * Q / K / Vt not 16-byte (O, o_bias: 8-byte) aligned. */
+int iir_attention_1h(const iir_attn_desc* a, int32_t head_dim, int32_t dtype, const void* o_bias, void* stream);
+
 /* nn.GroupNorm (+ fused nn.SiLU) on NHWC: module/min_sdxl.py:245,252,257,269-271,568,841.
  * workspace: iir_groupnorm_workspace_bytes(R, groups) bytes of fp32 partial sums. */
 int iir_groupnorm_nhwc_f16(const void* X, int64_t ldx, void* Y, int64_t ldy, int32_t R, int32_t HW, int32_t C,

@@ -17,6 +17,8 @@ hipcc $FLAGS -mllvm -amdgpu-mfma-vgpr-form=1 -fno-honor-nans -c attention.hip -o
 pids+=($!)
 hipcc $FLAGS -mllvm -amdgpu-mfma-vgpr-form=1 -fno-honor-nans -c attention_hd.hip -o build/attention_hd.o &
 pids+=($!)
+hipcc $FLAGS -mllvm -amdgpu-mfma-vgpr-form=1 -fno-honor-nans -c attention_1h.hip -o build/attention_1h.o &
+pids+=($!)
 hipcc $FLAGS -ffp-contract=off -c pointwise.hip -o build/pointwise.o &
 pids+=($!)
 hipcc $FLAGS -ffp-contract=off -c freeu.hip -o build/freeu.o &
@@ -24,5 +26,5 @@ pids+=($!)
 hipcc $FLAGS -ffp-contract=off -c colorfix.hip -o build/colorfix.o &
 pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT build/gemm_conv.o build/gemm8.o build/attention.o build/attention_hd.o build/norm.o build/pointwise.o build/freeu.o build/colorfix.o
+hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT build/gemm_conv.o build/gemm8.o build/attention.o build/attention_hd.o build/attention_1h.o build/norm.o build/pointwise.o build/freeu.o build/colorfix.o
 echo "built $(realpath $OUT)"

@@ -141,6 +141,9 @@ def build_parser():
     p.add_argument("--color_fix", choices=["none", "wavelet", "adain"], default="none",
                    help="transfer the colour of the LQ input onto the restored image after the VAE decode (pipe(..., color_fix=...)); "
                         "default none")
+    p.add_argument("--vae_flash_attention", action="store_true",
+                   help="run the VAE mid-block attention as one flash-style launch (pipe.vae.enable_flash_attention()): untiled "
+                        "encode / decode beyond 1024x1024; off by default")
     return p
 
 
@@ -225,6 +228,15 @@ def apply_pag(pipe, args):
     return {"pag_scale": scale, "pag_adaptive_scale": adaptive}
 
 
+def apply_vae_flash_attention(pipe, args):
+    """`--vae_flash_attention` -> pipe.vae.enable_flash_attention() (an addition: the reference's VAE attention goes through
+    torch SDPA at any size).  Without the flag the VAE is left as built (three GEMMs around a row softmax, 16384-pixel ceiling)."""
+    if getattr(args, "vae_flash_attention", False):
+        if pipe.vae is None:
+            raise SystemExit("--vae_flash_attention needs a pipeline with a VAE")
+        pipe.vae.enable_flash_attention()
+
+
 def apply_color_fix(args):
     """`--color_fix {none,wavelet,adain}` -> the call's `color_fix` keyword argument (an addition: the reference has no colour
     fix).  `none`, the default, adds nothing to the call."""
@@ -240,6 +252,7 @@ def main(args, device, rank=0, world=1):
     apply_scheduler(pipe, args)
     pag_kw = apply_pag(pipe, args)
     pag_kw.update(apply_color_fix(args))
+    apply_vae_flash_attention(pipe, args)
     post_fix = f"_{args.post_fix}" if args.post_fix else ""
     out_dir = f"{args.out_path}/{post_fix}"
     os.makedirs(out_dir, exist_ok=True)

@@ -106,6 +106,7 @@ SIGNATURES = {
     "iir_attention_d64_f16": (C.c_int, [C.POINTER(AttnDesc), _P]),
     "iir_attention_d64_ident_f16": (C.c_int, [C.POINTER(AttnDesc), _I32, _P]),
     "iir_attention_f16": (C.c_int, [C.POINTER(AttnDesc), _I32, _P]),
+    "iir_attention_1h": (C.c_int, [C.POINTER(AttnDesc), _I32, _I32, _P, _P]),
     "iir_groupnorm_nhwc_f16": (C.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _F, _I32, _P, _I64, _P]),
     "iir_groupnorm_nhwc": (C.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _F, _I32, _P, _I64, _I32, _P]),
     "iir_groupnorm_from_partials": (C.c_int, [_P, _I64, _P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _P, _P, _F, _I32, _P, _I64, _I32, _P]),

@@ -441,6 +441,38 @@ def attention(q, o, kv, batch, heads, Tq, scale=0.125, causal=False, q_prescaled
     return o
 
 
+def attention_1h(q, o, k, vt, vt_batch_stride, batch, Tq, Tkv, scale, bias=None):
+    """Single-head attention at head_dim = q.shape[1] (128 / 256 / 512: the VAE mid block), `iir_attention_1h`: one flash-style
+    launch for the whole batch.  q, o: 2-D views (batch*Tq, D); k: (batch*Tkv, D) view; vt: (D, cols) view with image b's keys
+    at columns b*vt_batch_stride + [0, Tkv), readable up to roundup8(Tkv) (values at and past Tkv are ignored); bias: (D,)
+    added to every output row.  fp16 or bf16, taken from the tensors."""
+    dt = q.dtype
+    if dt not in _DT:
+        raise ValueError(f"attention_1h: fp16 or bf16 expected, got {dt}")
+    for t_, n_ in ((q, "q"), (o, "o"), (k, "k"), (vt, "vt")):
+        _chk2d(t_, n_, dt)
+    D = q.shape[1]
+    if o.shape[1] != D or k.shape[1] != D or vt.shape[0] != D:
+        raise ValueError("attention_1h: q, o, k need the same width D and vt D rows")
+    if q.shape[0] < batch * Tq or o.shape[0] < batch * Tq or k.shape[0] < batch * Tkv:
+        raise ValueError("attention_1h: q / o need batch*Tq rows and k batch*Tkv rows")
+    last = (batch - 1) * vt_batch_stride
+    if last + Tkv > vt.shape[1] or last + (Tkv + 7) // 8 * 8 > vt.stride(0) or (batch > 1 and vt_batch_stride < Tkv):
+        raise ValueError("attention_1h: every image's Tkv columns must lie inside vt and their roundup8(Tkv) inside a row of its buffer")
+    if bias is not None and (bias.dtype != dt or bias.dim() != 1 or bias.numel() != D or not bias.is_contiguous() or not bias.is_cuda):
+        raise ValueError(f"attention_1h: bias must be a contiguous {dt} CUDA vector of {D}")
+    d = L.AttnDesc()
+    d.Q, d.ldq, d.q_batch_stride = q.data_ptr(), q.stride(0), Tq * q.stride(0)
+    d.O, d.ldo, d.o_batch_stride = o.data_ptr(), o.stride(0), Tq * o.stride(0)
+    d.batch, d.heads, d.Tq, d.nseg, d.scale = batch, 1, Tq, 1, scale
+    e = d.kv[0]
+    e.K, e.ldk, e.k_batch_stride = k.data_ptr(), k.stride(0), Tkv * k.stride(0)
+    e.Vt, e.ldvt, e.vt_batch_stride, e.Tkv = vt.data_ptr(), vt.stride(0), vt_batch_stride, Tkv
+    with _Timed("attn_1h_kernel", 4.0 * batch * Tq * D * Tkv, 2.0 * batch * D * (2 * Tq + 2 * Tkv)):
+        L.check(L.load().iir_attention_1h(C.byref(d), D, _DT[dt], _p(bias), _stream()), "iir_attention_1h")
+    return o
+
+
 _gn_ws = {}
 
 

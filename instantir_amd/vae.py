@@ -16,6 +16,24 @@ the mid block is three GEMMs around a row softmax: S = QK^T/sqrt(C) written as F
 P = softmax(S) (`iir_softmax_rows_f32`, fp32 in, 16-bit out), O = P V + b_v (rows of P sum to 1, so the V bias
 is added after the product).  T x T scores limit the untiled decode to 16384 latent pixels (1024^2 images); larger
 images decode tile by tile (`enable_tiling()`), as BASELINE configs[3] asks.
+
+`enable_flash_attention()` (off by default) runs that attention as ONE flash-style launch per mid block instead
+(`iir_attention_1h`, csrc/attention_1h.hip): q, k and V^T of all images are projected at once, the kernel keeps fp32 scores,
+softmax statistics and accumulators in registers, and nothing of size T x T is allocated, so any T >= 1 goes through (no
+ceiling, no T % 4 rule) and the arena shrinks by the score and probability buffers.  Tiling and slicing decide as before; the
+switch only changes how each mid-block attention is computed, inside tiles too.  The two paths round differently (the default
+normalises P before rounding it, the flash kernel after the product), so their images agree to the VAE's PSNR bars, not bit
+for bit.
+
+Size limit with the switch on, from reading the index arithmetic of every kernel on the path (not from running sizes up):
+GroupNorm (norm.hip), pack / unpack (pointwise.hip), the GEMM / conv operand gathers and the flash kernel address with 64-bit
+offsets throughout and hold pixel / row counts in int32.  The one 32-bit BYTE offset is the GEMM / conv output store
+(`store16` in gemm_geo.h, a buffer store with a 31-bit range), which the host enables only while M * ldc * 2 < 2^31 and
+otherwise replaces by plain 64-bit stores -- a path no test has ever taken.  The VAE therefore refuses, before any launch,
+a pass whose largest activation reaches 2 GiB: the decoder's is 256 channels at 64 T pixels (32768 T bytes per image), the
+encoder's 128 channels at 64 T (16384 T bytes), so decode needs R * T < 65536 and encode R * T < 131072 latent pixels at the
+SDXL widths (`_check_flash_geometry` computes it from the config).  1536 x 1024 (T = 24576) decodes untiled; 2048^2
+(T = 65536) is one pixel row past the limit and still goes through `enable_tiling()`.
 """
 from __future__ import annotations
 
@@ -46,6 +64,7 @@ class HipVAE:
         self.tile_overlap_factor = 0.25      # autoencoder_kl.py:124
         self.use_tiling = False              # `vae.enable_tiling()` (autoencoder_kl.py:130-143)
         self.use_slicing = False             # `vae.enable_slicing()` (autoencoder_kl.py:145-157)
+        self.use_flash_attention = False     # `vae.enable_flash_attention()`: mid-block attention as one `iir_attention_1h` launch
         self.dtype_name = "bf16" if dtype == torch.bfloat16 else "fp16"
         F16 = dtype          # (the rest of this class allocates its 16-bit tensors as `F16`: the VAE's element type)
         self._E = dtype
@@ -91,6 +110,29 @@ class HipVAE:
     def disable_slicing(self):
         self.use_slicing = False
 
+    def enable_flash_attention(self, on: bool = True):
+        """Run the mid-block attention as one flash-style launch per block (`iir_attention_1h`) instead of three GEMMs around
+        a row softmax per image: no T x T buffer, so no 16384-pixel ceiling and no T % 4 rule.  Off by default; inside tiles
+        too when tiling is on (which keeps deciding by size alone).  Results differ from the default path in the last bits."""
+        self.use_flash_attention = bool(on)      # (the arena is sized per (geometry, switch): `_run` keys)
+
+    def disable_flash_attention(self):
+        self.enable_flash_attention(False)
+
+    def _check_flash_geometry(self, what, R, T):
+        """With flash attention nothing of size T x T is left, so the other kernels set the limit.  The largest activation of a
+        pass over R images of T latent pixels must stay below 2 GiB (see the module header): raised before any launch."""
+        ch = self.cfg.block_out_channels
+        n = len(ch)
+        if what == "decode":      # up block i runs ch[-1-i] channels at 4^i T pixels and its upsampler writes them at 4^(i+1) T
+            per_pixel = max(ch[n - 1 - i] * 4 ** min(i + 1, n - 1) for i in range(n))
+        else:                     # down block i runs ch[i] channels at 4^(n-1-i) T pixels
+            per_pixel = max(ch[i] * 4 ** (n - 1 - i) for i in range(n))
+        if R * T * per_pixel * 2 >= 1 << 31:
+            raise ValueError(f"VAE {what} of {R} x {T} latent pixels: its largest activation ({R * T * per_pixel * 2} bytes) reaches "
+                             "2 GiB, beyond what the conv / GroupNorm launches have been verified for; use vae.enable_tiling() "
+                             "(and vae.enable_slicing() for batches)")
+
     @property
     def tile_latent_min_size(self):
         return self.tile_sample_size // 8       # sample_size / 2^(len(block_out_channels) - 1), autoencoder_kl.py:123
@@ -120,6 +162,8 @@ class HipVAE:
 
     def _attention(self, path, x, R, H, W):
         """Attention(heads=1, dim_head=C, group_norm, bias, residual) -- blocks :776-790, processor :346-412."""
+        if self.use_flash_attention:
+            return self._attention_flash(path, x, R, H, W)
         o, w, A = self.o, self.w, self.arena
         T, C = H * W, x.shape[1]
         out = A.alloc(R * T, C)
@@ -132,7 +176,8 @@ class HipVAE:
         a = A.alloc(R * T, C)
         if T > 16384 or T % 4:
             raise ValueError(f"VAE mid-block attention over {T} latent pixels: the untiled path handles up to 16384 (a 1024x1024 "
-                             "image); call vae.enable_tiling() for larger images (autoencoder_kl.py:130-136)")
+                             "image) with T % 4 == 0; call vae.enable_tiling() for larger images (autoencoder_kl.py:130-136) or "
+                             "vae.enable_flash_attention() for the attention without a T x T buffer")
         s32 = A.alloc(T, 2 * T).view(torch.float32)                               # fp32 scores (T, T)
         pr = A.alloc(T, T)                                                        # probabilities, 16-bit
         vt = A.alloc(C, T)
@@ -142,6 +187,32 @@ class HipVAE:
             o.gemm(q[rows], k[rows], s32, out_scale=C ** -0.5)                    # S = Q K^T / sqrt(C), kept in fp32
             o.softmax_rows_f32(s32, pr)
             o.gemm(pr, vt, a[rows], bias=w[path + ".to_v.b"])                     # O = P V + b_v
+        o.gemm(a, w[path + ".to_out.0.w"], out, bias=w[path + ".to_out.0.b"], res=x)
+        A.release(m)
+        return out
+
+    def _attention_flash(self, path, x, R, H, W):
+        """The same block with `use_flash_attention`: q, k and V^T of all images projected at once, then one `attention_1h`
+        launch (softmax(q k^T / sqrt(C)) v + b_v).  No score, probability or per-image buffer."""
+        o, w, A = self.o, self.w, self.arena
+        T, C = H * W, x.shape[1]
+        Tp = (T + 7) // 8 * 8                      # an image's V^T columns start at a multiple of 8 (16-byte chunks)
+        out = A.alloc(R * T, C)
+        m = A.mark()
+        nb = A.alloc(R * T + 8, C)                 # (8 spare rows: a padded V^T projection of the last image reads past its end)
+        n = nb[:R * T]
+        o.groupnorm(x, n, R, T, w[path + ".group_norm.g"], w[path + ".group_norm.b"], 1e-6, False, self.cfg.norm_groups, self._gnws)
+        q, k = A.alloc(R * T, C), A.alloc(R * T, C)
+        o.gemm(n, w[path + ".to_q.w"], q, bias=w[path + ".to_q.b"])
+        o.gemm(n, w[path + ".to_k.w"], k, bias=w[path + ".to_k.b"])
+        vt = A.alloc(C, R * Tp)
+        if Tp == T:
+            o.gemm(w[path + ".to_v.w"], n, vt)                                     # V^T of all images (bias added after P V)
+        else:                                      # the GEMM writes whole groups of 4 columns: per image, Tp columns from Tp rows
+            for r in range(R):                     # (columns [T, Tp) come from the next image's rows or the spare ones: never used)
+                o.gemm(w[path + ".to_v.w"], nb[r * T:r * T + Tp], vt[:, r * Tp:(r + 1) * Tp])
+        a = A.alloc(R * T, C)
+        o.attention_1h(q, a, k, vt, Tp, R, T, T, C ** -0.5, bias=w[path + ".to_v.b"])
         o.gemm(a, w[path + ".to_out.0.w"], out, bias=w[path + ".to_out.0.b"], res=x)
         A.release(m)
         return out
@@ -169,12 +240,14 @@ class HipVAE:
     # ---- decode -----------------------------------------------------------------------------------
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         """z: (B,4,h,w) fp32 latents ALREADY divided by the scaling factor.  Returns (B,3,8h,8w) fp32."""
+        if self.use_flash_attention:
+            self._check_flash_geometry("decode", z.shape[0], z.shape[2] * z.shape[3])
         z = z.to(self.device, torch.float32).contiguous()
         B, _, h, wd = z.shape
         out = torch.empty(B, 4, 8 * h, 8 * wd, dtype=torch.float32, device=self.device)
         zin = torch.zeros(B * h * wd, CPAD, dtype=self._E, device=self.device)
         ops.pack_latent(z, zin)
-        self._run(("dec", B, h, wd), lambda: self._decode(zin, B, h, wd, out))
+        self._run(("dec", B, h, wd, self.use_flash_attention), lambda: self._decode(zin, B, h, wd, out))
         return out[:, :3]
 
     def _decode(self, zin, R, H, W, out):
@@ -279,12 +352,14 @@ class HipVAE:
 
     def moments(self, image: torch.Tensor) -> torch.Tensor:
         """encoder + quant_conv: the 8-channel posterior moments (B, 8, H/8, W/8), fp32."""
+        if self.use_flash_attention:
+            self._check_flash_geometry("encode", image.shape[0], (image.shape[2] // 8) * (image.shape[3] // 8))
         image = image.to(self.device, torch.float32).contiguous()
         B, _, H, W = image.shape
         xin = torch.zeros(B * H * W, CPAD, dtype=self._E, device=self.device)
         ops.pack_latent(image, xin)
         mom = torch.empty(B, 8, H // 8, W // 8, dtype=torch.float32, device=self.device)
-        self._run(("enc", B, H, W), lambda: self._encode(xin, B, H, W, mom))
+        self._run(("enc", B, H, W, self.use_flash_attention), lambda: self._encode(xin, B, H, W, mom))
         if not torch.isfinite(mom).all():
             raise FloatingPointError(f"VAE encode produced non-finite moments (activation overflow in the {self.dtype_name} build)")
         return mom

@@ -215,4 +215,11 @@ for (cB, cH, cW) in [(1, 1024, 1024), (2, 768, 1024), (1, 257, 131)]:
         screen(f"colorfix {cf_mode} {cB}x3x{cH}x{cW}", lambda o: ops.colorfix(cf_c, cf_s, cf_mode, out=o), [(cB, 3, cH, cW)], dtype=torch.float32)
         screen(f"colorfix {cf_mode} {cB}x3x{cH}x{cW} in place", lambda o: (o.copy_(cf_c), ops.colorfix(o, cf_s, cf_mode, out=o)),
                [(cB, 3, cH, cW)], dtype=torch.float32)
+# single-head VAE attention (round 9, iir_attention_1h): tiny() and SDXL mid widths, both element types, below and at the old ceiling
+for a1D in (128, 512):
+    for a1dt in (torch.bfloat16, torch.half):
+        for a1T in (1024, 16384):
+            a1q, a1k, a1vt, a1b = rnd(a1T, a1D).to(a1dt), rnd(a1T, a1D).to(a1dt), rnd(a1D, a1T).to(a1dt), rnd(a1D).to(a1dt)
+            screen(f"attention_1h D={a1D} {'bf16' if a1dt == torch.bfloat16 else 'fp16'} T={a1T}",
+                   lambda o: ops.attention_1h(a1q, o, a1k, a1vt, a1T, 1, a1T, a1T, a1D ** -0.5, bias=a1b), [(a1T, a1D)], dtype=a1dt)
 print("kernels with run-to-run differences:", bad)
