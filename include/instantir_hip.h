@@ -317,6 +317,42 @@ int iir_sched_step_hist_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_
                             const float* eps_factor, void* stream);
 int iir_cfg_rescale_factor_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, const float* coef,
                                const float* pag_scale, float guidance_rescale, float* factor, void* stream);
+/* Region-selective restoration (a per-pixel restore map; no reference counterpart -- it extends the CFG + scheduler step of
+ * pipelines/sdxl_instantir.py:1619-1633, and "kept" means the trajectory of the LQ latent that :1388-1403 noises to the first
+ * timestep).  iir_sched_step_keep is iir_sched_step with every optional plane of the family (pag_scale, noise, hist, x0_out,
+ * eps_out, eps_factor: NULL = absent, meaning as in the entries above) plus the keep group, all four required:
+ *   keep_map   fp32 (B, HW): the map at latent resolution, values in [0, 1] (1 = denoised freely in every step)
+ *   keep_src   fp32 NCHW (B, C, H, W): the LQ latent;  keep_noise: fp32 NCHW, the noise that seeded the start of the loop
+ *   keep_coef  device fp32[4] {thr, a, b, 0}, read at launch time so that one captured launch serves every step
+ * After the update produced prev:  prev[b,c,p] = keep[b,c,p] if keep_map[b,p] <= thr else prev[b,c,p], with
+ * keep = a * keep_src + b * keep_noise -- the expression of iir_axpby_f32, bit for bit; a term whose coefficient is 0 is
+ * skipped, so {thr, 1, 0} returns the bits of keep_src whatever keep_noise holds.  The caller passes, for step i of N,
+ * thr = (N - 1 - i) / N and (a, b) = the add_noise pair of the timetable entry that follows the step ((1, 0) after the last).
+ * It is a SELECT on an fp32 compare, never an arithmetic blend: a free element has the bits of the launch without a map, a
+ * kept element those of add_noise, and NaN / Inf in a kept pixel's eps never reach prev.  x0_out, hist and eps_out are
+ * written exactly as without a map (a multistep solver's history stays the model's own x0).
+ * IIR_EINVAL: a NULL keep_* pointer, eps_out together with hist, keep_src or keep_noise aliasing prev, and whatever
+ * iir_sched_step refuses. */
+int iir_sched_step_keep(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg, const float* coef,
+                        const float* pag_scale, const float* x, const float* noise, float* hist, float* prev, float* x0_out,
+                        float* eps_out, const float* eps_factor, const float* keep_map, const float* keep_src,
+                        const float* keep_noise, const float* keep_coef, void* stream);
+/* The restore map at latent resolution: out (B, H / factor, W / factor) = the maximum of map_px (B, H, W) over each
+ * factor x factor block (a latent pixel is free if any pixel under it asked for freedom).  fp32; H and W multiples of
+ * factor, H, W <= 32768; `out` must not be `map_px`.  IIR_EINVAL for any other geometry, before any launch. */
+int iir_map_pool_max_f32(const float* map_px, int32_t B, int32_t H, int32_t W, int32_t factor, float* out, void* stream);
+/* Pixel composite of a restored image with its input under a restore map.  decoded, original, out: fp32 planar
+ * (B, C, H, W); map_px fp32 (B, H, W).  P = [map_px > 0]; cnt(y, x) = sum of P over the (2r+1) x (2r+1) window with
+ * coordinates clamped to the image (replicate edge); w = cnt / (2r+1)^2;
+ *   out = decoded where cnt == (2r+1)^2, original where cnt == 0, else w * decoded + (1 - w) * original   (fp32, no FMA)
+ * so a pixel whose window lies wholly in the kept region is the input pixel bit for bit.  r = 0 is a hard paste.  Two
+ * launches on integer counts: rows into `ws` (iir_region_composite_workspace_bytes(B, H, W) bytes; -1 for a geometry outside
+ * the limits), columns fused with the composite.  `out` may equal `decoded`, nothing else.  H, W <= 32768, B * C <= 32767,
+ * 0 <= r <= IIR_REGION_MAX_FEATHER; IIR_EINVAL otherwise, before any launch.  No atomics: equal inputs give equal bits. */
+#define IIR_REGION_MAX_FEATHER 512
+int64_t iir_region_composite_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int iir_region_composite_f32(const float* decoded, const float* original, const float* map_px, int32_t B, int32_t C, int32_t H,
+                             int32_t W, int32_t r, void* ws, int64_t ws_bytes, float* out, void* stream);
 /* Batched copy of disjoint byte ranges in one launch: `jobs` = device int64[njobs][3] {src address, dst address, n16}, each
  * job copying n16 x 16 bytes (addresses 16-byte aligned); max_units = the largest n16.  PAG uses it to give the perturbed
  * rows of every Aggregator residual the cond rows' values. */

@@ -25,6 +25,8 @@ hipcc $FLAGS -ffp-contract=off -c freeu.hip -o build/freeu.o &
 pids+=($!)
 hipcc $FLAGS -ffp-contract=off -c colorfix.hip -o build/colorfix.o &
 pids+=($!)
+hipcc $FLAGS -ffp-contract=off -c regionmap.hip -o build/regionmap.o &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT build/gemm_conv.o build/gemm8.o build/attention.o build/attention_hd.o build/attention_1h.o build/norm.o build/pointwise.o build/freeu.o build/colorfix.o
+hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT build/gemm_conv.o build/gemm8.o build/attention.o build/attention_hd.o build/attention_1h.o build/norm.o build/pointwise.o build/freeu.o build/colorfix.o build/regionmap.o
 echo "built $(realpath $OUT)"

@@ -153,34 +153,59 @@ __device__ __forceinline__ float guided_eps(const f16* eps_nhwc, long lde, int B
 // step's x0 on exit: each element is read, then overwritten by the thread that owns it, so one captured launch serves every
 // step.  With k_h == 0 the plane is never loaded (it is uninitialised or stale on a solver's first step, and 0 * NaN would
 // leak into prev).
+// a*x + b*y, the one expression behind add_noise (axpby_f32_kernel) and the kept value of a restore map (sched_step_kernel):
+// equal arguments give equal bits in both.
+__device__ __forceinline__ float axpby(float a, float x, float b, float y) { return a * x + b * y; }
+
+// The value a kept element takes: add_noise(src, noise) with the pair (a, b); a term whose coefficient is 0 is skipped, so
+// (1, 0) returns the bits of src whatever the noise plane holds.
+__device__ __forceinline__ float keep_value(float a, float src, float b, float nz) {
+    if (b == 0.f) return a * src;
+    if (a == 0.f) return b * nz;
+    return axpby(a, src, b, nz);
+}
+
+// (`kept`: the element takes `keep_v` instead of the update -- a select on the stored value only; x0 and hist are the model's.)
 __device__ __forceinline__ void sched_update(float e, long o, const float (&k)[7], const float* x, const float* noise, float* hist,
-                                             float* prev, float* x0_out) {
+                                             float* prev, float* x0_out, bool kept = false, float keep_v = 0.f) {
     const float xv = x[o];
     const float x0 = (xv - k[0] * e) / k[1];
     float pv = k[2] * x0 + k[3] * xv;
     if (k[4] != 0.f) pv = pv + k[4] * e;
     if (hist && k[6] != 0.f) pv = pv + k[6] * hist[o];
     if (noise && k[5] != 0.f) pv = pv + k[5] * noise[o];
-    prev[o] = pv;
+    prev[o] = kept ? keep_v : pv;
     if (hist) hist[o] = x0;
     if (x0_out) x0_out[o] = x0;
 }
 
-// One thread per latent pixel; pag_s, noise, hist, x0_out, eps_out and eps_factor are optional (every branch on them is
-// wave-uniform).  coef is read once, before the channel loop: prev may alias it as far as the compiler knows.
+// One thread per latent pixel; pag_s, noise, hist, x0_out, eps_out, eps_factor and the keep_* group are optional (every branch
+// on them is wave-uniform).  coef is read once, before the channel loop: prev may alias it as far as the compiler knows.
+// keep_map (restore map, fp32 B x HW) with keep_coef = {thr, a, b, 0}: a pixel with map <= thr (fp32 compare) stores
+// keep_value(a, keep_src, b, keep_noise) in prev instead of the update.  keep_src / keep_noise are loaded for every lane
+// (no per-lane-predicated load); the per-lane part is the select alone, so a free element has the bits of the launch
+// without a map and a kept one never sees its eps.
 __global__ void sched_step_kernel(const f16* eps_nhwc, long lde, int B, int C, int HW, int cfg, const float* coef,
                                   const float* pag_s, const float* x, const float* noise, float* hist, float* prev,
-                                  float* x0_out, float* eps_out, const float* eps_factor) {
+                                  float* x0_out, float* eps_out, const float* eps_factor, const float* keep_map,
+                                  const float* keep_src, const float* keep_noise, const float* keep_coef) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)B * HW) return;
     const int b = (int)(i / HW), p = (int)(i % HW);
     const float g = coef[0];
     const float k[7] = {coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7]};
     const float ps = pag_s ? *pag_s : 0.f;
+    float ka = 0.f, kb = 0.f;
+    bool kept = false;
+    if (keep_map) {
+        ka = keep_coef[1]; kb = keep_coef[2];
+        kept = keep_map[(long)b * HW + p] <= keep_coef[0];
+    }
     for (int c = 0; c < C; ++c) {
         const long o = ((long)b * C + c) * HW + p;
         const float e = guided_eps(eps_nhwc, lde, B, HW, cfg, g, ps, eps_factor, b, p, c);
-        sched_update(e, o, k, x, noise, hist, prev, x0_out);
+        const float kv = keep_map ? keep_value(ka, keep_src[o], kb, keep_noise[o]) : 0.f;
+        sched_update(e, o, k, x, noise, hist, prev, x0_out, kept, kv);
         if (eps_out) eps_out[o] = e;
     }
 }
@@ -273,14 +298,19 @@ inline bool hist_aliases(const float* hist, const float* x, const float* prev, c
     return hist && (hist == x || hist == prev || hist == x0_out);
 }
 
+// the restore-map group of a step launch: all four pointers, or none of them
+struct keep_args {
+    const float *map = nullptr, *src = nullptr, *noise = nullptr, *coef = nullptr;
+};
+
 int launch_sched_step(const void* eps_nhwc, long lde, int B, int C, int HW, int cfg, const float* coef, const float* pag_s,
                       const float* x, const float* noise, float* hist, float* prev, float* x0_out, float* eps_out,
-                      const float* eps_factor, void* stream) {
+                      const float* eps_factor, void* stream, keep_args keep = {}) {
     if (!eps_nhwc || !coef || !x || !prev || B <= 0 || C <= 0 || HW <= 0 || lde < C) return IIR_EINVAL;
     if (eps_factor && !cfg) return IIR_EINVAL;
     if (hist_aliases(hist, x, prev, x0_out)) return IIR_EINVAL;
     return launch_1d(sched_step_kernel, (long)B * HW, stream, (const f16*)eps_nhwc, lde, B, C, HW, cfg, coef, pag_s, x, noise, hist,
-                     prev, x0_out, eps_out, eps_factor);
+                     prev, x0_out, eps_out, eps_factor, keep.map, keep.src, keep.noise, keep.coef);
 }
 
 }  // namespace
@@ -381,6 +411,19 @@ extern "C" int iir_sched_step_hist_pag(const void* eps_nhwc, int64_t lde, int32_
                              stream);
 }
 
+extern "C" int iir_sched_step_keep(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
+                                   const float* coef, const float* pag_scale, const float* x, const float* noise, float* hist,
+                                   float* prev, float* x0_out, float* eps_out, const float* eps_factor, const float* keep_map,
+                                   const float* keep_src, const float* keep_noise, const float* keep_coef, void* stream) {
+    if (!keep_map || !keep_src || !keep_noise || !keep_coef) return IIR_EINVAL;
+    if (eps_out && hist) return IIR_EINVAL;
+    if (keep_src == prev || keep_noise == prev) return IIR_EINVAL;
+    keep_args keep;
+    keep.map = keep_map; keep.src = keep_src; keep.noise = keep_noise; keep.coef = keep_coef;
+    return launch_sched_step(eps_nhwc, (long)lde, B, C, HW, cfg, coef, pag_scale, x, noise, hist, prev, x0_out, eps_out, eps_factor,
+                             stream, keep);
+}
+
 extern "C" int iir_copy_segments(const void* jobs, int32_t njobs, int64_t max_units, void* stream) {
     if (!jobs || njobs <= 0 || njobs > 65535 || max_units <= 0) return IIR_EINVAL;
     (void)hipGetLastError();
@@ -446,7 +489,7 @@ __global__ void sched_step_f32_kernel(const float* eps, const float* x, const fl
 __global__ void axpby_f32_kernel(const float* x, const float* y, const float* coef, long n, float* out) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    out[i] = coef[0] * x[i] + coef[1] * y[i];
+    out[i] = axpby(coef[0], x[i], coef[1], y[i]);
 }
 
 int launch_sched_step_f32(const float* eps, const float* x, const float* noise, const float* coef, float* hist, long n, float* prev,

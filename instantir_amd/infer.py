@@ -144,6 +144,11 @@ def build_parser():
     p.add_argument("--vae_flash_attention", action="store_true",
                    help="run the VAE mid-block attention as one flash-style launch (pipe.vae.enable_flash_attention()): untiled "
                         "encode / decode beyond 1024x1024; off by default")
+    p.add_argument("--restore_map", type=str, default=None, metavar="PATH",
+                   help="per-pixel restoration strength (pipe(..., restore_map=...)): a grey-scale image file used for every input, or "
+                        "a directory holding one map per input file name; white = restore freely, black = keep the input pixels")
+    p.add_argument("--map_feather", type=int, default=4, help="half width in pixels of the seam between kept and restored pixels "
+                                                              "(pipe(..., map_feather=N)); 0 = hard paste; default 4")
     return p
 
 
@@ -246,6 +251,24 @@ def apply_color_fix(args):
     return {} if mode == "none" else {"color_fix": mode}
 
 
+def apply_restore_map(args, names, size):
+    """`--restore_map PATH [--map_feather N]` -> the call's `restore_map` / `map_feather` keyword arguments for the inputs
+    `names`, each map resized to `size` = (width, height) of the resized inputs with Image.BILINEAR (an addition: the reference
+    has no regional control).  PATH is one file for every input or a directory with a map per input file name; an input
+    without a map is an error naming it.  Without the flag nothing is added to the call."""
+    path = getattr(args, "restore_map", None)
+    feather = getattr(args, "map_feather", 4)
+    if feather is None or feather < 0:
+        raise SystemExit(f"--map_feather must be >= 0, got {feather}")
+    if path is None:
+        return {}
+    from .restore_map import load_maps
+    try:
+        return {"restore_map": load_maps(path, names, size), "map_feather": int(feather)}
+    except FileNotFoundError as e:
+        raise SystemExit(str(e))
+
+
 def main(args, device, rank=0, world=1):
     pipe, lcm_scheduler = build_pipeline(args, device)
     apply_freeu(pipe, args)
@@ -275,7 +298,7 @@ def main(args, device, rank=0, world=1):
         negs = (list(args.neg_prompt) if args.neg_prompt else [DEFAULT_NEG_PROMPT]) * len(lq)
         kw = dict(image=lq, num_inference_steps=args.num_inference_steps, generator=generator, guidance_scale=args.cfg,
                   previewer_scheduler=lcm_scheduler, preview_start=args.preview_start, control_guidance_end=args.creative_start,
-                  **pag_kw)
+                  **pag_kw, **apply_restore_map(args, lq_batch, lq[0].size))
         if args.synthetic:
             g = torch.Generator().manual_seed(args.seed)
             n = len(lq)

@@ -649,9 +649,12 @@ def _pag_entry(name, pag_scale):
     return getattr(L.load(), name + "_pag"), name + "_pag", [pag_scale.data_ptr()]
 
 
-def sched_step(eps2d, B, coef, x, prev, noise=None, cfg=True, x0_out=None, eps_out=None, eps_factor=None, pag_scale=None, hist=None):
+def sched_step(eps2d, B, coef, x, prev, noise=None, cfg=True, x0_out=None, eps_out=None, eps_factor=None, pag_scale=None, hist=None,
+               keep=None):
     """`pag_scale` (device fp32[1]): the PAG form -- eps2d holds the perturbed rows after the cond rows (iir_sched_step*_pag).
-    `hist` (shape of x, fp32): adds the history term coef[7] * hist and then holds this step's x0 (iir_sched_step_hist*)."""
+    `hist` (shape of x, fp32): adds the history term coef[7] * hist and then holds this step's x0 (iir_sched_step_hist*).
+    `keep` = (map (B, H*W), src, noise0, coef {thr, a, b, 0}), fp32 CUDA tensors: the restore-map form (iir_sched_step_keep) --
+    pixels with map <= thr store a * src + b * noise0 in prev instead of the update."""
     _, Cc, H, Wd = x.shape
     outs = [prev.data_ptr(), _p(x0_out), _p(eps_out)]
     if hist is not None:
@@ -659,6 +662,18 @@ def sched_step(eps2d, B, coef, x, prev, noise=None, cfg=True, x0_out=None, eps_o
         if eps_out is not None:
             raise ValueError("sched_step: eps_out is not available together with hist")
         outs = [hist.data_ptr(), prev.data_ptr(), _p(x0_out)]
+    if keep is not None:
+        kmap, ksrc, knoise, kcoef = keep
+        for name, t, numel in (("map", kmap, B * H * Wd), ("src", ksrc, x.numel()), ("noise", knoise, x.numel()), ("coef", kcoef, 4)):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel):
+                raise ValueError(f"sched_step: keep {name} must be a contiguous CUDA fp32 tensor of {numel} elements")
+        if pag_scale is not None:
+            _chk_pag(pag_scale)
+        L.check(L.load().iir_sched_step_keep(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(), _p(pag_scale),
+                                             x.data_ptr(), _p(noise), _p(hist), prev.data_ptr(), _p(x0_out), _p(eps_out),
+                                             _p(eps_factor), kmap.data_ptr(), ksrc.data_ptr(), knoise.data_ptr(), kcoef.data_ptr(),
+                                             _stream()), "iir_sched_step_keep")
+        return prev
     fn, name, ps = _pag_entry("iir_sched_step_hist" if hist is not None else "iir_sched_step", pag_scale)
     L.check(fn(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(), *ps, x.data_ptr(), _p(noise), *outs,
                _p(eps_factor), _stream()), name)
@@ -766,6 +781,7 @@ def blend_tiles(a, b, extent, vertical):
 
 
 COLOR_FIX_MODES = ("wavelet", "adain")
+MAX_MAP_FEATHER = 512      # IIR_REGION_MAX_FEATHER
 
 
 def colorfix(content, style, mode, out=None, ws=None):
@@ -797,4 +813,59 @@ def colorfix(content, style, mode, out=None, ws=None):
     fn = h.iir_colorfix_wavelet_f32 if mode == "wavelet" else h.iir_colorfix_adain_f32
     L.check(fn(content.data_ptr(), style.data_ptr(), out.data_ptr(), B, Cc, H, W, ws.data_ptr(), ws.numel() * ws.element_size(),
                _stream()), f"iir_colorfix_{mode}_f32")
+    return out
+
+
+def _chk_f32(t, name, dim):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == dim and t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous {dim}-D fp32 CUDA tensor")
+
+
+def map_pool_max(map_px, factor, out=None):
+    """Restore map at latent resolution: map_px fp32 (B, H, W) -> (B, H / factor, W / factor), the maximum over each
+    factor x factor block (iir_map_pool_max_f32).  H and W must be multiples of `factor`."""
+    _chk_f32(map_px, "map_pool_max: map_px", 3)
+    B, H, W = map_px.shape
+    if factor <= 0 or H % factor or W % factor:
+        raise ValueError(f"map_pool_max: {H}x{W} is not a multiple of the factor {factor}")
+    if out is None:
+        out = torch.empty(B, H // factor, W // factor, dtype=torch.float32, device=map_px.device)
+    else:
+        _chk_f32(out, "map_pool_max: out", 3)
+        if tuple(out.shape) != (B, H // factor, W // factor) or out.device != map_px.device:
+            raise ValueError("map_pool_max: out must be (B, H / factor, W / factor) on the map's device")
+    L.check(L.load().iir_map_pool_max_f32(map_px.data_ptr(), B, H, W, int(factor), out.data_ptr(), _stream()), "iir_map_pool_max_f32")
+    return out
+
+
+def region_composite(decoded, original, map_px, feather, out=None, ws=None):
+    """Pixel composite under a restore map (DESIGN.md section 7 "Restore map"): decoded, original fp32 (B, C, H, W), map_px
+    fp32 (B, H, W); `feather` = r, the half width of the box window in pixels (0: hard paste).  `out` may be `decoded` (in
+    place); `ws`: a byte workspace of at least iir_region_composite_workspace_bytes (allocated here when absent)."""
+    _chk_f32(decoded, "region_composite: decoded", 4)
+    _chk_f32(original, "region_composite: original", 4)
+    _chk_f32(map_px, "region_composite: map_px", 3)
+    B, Cc, H, W = decoded.shape
+    if original.shape != decoded.shape or tuple(map_px.shape) != (B, H, W) or original.device != decoded.device or map_px.device != decoded.device:
+        raise ValueError(f"region_composite: original {tuple(original.shape)} / map {tuple(map_px.shape)} do not match decoded "
+                         f"{tuple(decoded.shape)} on {decoded.device}")
+    h = L.load()
+    r = int(feather)
+    if r < 0 or r > MAX_MAP_FEATHER:
+        raise ValueError(f"region_composite: feather must be in [0, {MAX_MAP_FEATHER}], got {feather}")
+    if out is None:
+        out = torch.empty_like(decoded)
+    else:
+        _chk_f32(out, "region_composite: out", 4)
+        if out.shape != decoded.shape or out.device != decoded.device:
+            raise ValueError("region_composite: out must have decoded's shape and device")
+    need = h.iir_region_composite_workspace_bytes(B, H, W)
+    if need < 0:
+        raise ValueError(f"region_composite: unsupported geometry B={B} H={H} W={W}")
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=decoded.device)
+    elif not ws.is_cuda or not ws.is_contiguous() or ws.numel() * ws.element_size() < need:
+        raise ValueError(f"region_composite: workspace needs {need} contiguous bytes on the device")
+    L.check(h.iir_region_composite_f32(decoded.data_ptr(), original.data_ptr(), map_px.data_ptr(), B, Cc, H, W, r, ws.data_ptr(),
+                                       ws.numel() * ws.element_size(), out.data_ptr(), _stream()), "iir_region_composite_f32")
     return out

@@ -31,6 +31,7 @@ from typing import Callable, Dict, List, Optional, Union
 import torch
 
 from . import ops, pag
+from . import restore_map as rmap
 from .config import UNetConfig, VAEConfig
 from .engine import CPAD, F16, HipAggregator, HipUNet
 from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,  # noqa: F401
@@ -420,7 +421,7 @@ class InstantIRPipeline:
         self._apply_freeu(self._unet, self._unet_prev)
 
     def _loop_for(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale, pag_on=False,
-                  fresh=False):
+                  fresh=False, keep=None):
         """The step's buffers and captured hipGraphs are kept from one call to the next: a second image of the same geometry,
         through the same engines, re-uses them (its hoisted K / V, embeddings and LQ latent are copied into the captured
         tensors) instead of paying the warm-up step, the capture and the graph instantiation again (~0.1 s of a 1.9 s call
@@ -431,15 +432,16 @@ class InstantIRPipeline:
                self.overlap_sft, tuple(None if n is None else (id(n), n.arena_gen, n.inkernel_prefetch) for n in nets),
                self._freeu,           # the FreeU factors are launch arguments of the captured concats
                _sched_form(self.scheduler),   # the sigma schedulers launch the device-scale pack and the history step
-               self._pag_paths if pag_on else None)     # PAG: row count and the identity launches (its scale is a device scalar)
+               self._pag_paths if pag_on else None,     # PAG: row count and the identity launches (its scale is a device scalar)
+               keep is not None)      # a restore map: the step's last launch is iir_sched_step_keep, on buffers only such a loop has
         if not fresh:
             cached = self._loop_cache
             if cached is not None and cached[0] == key and os.environ.get("IIR_LOOP_CACHE", "1") != "0":
-                if cached[1].adopt(st, st_prev, st_agg, lq, reference_latents, previewer_scheduler):
+                if cached[1].adopt(st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, keep=keep):
                     return cached[1]
             self._loop_cache = cached = None         # drop the old graphs before building the new ones
         loop = _DenoiseLoop(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler,
-                            guidance_rescale=guidance_rescale, pag_on=pag_on)
+                            guidance_rescale=guidance_rescale, pag_on=pag_on, keep=keep)
         # the entry keeps the engines alive: `id()` in the key can then not be re-issued to a NEW engine (adapter switch, LoRA
         # scale change) while graphs captured on the old one's arena and weights are still cached
         if not fresh:
@@ -606,17 +608,24 @@ class InstantIRPipeline:
             image = self.vae.encode_to_latent(image, eps=vae_noise)
         return image.to(self.device, torch.float32)
 
-    def _decode_output(self, latents, output_type, color_fix=None, reference=None):
+    def _decode_output(self, latents, output_type, color_fix=None, reference=None, composite=None):
         """VAE decode of the final latents; with `color_fix` the decoded [0,1] image is corrected in place on the device
-        (ops.colorfix) before it becomes 'np' / 'pil'.  :1706-1729: any `output_type` but 'latent' needs the VAE."""
+        (ops.colorfix) before it becomes 'np' / 'pil'; with `composite` = (original, pixel map, feather) of a restore map the
+        kept region then gets the input's own pixels back (ops.region_composite, in place).  :1706-1729: any `output_type` but
+        'latent' needs the VAE."""
         if output_type == "latent":
             return latents
         if self.vae is None:
             raise NotImplementedError("output_type other than 'latent' needs a VAE attached to the pipeline")
-        if color_fix is None:
+        if color_fix is None and composite is None:
             return self.vae.decode_latent(latents, output_type)          # tiles when `vae.enable_tiling()` is on
         img = self.vae.decode_latent(latents, "pt").contiguous()
-        return self.vae.to_output(ops.colorfix(img, reference, color_fix, out=img), output_type)
+        if color_fix is not None:
+            ops.colorfix(img, reference, color_fix, out=img)
+        if composite is not None:
+            original, map_px, feather = composite
+            ops.region_composite(img, original, map_px, feather, out=img)
+        return self.vae.to_output(img, output_type)
 
     # ---- single-step previewer restoration (BASELINE configs[4]; spec train_previewer_lora.py:118-145) ------------
     @torch.no_grad()
@@ -655,7 +664,7 @@ class InstantIRPipeline:
         px = (Hl * self.vae_scale_factor, Wl * self.vae_scale_factor)
         time_ids = _time_ids([[px[0], px[1], 0, 0, px[0], px[1]]], B)
         st = net.prepare(prompt_embeds, pooled_prompt_embeds, time_ids, net.resampler(ip_adapter_image_embeds[0]), Hl, Wl)
-        x = self._initial_latents(sched, lq, timestep, generator, init_noise)
+        x, _ = self._initial_latents(sched, lq, timestep, generator, init_noise)
         lat16 = torch.zeros(B * Hl * Wl, CPAD, dtype=F16, device=dev)
         ops.pack_latent(x, lat16)
         t_dev = torch.full((B, 1), float(timestep), dtype=torch.float32, device=dev)
@@ -755,22 +764,26 @@ class InstantIRPipeline:
         return ts, keep, previewing, ccs
 
     def _initial_latents(self, sched, lq, t0, generator, init_noise, init_latents_with_lq=True, latents=None):
-        """:1388-1403: the LQ latent noised to the first timestep `t0`, or `latents` / a draw scaled by `init_noise_sigma`."""
+        """:1388-1403: the LQ latent noised to the first timestep `t0`, or `latents` / a draw scaled by `init_noise_sigma`
+        -> (the latents, `noise0`: the unit-variance tensor that seeded them, which a restore map's kept pixels follow)."""
         dev = self.device
         if not init_latents_with_lq:
             latents = _randn(lq.shape, generator, dev) if latents is None else latents
-            return (latents.to(dev, torch.float32) * sched.init_noise_sigma).contiguous()
+            noise0 = latents.to(dev, torch.float32)
+            return (noise0 * sched.init_noise_sigma).contiguous(), noise0
         init_noise = _randn(lq.shape, generator, dev) if init_noise is None else init_noise
-        return sched.add_noise(lq, init_noise.to(dev, torch.float32), torch.tensor([t0] * lq.shape[0])).contiguous()
+        noise0 = init_noise.to(dev, torch.float32)
+        return sched.add_noise(lq, noise0, torch.tensor([t0] * lq.shape[0])).contiguous(), noise0
 
     def _denoise(self, x, ctx, loop_of, ts, keep, previewing, ccs, lq, reference_latents, previewer_scheduler, guidance_scale, eta,
                  generator, step_noises, pag_scale, pag_adaptive_scale, adastep_restore, save_preview_row, callback_on_step_end,
-                 callback_on_step_end_tensor_inputs, negative_prompt_embeds):
+                 callback_on_step_end_tensor_inputs, negative_prompt_embeds, masked=False):
         """The denoising loop (:1497-1660) on the latents `x` -> (final latents, preview latents of each previewing step).
         `loop_of(ctx, fresh)`: the hoisted states and the `_DenoiseLoop` of a context."""
         loop = loop_of(ctx, False)
         B, rep, groups, pag_on, dev = loop.B, loop.rep, loop.groups, loop.pag_on, self.device
         preview_row = []
+        thr = rmap.thresholds(len(ts)) if masked else None
         preview_factor = torch.ones(B)
         compound = None            # per-image scale the Aggregator's (persistent, raw) outputs currently carry
         pv = None                  # positive half of `preview_latent`: what conditioned the Aggregator last (:1545-1582)
@@ -797,7 +810,8 @@ class InstantIRPipeline:
                 mode = "unet_res" if bool((compound != 0).any()) else "unet"
             x0 = loop.step(mode, t, x, (compound if mode != "unet" else scale_rows).repeat(groups), guidance_scale, eta,
                            None if step_noises is None else step_noises[i], generator, want_x0=adastep_restore, want_preview=save_preview_row or adastep_restore, i=i,
-                           pag_s=pag.scale_at(pag_scale, pag_adaptive_scale, t) if pag_on else 0.0)
+                           pag_s=pag.scale_at(pag_scale, pag_adaptive_scale, t) if pag_on else 0.0,
+                           keep_row=(thr[i],) + rmap.keep_pair(self.scheduler, i, t) if masked else None)
             if mode == "preview":
                 pv = loop.preview_f32[B * (rep - 1):]
                 if save_preview_row:
@@ -845,7 +859,8 @@ class InstantIRPipeline:
                  clip_skip=None, callback_on_step_end: Optional[Callable] = None,
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"], previewer_scheduler=None,
                  reference_latents=None, init_noise=None, step_noises=None, pag_scale: Optional[float] = None,
-                 pag_adaptive_scale: float = 0.0, color_fix: Optional[str] = None, color_fix_reference=None, **kwargs):
+                 pag_adaptive_scale: float = 0.0, color_fix: Optional[str] = None, color_fix_reference=None, restore_map=None,
+                 map_feather: int = 4, **kwargs):
         """Keyword arguments and defaults of pipelines/sdxl_instantir.py:1067-1115.  Two additions for
         bit-reproducible parity runs: `init_noise` (the randn of init_latents) and
         `step_noises` (list of per-step DDPM / Euler-ancestral / DPM++ SDE noises) replace draws from `generator` when given.
@@ -855,7 +870,19 @@ class InstantIRPipeline:
         means 3.0, and PAG runs when it is > 0 (s_t = max(pag_scale - pag_adaptive_scale * (1000 - t), 0) per step).
         `color_fix` (an addition, after StableSR's colour fixes): None, "wavelet" or "adain" transfers the colour of the LQ image
         onto the final images (never the preview row) after the VAE decode.  The reference is the pixel `image` mapped to
-        [0, 1] unless `color_fix_reference` (a [0, 1] tensor or PIL image(s) of the output size) is given."""
+        [0, 1] unless `color_fix_reference` (a [0, 1] tensor or PIL image(s) of the output size) is given.
+        `restore_map` (an addition, after inpaint-style latent blending and its soft form, differential diffusion): a per-pixel
+        strength in [0, 1] -- the fraction of the schedule, counted from its end, during which the pixel is denoised freely
+        (1: every step, today's behaviour; 0: never, the pixel comes out as the LQ input; until then it follows the LQ latent's
+        own noising trajectory).  A PIL image ("L", / 255) or a list of them, or a tensor / array (H, W) or (B|1, 1, H, W), at
+        the pixel size of `image` or at latent size; one map serves the whole batch, otherwise maps repeat per
+        `num_images_per_prompt` copy.  At latent resolution a pixel is free if any pixel of its 8 x 8 block is.  When `image` was
+        given as pixels and `output_type` is not "latent", the final images (never the preview row) are composited with the
+        input after the decode and `color_fix`: a box window of half width `map_feather` pixels (default 4; 0 = hard paste)
+        over [map > 0] weights decoded against input, and a pixel whose window lies wholly in the kept region is the input
+        pixel bit for bit.  None touches nothing."""
+        if restore_map is not None:
+            map_feather = rmap.check_feather(map_feather)
         lora_mult, pag_scale, pag_on = self._check_call(color_fix, output_type, cross_attention_kwargs, pag_scale, pag_adaptive_scale,
                                                         multistep_restore)
         ids_given = prompt is None and prompt_embeds is None and kwargs.get("prompt_ids") is not None and self.text_encoder is not None
@@ -892,6 +919,18 @@ class InstantIRPipeline:
         Hl, Wl = lq.shape[2], lq.shape[3]
         height, width = Hl * self.vae_scale_factor, Wl * self.vae_scale_factor
 
+        keep_map = composite = None
+        if restore_map is not None:
+            pixels_in = image.shape[1] != 4
+            will_composite = pixels_in and output_type != "latent"
+            m, at_pixels = rmap.prepare(restore_map, B, nipp, (height, width), (Hl, Wl), self.device)
+            if will_composite and not at_pixels:
+                raise ValueError(f"restore_map is at latent size ({Hl}, {Wl}) but the call composites pixels (pixel `image`, "
+                                 f"output_type={output_type!r}): pass the map at the image size ({height}, {width})")
+            keep_map = ops.map_pool_max(m, self.vae_scale_factor) if at_pixels else m
+            if will_composite:
+                composite = (self._color_fix_reference(None, image, B, nipp), m, map_feather)
+
         self._unet.set_pag(self._pag_paths if pag_on else None, rep * B)          # (refuses an fp8 engine)
         ids = list(original_size or (height, width)) + list(crops_coords_top_left) + list(target_size or (height, width))     # :965-981
         neg_ids = ids
@@ -911,19 +950,23 @@ class InstantIRPipeline:
         # -- step-invariant device state: the Aggregator's here, the UNets' per context
         st_agg = self._agg.prepare(pooled, time_ids, Hl, Wl, out_rows=(rep + 1) * B if pag_on else None)
 
+        keep_box = []              # (latent map, noise0) once the initial latents exist: the loop is built after them
+
         def loop_of(ctx_, fresh):
             st = self._main_state(ctx_, pooled, time_ids, img, Hl, Wl, B, rep, pag_on)
             prev = self._unet_prev
             st_prev = None if prev is None else prev.prepare(ctx_, pooled, time_ids, prev.resampler(img), Hl, Wl)
             return self._loop_for(B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale,
-                                  pag_on, fresh=fresh)
+                                  pag_on, fresh=fresh, keep=keep_box[0] if keep_box else None)
 
-        x = self._initial_latents(self.scheduler, lq, ts[0], generator, init_noise, init_latents_with_lq, latents)
+        x, noise0 = self._initial_latents(self.scheduler, lq, ts[0], generator, init_noise, init_latents_with_lq, latents)
+        if keep_map is not None:
+            keep_box.append((keep_map, noise0))
         x, preview_row = self._denoise(x, ctx, loop_of, ts, keep, previewing, ccs, lq, reference_latents, previewer_scheduler,
                                        guidance_scale, eta, generator, step_noises, pag_scale, pag_adaptive_scale, adastep_restore,
                                        save_preview_row, callback_on_step_end, callback_on_step_end_tensor_inputs,
-                                       negative_prompt_embeds)
-        image_out = self._decode_output(x, output_type, color_fix, cf_ref)
+                                       negative_prompt_embeds, masked=keep_map is not None)
+        image_out = self._decode_output(x, output_type, color_fix, cf_ref, composite)
         if save_preview_row and self.vae is not None and output_type != "latent":     # :1706-1729 (decoded independently, Q4)
             preview_row = [self.vae.decode_latent(pl, output_type) for pl in preview_row]
         if not return_dict:
@@ -937,12 +980,13 @@ def _sched_form(scheduler):
     return "hist" if hasattr(scheduler, "loop_coefficients") else "linear"
 
 
-def _scalar_row(rows):
+def _scalar_row(rows, masked=False):
     """Layout of a loop's per-step scalar row when its main UNet runs `rows` rows: ({name: slice}, length) of
-    [t x rows | lcm coef x4 | sched coef x8 | res scale x rows | c_in | PAG s_t].  `sched` is the (8,) coefficient vector the
-    iir_sched_step* and PAG kernels index themselves: guidance in [0], the history term k_h in [7]."""
+    [t x rows | lcm coef x4 | sched coef x8 | res scale x rows | c_in | PAG s_t], and for a loop with a restore map (`masked`)
+    [| keep x4] = {thr, a, b, 0} behind them.  `sched` is the (8,) coefficient vector the iir_sched_step* and PAG kernels index
+    themselves: guidance in [0], the history term k_h in [7]."""
     lay, off = {}, 0
-    for name, n in (("t", rows), ("lcm", 4), ("sched", 8), ("res_scale", rows), ("c_in", 1), ("pag_s", 1)):
+    for name, n in (("t", rows), ("lcm", 4), ("sched", 8), ("res_scale", rows), ("c_in", 1), ("pag_s", 1)) + ((("keep", 4),) if masked else ()):
         lay[name] = slice(off, off + n)
         off += n
     return lay, off
@@ -980,7 +1024,7 @@ class _DenoiseLoop:
     one more with perturbed-attention guidance (`pag_on`), whose rows copy the cond rows' inputs and residuals."""
 
     def __init__(self, pipe, B, rep, H, W, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale=0.0,
-                 pag_on=False):
+                 pag_on=False, keep=None):
         dev = pipe.device
         self.guidance_rescale = float(guidance_rescale or 0.0)
         self.cfg_factor = torch.ones(B, dtype=torch.float32, device=dev)
@@ -1008,7 +1052,15 @@ class _DenoiseLoop:
         self.form = _sched_form(pipe.scheduler)
         # the x0 history of a multistep solver, read and rewritten in place by every step's iir_sched_step_hist
         self.hist = torch.zeros_like(self.x_in) if self.form == "hist" else None
-        lay, n_sc = _scalar_row(Rm)                              # per-step scalars
+        # restore map: the latent map, the fp32 LQ latent and the loop's seed noise, persistent so that captured launches see
+        # the next call's values (`adopt`); {thr, a, b, 0} travels in the step's scalar row
+        self.masked = keep is not None
+        self.keep_map = self.keep_src = self.keep_noise = None
+        if self.masked:
+            self.keep_map = torch.empty(B, HW, dtype=torch.float32, device=dev)
+            self.keep_src, self.keep_noise = torch.empty_like(self.x_in), torch.empty_like(self.x_in)
+            self._adopt_keep(keep, lq)
+        lay, n_sc = _scalar_row(Rm, self.masked)                 # per-step scalars
         # ring of pinned staging rows: a row is rewritten only after the H2D copy that read it has completed
         self.sc_ring = [torch.zeros(n_sc, dtype=torch.float32).pin_memory() for _ in range(8)]
         self.sc_events = [None] * 8
@@ -1017,6 +1069,7 @@ class _DenoiseLoop:
         self.t_dev = self.sc_dev[lay["t"]].view(Rm, 1)
         self.lcm_coef, self.sched_coef, self.res_scale, self.c_in, self.pag_s = (
             self.sc_dev[lay[k]] for k in ("lcm", "sched", "res_scale", "c_in", "pag_s"))
+        self.keep_coef = self.sc_dev[lay["keep"]] if self.masked else None
         self.t_agg = self.t_dev[:R]                                         # the previewer's and the Aggregator's rows
         self.seg_jobs = None
         if self.pag_on:
@@ -1031,10 +1084,17 @@ class _DenoiseLoop:
         self.graphs = {}
         self.side = None
 
-    def adopt(self, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler):
+    def _adopt_keep(self, keep, lq):
+        kmap, noise0 = keep
+        self.keep_map.copy_(kmap.reshape(self.B, -1))
+        self.keep_src.copy_(lq)
+        self.keep_noise.copy_(noise0)
+
+    def adopt(self, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, keep=None):
         """Re-use this loop -- its buffers and captured graphs -- for another call of the same geometry: the new call's hoisted
-        state is copied into the tensors the graphs were captured on.  False when the states do not line up."""
-        if (self.ref16 is None) != (reference_latents is None):
+        state (and restore map, `keep`) is copied into the tensors the graphs were captured on.  False when the states do not
+        line up."""
+        if (self.ref16 is None) != (reference_latents is None) or self.masked != (keep is not None):
             return False
         if not (_copy_state(self.st, st) and _copy_state(self.st_prev, st_prev) and _copy_state(self.st_agg, st_agg)):
             return False
@@ -1046,6 +1106,8 @@ class _DenoiseLoop:
         self.cfg_factor.fill_(1.0)
         if self.hist is not None:
             self.hist.zero_()
+        if self.masked:
+            self._adopt_keep(keep, lq)
         return True
 
     def _on_side(self, fn):
@@ -1077,7 +1139,7 @@ class _DenoiseLoop:
             ops.copy_segments(*self.seg_jobs)
         return down, mid
 
-    def _launch(self, mode, use_noise, want_x0, want_preview):
+    def _launch(self, mode, use_noise, want_x0, want_preview, masked=False):
         p = self.p
         # scale_model_input(cat([latents]*2), t), :1503-1504: c_in from the step's scalar row (1 for DDPM / DDIM: x * 1 is exact)
         ops.pack_latent(self.x_in, self.lat16, rep=self.groups, scale=self.c_in)
@@ -1102,22 +1164,25 @@ class _DenoiseLoop:
         else:
             down, mid = self._condition(mode, want_preview, False)
             eps = p._unet.forward(self.lat16, self.t_dev, self.st, down, mid, self.res_scale)
-        self._sched(eps, use_noise, want_x0)
+        self._sched(eps, use_noise, want_x0, masked)
 
-    def _sched(self, eps, use_noise, want_x0):
-        """CFG (+ rescale_noise_cfg when guidance_rescale > 0, :181-192) + scheduler step, :1619-1633."""
+    def _sched(self, eps, use_noise, want_x0, masked=False):
+        """CFG (+ rescale_noise_cfg when guidance_rescale > 0, :181-192) + scheduler step, :1619-1633; `masked`: the restore-map
+        form of the step, which selects the kept pixels' values inside the same launch."""
         B, rep = self.B, self.rep
         ps = self.pag_s if self.pag_on else None          # PAG forms: + s_t * (c - p), s_t read from the step's scalar row
         fac = None
         if rep == 2 and self.guidance_rescale > 0.0:
             fac = ops.cfg_rescale_factor(eps, B, self.sched_coef, self.x_in, self.guidance_rescale, self.cfg_factor, pag_scale=ps)
         ops.sched_step(eps, B, self.sched_coef, self.x_in, self.x_out, noise=self.noise if use_noise else None, cfg=rep == 2,
-                       x0_out=self.x0 if want_x0 else None, eps_factor=fac, pag_scale=ps, hist=self.hist)
+                       x0_out=self.x0 if want_x0 else None, eps_factor=fac, pag_scale=ps, hist=self.hist,
+                       keep=(self.keep_map, self.keep_src, self.keep_noise, self.keep_coef) if masked else None)
 
     def step(self, mode, t, x, res_scale_rows, guidance, eta, noise, generator, want_x0=False, want_preview=False, i=None,
-             pag_s=0.0):
+             pag_s=0.0, keep_row=None):
         """`i`: the step's index in the scheduler's timetable (the sigma schedulers' coefficients are per index).  `res_scale_rows`:
-        one scale per main-UNet row.  `pag_s`: the step's PAG scale s_t."""
+        one scale per main-UNet row.  `pag_s`: the step's PAG scale s_t.  `keep_row`: (thr, a, b) of a restore map for this step (a loop
+        built with one)."""
         p, lay = self.p, self.sc_lay
         slot = self.sc_idx % len(self.sc_ring)
         self.sc_idx += 1
@@ -1142,6 +1207,8 @@ class _DenoiseLoop:
         sc[lay["sched"]] = torch.tensor(coef)
         sc[lay["res_scale"]] = res_scale_rows.float()
         sc[lay["pag_s"]] = float(pag_s)
+        if self.masked:
+            sc[lay["keep"]] = torch.tensor(list(keep_row) + [0.0])
         use_noise = coef[6] != 0.0
         if use_noise:
             noise = _randn(self.x_in.shape, generator, self.x_in.device) if noise is None else noise
@@ -1151,7 +1218,7 @@ class _DenoiseLoop:
         ev.record()
         self.sc_events[slot] = ev
         self.x_in.copy_(x)
-        key = (mode, use_noise, want_x0, want_preview)
+        key = (mode, use_noise, want_x0, want_preview, self.masked)
         if p.use_graphs:
             g = self.graphs.get(key)
             if g is None:

@@ -222,4 +222,19 @@ for a1D in (128, 512):
             a1q, a1k, a1vt, a1b = rnd(a1T, a1D).to(a1dt), rnd(a1T, a1D).to(a1dt), rnd(a1D, a1T).to(a1dt), rnd(a1D).to(a1dt)
             screen(f"attention_1h D={a1D} {'bf16' if a1dt == torch.bfloat16 else 'fp16'} T={a1T}",
                    lambda o: ops.attention_1h(a1q, o, a1k, a1vt, a1T, 1, a1T, a1T, a1D ** -0.5, bias=a1b), [(a1T, a1D)], dtype=a1dt)
+# restore map (round 10): the step with a map, the block-maximum pool and the pixel composite at the 1024^2 shapes
+rm_map = torch.rand(1, 128 * 128, generator=g).to(dev)
+rm_lq, rm_n0 = torch.randn(1, 4, 128, 128, generator=g).to(dev), torch.randn(1, 4, 128, 128, generator=g).to(dev)
+rm_coef = torch.tensor([0.5, 0.8, 0.6, 0.0], device=dev)
+screen("restore_map sched_step_keep (CFG + DDIM)", lambda o: ops.sched_step(eps2, 1, coef, xl, o, keep=(rm_map, rm_lq, rm_n0, rm_coef)),
+       [(1, 4, 128, 128)], dtype=torch.float32)
+rm_px = (torch.rand(1, 1024, 1024, generator=g) > 0.5).float().to(dev) * torch.rand(1, 1024, 1024, generator=g).to(dev)
+rm_px[:, :, :256] = 0.0
+screen("restore_map map_pool_max 1x1024x1024 factor 8", lambda o: ops.map_pool_max(rm_px, 8, out=o), [(1, 128, 128)], dtype=torch.float32)
+rm_dec, rm_orig = torch.rand(1, 3, 1024, 1024, generator=g).to(dev), torch.rand(1, 3, 1024, 1024, generator=g).to(dev)
+for rm_r in (0, 4):
+    screen(f"restore_map region_composite 1x3x1024x1024 r={rm_r}", lambda o: ops.region_composite(rm_dec, rm_orig, rm_px, rm_r, out=o),
+           [(1, 3, 1024, 1024)], dtype=torch.float32)
+    screen(f"restore_map region_composite 1x3x1024x1024 r={rm_r} in place", lambda o: (o.copy_(rm_dec), ops.region_composite(o, rm_orig, rm_px, rm_r, out=o)),
+           [(1, 3, 1024, 1024)], dtype=torch.float32)
 print("kernels with run-to-run differences:", bad)

@@ -7,6 +7,12 @@ Prints one line per timed call and a JSON summary:
   * ms/step of ddpm, euler and dpmpp_2m at `--steps` steps each, interleaved over `--pairs` rounds (the first call of each
     scheduler builds and captures its loop and is not timed);
   * wall time of a 20-step DPM++ 2M Karras call against a 30-step DDPM call.
+
+    python tools/sched_bench.py --map [--size 1024] [--pairs 3] [--steps 20]
+
+The restore map (restore_map=): the step launch alone, iir_sched_step against iir_sched_step_keep at the step's shapes
+(B = 1, cfg, DDPM noise; device events, alternating windows), and DDPM calls through the pipeline without and with a map,
+alternating pairs, ms/step medians.
 """
 import argparse
 import json
@@ -20,12 +26,49 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def timed_us(fn, n):
+    fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / n
+
+
+def map_launch_leg(size, n=500, windows=3):
+    """iir_sched_step against iir_sched_step_keep on one stream, back to back: each figure includes the launch boundary.  The map
+    adds three fp32 reads per latent element (map, LQ latent, seed noise) to x, eps and noise in, prev out."""
+    from instantir_amd import ops
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(1)
+    Hl = size // 8
+    x = (torch.randn(1, 4, Hl, Hl, generator=g) * 0.8).to(dev)
+    eps = torch.randn(2 * Hl * Hl, 64, generator=g).half().to(dev)
+    lq, n0, nz = (torch.randn(1, 4, Hl, Hl, generator=g).to(dev) for _ in range(3))
+    m = torch.rand(1, Hl * Hl, generator=g).to(dev)
+    prev = torch.empty_like(x)
+    coef = torch.tensor([7.0, 0.9, 0.3, 0.8, 0.5, 0.0, 0.1, 0.0], device=dev)
+    kcoef = torch.tensor([0.5, 0.8, 0.6, 0.0], device=dev)
+    legs = {"iir_sched_step": lambda: ops.sched_step(eps, 1, coef, x, prev, noise=nz),
+            "iir_sched_step_keep": lambda: ops.sched_step(eps, 1, coef, x, prev, noise=nz, keep=(m, lq, n0, kcoef))}
+    us = {k: [] for k in legs}
+    for _ in range(windows):
+        for k, fn in legs.items():
+            us[k].append(timed_us(fn, n))
+    for k, v in us.items():
+        print(f"step launch {size}^2 (B=1, cfg, DDPM noise) {k}: windows {[round(t, 2) for t in v]} us, best {min(v):.2f} us", flush=True)
+    return {k: round(min(v), 2) for k, v in us.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--tiny", action="store_true")
+    ap.add_argument("--map", action="store_true", help="only the restore-map legs: the step launch and pipe() without / with a map")
     args = ap.parse_args()
     from instantir_amd import schedulers as S, weights as W
     from instantir_amd.config import UNetConfig
@@ -53,15 +96,33 @@ def main():
               "dpmpp_2m": S.DPMSolverMultistepScheduler.from_config(base),
               "dpmpp_2m_karras": S.DPMSolverMultistepScheduler.from_config(base, use_karras_sigmas=True)}
 
-    def call(name, n):
+    def call(name, n, **extra):
         pipe.scheduler = scheds[name]
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = pipe(num_inference_steps=n, **kw).images
+        out = pipe(num_inference_steps=n, **kw, **extra).images
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         assert torch.isfinite(out).all(), name
         return dt
+
+    if args.map:
+        launch = map_launch_leg(args.size)
+        rmap = torch.zeros(Hl, Hl)
+        rmap[:, Hl // 2:] = 1.0
+        rmap[: Hl // 2, : Hl // 2] = 0.4
+        legs = {"no map": {}, "restore_map": {"restore_map": rmap}}
+        res = {k: [] for k in legs}
+        for r in range(args.pairs):
+            for name, extra in legs.items():
+                call("ddpm", 2, **extra)                # the loop cache holds one of the two forms: rebuild and capture, untimed
+                dt = call("ddpm", args.steps, **extra)
+                res[name].append(dt / args.steps * 1e3)
+                print(f"round {r} ddpm {name}: {dt / args.steps * 1e3:.2f} ms/step (call {dt:.3f} s, {args.steps} steps)", flush=True)
+        print(json.dumps({"size": args.size, "steps": args.steps, "step_launch_us_best": launch,
+                          "ms_per_step_median": {k: round(statistics.median(v), 2) for k, v in res.items()},
+                          "ms_per_step_all": {k: [round(x, 2) for x in v] for k, v in res.items()}}))
+        return
 
     # one untimed call per scheduler form (the loop cache holds one geometry x form: switching forms rebuilds and re-captures,
     # so every timed call below is preceded by an untimed call of the same form)
