@@ -199,5 +199,5 @@ def test_clip_vision_matches_transformers(act):
     assert psnr(f.float().cpu(), out.hidden_states[-2]) > 45 and psnr(z.float().cpu(), outz.hidden_states[-2]) > 45
     with pytest.raises(ValueError):          # fixed position table
         enc(torch.zeros(1, 3, 70, 70))
-    with pytest.raises(ValueError):          # head_dim 80 towers (ViT-H/14) are refused with the reason
+    with pytest.raises(ValueError):          # one head gives head dim 128: only 64, 80 and 104 have an attention kernel
         HipCLIPVision(sd, "cuda:0", num_heads=1)
