@@ -440,7 +440,7 @@ __global__ __launch_bounds__(256) void softmax_rows_f32_kernel(const float* S, l
 extern "C" int iir_softmax_rows_f32(const float* S, int64_t lds, void* P, int64_t ldp, int32_t rows, int32_t cols, int32_t dtype,
                                     void* stream) {
     (void)hipGetLastError();
-    if (!S || !P || rows <= 0 || cols <= 0 || cols % 4 || cols > 16384 || lds % 4 || ldp % 4) return IIR_EINVAL;
+    if (!S || !P || rows <= 0 || cols <= 0 || cols % 4 || cols > 16384 || lds % 4 || ldp % 4 || lds < cols || ldp < cols) return IIR_EINVAL;
     if (dtype == IIR_DT_BF16) hipLaunchKernelGGL(softmax_rows_f32_kernel<bf16>, dim3(rows), dim3(256), 0, (hipStream_t)stream, S, (long)lds, (f16*)P, (long)ldp, cols);
     else if (dtype == IIR_DT_F16) hipLaunchKernelGGL(softmax_rows_f32_kernel<f16>, dim3(rows), dim3(256), 0, (hipStream_t)stream, S, (long)lds, (f16*)P, (long)ldp, cols);
     else return IIR_EINVAL;
@@ -449,7 +449,7 @@ extern "C" int iir_softmax_rows_f32(const float* S, int64_t lds, void* P, int64_
 
 extern "C" int iir_softmax_rows_f16(void* X, int64_t ld, int32_t rows, int32_t cols, void* stream) {
     (void)hipGetLastError();
-    if (!X || rows <= 0 || cols <= 0 || cols % 8 || cols > 16384 || ld % 8) return IIR_EINVAL;
+    if (!X || rows <= 0 || cols <= 0 || cols % 8 || cols > 16384 || ld % 8 || ld < cols) return IIR_EINVAL;
     hipLaunchKernelGGL(softmax_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, (f16*)X, (long)ld, cols);
     return iir_launch_status();
 }
@@ -459,7 +459,8 @@ extern "C" int iir_groupnorm_nhwc(const void* X, int64_t ldx, void* Y, int64_t l
                                   void* workspace, int64_t workspace_bytes, int32_t dtype, void* stream) {
     (void)hipGetLastError();
     if (!X || !Y || !gamma || !beta || !workspace) return IIR_EINVAL;
-    if (C % 8 || C > GN_MAXC || groups <= 0 || groups > 64 || C % groups || ldx % 8 || ldy % 8) return IIR_EINVAL;
+    if (C <= 0 || C % 8 || C > GN_MAXC || groups <= 0 || groups > 64 || groups > C || C % groups) return IIR_EINVAL;
+    if (ldx % 8 || ldy % 8 || ldx < C || ldy < C) return IIR_EINVAL;
     if (R <= 0 || HW <= 0 || (dtype != IIR_DT_F16 && dtype != IIR_DT_BF16)) return IIR_EINVAL;
     // slabs: enough blocks to fill the chip, at least 8 pixels each (a 32x32 map of 1280-2560 channels took 14.6 us with
     // 64 workgroups walking 32 pixels each, 8 us with 256 walking 8)
@@ -493,7 +494,8 @@ extern "C" int iir_groupnorm_from_partials(const void* partials, int64_t ldp, co
                                            int32_t silu, void* workspace, int64_t workspace_bytes, int32_t dtype, void* stream) {
     (void)hipGetLastError();
     if (!partials || !X || !Y || !gamma || !beta || !workspace || (uintptr_t)partials % 8) return IIR_EINVAL;
-    if (C % 8 || C > GN_MAXC || groups <= 0 || groups > 64 || C % groups || ldx % 8 || ldy % 8 || ldp < C) return IIR_EINVAL;
+    if (C <= 0 || C % 8 || C > GN_MAXC || groups <= 0 || groups > 64 || groups > C || C % groups) return IIR_EINVAL;
+    if (ldx % 8 || ldy % 8 || ldx < C || ldy < C || ldp < C) return IIR_EINVAL;
     if (R <= 0 || HW <= 0 || HW % 64 || (dtype != IIR_DT_F16 && dtype != IIR_DT_BF16)) return IIR_EINVAL;
     const int slabs = HW / 64, cpg = C / groups;
     if ((long)slabs * cpg > 20 * 256) return IIR_EINVAL;
@@ -521,11 +523,11 @@ extern "C" int iir_layernorm_f16(const void* X, int64_t ldx, void* Y, int64_t ld
                                  const void* beta, float eps, const void* shift, const void* scale, int64_t ldmod,
                                  int32_t rows_per_mod, int32_t transposed, int32_t tr_rows, int64_t tr_bstride, void* stream) {
     (void)hipGetLastError();
-    if (!X || !Y || rows <= 0 || C % 8 || C > GN_MAXC || ldx % 8) return IIR_EINVAL;
+    if (!X || !Y || rows <= 0 || C <= 0 || C % 8 || C > GN_MAXC || ldx % 8 || ldx < C) return IIR_EINVAL;
     if ((shift == nullptr) != (scale == nullptr)) return IIR_EINVAL;
     if (shift && (rows_per_mod <= 0 || ldmod % 8)) return IIR_EINVAL;
     if (transposed < 0 || transposed > 2) return IIR_EINVAL;
-    if (transposed != 1 && ldy % 8) return IIR_EINVAL;       // (2: fp8 bytes out, 8 per store)
+    if (transposed != 1 && (ldy % 8 || ldy < C)) return IIR_EINVAL;       // (2: fp8 bytes out, 8 per store; 1: ldy is the transposed row stride)
     if (transposed == 1 && tr_rows <= 0) return IIR_EINVAL;
     hipLaunchKernelGGL(ln_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const f16*)X, (long)ldx, (f16*)Y,
                        (long)ldy, rows, C, (const f16*)gamma, (const f16*)beta, eps, (const f16*)shift, (const f16*)scale,

@@ -492,15 +492,25 @@ def gn_workspace(device, R, groups=32):
     return torch.empty(L.load().iir_groupnorm_workspace_bytes(R, groups) // 4, dtype=torch.float32, device=device)
 
 
+def _chk_cols(who, Cc, **vecs):
+    """Every given per-channel operand (a vector, or rows of modulation) has `Cc` unit-stride columns."""
+    for name, t in vecs.items():
+        if t is not None and (t.dim() < 1 or t.shape[-1] != Cc or t.stride(-1) != 1):
+            raise ValueError(f"{who}: {name} needs {Cc} contiguous columns, got {tuple(t.shape)} {t.stride()}")
+
+
 def groupnorm(x, out, R, HW, gamma, beta, eps, silu, groups=32, ws=None, partials=None):
     """x, out: 2-D views (R*HW, C).  `ws`: scratch from gn_workspace() (a shared per-stream one if omitted).
     `partials` (fp32 (R*HW / 64, C, 2)): the statistics the launch that PRODUCED x left (`gn_out=` of gemm / conv2d): no
     statistics pass over x."""
     dt = x.dtype
+    if x.dim() != 2 or tuple(out.shape) != tuple(x.shape) or x.shape[0] != R * HW:
+        raise ValueError(f"groupnorm: x and out are ({R} * {HW}, C), got {tuple(x.shape)} and {tuple(out.shape)}")
+    Cc = x.shape[1]
+    _chk_cols("groupnorm", Cc, gamma=gamma, beta=beta)
     _chk2d(x, "x", dt if dt in _DT else torch.float16); _chk2d(out, "out", dt)
     if gamma.dtype != dt or beta.dtype != dt:
         raise ValueError(f"gamma / beta must have the activations' dtype ({dt})")
-    Cc = x.shape[1]
     if ws is None:
         ws = _gn_workspace(x.device, R, groups)
     if partials is not None:
@@ -522,6 +532,20 @@ def layernorm(x, out, gamma=None, beta=None, eps=1e-5, shift=None, scale=None, r
               tr_rows=1, tr_bstride=0):
     """`out` of dtype torch.float8_e4m3fn (or uint8): the normalised rows are stored as E4M3 bytes (rounded to fp16 first) -- the
     A operand of an all-fp8 GEMM (`gemm_fp8`)."""
+    if x.dim() != 2 or out.dim() != 2:
+        raise ValueError(f"layernorm: x and out are 2-D, got {tuple(x.shape)} and {tuple(out.shape)}")
+    if transposed:
+        need = (x.shape[0] - 1) // tr_rows * tr_bstride + (x.shape[0] - 1) % tr_rows + 1 if tr_rows > 0 else 0
+        if tr_rows <= 0 or out.shape[0] != x.shape[1] or out.shape[1] < need:
+            raise ValueError(f"layernorm: a transposed `out` is ({x.shape[1]}, >= {need}) with tr_rows > 0, got {tuple(out.shape)}")
+    elif tuple(out.shape) != tuple(x.shape):
+        raise ValueError(f"layernorm: out needs x's shape {tuple(x.shape)}, got {tuple(out.shape)}")
+    _chk_cols("layernorm", x.shape[1], gamma=gamma, beta=beta, shift=shift, scale=scale)
+    if (shift is None) != (scale is None) or (shift is not None and (rows_per_mod <= 0 or shift.dim() != 2 or scale.dim() != 2
+                                                                      or scale.stride(0) != shift.stride(0)
+                                                                      or shift.shape[0] * rows_per_mod < x.shape[0]
+                                                                      or scale.shape[0] * rows_per_mod < x.shape[0])):
+        raise ValueError("layernorm: shift and scale come together, 2-D with one row stride, a row per `rows_per_mod` rows of x")
     _chk2d(x, "x")
     if out.dtype in (torch.float8_e4m3fn, torch.uint8):
         if transposed or out.dim() != 2 or out.stride(1) != 1 or out.stride(0) % 8 or not out.is_cuda or out.shape != x.shape:
@@ -542,6 +566,14 @@ def adaln_job_table(jobs, device):
     The caller keeps the views alive; the table holds raw addresses."""
     arr = (L.AdaLNJob * len(jobs))()
     for i, (x, out, shift, scale, tr) in enumerate(jobs):
+        if x.dim() != 2 or out.dim() != 2:
+            raise ValueError(f"adaln job {i}: x and out are 2-D, got {tuple(x.shape)} and {tuple(out.shape)}")
+        rows, Cc = x.shape
+        if Cc < 8 or Cc > 2560 or Cc % 8:       # ln_row walks 5 x 64 chunks of 8: a wider row would lose its tail silently
+            raise ValueError(f"adaln job {i}: C must be a multiple of 8 in 8..2560, got {Cc}")
+        if (out.shape[0] != Cc or out.shape[1] < rows) if tr else tuple(out.shape) != (rows, Cc):
+            raise ValueError(f"adaln job {i}: out {tuple(out.shape)} does not fit x {tuple(x.shape)} (transposed: {bool(tr)})")
+        _chk_cols(f"adaln job {i}", Cc, shift=shift, scale=scale)
         _chk2d(x, "x"); _chk2d(out, "out")
         arr[i] = L.AdaLNJob(x.data_ptr(), out.data_ptr(), shift.data_ptr(), scale.data_ptr(), x.stride(0), out.stride(0),
                             x.shape[1], int(tr))
@@ -765,8 +797,9 @@ def softmax_rows(x):
 
 def softmax_rows_f32(s, p):
     """p = softmax over the columns of the fp32 scores s (cols <= 16384, % 4 == 0); p is fp16 or bf16."""
-    if s.dtype != torch.float32 or s.dim() != 2 or s.stride(1) != 1 or p.dtype not in _DT or p.shape != s.shape:
-        raise ValueError("softmax_rows_f32: s fp32 2-D, p fp16/bf16 of the same shape")
+    if (s.dtype != torch.float32 or s.dim() != 2 or s.stride(1) != 1 or p.dtype not in _DT or p.shape != s.shape or p.stride(1) != 1
+            or not (s.is_cuda and p.is_cuda)):
+        raise ValueError("softmax_rows_f32: s fp32 2-D, p fp16/bf16 of the same shape, both on the GPU with unit column stride")
     L.check(L.load().iir_softmax_rows_f32(s.data_ptr(), s.stride(0), p.data_ptr(), p.stride(0), s.shape[0], s.shape[1], _DT[p.dtype],
                                           _stream()), "iir_softmax_rows_f32")
     return p

@@ -65,6 +65,64 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     a.nseg = 3
     assert h.iir_attention_d64_f16(ctypes.byref(a), None) == -1
     assert h.iir_silu_f16(4096, 4096, 7, None) == -1              # n % 8
+    import torch
+    if torch.cuda.is_available():      # the calls below are valid but for one argument: on a GPU a miss would launch on address 4096
+        return
+    P = 4096
+    ln = lambda C=64, ldx=64, ldy=64, tr=0, rows=4: h.iir_layernorm_f16(P, ldx, P, ldy, rows, C, None, None, 1e-5, None, None, 0, 1, tr, 1, 0, None)
+    assert ln() != -1                                              # the valid call passes validation (and fails at the launch)
+    assert ln(C=0) == -1 and ln(C=-8) == -1 and ln(ldx=56) == -1 and ln(ldy=56) == -1 and ln(tr=2, ldy=56) == -1
+    assert ln(tr=1, ldy=4) != -1                                   # transposed: ldy is the stride of the transposed rows
+    for entry in (h.iir_groupnorm_nhwc, None):
+        def gn(C=64, ldx=64, ldy=64, groups=32, ldp=64, HW=64):
+            if entry is None:
+                return h.iir_groupnorm_from_partials(P, ldp, P, ldx, P, ldy, 1, HW, C, groups, P, P, 1e-5, 0, P, 1 << 20, 0, None)
+            return entry(P, ldx, P, ldy, 1, HW, C, groups, P, P, 1e-5, 0, P, 1 << 20, 0, None)
+        assert gn() != -1
+        assert gn(C=0) == -1 and gn(C=-64) == -1 and gn(ldx=56) == -1 and gn(ldy=56) == -1 and gn(C=8, groups=16) == -1
+        assert gn(C=24, groups=64) == -1
+    assert h.iir_groupnorm_from_partials(P, 56, P, 64, P, 64, 1, 64, 64, 32, P, P, 1e-5, 0, P, 1 << 20, 0, None) == -1      # ldp < C
+    assert h.iir_softmax_rows_f16(P, 64, 2, 64, None) != -1 and h.iir_softmax_rows_f16(P, 56, 2, 64, None) == -1
+    assert h.iir_softmax_rows_f32(P, 64, P, 64, 2, 64, 0, None) != -1
+    assert h.iir_softmax_rows_f32(P, 60, P, 64, 2, 64, 0, None) == -1 and h.iir_softmax_rows_f32(P, 64, P, 60, 2, 64, 1, None) == -1
+
+
+def test_norm_wrappers_refuse_mismatched_shapes():
+    """The `ops` checks that come before the device test: shapes and column counts of groupnorm / layernorm / adaln_job_table /
+    softmax_rows_f32, on CPU tensors."""
+    import pytest
+    import torch
+    from instantir_amd import ops
+    z = lambda *s, dt=torch.float16: torch.zeros(*s, dtype=dt)
+    x, g = z(128, 64), z(64)
+    for bad in (dict(out=z(128, 72)), dict(out=z(64, 64)), dict(R=3), dict(gamma=z(72)), dict(beta=z(32)), dict(x=z(128, 64)[:, :56], out=z(128, 56))):
+        a = dict(x=x, out=z(128, 64), R=2, HW=64, gamma=g, beta=g, eps=1e-5, silu=False)
+        a.update(bad)
+        with pytest.raises(ValueError, match="groupnorm"):
+            ops.groupnorm(**a)
+    for bad in (dict(out=z(128, 72)), dict(out=z(120, 64)), dict(gamma=z(72)), dict(beta=z(8)), dict(shift=z(8, 72), scale=z(8, 64), rows_per_mod=16),
+                dict(shift=z(8, 64), scale=z(8, 56), rows_per_mod=16), dict(shift=z(8, 64), rows_per_mod=16), dict(shift=z(7, 64), scale=z(7, 64), rows_per_mod=16),
+                dict(out=z(64, 100), transposed=True, tr_rows=16, tr_bstride=16), dict(out=z(72, 128), transposed=True, tr_rows=16, tr_bstride=16),
+                dict(out=z(64, 128), transposed=True, tr_rows=16, tr_bstride=24), dict(out=z(128, 72, dt=torch.uint8))):
+        a = dict(x=x, out=z(128, 64))
+        a.update(bad)
+        with pytest.raises(ValueError, match="layernorm"):
+            ops.layernorm(**a)
+    ok = (z(32, 64), z(32, 64), z(2, 64), z(2, 64), False)
+    for i, bad in ((0, z(32, 2568)), (0, z(32, 4)), (0, z(32, 60)), (1, z(32, 72)), (1, z(31, 64)), (2, z(2, 72)), (3, z(2, 56))):
+        job = list(ok)
+        job[i] = bad
+        if i == 0:
+            job[1] = torch.zeros_like(bad)
+        with pytest.raises(ValueError, match="adaln job 0"):
+            ops.adaln_job_table([tuple(job)], "cpu")
+    for out in (z(60, 32), z(64, 31)):
+        with pytest.raises(ValueError, match="adaln job 0"):
+            ops.adaln_job_table([(z(32, 64), out, z(2, 64), z(2, 64), True)], "cpu")
+    s32 = z(4, 64, dt=torch.float32)
+    for s_, p_ in ((s32, z(4, 72)), (s32, z(4, 64, dt=torch.float32)), (s32, z(4, 128)[:, ::2]), (z(4, 64), z(4, 64)), (s32, z(4, 64))):
+        with pytest.raises(ValueError, match="softmax_rows_f32"):
+            ops.softmax_rows_f32(s_, p_)
 
 
 def test_xattn_epilogue_arguments_are_validated_without_a_gpu():
