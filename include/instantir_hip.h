@@ -337,6 +337,41 @@ int iir_sched_step_keep(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C,
                         const float* pag_scale, const float* x, const float* noise, float* hist, float* prev, float* x0_out,
                         float* eps_out, const float* eps_factor, const float* keep_map, const float* keep_src,
                         const float* keep_noise, const float* keep_coef, void* stream);
+/* Adaptive projected guidance (APG; Sadat et al., "Eliminating Oversaturation and Artifacts of High Guidance Scales in
+ * Diffusion Models"; no reference counterpart -- it replaces the CFG sum of pipelines/sdxl_instantir.py:1619-1621).  Applied to
+ * denoised predictions.  Per image b, sums over (C, H, W); u / c = the uncond / cond rows of the UNet output, x the unscaled fp32
+ * latent, w = coef[0], sb = coef[1], sa = coef[2] (the vector iir_sched_step reads, either scheduler form):
+ *   x0_c = (x - sb*c)/sa            x0_u = (x - sb*u)/sa
+ *   D    = x0_c - x0_u
+ *   A    = D + beta_t * A_prev      (skipped, and the plane not loaded, when beta_t == 0)
+ *   n    = ||A||_2                  s = r > 0 ? min(1, r / n) : 1
+ *   alpha= <A, x0_c> / <x0_c, x0_c>                  (0 when x0_c is all zero)
+ *   U    = s * (A - (1 - eta) * alpha * x0_c)        (orthogonal part + eta * parallel part, after the clamp)
+ *   x0_g = x0_c + (w - 1) * U
+ *   eps  = (x - sa*x0_g)/sb         (replaces  u + w*(c - u)  in the step; sb != 0, as at every step of the schedulers here)
+ * apg_par = device fp32[4] {eta, r, beta_t, 0}, read at launch time so that one captured launch serves every step;
+ * apg_avg = fp32 NCHW (B, C, H, W): A_prev on entry of iir_apg_project, A on exit (each element read, then overwritten, by
+ * the thread that owns it); apg_sa = device fp32[2B] {s, alpha} per image.
+ * iir_apg_project forms A and {s, alpha}: fp32 element math, fp64 accumulation.  An image is divided among a fixed number of
+ * workgroups, each leaving its three partial sums in `workspace` (device, 8-byte aligned, at least
+ * iir_apg_project_workspace_bytes(B) bytes, contents undefined afterwards); a second small launch adds an image's partials in
+ * index order.  Every order is fixed and there are no atomics: equal inputs give equal bits.  It reads columns [0, C) of rows
+ * [0, 2B) of eps_nhwc only.  apg_avg may not be x, apg_sa or the workspace.
+ * IIR_EINVAL (before any HIP call): a NULL pointer, B, C or HW <= 0, B > 65535, lde < C, a workspace too small or unaligned. */
+int64_t iir_apg_project_workspace_bytes(int32_t B);
+int iir_apg_project(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, const float* coef, const float* x,
+                    const float* apg_par, float* apg_avg, float* apg_sa, void* workspace, int64_t workspace_bytes, void* stream);
+/* iir_sched_step with every optional plane of the family (as iir_sched_step_keep; here the keep group is optional too: all four
+ * pointers or none) plus the APG group, all three required: the guided eps is the expression above, with A and {s, alpha} as
+ * iir_apg_project left them and eta = apg_par[0].  The uncond rows are not read.  The PAG term + s_t*(c - p), eps_factor, the
+ * scheduler update, the history term, the noise, x0_out and the restore-map select are as without APG.  With eta = 1, r = 0,
+ * beta_t = 0 the eps equals u + w*(c - u) algebraically, not bitwise.
+ * IIR_EINVAL: a NULL apg_* pointer, cfg == 0, apg_avg aliasing an output plane, and whatever iir_sched_step_keep refuses. */
+int iir_sched_step_apg(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg, const float* coef,
+                       const float* pag_scale, const float* x, const float* noise, float* hist, float* prev, float* x0_out,
+                       float* eps_out, const float* eps_factor, const float* keep_map, const float* keep_src,
+                       const float* keep_noise, const float* keep_coef, const float* apg_avg, const float* apg_sa,
+                       const float* apg_par, void* stream);
 /* The restore map at latent resolution: out (B, H / factor, W / factor) = the maximum of map_px (B, H, W) over each
  * factor x factor block (a latent pixel is free if any pixel under it asked for freedom).  fp32; H and W multiples of
  * factor, H, W <= 32768; `out` must not be `map_px`.  IIR_EINVAL for any other geometry, before any launch. */

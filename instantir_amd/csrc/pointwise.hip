@@ -1,5 +1,5 @@
 // K9 and layout glue: timestep sinusoid, SiLU, concat/copy with scaled add, latent pack/unpack,
-// classifier-free guidance + scheduler update, LCM one-step preview.  All HBM-bound pointwise work.
+// classifier-free guidance (plain, PAG, adaptive projected) + scheduler update, LCM one-step preview.  All HBM-bound pointwise work.
 // Compiled with -ffp-contract=off: the scheduler arithmetic follows the reference's fp32 op order
 // (no FMA contraction) so it can be compared with the CPU restatement at rounding level.
 //
@@ -127,18 +127,96 @@ __global__ __launch_bounds__(1024) void cfg_rescale_kernel(const f16* eps_nhwc, 
     }
 }
 
+// Adaptive projected guidance (APG, Sadat et al. 2024), the per-image half.  On denoised predictions, per image b over (C, H, W):
+//   x0_c = (x - sb*c)/sa   x0_u = (x - sb*u)/sa   A = (x0_c - x0_u) + beta_t * A_prev
+//   s = r > 0 ? min(1, r / ||A||) : 1            alpha = <A, x0_c> / <x0_c, x0_c>   (0 when x0_c is all zero)
+// par (device fp32[4]) = {eta, r, beta_t, 0}; sb = coef[1], sa = coef[2].  `avg` (fp32 NCHW) holds A_prev on entry and A on exit: each
+// element is read, then overwritten by the thread that owns it, and is never loaded when beta_t == 0 (uninitialised or stale
+// on a call's first step: 0 * NaN would leak).  fp32 element math, fp64 accumulation.  Only columns [0, C) of rows [0, 2B) are read.
+// An image is split over APG_PARTS workgroups (one alone is bound by what a single CU pulls through its L1: 133 us at 128 x 128
+// with lde = 64): workgroup (part, b) owns a contiguous run of pixels and writes its three sums to ws[(b * APG_PARTS + part) * 3 ..]
+// (zeros for an empty run); apg_finalize_kernel adds the APG_PARTS partials of an image in index order and writes
+// out[2b] = s, out[2b + 1] = alpha.  Every order is fixed and there are no atomics: equal inputs give equal bits.
+constexpr int APG_PARTS = 32, APG_THREADS = 256;
+
+__global__ __launch_bounds__(APG_THREADS) void apg_project_kernel(const f16* eps_nhwc, long lde, int B, int C, int HW, const float* coef,
+                                                                  const float* x, const float* par, float* avg, double* ws) {
+    __shared__ double red[3][APG_THREADS / 64];
+    const int part = blockIdx.x, b = blockIdx.y;
+    const float sb = coef[1], sa = coef[2];
+    const float beta = par[2];
+    const int chunk = (HW + APG_PARTS - 1) / APG_PARTS;
+    const int p0 = part * chunk, p1 = min(HW, p0 + chunk);
+    double aa = 0., ac = 0., cc = 0.;
+    for (int p = p0 + threadIdx.x; p < p1; p += APG_THREADS)
+        for (int c = 0; c < C; ++c) {
+            const long o = ((long)b * C + c) * HW + p;
+            const float u = (float)eps_nhwc[((long)b * HW + p) * lde + c];
+            const float t = (float)eps_nhwc[((long)(B + b) * HW + p) * lde + c];
+            const float xv = x[o];
+            const float x0c = (xv - sb * t) / sa;
+            const float x0u = (xv - sb * u) / sa;
+            float a = x0c - x0u;
+            if (beta != 0.f) a = a + beta * avg[o];
+            avg[o] = a;
+            aa += (double)a * a; ac += (double)a * x0c; cc += (double)x0c * x0c;
+        }
+    double v[3] = {aa, ac, cc};
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int k = 0; k < 3; ++k) {
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
+        if (lane == 0) red[k][wv] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double s = 0.;
+        for (int w = 0; w < APG_THREADS / 64; ++w) s += red[threadIdx.x][w];
+        ws[((long)b * APG_PARTS + part) * 3 + threadIdx.x] = s;
+    }
+}
+
+__global__ void apg_finalize_kernel(const double* ws, int B, const float* par, float* out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const float r = par[1];
+    double s[3] = {0., 0., 0.};
+    for (int part = 0; part < APG_PARTS; ++part)
+        for (int k = 0; k < 3; ++k) s[k] += ws[((long)b * APG_PARTS + part) * 3 + k];
+    double sc = 1.;
+    if (r > 0.f) sc = fmin(1., (double)r / sqrt(s[0]));
+    out[2 * b] = (float)sc;
+    out[2 * b + 1] = s[2] > 0. ? (float)(s[1] / s[2]) : 0.f;
+}
+
 // Perturbed-attention guidance (PAG) form: the UNet output has one more group of B rows, the perturbed prediction p
 // (rows [2B, 3B) with CFG, [B, 2B) without), and  eps = u + g * (c - u) + s * (c - p)  (CFG) or  c + s * (c - p),  s = *pag_s
 // (device: the per-step s_t of the adaptive scale).  The term is skipped when s == 0 (ps = 0 without PAG), so s = 0 gives
 // the plain bits and the perturbed rows are never read.
+// APG (apg_avg given, cfg only): u + g * (c - u) is replaced by the eps of the projected x0 guidance,
+//   x0_c = (x - sb*c)/sa   U = s * (A - ((1 - eta) * alpha) * x0_c)   x0_g = x0_c + (g - 1) * U   eps = (x - sa*x0_g)/sb
+// with A = apg_avg[o] and {s, alpha} = apg_sa[2b..] from apg_project_kernel, eta = apg_par[0]; the uncond rows are not read (A
+// carries them).  The PAG term and eps_factor follow as without APG.
+struct apg_lane {
+    const float* avg = nullptr;
+    float s = 0.f, k = 0.f, sb = 0.f, sa = 0.f;     // k = (1 - eta) * alpha
+};
+
 __device__ __forceinline__ float guided_eps(const f16* eps_nhwc, long lde, int B, int HW, int cfg, float g, float ps,
-                                            const float* eps_factor, int b, int p, int c) {
+                                            const float* eps_factor, int b, int p, int c, const apg_lane& apg = {}, long o = 0,
+                                            float xv = 0.f) {
     float e;
     if (cfg) {
         // the reference forms the guidance in the UNet dtype (fp16) -- keep fp32 here (>= precision)
-        const float u = (float)eps_nhwc[((long)b * HW + p) * lde + c];
         const float t = (float)eps_nhwc[((long)(B + b) * HW + p) * lde + c];
-        e = u + g * (t - u);
+        if (apg.avg) {
+            const float x0c = (xv - apg.sb * t) / apg.sa;
+            const float up = apg.s * (apg.avg[o] - apg.k * x0c);
+            const float x0g = x0c + (g - 1.f) * up;
+            e = (xv - apg.sa * x0g) / apg.sb;
+        } else {
+            const float u = (float)eps_nhwc[((long)b * HW + p) * lde + c];
+            e = u + g * (t - u);
+        }
         if (ps != 0.f) e = e + ps * (t - (float)eps_nhwc[((long)(2 * B + b) * HW + p) * lde + c]);
         if (eps_factor) e *= eps_factor[b];
     } else {
@@ -179,8 +257,8 @@ __device__ __forceinline__ void sched_update(float e, long o, const float (&k)[7
     if (x0_out) x0_out[o] = x0;
 }
 
-// One thread per latent pixel; pag_s, noise, hist, x0_out, eps_out, eps_factor and the keep_* group are optional (every branch
-// on them is wave-uniform).  coef is read once, before the channel loop: prev may alias it as far as the compiler knows.
+// One thread per latent pixel; pag_s, noise, hist, x0_out, eps_out, eps_factor, the keep_* group and the apg_* group are optional
+// (every branch on them is wave-uniform).  coef is read once, before the channel loop: prev may alias it as far as the compiler knows.
 // keep_map (restore map, fp32 B x HW) with keep_coef = {thr, a, b, 0}: a pixel with map <= thr (fp32 compare) stores
 // keep_value(a, keep_src, b, keep_noise) in prev instead of the update.  keep_src / keep_noise are loaded for every lane
 // (no per-lane-predicated load); the per-lane part is the select alone, so a free element has the bits of the launch
@@ -188,13 +266,19 @@ __device__ __forceinline__ void sched_update(float e, long o, const float (&k)[7
 __global__ void sched_step_kernel(const f16* eps_nhwc, long lde, int B, int C, int HW, int cfg, const float* coef,
                                   const float* pag_s, const float* x, const float* noise, float* hist, float* prev,
                                   float* x0_out, float* eps_out, const float* eps_factor, const float* keep_map,
-                                  const float* keep_src, const float* keep_noise, const float* keep_coef) {
+                                  const float* keep_src, const float* keep_noise, const float* keep_coef, const float* apg_avg,
+                                  const float* apg_sa, const float* apg_par) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)B * HW) return;
     const int b = (int)(i / HW), p = (int)(i % HW);
     const float g = coef[0];
     const float k[7] = {coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7]};
     const float ps = pag_s ? *pag_s : 0.f;
+    apg_lane apg;
+    if (apg_avg) {
+        apg.avg = apg_avg; apg.s = apg_sa[2 * b]; apg.k = (1.f - apg_par[0]) * apg_sa[2 * b + 1];
+        apg.sb = k[0]; apg.sa = k[1];
+    }
     float ka = 0.f, kb = 0.f;
     bool kept = false;
     if (keep_map) {
@@ -203,7 +287,8 @@ __global__ void sched_step_kernel(const f16* eps_nhwc, long lde, int B, int C, i
     }
     for (int c = 0; c < C; ++c) {
         const long o = ((long)b * C + c) * HW + p;
-        const float e = guided_eps(eps_nhwc, lde, B, HW, cfg, g, ps, eps_factor, b, p, c);
+        const float e = apg_avg ? guided_eps(eps_nhwc, lde, B, HW, cfg, g, ps, eps_factor, b, p, c, apg, o, x[o])
+                                : guided_eps(eps_nhwc, lde, B, HW, cfg, g, ps, eps_factor, b, p, c);
         const float kv = keep_map ? keep_value(ka, keep_src[o], kb, keep_noise[o]) : 0.f;
         sched_update(e, o, k, x, noise, hist, prev, x0_out, kept, kv);
         if (eps_out) eps_out[o] = e;
@@ -303,14 +388,31 @@ struct keep_args {
     const float *map = nullptr, *src = nullptr, *noise = nullptr, *coef = nullptr;
 };
 
+// the APG group of a step launch: the running-average plane, {s, alpha} per image and {eta, r, beta_t, 0}; all or none
+struct apg_args {
+    const float *avg = nullptr, *sa = nullptr, *par = nullptr;
+};
+
 int launch_sched_step(const void* eps_nhwc, long lde, int B, int C, int HW, int cfg, const float* coef, const float* pag_s,
                       const float* x, const float* noise, float* hist, float* prev, float* x0_out, float* eps_out,
-                      const float* eps_factor, void* stream, keep_args keep = {}) {
+                      const float* eps_factor, void* stream, keep_args keep = {}, apg_args apg = {}) {
     if (!eps_nhwc || !coef || !x || !prev || B <= 0 || C <= 0 || HW <= 0 || lde < C) return IIR_EINVAL;
     if (eps_factor && !cfg) return IIR_EINVAL;
     if (hist_aliases(hist, x, prev, x0_out)) return IIR_EINVAL;
     return launch_1d(sched_step_kernel, (long)B * HW, stream, (const f16*)eps_nhwc, lde, B, C, HW, cfg, coef, pag_s, x, noise, hist,
-                     prev, x0_out, eps_out, eps_factor, keep.map, keep.src, keep.noise, keep.coef);
+                     prev, x0_out, eps_out, eps_factor, keep.map, keep.src, keep.noise, keep.coef, apg.avg, apg.sa, apg.par);
+}
+
+int launch_apg_project(const void* eps_nhwc, long lde, int B, int C, int HW, const float* coef, const float* x, const float* par,
+                       float* avg, float* out, void* ws, long ws_bytes, void* stream) {
+    if (!eps_nhwc || !coef || !x || !par || !avg || !out || !ws || B <= 0 || C <= 0 || HW <= 0 || lde < C) return IIR_EINVAL;
+    if (B > 65535 || ws_bytes < (long)B * APG_PARTS * 3 * (long)sizeof(double) || ((uintptr_t)ws & 7)) return IIR_EINVAL;
+    if (avg == x || avg == out || (void*)avg == ws || (void*)out == ws) return IIR_EINVAL;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(apg_project_kernel, dim3(APG_PARTS, B), dim3(APG_THREADS), 0, (hipStream_t)stream, (const f16*)eps_nhwc, lde, B,
+                       C, HW, coef, x, par, avg, (double*)ws);
+    hipLaunchKernelGGL(apg_finalize_kernel, dim3(nblk(B, 64)), dim3(64), 0, (hipStream_t)stream, (const double*)ws, B, par, out);
+    return iir_launch_status();
 }
 
 }  // namespace
@@ -422,6 +524,36 @@ extern "C" int iir_sched_step_keep(const void* eps_nhwc, int64_t lde, int32_t B,
     keep.map = keep_map; keep.src = keep_src; keep.noise = keep_noise; keep.coef = keep_coef;
     return launch_sched_step(eps_nhwc, (long)lde, B, C, HW, cfg, coef, pag_scale, x, noise, hist, prev, x0_out, eps_out, eps_factor,
                              stream, keep);
+}
+
+extern "C" int64_t iir_apg_project_workspace_bytes(int32_t B) {
+    return B > 0 ? (int64_t)B * APG_PARTS * 3 * (int64_t)sizeof(double) : 0;
+}
+
+extern "C" int iir_apg_project(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, const float* coef, const float* x,
+                               const float* apg_par, float* apg_avg, float* apg_sa, void* workspace, int64_t workspace_bytes,
+                               void* stream) {
+    return launch_apg_project(eps_nhwc, (long)lde, B, C, HW, coef, x, apg_par, apg_avg, apg_sa, workspace, (long)workspace_bytes, stream);
+}
+
+extern "C" int iir_sched_step_apg(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
+                                  const float* coef, const float* pag_scale, const float* x, const float* noise, float* hist,
+                                  float* prev, float* x0_out, float* eps_out, const float* eps_factor, const float* keep_map,
+                                  const float* keep_src, const float* keep_noise, const float* keep_coef, const float* apg_avg,
+                                  const float* apg_sa, const float* apg_par, void* stream) {
+    if (!apg_avg || !apg_sa || !apg_par || !cfg) return IIR_EINVAL;
+    if (eps_out && hist) return IIR_EINVAL;
+    if (apg_avg == prev || apg_avg == x0_out || apg_avg == eps_out || apg_avg == hist) return IIR_EINVAL;
+    keep_args keep;
+    if (keep_map || keep_src || keep_noise || keep_coef) {
+        if (!keep_map || !keep_src || !keep_noise || !keep_coef) return IIR_EINVAL;
+        if (keep_src == prev || keep_noise == prev) return IIR_EINVAL;
+        keep.map = keep_map; keep.src = keep_src; keep.noise = keep_noise; keep.coef = keep_coef;
+    }
+    apg_args apg;
+    apg.avg = apg_avg; apg.sa = apg_sa; apg.par = apg_par;
+    return launch_sched_step(eps_nhwc, (long)lde, B, C, HW, cfg, coef, pag_scale, x, noise, hist, prev, x0_out, eps_out, eps_factor,
+                             stream, keep, apg);
 }
 
 extern "C" int iir_copy_segments(const void* jobs, int32_t njobs, int64_t max_units, void* stream) {

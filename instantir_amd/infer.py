@@ -11,7 +11,8 @@ and has no effect on the schedule, as in the reference (Q1).  Flags the referenc
 
 Extension (not in the reference): `--synthetic {tiny,sdxl}` builds every network from seeded synthetic weights so the
 driver can be exercised without checkpoints (none are available offline); with it the text prompt is replaced by
-seeded embeddings because no tokenizer vocabulary exists here.
+seeded embeddings because no tokenizer vocabulary exists here.  `--apg ETA NORM_THRESHOLD MOMENTUM` turns adaptive projected
+guidance on (`pipe.enable_apg(...)`: the CFG update's saturating parallel part down-weighted, its norm clamped, with momentum).
 """
 from __future__ import annotations
 
@@ -138,6 +139,9 @@ def build_parser():
                    help="PAG adaptive scale: s_t = max(pag_scale - pag_adaptive_scale * (1000 - t), 0)")
     p.add_argument("--pag_layers", type=str, default="mid",
                    help="comma-separated PAG layer expressions over the UNet's self-attention names (default mid), e.g. mid,up_blocks.0")
+    p.add_argument("--apg", type=float, nargs=3, default=None, metavar=("ETA", "NORM_THRESHOLD", "MOMENTUM"),
+                   help="adaptive projected guidance (pipe.enable_apg(eta, norm_threshold, momentum)); off by default. "
+                        "The pipeline's defaults: 0.0 15.0 -0.5")
     p.add_argument("--color_fix", choices=["none", "wavelet", "adain"], default="none",
                    help="transfer the colour of the LQ input onto the restored image after the VAE decode (pipe(..., color_fix=...)); "
                         "default none")
@@ -233,6 +237,13 @@ def apply_pag(pipe, args):
     return {"pag_scale": scale, "pag_adaptive_scale": adaptive}
 
 
+def apply_apg(pipe, args):
+    """`--apg ETA NORM_THRESHOLD MOMENTUM` -> pipe.enable_apg(...) (an addition: the reference has no APG).  Without the flag the
+    pipeline is left as built (APG off)."""
+    if getattr(args, "apg", None) is not None:
+        pipe.enable_apg(*args.apg)
+
+
 def apply_vae_flash_attention(pipe, args):
     """`--vae_flash_attention` -> pipe.vae.enable_flash_attention() (an addition: the reference's VAE attention goes through
     torch SDPA at any size).  Without the flag the VAE is left as built (three GEMMs around a row softmax, 16384-pixel ceiling)."""
@@ -274,6 +285,7 @@ def main(args, device, rank=0, world=1):
     apply_freeu(pipe, args)
     apply_scheduler(pipe, args)
     pag_kw = apply_pag(pipe, args)
+    apply_apg(pipe, args)
     pag_kw.update(apply_color_fix(args))
     apply_vae_flash_attention(pipe, args)
     post_fix = f"_{args.post_fix}" if args.post_fix else ""

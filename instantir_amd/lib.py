@@ -134,6 +134,10 @@ SIGNATURES = {
     "iir_sched_step_hist_pag": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "iir_cfg_rescale_factor_pag": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P, _F, _P, _P]),
     "iir_sched_step_keep": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "iir_apg_project_workspace_bytes": (C.c_int64, [_I32]),
+    "iir_apg_project": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "iir_sched_step_apg": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                     _P]),
     "iir_map_pool_max_f32": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
     "iir_region_composite_workspace_bytes": (C.c_int64, [_I32, _I32, _I32]),
     "iir_region_composite_f32": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P]),

@@ -681,13 +681,63 @@ def _pag_entry(name, pag_scale):
     return getattr(L.load(), name + "_pag"), name + "_pag", [pag_scale.data_ptr()]
 
 
+def _chk_group(what, items):
+    for name, t, numel in items:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel):
+            raise ValueError(f"{what} {name} must be a contiguous CUDA fp32 tensor of {numel} elements")
+
+
+def apg_workspace(B, device):
+    """The partial-sum workspace of `apg_project` for B images (iir_apg_project_workspace_bytes)."""
+    return torch.empty(int(L.load().iir_apg_project_workspace_bytes(int(B))) // 8, dtype=torch.float64, device=device)
+
+
+def apg_project(eps2d, B, coef, x, apg, ws):
+    """The per-image half of adaptive projected guidance (iir_apg_project).  `apg` = (avg (shape of x), sa (2B,), par
+    {eta, r, beta_t, 0}), fp32 CUDA tensors: avg holds the running average A_prev and then A (never loaded when beta_t == 0),
+    sa receives {s, alpha} per image.  `ws`: an `apg_workspace(B, device)`.  `coef` and `x` as for `sched_step`."""
+    _, Cc, H, Wd = x.shape
+    avg, sa, par = apg
+    _chk_group("apg_project: apg", (("avg", avg, x.numel()), ("sa", sa, 2 * B), ("par", par, 4)))
+    if not (torch.is_tensor(ws) and ws.is_cuda and ws.is_contiguous() and ws.dtype == torch.float64):
+        raise ValueError("apg_project: ws must be a contiguous CUDA fp64 tensor (ops.apg_workspace)")
+    L.check(L.load().iir_apg_project(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, coef.data_ptr(), x.data_ptr(), par.data_ptr(),
+                                     avg.data_ptr(), sa.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()), "iir_apg_project")
+    return sa
+
+
 def sched_step(eps2d, B, coef, x, prev, noise=None, cfg=True, x0_out=None, eps_out=None, eps_factor=None, pag_scale=None, hist=None,
-               keep=None):
+               keep=None, apg=None):
     """`pag_scale` (device fp32[1]): the PAG form -- eps2d holds the perturbed rows after the cond rows (iir_sched_step*_pag).
     `hist` (shape of x, fp32): adds the history term coef[7] * hist and then holds this step's x0 (iir_sched_step_hist*).
     `keep` = (map (B, H*W), src, noise0, coef {thr, a, b, 0}), fp32 CUDA tensors: the restore-map form (iir_sched_step_keep) --
-    pixels with map <= thr store a * src + b * noise0 in prev instead of the update."""
+    pixels with map <= thr store a * src + b * noise0 in prev instead of the update.
+    `apg` = (avg, sa, par), as `apg_project` left them: the guided eps is the projected form (iir_sched_step_apg); it needs `cfg`
+    and does not combine with `eps_factor` (the norm clamp is APG's answer to what rescale_noise_cfg addresses)."""
     _, Cc, H, Wd = x.shape
+    if apg is not None:
+        if eps_factor is not None:
+            raise ValueError("sched_step: apg is not available together with eps_factor")
+        if not cfg:
+            raise ValueError("sched_step: apg needs cfg (there is nothing to project without the uncond rows)")
+        if hist is not None and eps_out is not None:
+            raise ValueError("sched_step: eps_out is not available together with hist")
+        avg, sa, par = apg
+        _chk_group("sched_step: apg", (("avg", avg, x.numel()), ("sa", sa, 2 * B), ("par", par, 4)))
+        kp = [None] * 4
+        if keep is not None:
+            kp = list(keep)
+            _chk_group("sched_step: keep", (("map", kp[0], B * H * Wd), ("src", kp[1], x.numel()), ("noise", kp[2], x.numel()),
+                                            ("coef", kp[3], 4)))
+        if hist is not None:
+            assert hist.shape == x.shape and hist.dtype == torch.float32 and hist.is_contiguous()
+        if pag_scale is not None:
+            _chk_pag(pag_scale)
+        L.check(L.load().iir_sched_step_apg(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(), _p(pag_scale),
+                                            x.data_ptr(), _p(noise), _p(hist), prev.data_ptr(), _p(x0_out), _p(eps_out), None,
+                                            *[_p(t) for t in kp], avg.data_ptr(), sa.data_ptr(), par.data_ptr(), _stream()),
+                "iir_sched_step_apg")
+        return prev
     outs = [prev.data_ptr(), _p(x0_out), _p(eps_out)]
     if hist is not None:
         assert hist.shape == x.shape and hist.dtype == torch.float32 and hist.is_contiguous()

@@ -24,6 +24,7 @@ Latents are carried in fp32 between steps (the reference carries fp16); UNet inp
 from __future__ import annotations
 
 import dataclasses
+import math
 import os
 from types import SimpleNamespace
 from typing import Callable, Dict, List, Optional, Union
@@ -188,6 +189,7 @@ class InstantIRPipeline:
         self._freeu = None                          # (s1, s2, b1, b2) or None: see enable_freeu
         self._pag_layers = None                     # perturbed-attention guidance: the layer list of enable_pag, or None
         self._pag_paths = None                      # ... and the main UNet's `attn1` paths it selects
+        self._apg = None                            # adaptive projected guidance: (eta, norm_threshold, momentum) or None
 
     # ---- reference surface ----------------------------------------------------------------------
     @classmethod
@@ -341,6 +343,35 @@ class InstantIRPipeline:
     def pag_applied_layers(self):
         return None if self._pag_layers is None else list(self._pag_layers)
 
+    # ---- adaptive projected guidance (APG; Sadat et al. 2024) ----
+    def enable_apg(self, eta: float = 0.0, norm_threshold: float = 15.0, momentum: float = -0.5):
+        """Turn adaptive projected guidance on for later calls: the CFG update, formed on denoised predictions, is split into its
+        parts parallel and orthogonal to the cond prediction; the parallel part (which drives saturation) is weighted by `eta`
+        (0 <= eta <= 1), the update's per-image norm is clamped to `norm_threshold` (>= 0; 0 = no clamp) and it carries a running
+        average over the steps of a call with weight `momentum` (-1 < momentum < 1).  The defaults are this project's choice
+        (DESIGN.md).  Calls then need guidance_scale > 1 and guidance_rescale == 0."""
+        try:
+            f = tuple(float(v) for v in (eta, norm_threshold, momentum))
+        except (TypeError, ValueError):
+            raise ValueError(f"enable_apg: eta, norm_threshold and momentum must be numbers, got {(eta, norm_threshold, momentum)!r}")
+        if not all(math.isfinite(v) for v in f):
+            raise ValueError(f"enable_apg: eta, norm_threshold and momentum must be finite, got {f}")
+        if not 0.0 <= f[0] <= 1.0:
+            raise ValueError(f"enable_apg: eta must be in [0, 1], got {f[0]}")
+        if f[1] < 0.0:
+            raise ValueError(f"enable_apg: norm_threshold must be >= 0 (0 = no clamp), got {f[1]}")
+        if not -1.0 < f[2] < 1.0:
+            raise ValueError(f"enable_apg: momentum must be in (-1, 1), got {f[2]}")
+        self._apg = f
+
+    def disable_apg(self):
+        self._apg = None
+
+    @property
+    def apg(self):
+        """(eta, norm_threshold, momentum) of `enable_apg`, or None."""
+        return self._apg
+
     def _main_state(self, ctx, pooled, time_ids, img, Hl, Wl, B, rep, pag_on):
         """`prepare` of the main UNet: with PAG one more group of B rows, each a copy of its cond row (rows [(rep-1)B, rep B)
         of the prompt embeddings, pooled embeddings, time ids and IP tokens)."""
@@ -421,7 +452,7 @@ class InstantIRPipeline:
         self._apply_freeu(self._unet, self._unet_prev)
 
     def _loop_for(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale, pag_on=False,
-                  fresh=False, keep=None):
+                  fresh=False, keep=None, apg_on=False):
         """The step's buffers and captured hipGraphs are kept from one call to the next: a second image of the same geometry,
         through the same engines, re-uses them (its hoisted K / V, embeddings and LQ latent are copied into the captured
         tensors) instead of paying the warm-up step, the capture and the graph instantiation again (~0.1 s of a 1.9 s call
@@ -433,7 +464,8 @@ class InstantIRPipeline:
                self._freeu,           # the FreeU factors are launch arguments of the captured concats
                _sched_form(self.scheduler),   # the sigma schedulers launch the device-scale pack and the history step
                self._pag_paths if pag_on else None,     # PAG: row count and the identity launches (its scale is a device scalar)
-               keep is not None)      # a restore map: the step's last launch is iir_sched_step_keep, on buffers only such a loop has
+               keep is not None,      # a restore map: the step's last launch is iir_sched_step_keep, on buffers only such a loop has
+               bool(apg_on))          # APG: iir_apg_project + iir_sched_step_apg (its three parameters travel in the scalar row)
         if not fresh:
             cached = self._loop_cache
             if cached is not None and cached[0] == key and os.environ.get("IIR_LOOP_CACHE", "1") != "0":
@@ -441,7 +473,7 @@ class InstantIRPipeline:
                     return cached[1]
             self._loop_cache = cached = None         # drop the old graphs before building the new ones
         loop = _DenoiseLoop(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler,
-                            guidance_rescale=guidance_rescale, pag_on=pag_on, keep=keep)
+                            guidance_rescale=guidance_rescale, pag_on=pag_on, keep=keep, apg_on=apg_on)
         # the entry keeps the engines alive: `id()` in the key can then not be re-issued to a NEW engine (adapter switch, LoRA
         # scale change) while graphs captured on the old one's arena and weights are still cached
         if not fresh:
@@ -676,9 +708,17 @@ class InstantIRPipeline:
         return StableDiffusionXLPipelineOutput(images=self._decode_output(out, output_type, color_fix, cf_ref))
 
     # ---- the call: its stages, in the reference's order -----------------------------------------------------------
-    def _check_call(self, color_fix, output_type, cross_attention_kwargs, pag_scale, pag_adaptive_scale, multistep_restore):
+    def _check_call(self, color_fix, output_type, cross_attention_kwargs, pag_scale, pag_adaptive_scale, multistep_restore,
+                    guidance_scale=None, guidance_rescale=0.0):
         """Checks of the arguments `check_inputs` does not see -> (LoRA scale, `pag_scale` with its default, whether PAG runs)."""
         self._check_color_fix(color_fix, output_type)
+        if self._apg is not None:
+            if guidance_scale is not None and not guidance_scale > 1:
+                raise ValueError(f"adaptive projected guidance (enable_apg) projects the classifier-free guidance update: "
+                                 f"guidance_scale must be > 1, got {guidance_scale}; call pipe.disable_apg() to run without guidance")
+            if guidance_rescale and float(guidance_rescale) > 0.0:
+                raise ValueError(f"guidance_rescale={guidance_rescale} does not combine with adaptive projected guidance (enable_apg): "
+                                 "the APG norm clamp (norm_threshold) addresses the same over-exposure; use one of the two")
         # :1531-1535 merges the caller's dict over {"temb": emb} and hands it to both UNet passes.  What a key can do there:
         # "scale" is popped by diffusers' UNet forward and scales every LoRA layer for that pass (it also sets the text-encoder
         # LoRA scale, :1324-1326 -- no text-encoder LoRA exists on this path); "temb" / "external_kv" are the processors' own
@@ -811,7 +851,7 @@ class InstantIRPipeline:
             x0 = loop.step(mode, t, x, (compound if mode != "unet" else scale_rows).repeat(groups), guidance_scale, eta,
                            None if step_noises is None else step_noises[i], generator, want_x0=adastep_restore, want_preview=save_preview_row or adastep_restore, i=i,
                            pag_s=pag.scale_at(pag_scale, pag_adaptive_scale, t) if pag_on else 0.0,
-                           keep_row=(thr[i],) + rmap.keep_pair(self.scheduler, i, t) if masked else None)
+                           keep_row=(thr[i],) + rmap.keep_pair(self.scheduler, i, t) if masked else None, apg=self._apg)
             if mode == "preview":
                 pv = loop.preview_f32[B * (rep - 1):]
                 if save_preview_row:
@@ -837,11 +877,14 @@ class InstantIRPipeline:
                     if tuple(new_ctx.shape) != tuple(ctx.shape):
                         raise ValueError(f"callback_on_step_end returned prompt_embeds of shape {tuple(new_ctx.shape)}, expected {tuple(ctx.shape)}")
                     ctx = new_ctx
-                    mean_keep, hist_keep = loop.previewer_mean, loop.hist
+                    mean_keep, hist_keep, apg_keep = loop.previewer_mean, loop.hist, (loop.apg_avg, loop.apg_first)
                     loop = loop_of(ctx, True)
                     loop.previewer_mean = mean_keep
                     if hist_keep is not None:                # a multistep solver's x0 history continues across the rebuild
                         loop.hist.copy_(hist_keep)
+                    if apg_keep[0] is not None and loop.apg_avg is not None:      # and so does APG's running average
+                        loop.apg_avg.copy_(apg_keep[0])
+                        loop.apg_first = apg_keep[1]
         return x, preview_row
 
     @torch.no_grad()
@@ -884,7 +927,7 @@ class InstantIRPipeline:
         if restore_map is not None:
             map_feather = rmap.check_feather(map_feather)
         lora_mult, pag_scale, pag_on = self._check_call(color_fix, output_type, cross_attention_kwargs, pag_scale, pag_adaptive_scale,
-                                                        multistep_restore)
+                                                        multistep_restore, guidance_scale, guidance_rescale)
         ids_given = prompt is None and prompt_embeds is None and kwargs.get("prompt_ids") is not None and self.text_encoder is not None
         prompt_embeds_chk = kwargs["prompt_ids"] if ids_given else prompt_embeds      # ids stand in for the prompt in the exclusivity checks
         self.check_inputs(prompt, prompt_embeds_chk, negative_prompt_embeds,
@@ -957,7 +1000,7 @@ class InstantIRPipeline:
             prev = self._unet_prev
             st_prev = None if prev is None else prev.prepare(ctx_, pooled, time_ids, prev.resampler(img), Hl, Wl)
             return self._loop_for(B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale,
-                                  pag_on, fresh=fresh, keep=keep_box[0] if keep_box else None)
+                                  pag_on, fresh=fresh, keep=keep_box[0] if keep_box else None, apg_on=self._apg is not None)
 
         x, noise0 = self._initial_latents(self.scheduler, lq, ts[0], generator, init_noise, init_latents_with_lq, latents)
         if keep_map is not None:
@@ -980,13 +1023,15 @@ def _sched_form(scheduler):
     return "hist" if hasattr(scheduler, "loop_coefficients") else "linear"
 
 
-def _scalar_row(rows, masked=False):
+def _scalar_row(rows, masked=False, apg=False):
     """Layout of a loop's per-step scalar row when its main UNet runs `rows` rows: ({name: slice}, length) of
     [t x rows | lcm coef x4 | sched coef x8 | res scale x rows | c_in | PAG s_t], and for a loop with a restore map (`masked`)
-    [| keep x4] = {thr, a, b, 0} behind them.  `sched` is the (8,) coefficient vector the iir_sched_step* and PAG kernels index
+    [| keep x4] = {thr, a, b, 0} behind them, and for a loop with adaptive projected guidance (`apg`) [| apg x4] =
+    {eta, r, beta_t, 0} behind everything else.  `sched` is the (8,) coefficient vector the iir_sched_step* and PAG kernels index
     themselves: guidance in [0], the history term k_h in [7]."""
     lay, off = {}, 0
-    for name, n in (("t", rows), ("lcm", 4), ("sched", 8), ("res_scale", rows), ("c_in", 1), ("pag_s", 1)) + ((("keep", 4),) if masked else ()):
+    groups = (("t", rows), ("lcm", 4), ("sched", 8), ("res_scale", rows), ("c_in", 1), ("pag_s", 1))
+    for name, n in groups + ((("keep", 4),) if masked else ()) + ((("apg", 4),) if apg else ()):
         lay[name] = slice(off, off + n)
         off += n
     return lay, off
@@ -1024,7 +1069,7 @@ class _DenoiseLoop:
     one more with perturbed-attention guidance (`pag_on`), whose rows copy the cond rows' inputs and residuals."""
 
     def __init__(self, pipe, B, rep, H, W, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale=0.0,
-                 pag_on=False, keep=None):
+                 pag_on=False, keep=None, apg_on=False):
         dev = pipe.device
         self.guidance_rescale = float(guidance_rescale or 0.0)
         self.cfg_factor = torch.ones(B, dtype=torch.float32, device=dev)
@@ -1060,7 +1105,15 @@ class _DenoiseLoop:
             self.keep_map = torch.empty(B, HW, dtype=torch.float32, device=dev)
             self.keep_src, self.keep_noise = torch.empty_like(self.x_in), torch.empty_like(self.x_in)
             self._adopt_keep(keep, lq)
-        lay, n_sc = _scalar_row(Rm, self.masked)                 # per-step scalars
+        # adaptive projected guidance: the running average A of the guidance update, read and rewritten in place by every
+        # step's iir_apg_project (in-place state, like `hist`), {s, alpha} per image and the reduction's workspace;
+        # {eta, r, beta_t, 0} travels in the step's scalar row, beta_t = 0 on a call's first main-UNet step
+        self.apg_on = bool(apg_on)
+        self.apg_avg = torch.zeros_like(self.x_in) if self.apg_on else None
+        self.apg_sa = torch.zeros(2 * B, dtype=torch.float32, device=dev) if self.apg_on else None
+        self.apg_ws = ops.apg_workspace(B, dev) if self.apg_on else None
+        self.apg_first = True
+        lay, n_sc = _scalar_row(Rm, self.masked, self.apg_on)    # per-step scalars
         # ring of pinned staging rows: a row is rewritten only after the H2D copy that read it has completed
         self.sc_ring = [torch.zeros(n_sc, dtype=torch.float32).pin_memory() for _ in range(8)]
         self.sc_events = [None] * 8
@@ -1070,6 +1123,7 @@ class _DenoiseLoop:
         self.lcm_coef, self.sched_coef, self.res_scale, self.c_in, self.pag_s = (
             self.sc_dev[lay[k]] for k in ("lcm", "sched", "res_scale", "c_in", "pag_s"))
         self.keep_coef = self.sc_dev[lay["keep"]] if self.masked else None
+        self.apg_par = self.sc_dev[lay["apg"]] if self.apg_on else None
         self.t_agg = self.t_dev[:R]                                         # the previewer's and the Aggregator's rows
         self.seg_jobs = None
         if self.pag_on:
@@ -1106,6 +1160,9 @@ class _DenoiseLoop:
         self.cfg_factor.fill_(1.0)
         if self.hist is not None:
             self.hist.zero_()
+        if self.apg_on:
+            self.apg_avg.zero_()
+        self.apg_first = True
         if self.masked:
             self._adopt_keep(keep, lq)
         return True
@@ -1174,15 +1231,19 @@ class _DenoiseLoop:
         fac = None
         if rep == 2 and self.guidance_rescale > 0.0:
             fac = ops.cfg_rescale_factor(eps, B, self.sched_coef, self.x_in, self.guidance_rescale, self.cfg_factor, pag_scale=ps)
+        apg = None
+        if self.apg_on:
+            apg = (self.apg_avg, self.apg_sa, self.apg_par)
+            ops.apg_project(eps, B, self.sched_coef, self.x_in, apg, self.apg_ws)
         ops.sched_step(eps, B, self.sched_coef, self.x_in, self.x_out, noise=self.noise if use_noise else None, cfg=rep == 2,
                        x0_out=self.x0 if want_x0 else None, eps_factor=fac, pag_scale=ps, hist=self.hist,
-                       keep=(self.keep_map, self.keep_src, self.keep_noise, self.keep_coef) if masked else None)
+                       keep=(self.keep_map, self.keep_src, self.keep_noise, self.keep_coef) if masked else None, apg=apg)
 
     def step(self, mode, t, x, res_scale_rows, guidance, eta, noise, generator, want_x0=False, want_preview=False, i=None,
-             pag_s=0.0, keep_row=None):
+             pag_s=0.0, keep_row=None, apg=None):
         """`i`: the step's index in the scheduler's timetable (the sigma schedulers' coefficients are per index).  `res_scale_rows`:
         one scale per main-UNet row.  `pag_s`: the step's PAG scale s_t.  `keep_row`: (thr, a, b) of a restore map for this step (a loop
-        built with one)."""
+        built with one).  `apg`: (eta, norm_threshold, momentum) of adaptive projected guidance (a loop built with it)."""
         p, lay = self.p, self.sc_lay
         slot = self.sc_idx % len(self.sc_ring)
         self.sc_idx += 1
@@ -1209,6 +1270,10 @@ class _DenoiseLoop:
         sc[lay["pag_s"]] = float(pag_s)
         if self.masked:
             sc[lay["keep"]] = torch.tensor(list(keep_row) + [0.0])
+        if self.apg_on:
+            # beta_t = 0 on the call's first main-UNet step: the average starts from this step's update alone
+            sc[lay["apg"]] = torch.tensor([apg[0], apg[1], 0.0 if self.apg_first else apg[2], 0.0])
+            self.apg_first = False
         use_noise = coef[6] != 0.0
         if use_noise:
             noise = _randn(self.x_in.shape, generator, self.x_in.device) if noise is None else noise
@@ -1223,9 +1288,12 @@ class _DenoiseLoop:
             g = self.graphs.get(key)
             if g is None:
                 hist = self.hist.clone() if self.hist is not None else None
+                avg = self.apg_avg.clone() if self.apg_on else None
                 self._launch(*key)                        # warm-up: one-time attribute / workspace setup
                 if hist is not None:
                     self.hist.copy_(hist)                 # the warm-up consumed the history: the replay below is the step
+                if avg is not None:
+                    self.apg_avg.copy_(avg)               # and overwrote APG's running average
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):

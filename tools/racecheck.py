@@ -62,5 +62,28 @@ q4 = qkv[:, :Cc].float().reshape(B, T, heads, 64).transpose(1, 2); k4 = qkv[:, C
 v4 = vt.float().T.reshape(B, T, heads, 64).transpose(1, 2)
 want = F.scaled_dot_product_attention(q4, k4, v4).transpose(1, 2).reshape(B * T, Cc).flatten().cpu()
 screen(f"attention B={B} h={heads} T={T}", lambda o: ops.attention(qkv[:, :Cc], o, [(qkv[:, Cc:], T, vt, T, T)], B, heads, T), want, [(B * T, Cc)])
+# adaptive projected guidance: iir_apg_project + iir_sched_step_apg (fp32 planes; prev against plain CFG at the identity parameters
+# eta = 1, r = 0, beta = 0, which equal it algebraically), bit-identical over REP launches at the library defaults
+for apB in (1, 8):
+    ap_x = (torch.randn(apB, 4, 128, 128, generator=g) * 0.8).to(dev)
+    ap_eps = rnd(2 * apB * 128 * 128, 64).to(dev)
+    ap_a0 = torch.randn(apB, 4, 128, 128, generator=g).to(dev)
+    ap_coef = torch.tensor([7.0, 0.9, 0.3, 0.8, 0.5, 0.0, 0.0, 0.0], device=dev)
+    ap_ref, ap_ws = torch.empty_like(ap_x), ops.apg_workspace(apB, dev)
+    ops.sched_step(ap_eps, apB, ap_coef, ap_x, ap_ref)
+    for ap_name, ap_par in (("identity", [1.0, 0.0, 0.0, 0.0]), ("defaults", [0.0, 15.0, -0.5, 0.0])):
+        ap_pd = torch.tensor(ap_par, device=dev)
+        first = None; nd = 0
+        for it in range(REP):
+            a, sa, o = ap_a0.clone(), torch.zeros(2 * apB, device=dev), torch.zeros_like(ap_x)
+            ops.apg_project(ap_eps, apB, ap_coef, ap_x, (a, sa, ap_pd), ap_ws)
+            ops.sched_step(ap_eps, apB, ap_coef, ap_x, o, apg=(a, sa, ap_pd))
+            torch.cuda.synchronize()
+            cat = torch.cat([o.flatten(), a.flatten(), sa])
+            if first is None: first = cat
+            elif not torch.equal(cat, first): nd += 1
+        ok = ap_name != "identity" or bool(((first[:ap_x.numel()] - ap_ref.flatten()).abs() <= 1e-4 + 1e-5 * ap_ref.flatten().abs()).all())
+        bad_total += (not ok) + nd
+        print(f"{'apg_project + sched_step_apg B=%d %s' % (apB, ap_name):56s} ref_ok={ok} nondeterministic_runs={nd}/{REP - 1}", flush=True)
 print("TOTAL anomalies:", bad_total)
 sys.exit(1 if bad_total else 0)

@@ -237,4 +237,19 @@ for rm_r in (0, 4):
            [(1, 3, 1024, 1024)], dtype=torch.float32)
     screen(f"restore_map region_composite 1x3x1024x1024 r={rm_r} in place", lambda o: (o.copy_(rm_dec), ops.region_composite(o, rm_orig, rm_px, rm_r, out=o)),
            [(1, 3, 1024, 1024)], dtype=torch.float32)
+# adaptive projected guidance (round 11): the per-image reduction (A in place, {s, alpha}) and the step that consumes them, B = 1 and 8
+for apB in (1, 8):
+    ap_x = (torch.randn(apB, 4, 128, 128, generator=g) * 0.8).to(dev)
+    ap_eps = rnd(2 * apB * 128 * 128, 64)
+    ap_a0 = torch.randn(apB, 4, 128, 128, generator=g).to(dev)
+    ap_nz = torch.randn(apB, 4, 128, 128, generator=g).to(dev)
+    ap_par = torch.tensor([0.0, 15.0, -0.5, 0.0], device=dev)
+    ap_coef = torch.tensor([7.0, 0.9, 0.3, 0.8, 0.5, 0.0, 0.1, 0.0], device=dev)
+    ap_ws = ops.apg_workspace(apB, dev)
+    def apg_launch(o, a, sa):
+        a.copy_(ap_a0)
+        ops.apg_project(ap_eps, apB, ap_coef, ap_x, (a, sa, ap_par), ap_ws)
+        ops.sched_step(ap_eps, apB, ap_coef, ap_x, o, noise=ap_nz, apg=(a, sa, ap_par))
+    screen(f"apg_project + sched_step_apg B={apB} (CFG + DDPM noise)", apg_launch, [(apB, 4, 128, 128), (apB, 4, 128, 128), (2 * apB,)],
+           dtype=torch.float32)
 print("kernels with run-to-run differences:", bad)

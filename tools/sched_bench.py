@@ -13,6 +13,12 @@ Prints one line per timed call and a JSON summary:
 The restore map (restore_map=): the step launch alone, iir_sched_step against iir_sched_step_keep at the step's shapes
 (B = 1, cfg, DDPM noise; device events, alternating windows), and DDPM calls through the pipeline without and with a map,
 alternating pairs, ms/step medians.
+
+    python tools/sched_bench.py --apg [--size 1024] [--pairs 3] [--steps 20]
+
+Adaptive projected guidance (enable_apg): iir_sched_step against iir_apg_project + iir_sched_step_apg at B = 1 and B = 8 (cfg,
+DDPM noise; device events, alternating windows), and DDPM calls through the pipeline with APG off and on, alternating pairs,
+ms/step medians.
 """
 import argparse
 import json
@@ -62,6 +68,38 @@ def map_launch_leg(size, n=500, windows=3):
     return {k: round(min(v), 2) for k, v in us.items()}
 
 
+def apg_launch_leg(size, B, n=500, windows=3):
+    """iir_sched_step against iir_apg_project + iir_sched_step_apg on one stream, back to back: each figure includes the launch
+    boundaries (two for APG).  APG adds one reduction pass (both eps row groups and x in, the average plane in and out) and one
+    fp32 read per latent element in the step (the average; the uncond rows are no longer read there)."""
+    from instantir_amd import ops
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(1)
+    Hl = size // 8
+    x = (torch.randn(B, 4, Hl, Hl, generator=g) * 0.8).to(dev)
+    eps = torch.randn(2 * B * Hl * Hl, 64, generator=g).half().to(dev)
+    nz = torch.randn(B, 4, Hl, Hl, generator=g).to(dev)
+    avg, sa, ws = torch.zeros_like(x), torch.zeros(2 * B, device=dev), ops.apg_workspace(B, dev)
+    prev = torch.empty_like(x)
+    coef = torch.tensor([7.0, 0.9, 0.3, 0.8, 0.5, 0.0, 0.1, 0.0], device=dev)
+    par = torch.tensor([0.0, 15.0, -0.5, 0.0], device=dev)
+
+    def apg():
+        ops.apg_project(eps, B, coef, x, (avg, sa, par), ws)
+        ops.sched_step(eps, B, coef, x, prev, noise=nz, apg=(avg, sa, par))
+    legs = {"iir_sched_step": lambda: ops.sched_step(eps, B, coef, x, prev, noise=nz),
+            "iir_apg_project": lambda: ops.apg_project(eps, B, coef, x, (avg, sa, par), ws),
+            "iir_apg_project + iir_sched_step_apg": apg}
+    us = {k: [] for k in legs}
+    for _ in range(windows):
+        for k, fn in legs.items():
+            avg.zero_()                      # the average is a geometric series under momentum -0.5: bounded, but start each window alike
+            us[k].append(timed_us(fn, n))
+    for k, v in us.items():
+        print(f"step launch {size}^2 (B={B}, cfg, DDPM noise) {k}: windows {[round(t, 2) for t in v]} us, best {min(v):.2f} us", flush=True)
+    return {k: round(min(v), 2) for k, v in us.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=1024)
@@ -69,6 +107,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--tiny", action="store_true")
     ap.add_argument("--map", action="store_true", help="only the restore-map legs: the step launch and pipe() without / with a map")
+    ap.add_argument("--apg", action="store_true", help="only the APG legs: the step launches and pipe() with APG off / on")
     args = ap.parse_args()
     from instantir_amd import schedulers as S, weights as W
     from instantir_amd.config import UNetConfig
@@ -119,6 +158,23 @@ def main():
                 dt = call("ddpm", args.steps, **extra)
                 res[name].append(dt / args.steps * 1e3)
                 print(f"round {r} ddpm {name}: {dt / args.steps * 1e3:.2f} ms/step (call {dt:.3f} s, {args.steps} steps)", flush=True)
+        print(json.dumps({"size": args.size, "steps": args.steps, "step_launch_us_best": launch,
+                          "ms_per_step_median": {k: round(statistics.median(v), 2) for k, v in res.items()},
+                          "ms_per_step_all": {k: [round(x, 2) for x in v] for k, v in res.items()}}))
+        return
+
+    if args.apg:
+        launch = {f"B={B}": apg_launch_leg(args.size, B) for B in (1, 8)}
+        legs = {"apg off": None, "apg on": (0.0, 15.0, -0.5)}
+        res = {k: [] for k in legs}
+        for r in range(args.pairs):
+            for name, par in legs.items():
+                pipe.disable_apg() if par is None else pipe.enable_apg(*par)
+                call("ddpm", 2)                         # the loop cache holds one of the two forms: rebuild and capture, untimed
+                dt = call("ddpm", args.steps)
+                res[name].append(dt / args.steps * 1e3)
+                print(f"round {r} ddpm {name}: {dt / args.steps * 1e3:.2f} ms/step (call {dt:.3f} s, {args.steps} steps)", flush=True)
+        pipe.disable_apg()
         print(json.dumps({"size": args.size, "steps": args.steps, "step_launch_us_best": launch,
                           "ms_per_step_median": {k: round(statistics.median(v), 2) for k, v in res.items()},
                           "ms_per_step_all": {k: [round(x, 2) for x in v] for k, v in res.items()}}))
