@@ -19,6 +19,7 @@
 // tile in two 128-row halves (256 x 640 B does not fit the ring).
 #include "common.h"
 #include "gemm_geo.h"
+#include <type_traits>
 #include "../../include/instantir_hip.h"
 
 namespace {
@@ -28,8 +29,9 @@ constexpr int BK = 64;
 constexpr int PF_TOUCHES = 2;
 
 // F8: both operands fp8-E4M3 (gemm_conv.hip, same scheme: K counted in 2-byte units by the host, two fp8 MFMAs per 16-byte fragment pair,
-// wscale[n] * a_scale in the epilogue)
-template <int BN, bool F8 = false>
+// wscale[n] * a_scale in the epilogue).  GEGLU: the epilogue form (g.epi) as a compile-time value, so phase 1 of an epilogue chunk
+// is straight-line code; the plain form decides g.act once per chunk.
+template <int BN, bool F8, bool GEGLU>
 __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
     using E = f16;
     using E4 = f16x4;
@@ -92,7 +94,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
     }
 
     // LayerNorm statistics of this tile's rows from the producer's partials, parked in LDS until the epilogue
-    if (g.ln_in && tid < BM) rowstat[tid] = iir::ln_row_stat(g, min(m0 + tid, g.M - 1));
+    // ((1, 0) without ln_in, so that the epilogue reads them without a test)
+    if (tid < BM) rowstat[tid] = g.ln_in ? iir::ln_row_stat(g, min(m0 + tid, g.M - 1)) : make_float2(1.f, 0.f);
 
     E8 bfr[2][NI], a0[2], a1[2];
     auto read_b = [&](const char* st) {
@@ -149,8 +152,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
     // barrier, then whole-row 16-byte stores -- which are asynchronous, so they drain under the vector work of chunk c+1
     // (with all 256 workgroups of a one-round launch reaching their write-out together, a monolithic epilogue left both the
     // erf arithmetic and the HBM write exposed).
-    const bool paired = g.epi != IIR_EPI_PLAIN;
-    const int cs = (paired ? BN : 2 * BN) + 32;          // staged row stride in bytes (odd multiple of 32 mod 256)
+    constexpr int cs = (GEGLU ? BN : 2 * BN) + 32;       // staged row stride in bytes (odd multiple of 32 mod 256)
     constexpr int CHUNK_ROWS = 64, STAGE_STRIDE = CHUNK_ROWS * (2 * BN + 32);
     // column constants of this lane's NI column quads
     f32x4 c1v[NI], scv[F8 ? NI : 1];
@@ -163,39 +165,49 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
         if (g.bias) c0v[j] = *(const E4*)(g.bias + nc);
         else for (int t = 0; t < 4; ++t) c0v[j][t] = (E)0.f;
     }
-    const int cpr = paired ? BN / 16 : BN / 8;                 // 16-byte chunks per staged row
-    const int no_tile = paired ? n0 / 2 : n0;
-    const bool use_res = g.res && !paired;
-    const int total = CHUNK_ROWS * cpr;                        // 16-byte pieces of one chunk (1280 or 2560)
+    constexpr int cpr = GEGLU ? BN / 16 : BN / 8;              // 16-byte chunks per staged row
+    const int no_tile = GEGLU ? n0 / 2 : n0;
+    const bool use_res = g.res && !GEGLU;
+    constexpr int total = CHUNK_ROWS * cpr;                    // 16-byte pieces of one chunk (1280 or 2560)
+    const int pair_col = iir::geglu_col(fq);
     iir::touch_next_weights<NT, PF_TOUCHES>(g, tid, smem + RING_BYTES + wave * 256);
-#pragma unroll
-    for (int c = 0; c < MI / 2; ++c) {
-        char* ct = smem + (c & 1) * STAGE_STRIDE;
+    // phase 1 of chunk c: no run-time test inside (GEGLU: one basic block; plain: `act` is a template value)
+    auto phase1 = [&](int c, char* ct, auto act_tag) {
+        constexpr int ACT = decltype(act_tag)::value;
 #pragma unroll
         for (int ii = 0; ii < 2; ++ii) {
             const int i = 2 * c + ii;
             const int lr = wm * WM + i * 16 + frow;                       // row inside the tile
-            const float2 rs = g.ln_in ? rowstat[lr] : make_float2(1.f, 0.f);
+            const float2 rs = rowstat[lr];
             char* rowp = ct + (wm * 32 + ii * 16 + frow) * cs;            // row inside the chunk
 #pragma unroll
             for (int j = 0; j < NI; ++j) {
                 float a[4];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) a[t] = iir::epi_affine(F8 ? acc[i][j][t] * scv[F8 ? j : 0][t] : acc[i][j][t], rs, c1v[j][t], (float)c0v[j][t]);
-                if (!paired) {
-                    iir::epi_act(g.act, a);
+                if constexpr (!GEGLU) {
+                    iir::epi_act<ACT>(a);
                     E4 o;
-                    for (int t = 0; t < 4; ++t) o[t] = (E)a[t];
+                    for (int t = 0; t < 4; ++t) o[t] = (E)iir::rounded_f32(a[t]);
                     *(E4*)(rowp + (wn * WN + j * 16 + fq * 4) * 2) = o;
                 } else {
-                    int col;
-                    const f16x2 o2 = iir::geglu_pair<E>(a, fq, col);
-                    *(f16x2*)(rowp + ((wn * WN + j * 16) / 2 + col) * 2) = o2;
+                    *(f16x2*)(rowp + ((wn * WN + j * 16) / 2 + pair_col) * 2) = iir::geglu_pair<E>(a);
                 }
             }
         }
+    };
+#pragma unroll
+    for (int c = 0; c < MI / 2; ++c) {
+        char* ct = smem + (c & 1) * STAGE_STRIDE;
+        if constexpr (GEGLU) phase1(c, ct, std::integral_constant<int, IIR_ACT_NONE>{});
+        else switch (g.act) {
+            case IIR_ACT_SILU: phase1(c, ct, std::integral_constant<int, IIR_ACT_SILU>{}); break;
+            case IIR_ACT_GELU: phase1(c, ct, std::integral_constant<int, IIR_ACT_GELU>{}); break;
+            case IIR_ACT_QUICKGELU: phase1(c, ct, std::integral_constant<int, IIR_ACT_QUICKGELU>{}); break;
+            default: phase1(c, ct, std::integral_constant<int, IIR_ACT_NONE>{}); break;
+        }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // chunk c staged (and chunk c-1's LDS reads long done)
-        if (g.Ct && n0 >= g.tr_from) {
+        if (!GEGLU && g.Ct && n0 >= g.tr_from) {
             // transposed write-out (the V third of a fused q|k|v projection -> the V^T image the attention kernel reads): a lane
             // gathers 8 consecutive tile rows of one column from the staged chunk and stores them as 16 contiguous bytes of Ct
             // (8 staged rows 8g .. 8g+7 are consecutive tile rows: they lie inside one 32-row run of a wave row)
@@ -230,16 +242,21 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const Geo g) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the LDS-DMA touches must land before the LDS is released
 }
 
-template <int BN, bool F8 = false>
-int launch8(const Geo& g0, hipStream_t stream) {
+template <int BN, bool F8, bool GEGLU>
+int launch8_form(const Geo& g, hipStream_t stream) {
     constexpr int BM = 256;
-    Geo g = g0;
-    iir::xcd_partition(g, BM, BN, HUGE_VAL);      // whole tiles (gemm8_covers); the split whose per-XCD operand panels are smallest
     const size_t lds = 2 * (BM * 128 + BN * 128) + 2048 + BM * 8;
     static unsigned long long lds_set = 0;
-    if (!iir_ensure_dynamic_lds((const void*)gemm8_kernel<BN, F8>, lds, lds_set)) return IIR_ELAUNCH;
-    iir_launch(gemm8_kernel<BN, F8>, dim3(8 * g.rm * g.rn), dim3(512), lds, stream, g);
+    if (!iir_ensure_dynamic_lds((const void*)gemm8_kernel<BN, F8, GEGLU>, lds, lds_set)) return IIR_ELAUNCH;
+    iir_launch(gemm8_kernel<BN, F8, GEGLU>, dim3(8 * g.rm * g.rn), dim3(512), lds, stream, g);
     return iir_launch_status();
+}
+
+template <int BN, bool F8 = false>
+int launch8(const Geo& g0, hipStream_t stream) {
+    Geo g = g0;
+    iir::xcd_partition(g, 256, BN, HUGE_VAL);     // whole tiles (gemm8_covers); the split whose per-XCD operand panels are smallest
+    return g.epi == IIR_EPI_GEGLU ? launch8_form<BN, F8, true>(g, stream) : launch8_form<BN, F8, false>(g, stream);
 }
 
 }  // namespace

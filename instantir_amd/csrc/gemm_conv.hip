@@ -1001,8 +1001,21 @@ Resolved resolve_tile(int M, int N, int K, bool conv, int dtype, bool wscale, bo
     return {tile + 10 * stages, bm, bn, stages, tile == 6 ? 512 : 256, false};     // (6: the 8-wave build)
 }
 
-bool gemm8_auto(const Geo& g, bool conv) {
-    return !conv && (g.f8 ? 2 * g.K : g.K) >= 640 && (long)(g.M / 256) * (g.N / 320) >= 256 && iir::gemm8_covers(g, 320);
+// Which build of the 8-wave kernel a tile = 0 launch goes to: 320 / 256 (its BN), or 0 = none (the 4-wave kernel).
+//   320: the large-N linears whose 256 x 320 tiles fill the chip (the GEGLU projections);
+//   256: a long-K fused q|k|v projection (transposed V range) of exactly one round of 256 x 256 tiles on at least 15/16 of the
+//        CUs (240-256 tiles; the Aggregator's level-2 projection 4096 x 3840 x 1280, which the 4-wave kernel runs as 960
+//        128 x 128 tiles, two per CU and twice the 128-byte line requests per FLOP).  Only that form was measured, so a plain
+//        linear layer of the same shape keeps the 4-wave tile.
+int gemm8_auto(const Geo& g, bool conv) {
+    if (conv) return 0;
+    const int K = g.f8 ? 2 * g.K : g.K;
+    if (K >= 640 && (long)(g.M / 256) * (g.N / 320) >= 256 && iir::gemm8_covers(g, 320)) return 320;
+    if (g.Ct && K >= 1280 && g.N % 256 == 0 && iir::gemm8_covers(g, 256)) {
+        const long tiles = (long)(g.M / 256) * (g.N / 256);
+        if (tiles >= 240 && tiles <= 256) return 256;
+    }
+    return 0;
 }
 
 int dispatch(const Geo& g, bool conv, int tile, hipStream_t stream) {
@@ -1010,7 +1023,10 @@ int dispatch(const Geo& g, bool conv, int tile, hipStream_t stream) {
     // tile: 0 = auto; t in {1: 128x128, 2: 128x64, 3: 64x64, 4: 128x160, 5: 64x160, 6: 256x128}; t + 10*stages selects the ring depth.
     // large-N linears whose 256 x 320 tiles fill the chip (the GEGLU projections): the 8-wave two-tile-deep kernel of
     // gemm8.hip (142 FLOP per staged byte against 71 for two 128x160 workgroups per CU).
-    if (tile == 0 && gemm8_auto(g, conv)) return iir::gemm8_launch(g, 320, stream);
+    if (tile == 0) {
+        const int bn8 = gemm8_auto(g, conv);
+        if (bn8) return iir::gemm8_launch(g, bn8, stream);
+    }
     if (tile == 91 || tile == 92) return conv ? IIR_EINVAL : iir::gemm8_launch(g, tile == 91 ? 320 : 256, stream);
     if (tile < 10) tile = resolve_tile(g.M, g.N, g.f8 ? 2 * g.K : g.K, conv, g.dtype, g.wscale != nullptr, g.f8 != 0, tile).id;     // (all-fp8: g.K counts 2-byte units)
     switch (tile) {
@@ -1085,7 +1101,7 @@ extern "C" int iir_gemm_f16(const iir_gemm_desc* d, void* stream) {
     return dispatch(g, false, d->tile, (hipStream_t)stream);
 }
 
-// Which kernel / tile `iir_gemm_f16(d)` resolves to, without launching: 91 = the 8-wave 256x320 kernel (gemm8.hip), 93 = the
+// Which kernel / tile `iir_gemm_f16(d)` resolves to, without launching: 91 / 92 = the 8-wave 256x320 / 256x256 kernel (gemm8.hip), 93 = the
 // cross-attention tile, otherwise the dispatch() case of the 4-wave kernel (base tile + 10 x stages, or a loader-wave build such as
 // 55 / 54; id % 10 is the base shape of `iir_gemm_tile_bn`), or d->tile when the caller forces one.  Used to NAME launches (bench.py roofline classes).
 extern "C" int iir_gemm_resolve_tile(const iir_gemm_desc* d) {
@@ -1093,7 +1109,8 @@ extern "C" int iir_gemm_resolve_tile(const iir_gemm_desc* d) {
     if (fill_gemm_geo(d, g) != IIR_OK) return -1;
     if (g.xa_on) return 93;
     if (d->tile != 0) return d->tile;
-    if (gemm8_auto(g, false)) return 91;
+    const int bn8 = gemm8_auto(g, false);
+    if (bn8) return bn8 == 320 ? 91 : 92;
     return resolve_tile(g.M, g.N, g.f8 ? 2 * g.K : g.K, false, g.dtype, g.wscale != nullptr, g.f8 != 0, 0).id;
 }
 

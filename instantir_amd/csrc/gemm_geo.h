@@ -138,25 +138,43 @@ __device__ __forceinline__ f32x4 mfma16_f8x2(V w, V a, f32x4 c) {
 // Phase 1 of the epilogue, per accumulator value x (already times the fp8 scales where there are any): the LayerNorm fold
 // rs = (rstd, -rstd * mean) -- (1, 0) without ln_in -- about the column sum of W, plus bias; then the activation.
 __device__ __forceinline__ float epi_affine(float x, float2 rs, float colsum, float bias) { return fmaf(x, rs.x, fmaf(rs.y, colsum, bias)); }
-__device__ __forceinline__ void epi_act(int act, float (&v)[4]) {
-    if (act == IIR_ACT_SILU) for (int t = 0; t < 4; ++t) v[t] = silu_f(v[t]);
-    else if (act == IIR_ACT_GELU) for (int t = 0; t < 4; ++t) v[t] = gelu_erf_f(v[t]);
-    else if (act == IIR_ACT_QUICKGELU) for (int t = 0; t < 4; ++t) v[t] = quick_gelu_f(v[t]);
+// The fp32 value as it stands, before the fp16 rounding of the store.  Without it hipcc fuses an fp32 multiply (or fma) and the
+// conversion behind it into one v_fma_mixlo_f16 -- a single rounding -- for whichever elements it pleases, build by build,
+// while the 4-wave kernel rounds twice (fp32, then fp16): one element in ~2^13 then differs by an fp16 ulp.
+__device__ __forceinline__ float rounded_f32(float x) {
+    asm("" : "+v"(x));
+    return x;
+}
+
+// (ACT is a compile-time value: the caller decides the activation once per chunk, outside its unrolled quad loops)
+template <int ACT>
+__device__ __forceinline__ void epi_act(float (&v)[4]) {
+    if constexpr (ACT == IIR_ACT_SILU) for (int t = 0; t < 4; ++t) v[t] = silu_f(v[t]);
+    else if constexpr (ACT == IIR_ACT_GELU) for (int t = 0; t < 4; ++t) v[t] = gelu_erf_f(v[t]);
+    else if constexpr (ACT == IIR_ACT_QUICKGELU) for (int t = 0; t < 4; ++t) v[t] = quick_gelu_f(v[t]);
+}
+
+// Cross-half swap (v_permlane32_swap, VALU, no LDS): lanes 0-31 keep `lo` and receive their partner's (lane + 32) `lo` as the
+// second value; lanes 32-63 receive their partner's (lane - 32) `hi` as the first value and keep `hi` as the second.
+__device__ __forceinline__ void xhalf_swap(float lo, float hi, float& first, float& second) {
+    const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(lo), __float_as_uint(hi), false, false);
+    first = __uint_as_float(s[0]);
+    second = __uint_as_float(s[1]);
 }
 
 // GEGLU pair step, value * gelu(gate).  A lane (frow, fq) holds 4 consecutive columns `a`; value lanes (fq = 0,1) and their gate
-// lanes (fq + 2) sit 32 lanes apart: one cross-half exchange per register, in which every lane must take part.  The value lane
-// finishes columns 0,1 of the quad, its gate lane columns 2,3; `col` is their first column inside the group's 8 output columns.
+// lanes (fq + 2) sit 32 lanes apart.  The value lane finishes columns 0,1 of the quad (its a[0], a[1] times the gelu of the gate
+// lane's a[0], a[1]), its gate lane columns 2,3 (the value lane's a[2], a[3] times the gelu of its own a[2], a[3]): one swap of
+// (a[0], a[2]) and one of (a[1], a[3]) hand every lane exactly its (value, gate) pairs.  `geglu_col` is the first of the lane's
+// two columns inside the group's 8 output columns.
+__device__ __forceinline__ int geglu_col(int fq) { return (fq & 1) * 4 + (fq >= 2 ? 2 : 0); }
 template <typename E>
-__device__ __forceinline__ auto geglu_pair(const float (&a)[4], int fq, int& col) {
+__device__ __forceinline__ auto geglu_pair(const float (&a)[4]) {
     typedef E E2 __attribute__((ext_vector_type(2)));
-    float b[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) b[t] = __shfl_xor(a[t], 32, 64);
-    const bool gate = fq >= 2;
-    col = (fq & 1) * 4 + (gate ? 2 : 0);
-    const float v0 = gate ? b[2] : a[0], v1 = gate ? b[3] : a[1], g0 = gate ? a[2] : b[0], g1 = gate ? a[3] : b[1];
-    return (E2){(E)(v0 * gelu_erf_f(g0)), (E)(v1 * gelu_erf_f(g1))};
+    float v0, g0, v1, g1;
+    xhalf_swap(a[0], a[2], v0, g0);
+    xhalf_swap(a[1], a[3], v1, g1);
+    return (E2){(E)rounded_f32(v0 * gelu_erf_f(g0)), (E)rounded_f32(v1 * gelu_erf_f(g1))};
 }
 
 // Weight prefetch for the launches that follow (see iir_gemm_desc.prefetch): 4-byte LDS-DMA touches of this workgroup's share

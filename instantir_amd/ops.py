@@ -345,8 +345,8 @@ def gemm(a, w, out, bias=None, rowbias=None, rows_per_rb=1, res=None, epi=EPI_PL
     No = N // 2 if epi not in (EPI_PLAIN, EPI_XATTN) else N
     if xattn is not None:
         cls = "gemm_kernel<64x128,gemm+xattn>"
-    elif PROFILER is not None and d.tile == 0 and L.load().iir_gemm_resolve_tile(C.byref(d)) == 91:
-        cls = "gemm8_kernel<256x320,gemm>"             # the 8-wave kernel of csrc/gemm8.hip
+    elif PROFILER is not None and d.tile == 0 and L.load().iir_gemm_resolve_tile(C.byref(d)) in (91, 92):
+        cls = "gemm8_kernel<256x%d,gemm>" % (320 if L.load().iir_gemm_resolve_tile(C.byref(d)) == 91 else 256)      # the 8-wave kernel of csrc/gemm8.hip
     else:
         cls = "gemm_kernel<%s,%s>" % (_TILE_NAMES[tile % 10], "gemm" if wscale is None else "gemm-w8")
     xa_flops = 4.0 * M * N * sum(k[4] for k in xattn[0]) if xattn is not None else 0.0

@@ -18,6 +18,15 @@ def timeit(fn, iters=30, warm=5):
     return e0.elapsed_time(e1) / iters * 1e3
 
 
+def _sha(*ts):
+    """fingerprint of the output bytes: two builds of the library are compared by running this script with each"""
+    import hashlib
+    h = hashlib.sha1()
+    for t in ts:
+        h.update(t.cpu().contiguous().view(torch.uint8).numpy().tobytes())
+    return h.hexdigest()[:12]
+
+
 def case(M, N, K, geglu, fold, res, act=ops.ACT_NONE, tile_new=91, tile_old=24, time_it=True):
     g = torch.Generator(device="cpu").manual_seed(M + N + K)
     a = torch.randn(M, K, generator=g).half().to(dev)
@@ -48,7 +57,7 @@ def case(M, N, K, geglu, fold, res, act=ops.ACT_NONE, tile_new=91, tile_old=24, 
     same = torch.equal(o_new, o_old)
     md = (o_new.float() - o_old.float()).abs().max().item()
     ref = (a.float() @ w.float().t())
-    msg = f"M={M:5d} N={N:5d} K={K:4d} geglu={int(geglu)} fold={int(fold)} res={int(res)} act={act}: bit-equal={same} max|d|={md:.3g} finite={bool(torch.isfinite(o_new).all())}"
+    msg = f"M={M:5d} N={N:5d} K={K:4d} geglu={int(geglu)} fold={int(fold)} res={int(res)} act={act}: bit-equal={same} sha={_sha(o_new)} max|d|={md:.3g} finite={bool(torch.isfinite(o_new).all())}"
     if time_it:
         fl = 2 * M * N * K
         t_old = timeit(lambda: ops.gemm(a, w, o_old, bias=bias, tile=tile_old, **kw))
@@ -59,7 +68,7 @@ def case(M, N, K, geglu, fold, res, act=ops.ACT_NONE, tile_new=91, tile_old=24, 
     return same
 
 
-def case_qkv(M, C, fold=True, time_it=True):
+def case_qkv(M, C, fold=True, time_it=True, tile_new=91):
     """fused q|k|v projection: columns >= 2C leave the GEMM transposed (out_t)."""
     g = torch.Generator(device="cpu").manual_seed(M + C)
     N, K = 3 * C, C
@@ -76,17 +85,17 @@ def case_qkv(M, C, fold=True, time_it=True):
         a, w, b = h, f.w, f.bias
         kw["ln_in"] = (st, f.colsum, 1e-5)
     outs = []
-    for tile in (21, 91):
+    for tile in (21, tile_new):
         qk = torch.zeros(M, 2 * C, device=dev, dtype=torch.half); vt = torch.zeros(C, M, device=dev, dtype=torch.half)
         ops.gemm(a, w, qk, bias=b, tile=tile, out_t=(vt, 2 * C), **kw)
         outs.append((qk, vt))
     torch.cuda.synchronize()
     same = torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
-    msg = f"qkv M={M} C={C} fold={int(fold)}: bit-equal={same}"
+    msg = f"qkv M={M} C={C} fold={int(fold)}: bit-equal={same} sha={_sha(outs[1][0], outs[1][1])}"
     if time_it:
         qk, vt = outs[0]
-        ts = [timeit(lambda: ops.gemm(a, w, qk, bias=b, tile=t_, out_t=(vt, 2 * C), **kw)) for t_ in (21, 0, 91)]
-        msg += f" | t21 {ts[0]:6.1f} us  auto {ts[1]:6.1f} us  t91 {ts[2]:6.1f} us ({2 * M * N * K / ts[2] / 1e6:5.0f} TF)"
+        ts = [timeit(lambda: ops.gemm(a, w, qk, bias=b, tile=t_, out_t=(vt, 2 * C), **kw)) for t_ in (21, 0, tile_new)]
+        msg += f" | t21 {ts[0]:6.1f} us  auto {ts[1]:6.1f} us  t{tile_new} {ts[2]:6.1f} us ({2 * M * N * K / ts[2] / 1e6:5.0f} TF)"
     print(msg, flush=True)
     return same
 
@@ -98,6 +107,13 @@ if __name__ == "__main__":
         ok &= case_qkv(8192, 640)
         ok &= case_qkv(16384, 640)
         ok &= case_qkv(2048, 1280)
+        print("ALL BIT-EQUAL" if ok else "MISMATCH")
+        sys.exit(0)
+    if "ab" in sys.argv:      # the launches an epilogue / chooser change moves; run once per library build, compare us and sha
+        for M, N, K in ((2048, 10240, 1280), (4096, 10240, 1280), (8192, 5120, 640), (16384, 5120, 640)):
+            ok &= case(M, N, K, True, True, False)
+        ok &= case(2048, 10240, 1280, False, False, False)             # plain epilogue: the floor
+        ok &= case_qkv(4096, 1280, tile_new=92)
         print("ALL BIT-EQUAL" if ok else "MISMATCH")
         sys.exit(0)
     if "quick" in sys.argv:

@@ -162,6 +162,9 @@ for (M8, N8, K8, geglu8) in [(2048, 10240, 1280, True), (4096, 10240, 1280, True
         w8, b8 = pair_rows(w8[:N8 // 2], w8[N8 // 2:]), pair_rows(b8[:N8 // 2], b8[N8 // 2:])
     screen(f"gemm8 (256x320, 8 waves) {M8}x{N8}x{K8} {'GEGLU' if geglu8 else 'plain'}",
            lambda o: ops.gemm(x8, w8, o, bias=b8, tile=91, epi=ops.EPI_GEGLU if geglu8 else ops.EPI_PLAIN), [(M8, N8 // 2 if geglu8 else N8)])
+# the Aggregator's level-2 fused q|k|v projection, which the chooser sends to the 256 x 256 build (tile = 0; V transposed)
+xq8, wq8, bq8 = rnd(4096, 1280), rnd(3840, 1280, scale=1280 ** -0.5), rnd(3840)
+screen("gemm8 (256x256, 8 waves) q|k|v 4096x3840x1280 (V transposed)", lambda qk, vt: ops.gemm(xq8, wq8, qk, bias=bq8, out_t=(vt, 2560)), [(4096, 2560), (1280, 4096)])
 # to_q + cross-attention in one launch (IIR_EPI_XATTN), level-2 and level-1 geometry
 for (Rx, Tx, hx) in [(2, 1024, 20), (2, 4096, 10)]:
     Cx = hx * 64
