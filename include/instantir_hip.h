@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define IIR_ABI_VERSION 2
+#define IIR_ABI_VERSION 3
 
 /* epilogue selectors */
 #define IIR_EPI_PLAIN 0 /* C = act(acc + bias + rowbias) + res                                    */
@@ -283,44 +283,39 @@ int iir_unpack_latent_t(const void* in, int64_t ldi, int32_t R, int32_t C, int32
 int iir_pack_latent_dscale(const float* x, int32_t B, int32_t C, int32_t HW, void* out, int64_t ldo, int32_t rep, const float* scale,
                            int32_t dtype, void* stream);
 
-/* CFG + main scheduler step (pipelines/sdxl_instantir.py:1619-1633).  coef = device fp32[8]:
- * {guidance, sqrt(1-abar_t), sqrt(abar_t), k_x0, k_x, k_eps, k_noise, 0}; prev = k_x0*x0 + k_x*x + k_eps*eps
- * + k_noise*noise with x0 = (x - sqrt(1-abar_t)*eps)/sqrt(abar_t).  DDPM: k_eps = 0; DDIM: k_x = 0. */
-int iir_sched_step(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg, const float* coef,
-                   const float* x, const float* noise, float* prev, float* x0_out, float* eps_out,
-                   const float* eps_factor, void* stream);
-/* rescale_noise_cfg, pipelines/sdxl_instantir.py:181-192 (used at :1623-1626 when guidance_rescale > 0): per image
- * factor[b] = phi * std(eps_text) / std(eps_cfg) + (1 - phi) over (C,H,W); iir_sched_step multiplies the guided
- * eps of image b by eps_factor[b] (NULL = 1).  coef[0] = guidance scale, as for iir_sched_step. */
-/* iir_sched_step plus one history term, for the Euler / Euler-ancestral / DPM++ 2M schedulers, each in its own sample
- * space: coef = device fp32[8] {guidance, sb, sa, k_x0, k_x, k_eps, k_noise, k_h};
+/* CFG + main scheduler step (pipelines/sdxl_instantir.py:1619-1633): one descriptor, one launch.  `groups` states which
+ * optional groups the caller means (IIR_STEP_* bits); a set bit with a NULL pointer of its group, a non-NULL pointer of a group
+ * whose bit is clear, and a bit outside the four are IIR_EINVAL, so a forgotten pointer never runs another formula silently.
+ * noise, x0_out, eps_out and eps_factor are plain optional planes (NULL = absent).
+ *
+ * The step.  coef = device fp32[8] {guidance, sb, sa, k_x0, k_x, k_eps, k_noise, k_h}, read at launch time:
+ *   eps  = cfg ? u + g*(c - u) : c        (u = rows [0, B), c = rows [B, 2B) of eps_nhwc, fp16 NHWC rows of width lde >= C)
+ *   x0   = (x - sb*eps)/sa                prev = k_x0*x0 + k_x*x + k_eps*eps + k_noise*noise
+ * with sb = sqrt(1-abar_t), sa = sqrt(abar_t) for DDPM (k_eps = 0) and DDIM (k_x = 0).  x, noise, prev, x0_out, eps_out: fp32 NCHW
+ * (B, C, H, W), HW = H*W.  eps_out receives the guided eps.
+ *
+ * eps_factor / iir_cfg_rescale_factor.  rescale_noise_cfg, pipelines/sdxl_instantir.py:181-192 (used at :1623-1626 when
+ * guidance_rescale > 0): per image factor[b] = phi * std(eps_text) / std(eps_cfg) + (1 - phi) over (C,H,W); iir_sched_step
+ * multiplies the guided eps of image b by eps_factor[b] (NULL = 1; it needs cfg).  coef[0] = guidance scale, as for the step.
+ * iir_cfg_rescale_factor reads eps_nhwc, lde, B, C, HW, coef and, under IIR_STEP_PAG, pag_scale -- nothing else of the
+ * descriptor, so the descriptor of the step that follows serves both calls.
+ *
+ * IIR_STEP_PAG (pag_scale).  Perturbed-attention guidance (PAG, Ahn et al. 2024).  The UNet output holds one more group of B
+ * rows, the perturbed prediction p: rows [2B, 3B) with cfg, [B, 2B) without.  The guided eps is u + g*(c - u) + s*(c - p) (cfg)
+ * or c + s*(c - p), s = *pag_scale (device fp32[1], the step's s_t), formed before the rescale factor is applied
+ * (iir_cfg_rescale_factor: the same sum inside eps_cfg).  s == 0 skips the term: the outputs are then bit-identical to the
+ * launches without the bit.
+ *
+ * IIR_STEP_HIST (hist).  One history term, for the Euler / Euler-ancestral / DPM++ 2M schedulers, each in its own sample space:
  * prev = k_x0*x0 + k_x*x + k_eps*eps + k_h*m_prev + k_noise*noise with x0 = (x - sb*eps)/sa
  * (Euler: sb = sigma_i, sa = 1; DPM++: sb = sigma_i/sqrt(sigma_i^2+1), sa = 1/sqrt(sigma_i^2+1)).
  * `hist` = fp32 NCHW (B, C, H, W), updated in place: each element reads m_prev, then stores this step's x0, so one captured
  * launch serves every step.  It is never loaded when k_h == 0 (a solver's first step: the plane may hold garbage).
- * `hist` must not alias x, prev or x0_out. */
-int iir_sched_step_hist(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg, const float* coef,
-                        const float* x, const float* noise, float* hist, float* prev, float* x0_out, const float* eps_factor,
-                        void* stream);
-int iir_cfg_rescale_factor(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, const float* coef,
-                           float guidance_rescale, float* factor, void* stream);
-/* Perturbed-attention guidance (PAG, Ahn et al. 2024) forms of the three launches above.  The UNet output holds one more
- * group of B rows, the perturbed prediction p: rows [2B, 3B) with cfg, [B, 2B) without.  The guided eps is
- * u + g*(c - u) + s*(c - p) (cfg) or c + s*(c - p), s = *pag_scale (device fp32[1], the step's s_t), formed before the
- * rescale factor is applied (iir_cfg_rescale_factor_pag: the same sum inside eps_cfg).  s == 0 skips the term: the
- * outputs are then bit-identical to the plain launches. */
-int iir_sched_step_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg, const float* coef,
-                       const float* pag_scale, const float* x, const float* noise, float* prev, float* x0_out, float* eps_out,
-                       const float* eps_factor, void* stream);
-int iir_sched_step_hist_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg, const float* coef,
-                            const float* pag_scale, const float* x, const float* noise, float* hist, float* prev, float* x0_out,
-                            const float* eps_factor, void* stream);
-int iir_cfg_rescale_factor_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, const float* coef,
-                               const float* pag_scale, float guidance_rescale, float* factor, void* stream);
-/* Region-selective restoration (a per-pixel restore map; no reference counterpart -- it extends the CFG + scheduler step of
- * pipelines/sdxl_instantir.py:1619-1633, and "kept" means the trajectory of the LQ latent that :1388-1403 noises to the first
- * timestep).  iir_sched_step_keep is iir_sched_step with every optional plane of the family (pag_scale, noise, hist, x0_out,
- * eps_out, eps_factor: NULL = absent, meaning as in the entries above) plus the keep group, all four required:
+ * `hist` must not alias x, prev or x0_out, and does not combine with eps_out.  Without the bit coef[7] is ignored.
+ *
+ * IIR_STEP_KEEP (keep_map, keep_src, keep_noise, keep_coef).  Region-selective restoration (a per-pixel restore map; no
+ * reference counterpart -- it extends the CFG + scheduler step of pipelines/sdxl_instantir.py:1619-1633, and "kept" means the
+ * trajectory of the LQ latent that :1388-1403 noises to the first timestep):
  *   keep_map   fp32 (B, HW): the map at latent resolution, values in [0, 1] (1 = denoised freely in every step)
  *   keep_src   fp32 NCHW (B, C, H, W): the LQ latent;  keep_noise: fp32 NCHW, the noise that seeded the start of the loop
  *   keep_coef  device fp32[4] {thr, a, b, 0}, read at launch time so that one captured launch serves every step
@@ -330,13 +325,38 @@ int iir_cfg_rescale_factor_pag(const void* eps_nhwc, int64_t lde, int32_t B, int
  * thr = (N - 1 - i) / N and (a, b) = the add_noise pair of the timetable entry that follows the step ((1, 0) after the last).
  * It is a SELECT on an fp32 compare, never an arithmetic blend: a free element has the bits of the launch without a map, a
  * kept element those of add_noise, and NaN / Inf in a kept pixel's eps never reach prev.  x0_out, hist and eps_out are
- * written exactly as without a map (a multistep solver's history stays the model's own x0).
- * IIR_EINVAL: a NULL keep_* pointer, eps_out together with hist, keep_src or keep_noise aliasing prev, and whatever
- * iir_sched_step refuses. */
-int iir_sched_step_keep(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg, const float* coef,
-                        const float* pag_scale, const float* x, const float* noise, float* hist, float* prev, float* x0_out,
-                        float* eps_out, const float* eps_factor, const float* keep_map, const float* keep_src,
-                        const float* keep_noise, const float* keep_coef, void* stream);
+ * written exactly as without a map (a multistep solver's history stays the model's own x0).  keep_src and keep_noise may
+ * not alias prev.
+ *
+ * IIR_STEP_APG (apg_avg, apg_sa, apg_par).  The guided eps is the projected form described at iir_apg_project below, with A and
+ * {s, alpha} as iir_apg_project left them and eta = apg_par[0]; it needs cfg.  The uncond rows are not read.  The PAG term
+ * + s_t*(c - p), eps_factor, the scheduler update, the history term, the noise, x0_out and the restore-map select are as without
+ * APG.  With eta = 1, r = 0, beta_t = 0 the eps equals u + w*(c - u) algebraically, not bitwise.  apg_avg may not alias prev,
+ * x0_out, eps_out or hist.
+ *
+ * IIR_EINVAL, before any HIP call: a NULL d, eps_nhwc, coef, x or prev; B, C or HW <= 0; lde < C; eps_factor without cfg; hist
+ * equal to x, prev or x0_out; eps_out together with hist; a group bit and its pointers disagreeing, or an unknown bit; keep_src
+ * or keep_noise equal to prev; under IIR_STEP_APG cfg == 0 or apg_avg equal to prev, x0_out, eps_out or hist.
+ * iir_cfg_rescale_factor: a NULL d, factor, eps_nhwc or coef; B, C or HW <= 0; lde < C; C*HW < 2; IIR_STEP_PAG with a NULL
+ * pag_scale. */
+#define IIR_STEP_PAG  1u   /* pag_scale: one more group of B perturbed rows in eps_nhwc */
+#define IIR_STEP_HIST 2u   /* hist: the k_h * m_prev term; the plane is rewritten with x0 */
+#define IIR_STEP_KEEP 4u   /* keep_map, keep_src, keep_noise, keep_coef: restore-map select */
+#define IIR_STEP_APG  8u   /* apg_avg, apg_sa, apg_par: projected guidance replaces the CFG sum */
+
+typedef struct iir_sched_desc {
+    const void* eps_nhwc; int64_t lde;
+    int32_t B, C, HW, cfg;
+    const float* coef;
+    uint32_t groups;
+    const float *x, *noise;  float *prev, *x0_out, *eps_out;  const float* eps_factor;
+    const float* pag_scale;  float* hist;
+    const float *keep_map, *keep_src, *keep_noise, *keep_coef;
+    const float *apg_avg, *apg_sa, *apg_par;
+} iir_sched_desc;
+
+int iir_sched_step(const iir_sched_desc* d, void* stream);
+int iir_cfg_rescale_factor(const iir_sched_desc* d, float guidance_rescale, float* factor, void* stream);
 /* Adaptive projected guidance (APG; Sadat et al., "Eliminating Oversaturation and Artifacts of High Guidance Scales in
  * Diffusion Models"; no reference counterpart -- it replaces the CFG sum of pipelines/sdxl_instantir.py:1619-1621).  Applied to
  * denoised predictions.  Per image b, sums over (C, H, W); u / c = the uncond / cond rows of the UNet output, x the unscaled fp32
@@ -361,17 +381,6 @@ int iir_sched_step_keep(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C,
 int64_t iir_apg_project_workspace_bytes(int32_t B);
 int iir_apg_project(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, const float* coef, const float* x,
                     const float* apg_par, float* apg_avg, float* apg_sa, void* workspace, int64_t workspace_bytes, void* stream);
-/* iir_sched_step with every optional plane of the family (as iir_sched_step_keep; here the keep group is optional too: all four
- * pointers or none) plus the APG group, all three required: the guided eps is the expression above, with A and {s, alpha} as
- * iir_apg_project left them and eta = apg_par[0].  The uncond rows are not read.  The PAG term + s_t*(c - p), eps_factor, the
- * scheduler update, the history term, the noise, x0_out and the restore-map select are as without APG.  With eta = 1, r = 0,
- * beta_t = 0 the eps equals u + w*(c - u) algebraically, not bitwise.
- * IIR_EINVAL: a NULL apg_* pointer, cfg == 0, apg_avg aliasing an output plane, and whatever iir_sched_step_keep refuses. */
-int iir_sched_step_apg(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg, const float* coef,
-                       const float* pag_scale, const float* x, const float* noise, float* hist, float* prev, float* x0_out,
-                       float* eps_out, const float* eps_factor, const float* keep_map, const float* keep_src,
-                       const float* keep_noise, const float* keep_coef, const float* apg_avg, const float* apg_sa,
-                       const float* apg_par, void* stream);
 /* The restore map at latent resolution: out (B, H / factor, W / factor) = the maximum of map_px (B, H, W) over each
  * factor x factor block (a latent pixel is free if any pixel under it asked for freedom).  fp32; H and W multiples of
  * factor, H, W <= 32768; `out` must not be `map_px`.  IIR_EINVAL for any other geometry, before any launch. */
@@ -403,7 +412,7 @@ int iir_lcm_step(const void* eps_nhwc, int64_t lde, int32_t B, int32_t rep, int3
 int iir_sched_step_f32(const float* eps, const float* x, const float* noise, const float* coef, int64_t n, float* prev,
                        float* x0_out, void* stream);
 int iir_axpby_f32(const float* x, const float* y, const float* coef, int64_t n, float* out, void* stream);
-/* iir_sched_step_f32 with the history term of iir_sched_step_hist (coef[7] = k_h, `hist` fp32[n] read iff k_h != 0,
+/* iir_sched_step_f32 with the history term of IIR_STEP_HIST (coef[7] = k_h, `hist` fp32[n] read iff k_h != 0,
  * then overwritten with x0): the sigma schedulers' `.step()`.  `hist` must not alias eps, x, prev or x0_out. */
 int iir_sched_step_hist_f32(const float* eps, const float* x, const float* noise, const float* coef, float* hist, int64_t n,
                             float* prev, float* x0_out, void* stream);

@@ -346,7 +346,7 @@ __global__ void copy_segments_kernel(const long long* jobs) {
 inline int nblk(long n, int t) { return (int)((n + t - 1) / t); }
 
 // One launcher per family: the validation the exported entries share is here, what an entry refuses on its own (a missing
-// pag_scale / hist / device scale) is in its forwarder below.
+// device scale) is in its forwarder below.
 template <typename... A>
 int launch_1d(void (*kern)(A...), long n, void* stream, A... args) {
     (void)hipGetLastError();
@@ -369,38 +369,46 @@ int launch_unpack(const void* in, long ldi, int R, int C, int HW, float* out, in
     return IIR_EINVAL;
 }
 
-int launch_cfg_rescale(const void* eps_nhwc, long lde, int B, int C, int HW, const float* coef, const float* pag_s, float phi,
-                       float* factor, void* stream) {
-    if (!eps_nhwc || !coef || !factor || B <= 0 || C <= 0 || HW <= 0 || lde < C || (long)C * HW < 2) return IIR_EINVAL;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(cfg_rescale_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, (const f16*)eps_nhwc, lde, B, C, HW, coef,
-                       pag_s, phi, factor);
-    return iir_launch_status();
-}
-
 // hist, when given, is read and rewritten per element: it may not be one of the other planes
 inline bool hist_aliases(const float* hist, const float* x, const float* prev, const float* x0_out) {
     return hist && (hist == x || hist == prev || hist == x0_out);
 }
 
-// the restore-map group of a step launch: all four pointers, or none of them
-struct keep_args {
-    const float *map = nullptr, *src = nullptr, *noise = nullptr, *coef = nullptr;
-};
+// pointers of an optional group against its bit in iir_sched_desc.groups: all given with the bit, none without it
+inline bool group_ok(bool on, std::initializer_list<const void*> ptrs) {
+    for (const void* q : ptrs)
+        if (on != (q != nullptr)) return false;
+    return true;
+}
 
-// the APG group of a step launch: the running-average plane, {s, alpha} per image and {eta, r, beta_t, 0}; all or none
-struct apg_args {
-    const float *avg = nullptr, *sa = nullptr, *par = nullptr;
-};
+int launch_cfg_rescale(const iir_sched_desc* d, float phi, float* factor, void* stream) {
+    if (!d || !d->eps_nhwc || !d->coef || !factor || d->B <= 0 || d->C <= 0 || d->HW <= 0 || d->lde < d->C || (long)d->C * d->HW < 2)
+        return IIR_EINVAL;
+    const float* pag_s = (d->groups & IIR_STEP_PAG) ? d->pag_scale : nullptr;
+    if ((d->groups & IIR_STEP_PAG) && !pag_s) return IIR_EINVAL;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(cfg_rescale_kernel, dim3(d->B), dim3(1024), 0, (hipStream_t)stream, (const f16*)d->eps_nhwc, (long)d->lde, d->B,
+                       d->C, d->HW, d->coef, pag_s, phi, factor);
+    return iir_launch_status();
+}
 
-int launch_sched_step(const void* eps_nhwc, long lde, int B, int C, int HW, int cfg, const float* coef, const float* pag_s,
-                      const float* x, const float* noise, float* hist, float* prev, float* x0_out, float* eps_out,
-                      const float* eps_factor, void* stream, keep_args keep = {}, apg_args apg = {}) {
-    if (!eps_nhwc || !coef || !x || !prev || B <= 0 || C <= 0 || HW <= 0 || lde < C) return IIR_EINVAL;
-    if (eps_factor && !cfg) return IIR_EINVAL;
-    if (hist_aliases(hist, x, prev, x0_out)) return IIR_EINVAL;
-    return launch_1d(sched_step_kernel, (long)B * HW, stream, (const f16*)eps_nhwc, lde, B, C, HW, cfg, coef, pag_s, x, noise, hist,
-                     prev, x0_out, eps_out, eps_factor, keep.map, keep.src, keep.noise, keep.coef, apg.avg, apg.sa, apg.par);
+// Every refusal of the step, then the one place where the descriptor is spread into the kernel's arguments.
+int launch_sched_step(const iir_sched_desc& d, void* stream) {
+    if (!d.eps_nhwc || !d.coef || !d.x || !d.prev || d.B <= 0 || d.C <= 0 || d.HW <= 0 || d.lde < d.C) return IIR_EINVAL;
+    if (d.eps_factor && !d.cfg) return IIR_EINVAL;
+    const uint32_t g = d.groups;
+    if (g & ~(IIR_STEP_PAG | IIR_STEP_HIST | IIR_STEP_KEEP | IIR_STEP_APG)) return IIR_EINVAL;
+    if (!group_ok(g & IIR_STEP_PAG, {d.pag_scale}) || !group_ok(g & IIR_STEP_HIST, {d.hist}) ||
+        !group_ok(g & IIR_STEP_KEEP, {d.keep_map, d.keep_src, d.keep_noise, d.keep_coef}) ||
+        !group_ok(g & IIR_STEP_APG, {d.apg_avg, d.apg_sa, d.apg_par}))
+        return IIR_EINVAL;
+    if (hist_aliases(d.hist, d.x, d.prev, d.x0_out) || (d.hist && d.eps_out)) return IIR_EINVAL;
+    if (d.keep_map && (d.keep_src == d.prev || d.keep_noise == d.prev)) return IIR_EINVAL;
+    if (d.apg_avg && (!d.cfg || d.apg_avg == d.prev || d.apg_avg == d.x0_out || d.apg_avg == d.eps_out || d.apg_avg == d.hist))
+        return IIR_EINVAL;
+    return launch_1d(sched_step_kernel, (long)d.B * d.HW, stream, (const f16*)d.eps_nhwc, (long)d.lde, (int)d.B, (int)d.C, (int)d.HW,
+                     (int)d.cfg, d.coef, d.pag_scale, d.x, d.noise, d.hist, d.prev, d.x0_out, d.eps_out, d.eps_factor, d.keep_map,
+                     d.keep_src, d.keep_noise, d.keep_coef, d.apg_avg, d.apg_sa, d.apg_par);
 }
 
 int launch_apg_project(const void* eps_nhwc, long lde, int B, int C, int HW, const float* coef, const float* x, const float* par,
@@ -471,59 +479,12 @@ extern "C" int iir_unpack_latent(const void* in, int64_t ldi, int32_t R, int32_t
     return launch_unpack(in, (long)ldi, R, C, HW, out, IIR_DT_F16, stream);
 }
 
-extern "C" int iir_cfg_rescale_factor(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, const float* coef,
-                                      float guidance_rescale, float* factor, void* stream) {
-    return launch_cfg_rescale(eps_nhwc, (long)lde, B, C, HW, coef, nullptr, guidance_rescale, factor, stream);
+extern "C" int iir_cfg_rescale_factor(const iir_sched_desc* d, float guidance_rescale, float* factor, void* stream) {
+    return launch_cfg_rescale(d, guidance_rescale, factor, stream);
 }
 
-extern "C" int iir_cfg_rescale_factor_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, const float* coef,
-                                          const float* pag_scale, float guidance_rescale, float* factor, void* stream) {
-    if (!pag_scale) return IIR_EINVAL;
-    return launch_cfg_rescale(eps_nhwc, (long)lde, B, C, HW, coef, pag_scale, guidance_rescale, factor, stream);
-}
-
-extern "C" int iir_sched_step(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
-                              const float* coef, const float* x, const float* noise, float* prev, float* x0_out,
-                              float* eps_out, const float* eps_factor, void* stream) {
-    return launch_sched_step(eps_nhwc, (long)lde, B, C, HW, cfg, coef, nullptr, x, noise, nullptr, prev, x0_out, eps_out, eps_factor,
-                             stream);
-}
-
-extern "C" int iir_sched_step_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
-                                  const float* coef, const float* pag_scale, const float* x, const float* noise, float* prev,
-                                  float* x0_out, float* eps_out, const float* eps_factor, void* stream) {
-    if (!pag_scale) return IIR_EINVAL;
-    return launch_sched_step(eps_nhwc, (long)lde, B, C, HW, cfg, coef, pag_scale, x, noise, nullptr, prev, x0_out, eps_out,
-                             eps_factor, stream);
-}
-
-extern "C" int iir_sched_step_hist(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
-                                   const float* coef, const float* x, const float* noise, float* hist, float* prev, float* x0_out,
-                                   const float* eps_factor, void* stream) {
-    if (!hist) return IIR_EINVAL;
-    return launch_sched_step(eps_nhwc, (long)lde, B, C, HW, cfg, coef, nullptr, x, noise, hist, prev, x0_out, nullptr, eps_factor,
-                             stream);
-}
-
-extern "C" int iir_sched_step_hist_pag(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
-                                       const float* coef, const float* pag_scale, const float* x, const float* noise, float* hist,
-                                       float* prev, float* x0_out, const float* eps_factor, void* stream) {
-    if (!pag_scale || !hist) return IIR_EINVAL;
-    return launch_sched_step(eps_nhwc, (long)lde, B, C, HW, cfg, coef, pag_scale, x, noise, hist, prev, x0_out, nullptr, eps_factor,
-                             stream);
-}
-
-extern "C" int iir_sched_step_keep(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
-                                   const float* coef, const float* pag_scale, const float* x, const float* noise, float* hist,
-                                   float* prev, float* x0_out, float* eps_out, const float* eps_factor, const float* keep_map,
-                                   const float* keep_src, const float* keep_noise, const float* keep_coef, void* stream) {
-    if (!keep_map || !keep_src || !keep_noise || !keep_coef) return IIR_EINVAL;
-    if (eps_out && hist) return IIR_EINVAL;
-    if (keep_src == prev || keep_noise == prev) return IIR_EINVAL;
-    keep_args keep;
-    keep.map = keep_map; keep.src = keep_src; keep.noise = keep_noise; keep.coef = keep_coef;
-    return launch_sched_step(eps_nhwc, (long)lde, B, C, HW, cfg, coef, pag_scale, x, noise, hist, prev, x0_out, eps_out, eps_factor,
-                             stream, keep);
+extern "C" int iir_sched_step(const iir_sched_desc* d, void* stream) {
+    return d ? launch_sched_step(*d, stream) : IIR_EINVAL;
 }
 
 extern "C" int64_t iir_apg_project_workspace_bytes(int32_t B) {
@@ -534,26 +495,6 @@ extern "C" int iir_apg_project(const void* eps_nhwc, int64_t lde, int32_t B, int
                                const float* apg_par, float* apg_avg, float* apg_sa, void* workspace, int64_t workspace_bytes,
                                void* stream) {
     return launch_apg_project(eps_nhwc, (long)lde, B, C, HW, coef, x, apg_par, apg_avg, apg_sa, workspace, (long)workspace_bytes, stream);
-}
-
-extern "C" int iir_sched_step_apg(const void* eps_nhwc, int64_t lde, int32_t B, int32_t C, int32_t HW, int32_t cfg,
-                                  const float* coef, const float* pag_scale, const float* x, const float* noise, float* hist,
-                                  float* prev, float* x0_out, float* eps_out, const float* eps_factor, const float* keep_map,
-                                  const float* keep_src, const float* keep_noise, const float* keep_coef, const float* apg_avg,
-                                  const float* apg_sa, const float* apg_par, void* stream) {
-    if (!apg_avg || !apg_sa || !apg_par || !cfg) return IIR_EINVAL;
-    if (eps_out && hist) return IIR_EINVAL;
-    if (apg_avg == prev || apg_avg == x0_out || apg_avg == eps_out || apg_avg == hist) return IIR_EINVAL;
-    keep_args keep;
-    if (keep_map || keep_src || keep_noise || keep_coef) {
-        if (!keep_map || !keep_src || !keep_noise || !keep_coef) return IIR_EINVAL;
-        if (keep_src == prev || keep_noise == prev) return IIR_EINVAL;
-        keep.map = keep_map; keep.src = keep_src; keep.noise = keep_noise; keep.coef = keep_coef;
-    }
-    apg_args apg;
-    apg.avg = apg_avg; apg.sa = apg_sa; apg.par = apg_par;
-    return launch_sched_step(eps_nhwc, (long)lde, B, C, HW, cfg, coef, pag_scale, x, noise, hist, prev, x0_out, eps_out, eps_factor,
-                             stream, keep, apg);
 }
 
 extern "C" int iir_copy_segments(const void* jobs, int32_t njobs, int64_t max_units, void* stream) {

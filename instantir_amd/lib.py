@@ -91,6 +91,23 @@ class AttnDesc(C.Structure):
     ]
 
 
+STEP_PAG, STEP_HIST, STEP_KEEP, STEP_APG = 1, 2, 4, 8      # IIR_STEP_*: the optional groups of a SchedDesc
+
+
+class SchedDesc(C.Structure):
+    _fields_ = [
+        ("eps_nhwc", C.c_void_p), ("lde", C.c_int64),
+        ("B", C.c_int32), ("C", C.c_int32), ("HW", C.c_int32), ("cfg", C.c_int32),
+        ("coef", C.c_void_p),
+        ("groups", C.c_uint32),
+        ("x", C.c_void_p), ("noise", C.c_void_p), ("prev", C.c_void_p), ("x0_out", C.c_void_p), ("eps_out", C.c_void_p),
+        ("eps_factor", C.c_void_p),
+        ("pag_scale", C.c_void_p), ("hist", C.c_void_p),
+        ("keep_map", C.c_void_p), ("keep_src", C.c_void_p), ("keep_noise", C.c_void_p), ("keep_coef", C.c_void_p),
+        ("apg_avg", C.c_void_p), ("apg_sa", C.c_void_p), ("apg_par", C.c_void_p),
+    ]
+
+
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # symbol -> (restype, argtypes); must list every function declared in include/instantir_hip.h
@@ -127,17 +144,10 @@ SIGNATURES = {
     "iir_pack_latent_t": (C.c_int, [_P, _I32, _I32, _I32, _P, _I64, _I32, _F, _I32, _P]),
     "iir_unpack_latent_t": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _I32, _P]),
     "iir_pack_latent_dscale": (C.c_int, [_P, _I32, _I32, _I32, _P, _I64, _I32, _P, _I32, _P]),
-    "iir_sched_step": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "iir_sched_step_hist": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "iir_cfg_rescale_factor": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _F, _P, _P]),
-    "iir_sched_step_pag": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "iir_sched_step_hist_pag": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "iir_cfg_rescale_factor_pag": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P, _F, _P, _P]),
-    "iir_sched_step_keep": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "iir_sched_step": (C.c_int, [C.POINTER(SchedDesc), _P]),
+    "iir_cfg_rescale_factor": (C.c_int, [C.POINTER(SchedDesc), _F, _P, _P]),
     "iir_apg_project_workspace_bytes": (C.c_int64, [_I32]),
     "iir_apg_project": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P]),
-    "iir_sched_step_apg": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                     _P]),
     "iir_map_pool_max_f32": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
     "iir_region_composite_workspace_bytes": (C.c_int64, [_I32, _I32, _I32]),
     "iir_region_composite_f32": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P]),
@@ -194,7 +204,7 @@ def load():
         except AttributeError as e:
             raise HipLibraryError(f"{LIB_PATH} does not export {name}") from e
         fn.restype, fn.argtypes = SIGNATURES[name]
-    if lib.iir_abi_version() != 2:
+    if lib.iir_abi_version() != 3:
         raise HipLibraryError("ABI version mismatch")
     _lib = lib
     return lib

@@ -673,12 +673,14 @@ def _chk_pag(pag_scale):
         raise ValueError("pag_scale must be a CUDA fp32 tensor (the step's s_t, read at launch time)")
 
 
-def _pag_entry(name, pag_scale):
-    """(exported entry, its name, the pag_scale argument list) of `name` or its PAG form."""
-    if pag_scale is None:
-        return getattr(L.load(), name), name, []
-    _chk_pag(pag_scale)
-    return getattr(L.load(), name + "_pag"), name + "_pag", [pag_scale.data_ptr()]
+def _sched_desc(eps2d, B, coef, x, pag_scale, cfg=True):
+    """A SchedDesc with the fields iir_cfg_rescale_factor and iir_sched_step share."""
+    _, Cc, H, Wd = x.shape
+    d = L.SchedDesc(eps_nhwc=eps2d.data_ptr(), lde=eps2d.stride(0), B=B, C=Cc, HW=H * Wd, cfg=int(cfg), coef=coef.data_ptr())
+    if pag_scale is not None:
+        _chk_pag(pag_scale)
+        d.groups, d.pag_scale = L.STEP_PAG, pag_scale.data_ptr()
+    return d
 
 
 def _chk_group(what, items):
@@ -708,67 +710,44 @@ def apg_project(eps2d, B, coef, x, apg, ws):
 
 def sched_step(eps2d, B, coef, x, prev, noise=None, cfg=True, x0_out=None, eps_out=None, eps_factor=None, pag_scale=None, hist=None,
                keep=None, apg=None):
-    """`pag_scale` (device fp32[1]): the PAG form -- eps2d holds the perturbed rows after the cond rows (iir_sched_step*_pag).
-    `hist` (shape of x, fp32): adds the history term coef[7] * hist and then holds this step's x0 (iir_sched_step_hist*).
-    `keep` = (map (B, H*W), src, noise0, coef {thr, a, b, 0}), fp32 CUDA tensors: the restore-map form (iir_sched_step_keep) --
+    """One iir_sched_step call; each optional group sets its IIR_STEP_* bit in the descriptor.
+    `pag_scale` (device fp32[1]): the PAG form -- eps2d holds the perturbed rows after the cond rows (IIR_STEP_PAG).
+    `hist` (shape of x, fp32): adds the history term coef[7] * hist and then holds this step's x0 (IIR_STEP_HIST).
+    `keep` = (map (B, H*W), src, noise0, coef {thr, a, b, 0}), fp32 CUDA tensors: the restore-map form (IIR_STEP_KEEP) --
     pixels with map <= thr store a * src + b * noise0 in prev instead of the update.
-    `apg` = (avg, sa, par), as `apg_project` left them: the guided eps is the projected form (iir_sched_step_apg); it needs `cfg`
+    `apg` = (avg, sa, par), as `apg_project` left them: the guided eps is the projected form (IIR_STEP_APG); it needs `cfg`
     and does not combine with `eps_factor` (the norm clamp is APG's answer to what rescale_noise_cfg addresses)."""
-    _, Cc, H, Wd = x.shape
-    if apg is not None:
-        if eps_factor is not None:
-            raise ValueError("sched_step: apg is not available together with eps_factor")
-        if not cfg:
-            raise ValueError("sched_step: apg needs cfg (there is nothing to project without the uncond rows)")
-        if hist is not None and eps_out is not None:
-            raise ValueError("sched_step: eps_out is not available together with hist")
-        avg, sa, par = apg
-        _chk_group("sched_step: apg", (("avg", avg, x.numel()), ("sa", sa, 2 * B), ("par", par, 4)))
-        kp = [None] * 4
-        if keep is not None:
-            kp = list(keep)
-            _chk_group("sched_step: keep", (("map", kp[0], B * H * Wd), ("src", kp[1], x.numel()), ("noise", kp[2], x.numel()),
-                                            ("coef", kp[3], 4)))
-        if hist is not None:
-            assert hist.shape == x.shape and hist.dtype == torch.float32 and hist.is_contiguous()
-        if pag_scale is not None:
-            _chk_pag(pag_scale)
-        L.check(L.load().iir_sched_step_apg(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(), _p(pag_scale),
-                                            x.data_ptr(), _p(noise), _p(hist), prev.data_ptr(), _p(x0_out), _p(eps_out), None,
-                                            *[_p(t) for t in kp], avg.data_ptr(), sa.data_ptr(), par.data_ptr(), _stream()),
-                "iir_sched_step_apg")
-        return prev
-    outs = [prev.data_ptr(), _p(x0_out), _p(eps_out)]
+    if apg is not None and eps_factor is not None:
+        raise ValueError("sched_step: apg is not available together with eps_factor")
+    if apg is not None and not cfg:
+        raise ValueError("sched_step: apg needs cfg (there is nothing to project without the uncond rows)")
+    d = _sched_desc(eps2d, B, coef, x, pag_scale, cfg)
+    d.x, d.noise, d.prev = x.data_ptr(), _p(noise), prev.data_ptr()
+    d.x0_out, d.eps_out, d.eps_factor = _p(x0_out), _p(eps_out), _p(eps_factor)
     if hist is not None:
         assert hist.shape == x.shape and hist.dtype == torch.float32 and hist.is_contiguous()
         if eps_out is not None:
             raise ValueError("sched_step: eps_out is not available together with hist")
-        outs = [hist.data_ptr(), prev.data_ptr(), _p(x0_out)]
+        d.groups |= L.STEP_HIST
+        d.hist = hist.data_ptr()
     if keep is not None:
-        kmap, ksrc, knoise, kcoef = keep
-        for name, t, numel in (("map", kmap, B * H * Wd), ("src", ksrc, x.numel()), ("noise", knoise, x.numel()), ("coef", kcoef, 4)):
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel):
-                raise ValueError(f"sched_step: keep {name} must be a contiguous CUDA fp32 tensor of {numel} elements")
-        if pag_scale is not None:
-            _chk_pag(pag_scale)
-        L.check(L.load().iir_sched_step_keep(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(), _p(pag_scale),
-                                             x.data_ptr(), _p(noise), _p(hist), prev.data_ptr(), _p(x0_out), _p(eps_out),
-                                             _p(eps_factor), kmap.data_ptr(), ksrc.data_ptr(), knoise.data_ptr(), kcoef.data_ptr(),
-                                             _stream()), "iir_sched_step_keep")
-        return prev
-    fn, name, ps = _pag_entry("iir_sched_step_hist" if hist is not None else "iir_sched_step", pag_scale)
-    L.check(fn(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, int(cfg), coef.data_ptr(), *ps, x.data_ptr(), _p(noise), *outs,
-               _p(eps_factor), _stream()), name)
+        n = x.numel()
+        _chk_group("sched_step: keep", zip(("map", "src", "noise", "coef"), keep, (B * d.HW, n, n, 4)))
+        d.groups |= L.STEP_KEEP
+        d.keep_map, d.keep_src, d.keep_noise, d.keep_coef = [t.data_ptr() for t in keep]
+    if apg is not None:
+        _chk_group("sched_step: apg", zip(("avg", "sa", "par"), apg, (x.numel(), 2 * B, 4)))
+        d.groups |= L.STEP_APG
+        d.apg_avg, d.apg_sa, d.apg_par = [t.data_ptr() for t in apg]
+    L.check(L.load().iir_sched_step(C.byref(d), _stream()), "iir_sched_step")
     return prev
 
 
 def cfg_rescale_factor(eps2d, B, coef, x, guidance_rescale, factor, pag_scale=None):
     """factor (B,) fp32 device: the per-image multiplier `rescale_noise_cfg` applies to the guided eps (with `pag_scale`: the
     guided eps includes the PAG term of rows [2B, 3B))."""
-    _, Cc, H, Wd = x.shape
-    fn, name, ps = _pag_entry("iir_cfg_rescale_factor", pag_scale)
-    L.check(fn(eps2d.data_ptr(), eps2d.stride(0), B, Cc, H * Wd, coef.data_ptr(), *ps, float(guidance_rescale), factor.data_ptr(),
-               _stream()), name)
+    d = _sched_desc(eps2d, B, coef, x, pag_scale)
+    L.check(L.load().iir_cfg_rescale_factor(C.byref(d), float(guidance_rescale), factor.data_ptr(), _stream()), "iir_cfg_rescale_factor")
     return factor
 
 

@@ -464,8 +464,8 @@ class InstantIRPipeline:
                self._freeu,           # the FreeU factors are launch arguments of the captured concats
                _sched_form(self.scheduler),   # the sigma schedulers launch the device-scale pack and the history step
                self._pag_paths if pag_on else None,     # PAG: row count and the identity launches (its scale is a device scalar)
-               keep is not None,      # a restore map: the step's last launch is iir_sched_step_keep, on buffers only such a loop has
-               bool(apg_on))          # APG: iir_apg_project + iir_sched_step_apg (its three parameters travel in the scalar row)
+               keep is not None,      # a restore map: the step's last launch carries IIR_STEP_KEEP, on buffers only such a loop has
+               bool(apg_on))          # APG: iir_apg_project + IIR_STEP_APG in the step (its three parameters travel in the scalar row)
         if not fresh:
             cached = self._loop_cache
             if cached is not None and cached[0] == key and os.environ.get("IIR_LOOP_CACHE", "1") != "0":
@@ -1019,7 +1019,7 @@ class InstantIRPipeline:
 
 def _sched_form(scheduler):
     """"hist": a sigma scheduler (Euler, Euler-ancestral, DPM++) driven through `loop_coefficients`, c_in-scaled UNet input
-    and iir_sched_step_hist; "linear": DDPM / DDIM through `step_coefficients` and iir_sched_step."""
+    and iir_sched_step with IIR_STEP_HIST; "linear": DDPM / DDIM through `step_coefficients` and iir_sched_step."""
     return "hist" if hasattr(scheduler, "loop_coefficients") else "linear"
 
 
@@ -1027,7 +1027,7 @@ def _scalar_row(rows, masked=False, apg=False):
     """Layout of a loop's per-step scalar row when its main UNet runs `rows` rows: ({name: slice}, length) of
     [t x rows | lcm coef x4 | sched coef x8 | res scale x rows | c_in | PAG s_t], and for a loop with a restore map (`masked`)
     [| keep x4] = {thr, a, b, 0} behind them, and for a loop with adaptive projected guidance (`apg`) [| apg x4] =
-    {eta, r, beta_t, 0} behind everything else.  `sched` is the (8,) coefficient vector the iir_sched_step* and PAG kernels index
+    {eta, r, beta_t, 0} behind everything else.  `sched` is the (8,) coefficient vector the iir_sched_step and PAG kernels index
     themselves: guidance in [0], the history term k_h in [7]."""
     lay, off = {}, 0
     groups = (("t", rows), ("lcm", 4), ("sched", 8), ("res_scale", rows), ("c_in", 1), ("pag_s", 1))
@@ -1095,7 +1095,7 @@ class _DenoiseLoop:
         self.preview_f32 = torch.zeros(R, 4, H, W, dtype=torch.float32, device=dev)
         self.previewer_mean = torch.zeros_like(self.x_in)
         self.form = _sched_form(pipe.scheduler)
-        # the x0 history of a multistep solver, read and rewritten in place by every step's iir_sched_step_hist
+        # the x0 history of a multistep solver, read and rewritten in place by every step's iir_sched_step (IIR_STEP_HIST)
         self.hist = torch.zeros_like(self.x_in) if self.form == "hist" else None
         # restore map: the latent map, the fp32 LQ latent and the loop's seed noise, persistent so that captured launches see
         # the next call's values (`adopt`); {thr, a, b, 0} travels in the step's scalar row

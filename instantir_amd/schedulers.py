@@ -17,7 +17,7 @@ API mirrors what `pipelines/sdxl_instantir.py` touches on a scheduler object (SU
 * `EulerDiscreteScheduler` / `EulerAncestralDiscreteScheduler` / `DPMSolverMultistepScheduler`: the diffusers-0.28.1 classes a
   user swaps in with `Cls.from_config(pipe.scheduler.config)` (the reference's loop calls `scale_model_input`,
   pipelines/sdxl_instantir.py:1503-1504).  Epsilon prediction; the options each class refuses raise ValueError naming the key.
-  `loop_coefficients(i)` drives the captured loop (`iir_pack_latent_dscale` + `iir_sched_step_hist`).
+  `loop_coefficients(i)` drives the captured loop (`iir_pack_latent_dscale` + `iir_sched_step` with IIR_STEP_HIST).
 """
 from __future__ import annotations
 
@@ -291,7 +291,7 @@ class LCMSingleStepScheduler(_Base):
 #
 # Every update of these schedulers is, in the scheduler's own sample space, the linear form of `_Base` plus one history
 # term:  prev = k_x0*x0 + k_x*x + k_eps*eps + k_h*m_prev + k_noise*noise,  x0 = (x - sb*eps)/sa.  Host coefficients are
-# formed in fp64 from the fp32 sigma table and rounded once to fp32; the tensor update runs in iir_sched_step_hist(_f32).
+# formed in fp64 from the fp32 sigma table and rounded once to fp32; the tensor update runs in iir_sched_step (IIR_STEP_HIST) / iir_sched_step_hist_f32.
 
 def _sigma_table(alphas_cumprod):
     """sigma(t) = sqrt((1 - abar_t) / abar_t) over the training steps, fp32 (as diffusers forms it), and its fp32 log."""

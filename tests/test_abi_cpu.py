@@ -18,7 +18,7 @@ def test_library_exports_every_declared_symbol():
     for s in lib.declared_symbols():
         assert hasattr(h, s), s
     h.iir_abi_version.restype = ctypes.c_int
-    assert h.iir_abi_version() == 2
+    assert h.iir_abi_version() == 3
 
 
 def test_k_split_workspace_has_left_the_abi():
@@ -30,19 +30,36 @@ def test_k_split_workspace_has_left_the_abi():
     assert "split" not in open(lib.HEADER_PATH).read().lower()
 
 
+def test_positional_step_entries_have_left_the_abi():
+    """The CFG + scheduler step went onto a descriptor with ABI version 3 (iir_sched_desc, iir_sched_step, iir_cfg_rescale_factor):
+    none of the positional spellings of the same two launches is declared, bound or exported any more."""
+    gone = ("iir_sched_step_hist", "iir_sched_step_pag", "iir_sched_step_hist_pag", "iir_sched_step_keep", "iir_sched_step_apg",
+            "iir_cfg_rescale_factor_pag")
+    h = ctypes.CDLL(lib.LIB_PATH)
+    syms = lib.declared_symbols()
+    for s in gone:
+        assert s not in syms and s not in lib.SIGNATURES and not hasattr(h, s), s
+    # the seventh, the 14-argument iir_sched_step, gave its name to the descriptor entry
+    assert lib.SIGNATURES["iir_sched_step"][1][0] == ctypes.POINTER(lib.SchedDesc) and len(lib.SIGNATURES["iir_sched_step"][1]) == 2
+    assert lib.SIGNATURES["iir_cfg_rescale_factor"][1][0] == ctypes.POINTER(lib.SchedDesc)
+    text = open(lib.HEADER_PATH).read()
+    assert "iir_sched_step(const iir_sched_desc* d, void* stream)" in text
+
+
 def test_descriptor_layouts_match_header():
     """ctypes mirrors of the structs: natural alignment, sizes as a C compiler lays them out."""
     import shutil
     import subprocess
     import tempfile
     sizes = (ctypes.sizeof(lib.GemmDesc), ctypes.sizeof(lib.ConvDesc), ctypes.sizeof(lib.AttnKV), ctypes.sizeof(lib.AttnDesc),
-             ctypes.sizeof(lib.AdaLNJob))
+             ctypes.sizeof(lib.AdaLNJob), ctypes.sizeof(lib.SchedDesc))
     assert all(s % 8 == 0 for s in sizes) and sizes[2] == 56
     if shutil.which("gcc"):      # ask the C compiler itself
         with tempfile.TemporaryDirectory() as td:
             src = os.path.join(td, "sz.c")
-            open(src, "w").write('#include <stdio.h>\n#include "%s"\nint main(){printf("%%zu %%zu %%zu %%zu %%zu", sizeof(iir_gemm_desc),'
-                                 'sizeof(iir_conv_desc), sizeof(iir_attn_kv), sizeof(iir_attn_desc), sizeof(iir_adaln_job));}' % lib.HEADER_PATH)
+            open(src, "w").write('#include <stdio.h>\n#include "%s"\nint main(){printf("%%zu %%zu %%zu %%zu %%zu %%zu", sizeof(iir_gemm_desc),'
+                                 'sizeof(iir_conv_desc), sizeof(iir_attn_kv), sizeof(iir_attn_desc), sizeof(iir_adaln_job),'
+                                 'sizeof(iir_sched_desc));}' % lib.HEADER_PATH)
             subprocess.run(["gcc", src, "-o", os.path.join(td, "sz")], check=True)
             out = subprocess.run([os.path.join(td, "sz")], capture_output=True, text=True, check=True).stdout
         assert tuple(int(x) for x in out.split()) == sizes

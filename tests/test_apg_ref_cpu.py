@@ -185,16 +185,21 @@ def test_scalar_row_gains_the_apg_group_last(rows):
 
 def test_abi_table_has_both_entries():
     from instantir_amd import lib
-    assert "iir_apg_project" in lib.SIGNATURES and "iir_sched_step_apg" in lib.SIGNATURES
-    assert len(lib.SIGNATURES["iir_apg_project"][1]) == 13 and len(lib.SIGNATURES["iir_sched_step_apg"][1]) == 23
+    import ctypes
+    assert "iir_apg_project" in lib.SIGNATURES and "iir_sched_step" in lib.SIGNATURES
+    fields = [name for name, _ in lib.SchedDesc._fields_]
+    assert len(lib.SIGNATURES["iir_apg_project"][1]) == 13 and all(k in fields for k in ("apg_avg", "apg_sa", "apg_par"))
     declared = lib.declared_symbols()
-    assert "iir_apg_project" in declared and "iir_sched_step_apg" in declared
+    assert "iir_apg_project" in declared and "iir_sched_step" in declared
+    h = ctypes.CDLL(lib.LIB_PATH)
+    assert hasattr(h, "iir_apg_project") and hasattr(h, "iir_sched_step")
 
 
 def test_apg_entries_reject_bad_arguments_without_a_gpu():
+    import ctypes
     from instantir_amd import lib
     h = lib.load()
-    assert h.iir_abi_version() == 2
+    assert h.iir_abi_version() == 3
     P = 4096
 
     need = h.iir_apg_project_workspace_bytes(1)
@@ -213,17 +218,21 @@ def test_apg_entries_reject_bad_arguments_without_a_gpu():
     assert proj(nws=need - 1) == -1 and proj(ws=P + 8196) == -1 and proj(B=2) == -1      # workspace too small / unaligned
 
     def step(**kw):
-        a = dict(eps=P, lde=8, B=1, C=4, HW=64, cfg=1, coef=P, ps=None, x=P + 1024, noise=None, hist=None, prev=P + 2048, x0=None,
-                 eo=None, fac=None, km=None, ks=None, kn=None, kc=None, avg=P + 4096, sa=P + 8192, par=P)
+        a = dict(eps_nhwc=P, lde=8, B=1, C=4, HW=64, cfg=1, coef=P, x=P + 1024, prev=P + 2048, apg_avg=P + 4096, apg_sa=P + 8192,
+                 apg_par=P)
         a.update(kw)
-        return h.iir_sched_step_apg(*[a[k] for k in ("eps", "lde", "B", "C", "HW", "cfg", "coef", "ps", "x", "noise", "hist", "prev",
-                                                     "x0", "eo", "fac", "km", "ks", "kn", "kc", "avg", "sa", "par")], None)
+        # what iir_sched_step_apg implied: the APG bit, and the bit of every optional group with a pointer given
+        a.setdefault("groups", lib.STEP_APG | (lib.STEP_HIST if a.get("hist") else 0)
+                     | (lib.STEP_KEEP if any(a.get("keep_" + k) for k in ("map", "src", "noise", "coef")) else 0))
+        return h.iir_sched_step(ctypes.byref(lib.SchedDesc(**a)), None)
 
-    for k in ("eps", "coef", "x", "prev", "avg", "sa", "par"):
+    for k in ("eps_nhwc", "coef", "x", "prev", "apg_avg", "apg_sa", "apg_par"):
         assert step(**{k: None}) == -1, k
     assert step(B=0) == -1 and step(C=0) == -1 and step(HW=0) == -1 and step(lde=3) == -1
     assert step(cfg=0) == -1                                      # nothing to project without the uncond rows
-    assert step(km=P) == -1 and step(km=P, ks=P, kn=P) == -1      # the keep group: all four pointers or none
-    assert step(hist=P + 16384, eo=P + 32768) == -1               # eps_out together with hist
-    assert step(avg=P + 2048) == -1                               # the average may not be an output plane
+    assert step(keep_map=P) == -1 and step(keep_map=P, keep_src=P, keep_noise=P) == -1      # the keep group: all four pointers or none
+    assert step(hist=P + 16384, eps_out=P + 32768) == -1          # eps_out together with hist
+    assert step(apg_avg=P + 2048) == -1                           # the average may not be an output plane
     assert step(hist=P + 1024) == -1                              # hist aliases x
+    assert step(groups=0) == -1 and step(apg_avg=None, apg_sa=None, groups=0) == -1      # pointers without the bit
+    assert step(keep_map=P, groups=lib.STEP_APG) == -1 and step(groups=lib.STEP_APG | 64) == -1      # ... and a bit outside the four

@@ -67,7 +67,7 @@ def test_new_entries_are_declared_bound_and_exported():
     h = C.CDLL(lib.LIB_PATH)
     for name in NEW:
         assert hasattr(h, name), name
-    assert lib.load().iir_abi_version() == 2
+    assert lib.load().iir_abi_version() == 3
 
 
 def test_workspace_bytes():

@@ -113,34 +113,40 @@ def test_ident_attention_rejects_bad_arguments_without_a_gpu():
 
 
 def test_pag_step_entries_reject_bad_arguments_without_a_gpu():
+    import ctypes
     from instantir_amd import lib
     h = lib.load()
     P = 4096
     B, C, HW = 1, 4, 64
 
-    def step(**kw):
-        a = dict(eps=P, lde=64, B=B, C=C, HW=HW, cfg=1, coef=P, ps=P, x=P, noise=None, prev=P, x0=None, eo=None, fac=None)
+    def step(**kw):           # the descriptor spelling of the former iir_sched_step_pag: the PAG bit
+        a = dict(eps_nhwc=P, lde=64, B=B, C=C, HW=HW, cfg=1, coef=P, groups=lib.STEP_PAG, pag_scale=P, x=P, prev=P)
         a.update(kw)
-        return h.iir_sched_step_pag(a["eps"], a["lde"], a["B"], a["C"], a["HW"], a["cfg"], a["coef"], a["ps"], a["x"], a["noise"],
-                                    a["prev"], a["x0"], a["eo"], a["fac"], None)
+        return h.iir_sched_step(ctypes.byref(lib.SchedDesc(**a)), None)
 
-    assert step(ps=None) == -1 and step(eps=None) == -1 and step(coef=None) == -1 and step(x=None) == -1
+    assert step(pag_scale=None) == -1 and step(eps_nhwc=None) == -1 and step(coef=None) == -1 and step(x=None) == -1
     assert step(B=0) == -1 and step(lde=3) == -1
-    assert step(cfg=0, fac=P) == -1                 # rescale factor only with CFG
+    assert step(cfg=0, eps_factor=P) == -1          # rescale factor only with CFG
+    assert step(groups=0) == -1                     # a pag_scale without its bit
+    assert step(groups=lib.STEP_PAG | 16) == -1 and step(groups=lib.STEP_PAG | 1 << 31) == -1      # a bit outside the four
+    assert h.iir_sched_step(None, None) == -1
 
-    def hist(**kw):
-        a = dict(eps=P, lde=64, B=B, C=C, HW=HW, cfg=1, coef=P, ps=P, x=P, noise=None, hist=P + 1024, prev=P + 2048, x0=None, fac=None)
-        a.update(kw)
-        return h.iir_sched_step_hist_pag(a["eps"], a["lde"], a["B"], a["C"], a["HW"], a["cfg"], a["coef"], a["ps"], a["x"],
-                                         a["noise"], a["hist"], a["prev"], a["x0"], a["fac"], None)
+    def hist(**kw):           # ... of iir_sched_step_hist_pag: both bits
+        return step(**dict(dict(groups=lib.STEP_PAG | lib.STEP_HIST, hist=P + 1024, prev=P + 2048), **kw))
 
-    assert hist(ps=None) == -1 and hist(hist=None) == -1
+    assert hist(pag_scale=None) == -1 and hist(hist=None) == -1
     assert hist(hist=P) == -1                       # hist aliases x
     assert hist(prev=P + 1024) == -1                # hist aliases prev
-    assert hist(cfg=0, fac=P) == -1 and hist(C=0) == -1
-    r = lambda **kw: h.iir_cfg_rescale_factor_pag(kw.get("eps", P), 64, kw.get("B", B), C, HW, P, kw.get("ps", P), 0.7,
-                                                  kw.get("fac", P), None)
-    assert r(ps=None) == -1 and r(eps=None) == -1 and r(fac=None) == -1 and r(B=0) == -1
+    assert hist(cfg=0, eps_factor=P) == -1 and hist(C=0) == -1
+    assert hist(groups=lib.STEP_PAG) == -1          # a hist without its bit
+
+    def r(fac=P, **kw):       # ... of iir_cfg_rescale_factor_pag
+        a = dict(eps_nhwc=P, lde=64, B=B, C=C, HW=HW, coef=P, groups=lib.STEP_PAG, pag_scale=P)
+        a.update(kw)
+        return h.iir_cfg_rescale_factor(ctypes.byref(lib.SchedDesc(**a)), 0.7, fac, None)
+
+    assert r(pag_scale=None) == -1 and r(eps_nhwc=None) == -1 and r(fac=None) == -1 and r(B=0) == -1
+    assert h.iir_cfg_rescale_factor(None, 0.7, P, None) == -1
     cs = h.iir_copy_segments
     assert cs(None, 1, 16, None) == -1 and cs(P, 0, 16, None) == -1 and cs(P, 1, 0, None) == -1 and cs(P, 70000, 16, None) == -1
 

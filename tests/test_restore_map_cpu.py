@@ -169,7 +169,7 @@ def test_cli_map_lookup(tmp_path):
 
 
 # ---- C ABI --------------------------------------------------------------------------------------------------------
-NEW = ("iir_sched_step_keep", "iir_map_pool_max_f32", "iir_region_composite_workspace_bytes", "iir_region_composite_f32")
+NEW = ("iir_sched_step", "iir_map_pool_max_f32", "iir_region_composite_workspace_bytes", "iir_region_composite_f32")
 
 
 def test_new_entries_are_declared_bound_and_exported():
@@ -177,7 +177,8 @@ def test_new_entries_are_declared_bound_and_exported():
     h = ctypes.CDLL(lib.LIB_PATH)
     for s in NEW:
         assert s in syms and s in lib.SIGNATURES and hasattr(h, s), s
-    assert len(lib.SIGNATURES["iir_sched_step_keep"][1]) == 20
+    fields = [name for name, _ in lib.SchedDesc._fields_]
+    assert all(k in fields for k in ("keep_map", "keep_src", "keep_noise", "keep_coef"))
     header = open(lib.HEADER_PATH).read()
     assert "pipelines/sdxl_instantir.py:1619-1633" in header and ":1388-1403" in header
 
@@ -189,17 +190,19 @@ def test_new_entries_refuse_bad_arguments_without_a_gpu():
     eps, coef, x, prev, kmap, ksrc, knoise, kcoef, hist, eps_out = P[:10]
 
     def step(**kw):
-        a = dict(eps=eps, coef=coef, pag=None, x=x, noise=None, hist=None, prev=prev, x0=None, eps_out=None, fac=None, kmap=kmap,
-                 ksrc=ksrc, knoise=knoise, kcoef=kcoef, B=2, C=4, HW=35)
+        a = dict(eps_nhwc=eps, lde=64, B=2, C=4, HW=35, cfg=1, coef=coef, x=x, prev=prev, keep_map=kmap, keep_src=ksrc,
+                 keep_noise=knoise, keep_coef=kcoef)
         a.update(kw)
-        return h.iir_sched_step_keep(a["eps"], 64, a["B"], a["C"], a["HW"], 1, a["coef"], a["pag"], a["x"], a["noise"], a["hist"],
-                                     a["prev"], a["x0"], a["eps_out"], a["fac"], a["kmap"], a["ksrc"], a["knoise"], a["kcoef"], None)
+        a.setdefault("groups", lib.STEP_KEEP | (lib.STEP_HIST if a.get("hist") else 0))      # what iir_sched_step_keep implied
+        return h.iir_sched_step(ctypes.byref(lib.SchedDesc(**a)), None)
 
-    for k in ("kmap", "ksrc", "knoise", "kcoef", "eps", "coef", "x", "prev"):
+    for k in ("keep_map", "keep_src", "keep_noise", "keep_coef", "eps_nhwc", "coef", "x", "prev"):
         assert step(**{k: None}) == -1, k
-    assert step(ksrc=prev) == -1 and step(knoise=prev) == -1         # the kept value's sources may not be the output
+    assert step(keep_src=prev) == -1 and step(keep_noise=prev) == -1 # the kept value's sources may not be the output
     assert step(hist=hist, eps_out=eps_out) == -1                    # as the existing entries: no eps_out with a history plane
     assert step(hist=x) == -1 and step(HW=0) == -1
+    assert step(groups=0) == -1 and step(keep_map=None, keep_src=None, keep_noise=None, groups=0) == -1     # pointers without the bit
+    assert step(groups=lib.STEP_KEEP | 32) == -1                     # a bit outside the four
 
     pool = lambda H, W, f, src=P[0], dst=P[1]: h.iir_map_pool_max_f32(src, 2, H, W, f, dst, None)
     assert pool(25, 40, 8) == -1 and pool(24, 41, 8) == -1 and pool(24, 40, 0) == -1 and pool(0, 40, 8) == -1

@@ -330,15 +330,14 @@ def test_new_entries_reject_bad_arguments_without_a_gpu():
     assert h.iir_pack_latent_dscale(P, 1, 4, 16, P, 8, 0, P, 0, None) == -1             # rep
     assert h.iir_pack_latent_dscale(P, 0, 4, 16, P, 8, 1, P, 0, None) == -1             # B
     assert h.iir_pack_latent_dscale(P, 1, 4, 16, P, 8, 1, P, 7, None) == -1             # dtype
-    # iir_sched_step_hist(eps, lde, B, C, HW, cfg, coef, x, noise, hist, prev, x0_out, eps_factor, stream)
-    ok = dict(eps=P, lde=8, B=1, C=4, HW=16, cfg=1, coef=P, x=P + 256, noise=None, hist=P + 512, prev=P + 768, x0=None, fac=None)
+    # iir_sched_step on a descriptor with the HIST bit (the former iir_sched_step_hist)
+    ok = dict(eps_nhwc=P, lde=8, B=1, C=4, HW=16, cfg=1, coef=P, groups=lib.STEP_HIST, x=P + 256, hist=P + 512, prev=P + 768)
 
     def call(**kw):
-        a = dict(ok, **kw)
-        return h.iir_sched_step_hist(a["eps"], a["lde"], a["B"], a["C"], a["HW"], a["cfg"], a["coef"], a["x"], a["noise"], a["hist"],
-                                     a["prev"], a["x0"], a["fac"], None)
-    for bad in (dict(eps=None), dict(coef=None), dict(x=None), dict(hist=None), dict(prev=None), dict(B=0), dict(C=0), dict(HW=0),
-                dict(lde=3), dict(cfg=0, fac=P), dict(hist=P + 256), dict(hist=P + 768), dict(x0=P + 512)):
+        return h.iir_sched_step(ctypes.byref(lib.SchedDesc(**dict(ok, **kw))), None)
+    for bad in (dict(eps_nhwc=None), dict(coef=None), dict(x=None), dict(hist=None), dict(prev=None), dict(B=0), dict(C=0), dict(HW=0),
+                dict(lde=3), dict(cfg=0, eps_factor=P), dict(hist=P + 256), dict(hist=P + 768), dict(x0_out=P + 512),
+                dict(groups=0), dict(groups=lib.STEP_HIST | 256)):          # ... a hist without its bit, a bit outside the four
         assert call(**bad) == -1, bad
     # iir_sched_step_hist_f32(eps, x, noise, coef, hist, n, prev, x0_out, stream)
     assert h.iir_sched_step_hist_f32(None, P, None, P, P + 64, 8, P + 128, None, None) == -1

@@ -123,6 +123,18 @@ def test_update_bits_match_the_recorded_library(dev, golden_dir):
     assert not bad, bad
 
 
+def test_keep_and_apg_update_bits_match_the_recorded_library(dev, golden_dir):
+    """The restore-map and APG forms of the step (keep x hist x pag x cfg, apg x keep x hist) through ops.sched_step /
+    ops.apg_project, against the bits recorded in tests/golden/sched_update_bits_keep_apg.npz before the positional step entries
+    were replaced by iir_sched_step on a descriptor: a pointer in the wrong field of the descriptor shows here."""
+    from golden.make_sched_update_bits import replay_keep_apg
+    want = np.load(os.path.join(golden_dir, "sched_update_bits_keep_apg.npz"))
+    got = replay_keep_apg()
+    assert sorted(got) == sorted(want.files)
+    bad = [k for k in want.files if not np.array_equal(got[k], want[k])]
+    assert not bad, bad
+
+
 @pytest.mark.parametrize("B,H,W,rep", [(1, 128, 128, 2), (2, 5, 7, 1), (2, 16, 16, 2)])
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 def test_device_scale_pack_bit_identical_to_host_scale(dev, B, H, W, rep, dtype):

@@ -19,7 +19,7 @@ def test_entry_is_exported_and_bound():
     assert "iir_attention_1h" in lib.declared_symbols()
     assert lib.SIGNATURES["iir_attention_1h"] == SIG
     assert hasattr(ctypes.CDLL(lib.LIB_PATH), "iir_attention_1h")
-    assert lib.load().iir_abi_version() == 2
+    assert lib.load().iir_abi_version() == 3
 
 
 def _valid_desc(D=512, T=333):

@@ -62,7 +62,7 @@ q4 = qkv[:, :Cc].float().reshape(B, T, heads, 64).transpose(1, 2); k4 = qkv[:, C
 v4 = vt.float().T.reshape(B, T, heads, 64).transpose(1, 2)
 want = F.scaled_dot_product_attention(q4, k4, v4).transpose(1, 2).reshape(B * T, Cc).flatten().cpu()
 screen(f"attention B={B} h={heads} T={T}", lambda o: ops.attention(qkv[:, :Cc], o, [(qkv[:, Cc:], T, vt, T, T)], B, heads, T), want, [(B * T, Cc)])
-# adaptive projected guidance: iir_apg_project + iir_sched_step_apg (fp32 planes; prev against plain CFG at the identity parameters
+# adaptive projected guidance: iir_apg_project + iir_sched_step with IIR_STEP_APG (fp32 planes; prev against plain CFG at the identity parameters
 # eta = 1, r = 0, beta = 0, which equal it algebraically), bit-identical over REP launches at the library defaults
 for apB in (1, 8):
     ap_x = (torch.randn(apB, 4, 128, 128, generator=g) * 0.8).to(dev)

@@ -10,14 +10,14 @@ Prints one line per timed call and a JSON summary:
 
     python tools/sched_bench.py --map [--size 1024] [--pairs 3] [--steps 20]
 
-The restore map (restore_map=): the step launch alone, iir_sched_step against iir_sched_step_keep at the step's shapes
-(B = 1, cfg, DDPM noise; device events, alternating windows), and DDPM calls through the pipeline without and with a map,
+The restore map (restore_map=): the step launch alone, iir_sched_step without and with the IIR_STEP_KEEP group (the leg labelled
+iir_sched_step_keep) at the step's shapes (B = 1, cfg, DDPM noise; device events, alternating windows), and DDPM calls through the pipeline without and with a map,
 alternating pairs, ms/step medians.
 
     python tools/sched_bench.py --apg [--size 1024] [--pairs 3] [--steps 20]
 
-Adaptive projected guidance (enable_apg): iir_sched_step against iir_apg_project + iir_sched_step_apg at B = 1 and B = 8 (cfg,
-DDPM noise; device events, alternating windows), and DDPM calls through the pipeline with APG off and on, alternating pairs,
+Adaptive projected guidance (enable_apg): iir_sched_step against iir_apg_project + iir_sched_step with the IIR_STEP_APG group (the
+leg labelled iir_sched_step_apg) at B = 1 and B = 8 (cfg, DDPM noise; device events, alternating windows), and DDPM calls through the pipeline with APG off and on, alternating pairs,
 ms/step medians.
 """
 import argparse
@@ -44,7 +44,7 @@ def timed_us(fn, n):
 
 
 def map_launch_leg(size, n=500, windows=3):
-    """iir_sched_step against iir_sched_step_keep on one stream, back to back: each figure includes the launch boundary.  The map
+    """iir_sched_step without and with the keep group on one stream, back to back: each figure includes the launch boundary.  The map
     adds three fp32 reads per latent element (map, LQ latent, seed noise) to x, eps and noise in, prev out."""
     from instantir_amd import ops
     dev = torch.device("cuda:0")
@@ -69,8 +69,8 @@ def map_launch_leg(size, n=500, windows=3):
 
 
 def apg_launch_leg(size, B, n=500, windows=3):
-    """iir_sched_step against iir_apg_project + iir_sched_step_apg on one stream, back to back: each figure includes the launch
-    boundaries (two for APG).  APG adds one reduction pass (both eps row groups and x in, the average plane in and out) and one
+    """iir_sched_step against iir_apg_project + iir_sched_step with the APG group on one stream, back to back: each figure includes
+    the launch boundaries (two for APG).  APG adds one reduction pass (both eps row groups and x in, the average plane in and out) and one
     fp32 read per latent element in the step (the average; the uncond rows are no longer read there)."""
     from instantir_amd import ops
     dev = torch.device("cuda:0")
