@@ -269,6 +269,22 @@ int iir_freeu_concat_f16(const void* x, int64_t ldx, int32_t cx, const void* mid
                          float b, float s, const float* partials, int64_t partials_bytes, void* cat, int64_t ldc,
                          int64_t cat_off, void* stream);
 
+/* Smoothed-energy guidance (SEG, Hong 2024): the 2-D Gaussian blur of the queries of the perturbed batch rows of a self-attention,
+ * in place in the q | k buffer of the fused projection, between that GEMM and the (plain) attention launch.
+ * `q`: the first perturbed row, 16-byte aligned; `images` images of H * W consecutive rows (the token grid, x fastest) follow;
+ * row stride `ldq` elements (ldq % 8 == 0, ldq >= C); columns [0, C) are filtered (C % 8 == 0), each channel on its own:
+ *   q'[y][x][c] = sum_j wy[j] * (sum_i wx[i] * q[ry(y + j - ky/2)][rx(x + i - kx/2)][c])
+ * rx / ry reflect without repeating the edge (-i -> i, n-1+i -> n-1-i).  wy (ky taps) / wx (kx taps): fp32 device memory, read
+ * at launch; ky, kx odd with k / 2 <= extent - 1 (k = 1, weight 1: that axis is left alone).  fp16 in, both passes and the
+ * intermediate in fp32, taps summed in index order, one fp16 rounding at the store.  `mean` != 0 (the blur's sigma -> inf
+ * limit): q'[.][.][c] = mean over the image's H * W tokens, by a pairwise fp32 tree; wy / wx / ky / kx are not read.
+ * Columns [C, ldq), rows outside the `images` images and every other byte keep their bits; no atomics: equal inputs give
+ * equal bits.  H, W <= IIR_SEG_MAX_EXTENT.  IIR_EINVAL, before any HIP call, for a NULL or misaligned q, NULL taps, a
+ * non-positive extent, C % 8, ldq < C or ldq % 8, an even k, k / 2 > extent - 1 or an extent beyond the limit. */
+#define IIR_SEG_MAX_EXTENT 128
+int iir_seg_blur_q_f16(void* q, int64_t ldq, int32_t images, int32_t H, int32_t W, int32_t C, const float* wy, int32_t ky,
+                       const float* wx, int32_t kx, int32_t mean, void* stream);
+
 /* fp32 NCHW latents <-> fp16 NHWC rows (pipelines/sdxl_instantir.py:1503 cat([latents]*2) = rep 2). */
 int iir_pack_latent(const float* x, int32_t B, int32_t C, int32_t HW, void* out, int64_t ldo, int32_t rep, float scale,
                     void* stream);

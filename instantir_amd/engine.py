@@ -34,7 +34,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import ops, pag
+from . import ops, pag, seg
 from .config import UNetConfig
 from .packing import conv_weight_nhwc, pair_rows
 from .weights import skip_channels
@@ -153,6 +153,8 @@ class _Net:
         # perturbed-attention guidance: None, or (frozenset of selected `attn1` paths, ident_from) -- set on the main UNet only
         # (HipUNet.set_pag)
         self.pag = None
+        # smoothed-energy guidance: None, or a `_SegState` -- the other way to perturb those rows (HipUNet.set_seg); never both
+        self.seg = None
         # The two launch-path options a caller may set (both are part of the pipeline's loop key).  `inkernel_prefetch`: GEMMs and
         # convs pull the weights that follow their own towards the Infinity Cache (`_pf`).
         # `fp8_act`, fp8 build (BASELINE configs[4]): the activations of the transformer linears are STORED as fp8 by the launch that
@@ -407,8 +409,8 @@ class _Net:
         A.release(m)
         return out
 
-    def _tblock(self, p, h, R, T, heads, st, ada, lnst=None, last=False):
-        """One BasicTransformerBlock in place on h (R*T, C).  module/min_sdxl.py:541-562.
+    def _tblock(self, p, h, R, T, heads, st, ada, lnst=None, last=False, grid=None):
+        """One BasicTransformerBlock in place on h (R*T, C).  module/min_sdxl.py:541-562.  `grid`: (H, W) of the token grid.
         `lnst` (fp32 (parts, M, 2)): the LayerNorm partials of `h` left by the GEMM that wrote it.  When given, no LayerNorm
         kernel runs in this block: each of the three norms is folded into the GEMM behind it (reads raw `h`, `ln_in`) and each
         GEMM that writes `h` refreshes the partials (`ln_out`) for the next norm -- also the next block's, unless `last`."""
@@ -419,7 +421,7 @@ class _Net:
         m = A.mark()
         fold = lnst is not None
         if self.fp8_act and not fold and C % 128 == 0 and isinstance(w[p + ".attn1.qkv.w"], ops.Fp8Weight) and h.dtype == F16:
-            assert self.pag is None           # (set_pag refuses fp8 engines)
+            assert self.pag is None and self.seg is None           # (set_pag / set_seg refuse fp8 engines)
             self._tblock_fp8(p, h, R, T, heads, st)
             A.release(m)
             return
@@ -438,6 +440,12 @@ class _Net:
         a = A.alloc(M, C)
         # PAG: the perturbed rows [ident_from, R) of a selected attn1 get the identity attention map, a = v, in the same launch
         ident = self.pag[1] if self.pag is not None and (p + ".attn1") in self.pag[0] else 0
+        # SEG: the queries of the perturbed rows [first, R) of a selected attn1 are blurred over the token grid, in place in the
+        # q columns the projection just wrote; the attention launch then is the plain one for every row
+        sg = self.seg
+        if sg is not None and (p + ".attn1") in sg.paths:
+            wy, wx = (None, None) if sg.mean else (sg.taps[grid[0]], sg.taps[grid[1]])
+            o.seg_blur_q(qk[sg.first * T:, :C], R - sg.first, grid[0], grid[1], wy, wx, mean=sg.mean)
         o.attention(qk[:, :C], a, [(qk[:, C:], T, vt, T, T)], R, heads, T, q_prescaled=True, ident_from=ident)
         o.gemm(a, w[p + ".attn1.to_out.0.w"], h, bias=w[p + ".attn1.to_out.0.b"], res=h,
                prefetch=self._pf(w[p + ".attn1.to_out.0.w"]), ln_out=lnst)
@@ -532,7 +540,8 @@ class _Net:
                 lnst = A.alloc(parts.pop() * R * T, 4).view(torch.float32).view(-1, R * T, 2)      # (parts, M, 2) fp32
         o.gemm(g, w[path + ".proj_in.w"], h, bias=w[path + ".proj_in.b"], ln_out=lnst)
         for k in range(depth):
-            self._tblock(f"{path}.transformer_blocks.{k}", h, R, T, C // self.cfg.head_dim, st, ada, lnst, last=k == depth - 1)
+            self._tblock(f"{path}.transformer_blocks.{k}", h, R, T, C // self.cfg.head_dim, st, ada, lnst, last=k == depth - 1,
+                         grid=(H, W))
         o.gemm(h, w[path + ".proj_out.w"], out, bias=w[path + ".proj_out.b"], res=x, gn_out=p_out)
         A.release(m)
         return out
@@ -600,6 +609,14 @@ class _Net:
         return x, H, W, skips
 
 
+class _SegState:
+    """What `_tblock` needs to perturb a selected attn1 the SEG way: the selected paths, the first perturbed batch row, and the
+    Gaussian taps per axis extent as fp32 device vectors (`mean`: the sigma -> inf form, no taps)."""
+
+    def __init__(self, paths, first, mean, taps):
+        self.paths, self.first, self.mean, self.taps = frozenset(paths), int(first), bool(mean), taps
+
+
 class HipUNet(_Net):
     """SDXL UNet with TA-IP cross-attention.  `lora`/`lora_scaling` build the previewer weight set."""
 
@@ -636,6 +653,31 @@ class HipUNet(_Net):
         if int(ident_from) < 1:
             raise ValueError(f"set_pag: ident_from must be >= 1, got {ident_from}")
         self.pag = (frozenset(paths), int(ident_from))
+
+    def set_seg(self, paths, first, sigma=seg.DEFAULT_SEG_BLUR_SIGMA, H=None, W=None):
+        """Smoothed-energy guidance: in every `attn1` named in `paths`, the queries of the batch rows [first, R) of a forward on
+        an H x W latent are blurred over the token grid with a Gaussian of `sigma` (`seg.weights`; beyond `seg.MEAN_ABOVE` the
+        image's mean query) before a plain attention; every other launch is unchanged.  `paths` None / empty: off.  The taps
+        of a (sigma, extent) pair are packed once and kept, so launches captured into a graph keep reading valid memory.
+        An engine built with fp8 linears, PAG set on the same engine and a grid beyond `seg.MAX_EXTENT` are refused (ValueError)."""
+        if not paths:
+            self.seg = None
+            return
+        seg.check_engine(self)
+        if self.pag is not None:
+            raise ValueError("set_seg: perturbed-attention guidance is set on this UNet; both claim the perturbed rows")
+        if int(first) < 1:
+            raise ValueError(f"set_seg: first must be >= 1, got {first}")
+        sigma = seg.check_sigma(sigma)
+        seg.check_grids(self.cfg, paths, H, W)
+        mean, taps = seg.is_mean(sigma), {}
+        if not mean:
+            cache = self.__dict__.setdefault("_seg_taps", {})
+            for n in {n for hw in seg.level_grids(self.cfg, H, W) for n in hw}:
+                if (sigma, n) not in cache:
+                    cache[(sigma, n)] = torch.tensor(seg.weights(sigma, n), dtype=torch.float64).to(torch.float32).to(self.device)
+                taps[n] = cache[(sigma, n)]
+        self.seg = _SegState(paths, first, mean, taps)
 
     # ---- Resampler (runs once per image batch) ------------------------------------------------
     def _pack_resampler(self, sd):

@@ -139,6 +139,12 @@ def build_parser():
                    help="PAG adaptive scale: s_t = max(pag_scale - pag_adaptive_scale * (1000 - t), 0)")
     p.add_argument("--pag_layers", type=str, default="mid",
                    help="comma-separated PAG layer expressions over the UNet's self-attention names (default mid), e.g. mid,up_blocks.0")
+    p.add_argument("--seg_scale", type=float, default=0.0,
+                   help="smoothed-energy guidance scale; 0 (default) = off, > 0 calls pipe.enable_seg(--seg_layers, --seg_blur_sigma)")
+    p.add_argument("--seg_blur_sigma", type=float, default=100.0,
+                   help="SEG: sigma of the Gaussian blur of the perturbed rows' queries, in tokens (default 100; inf = the mean query)")
+    p.add_argument("--seg_layers", type=str, default="mid",
+                   help="comma-separated SEG layer expressions over the UNet's self-attention names (default mid), e.g. mid,up_blocks.0")
     p.add_argument("--apg", type=float, nargs=3, default=None, metavar=("ETA", "NORM_THRESHOLD", "MOMENTUM"),
                    help="adaptive projected guidance (pipe.enable_apg(eta, norm_threshold, momentum)); off by default. "
                         "The pipeline's defaults: 0.0 15.0 -0.5")
@@ -221,6 +227,19 @@ def apply_freeu(pipe, args):
         pipe.enable_freeu(*args.freeu)
 
 
+def apply_seg(pipe, args):
+    """`--seg_scale S` (> 0) -> pipe.enable_seg(--seg_layers split at commas, --seg_blur_sigma); returns the call's SEG keyword
+    arguments (an addition: the reference has no SEG).  With `--pag_scale` as well, enable_seg refuses (ValueError)."""
+    scale = float(getattr(args, "seg_scale", 0.0) or 0.0)
+    if scale < 0:
+        raise SystemExit(f"--seg_scale must be >= 0, got {scale}")
+    if scale == 0:
+        return {}
+    layers = [e.strip() for e in str(getattr(args, "seg_layers", "mid") or "").split(",") if e.strip()]
+    pipe.enable_seg(layers, getattr(args, "seg_blur_sigma", 100.0))
+    return {"seg_scale": scale}
+
+
 def apply_pag(pipe, args):
     """`--pag_scale S` (> 0) -> pipe.enable_pag(--pag_layers split at commas); returns the call's PAG keyword arguments (an
     addition: the reference has no PAG).  `--pag_adaptive_scale` without `--pag_scale` is refused."""
@@ -285,6 +304,7 @@ def main(args, device, rank=0, world=1):
     apply_freeu(pipe, args)
     apply_scheduler(pipe, args)
     pag_kw = apply_pag(pipe, args)
+    pag_kw.update(apply_seg(pipe, args))
     apply_apg(pipe, args)
     pag_kw.update(apply_color_fix(args))
     apply_vae_flash_attention(pipe, args)

@@ -139,6 +139,7 @@ SIGNATURES = {
     "iir_freeu_stats_f16": (C.c_int, [_P, _I64, _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _I64, _P]),
     "iir_freeu_concat_f16": (C.c_int, [_P, _I64, _I32, _P, _I64, _P, _I64, _I32, _P, _I64, _P, _I64, _I32, _I32, _F, _F, _P, _I64,
                                        _P, _I64, _I64, _P]),
+    "iir_seg_blur_q_f16": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _I32, _P]),
     "iir_pack_latent": (C.c_int, [_P, _I32, _I32, _I32, _P, _I64, _I32, _F, _P]),
     "iir_unpack_latent": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P]),
     "iir_pack_latent_t": (C.c_int, [_P, _I32, _I32, _I32, _P, _I64, _I32, _F, _I32, _P]),

@@ -645,6 +645,26 @@ def freeu_concat(x, skip, dst, partials, H, W, b, s, dst_off=0, mid_add=None, ad
     return dst
 
 
+SEG_MAX_EXTENT = 128      # IIR_SEG_MAX_EXTENT
+
+
+def seg_blur_q(q, images, H, W, wy=None, wx=None, mean=False):
+    """Smoothed-energy guidance: blur the (images * H * W, C) query view `q` (a column slice of the q | k buffer, starting at
+    the first perturbed row) over the H x W token grid, in place: fp32 taps `wy` (along H) and `wx` (along W), reflect border;
+    `mean`: every token becomes its image's mean instead (the taps are not read)."""
+    _chk2d(q, "q")
+    M, Cc = q.shape
+    if M != images * H * W:
+        raise ValueError(f"seg_blur_q: q has {M} rows, {images} images of {H} x {W} tokens need {images * H * W}")
+    if not mean:
+        for name, t in (("wy", wy), ("wx", wx)):
+            if t is None or t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"seg_blur_q: {name} must be a contiguous 1-D fp32 CUDA tensor")
+    L.check(L.load().iir_seg_blur_q_f16(q.data_ptr(), q.stride(0), images, H, W, Cc, _p(wy), 0 if wy is None else wy.numel(),
+                                        _p(wx), 0 if wx is None else wx.numel(), int(bool(mean)), _stream()), "iir_seg_blur_q_f16")
+    return q
+
+
 def pack_latent(x, out, rep=1, scale=1.0):
     """x fp32 (B,C,H,W) contiguous -> out 2-D fp16 view (rep*B*H*W, ld>=C).  `scale`: a float, or an fp32 CUDA tensor (one
     element) read at launch time (iir_pack_latent_dscale)."""

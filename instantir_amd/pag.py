@@ -24,34 +24,34 @@ def attn1_paths(cfg) -> List[str]:
     return out
 
 
-def normalize_layers(layers: Union[str, Sequence[str]]) -> List[str]:
+def normalize_layers(layers: Union[str, Sequence[str]], what: str = "pag_applied_layers") -> List[str]:
     if isinstance(layers, str):
         layers = [layers]
     layers = list(layers)
     if not layers:
-        raise ValueError("pag_applied_layers is empty: name at least one layer (e.g. 'mid')")
+        raise ValueError(f"{what} is empty: name at least one layer (e.g. 'mid')")
     for e in layers:
         if not isinstance(e, str) or not e:
-            raise ValueError(f"pag_applied_layers entries must be non-empty strings, got {e!r}")
+            raise ValueError(f"{what} entries must be non-empty strings, got {e!r}")
     return layers
 
 
-def select(layers: Union[str, Sequence[str]], paths: Iterable[str]) -> List[str]:
+def select(layers: Union[str, Sequence[str]], paths: Iterable[str], what: str = "pag_applied_layers") -> List[str]:
     """The `attn1` paths selected by `layers`: each entry is a regular expression, and a path is selected when it contains a
     match of it that ends at a '.', at a '_' or at the end of the name ('down_blocks.1' never selects 'down_blocks.10...',
     'blocks.1' never 'blocks.10', 'up_blocks.0.att' nothing; '_' lets 'mid' select 'mid_block...').  An entry that selects
-    nothing, or an empty list, raises ValueError naming it."""
-    layers = normalize_layers(layers)
+    nothing, or an empty list, raises ValueError naming it (and `what`, the argument the list came from)."""
+    layers = normalize_layers(layers, what)
     paths = list(paths)
     chosen = set()
     for e in layers:
         try:
             rx = re.compile(f"(?:{e})(?=[._]|$)")
         except re.error as err:
-            raise ValueError(f"pag_applied_layers entry {e!r} is not a regular expression: {err}") from None
+            raise ValueError(f"{what} entry {e!r} is not a regular expression: {err}") from None
         hit = [p for p in paths if rx.search(p)]
         if not hit:
-            raise ValueError(f"pag_applied_layers entry {e!r} selects no self-attention layer of the UNet")
+            raise ValueError(f"{what} entry {e!r} selects no self-attention layer of the UNet")
         chosen.update(hit)
     return [p for p in paths if p in chosen]
 

@@ -20,6 +20,9 @@ Observable deviations, all documented in SURVEY.md Appendix C and DESIGN.md:
       `ip_adapter_image_embeds` always trips its own "provide either ... or ..." check (:850-853); here the default is
       applied only when no embeds are given, so the embeds path (the parity hook) is usable.
 Latents are carried in fp32 between steps (the reference carries fp16); UNet inputs are fp16.
+Guidance additions the reference does not have: perturbed-attention guidance (`enable_pag`), adaptive
+projected guidance (`enable_apg`) and smoothed-energy guidance (`enable_seg`, `seg_scale`: the perturbed rows of PAG with their
+queries Gaussian-blurred over the token grid instead of an identity attention map; PAG and SEG exclude each other).
 """
 from __future__ import annotations
 
@@ -31,7 +34,7 @@ from typing import Callable, Dict, List, Optional, Union
 
 import torch
 
-from . import ops, pag
+from . import ops, pag, seg
 from . import restore_map as rmap
 from .config import UNetConfig, VAEConfig
 from .engine import CPAD, F16, HipAggregator, HipUNet
@@ -189,6 +192,8 @@ class InstantIRPipeline:
         self._freeu = None                          # (s1, s2, b1, b2) or None: see enable_freeu
         self._pag_layers = None                     # perturbed-attention guidance: the layer list of enable_pag, or None
         self._pag_paths = None                      # ... and the main UNet's `attn1` paths it selects
+        self._seg_layers = self._seg_paths = None   # smoothed-energy guidance: the same pair for enable_seg ...
+        self._seg_sigma = None                      # ... and its blur sigma
         self._apg = None                            # adaptive projected guidance: (eta, norm_threshold, momentum) or None
 
     # ---- reference surface ----------------------------------------------------------------------
@@ -327,6 +332,9 @@ class InstantIRPipeline:
         """Turn PAG on for later calls (`pag_scale`, default 3.0; `pag_adaptive_scale`).  Each entry of `pag_applied_layers` is a
         regular expression over the main UNet's self-attention module names (e.g. 'mid', 'down_blocks.2', 'up_blocks.0',
         'up_blocks.1.attentions.2'); see `instantir_amd.pag.select`."""
+        if self._seg_layers is not None:
+            raise ValueError("enable_pag: smoothed-energy guidance is enabled and both methods claim the one perturbed row group; "
+                             "call pipe.disable_seg() first")
         if self._unet is not None:
             pag.check_engine(self._unet)
         self.set_pag_applied_layers(pag_applied_layers)
@@ -342,6 +350,39 @@ class InstantIRPipeline:
     @property
     def pag_applied_layers(self):
         return None if self._pag_layers is None else list(self._pag_layers)
+
+    # ---- smoothed-energy guidance (SEG; Hong 2024) ----
+    def enable_seg(self, seg_applied_layers: Union[str, List[str]] = "mid", seg_blur_sigma: float = seg.DEFAULT_SEG_BLUR_SIGMA):
+        """Turn SEG on for later calls (`seg_scale`, default 3.0): the main UNet runs one more row group whose queries, in the
+        self-attention layers `seg_applied_layers` selects (the expressions of `enable_pag`), are blurred over the token grid by a
+        Gaussian of `seg_blur_sigma` (> 0; beyond 9999, `math.inf` included, the image's mean query), and the step adds
+        seg_scale * (cond - perturbed).  Needs no prompt and no CFG.  PAG and SEG exclude each other."""
+        if self._pag_layers is not None:
+            raise ValueError("enable_seg: perturbed-attention guidance is enabled and both methods claim the one perturbed row group; "
+                             "call pipe.disable_pag() first")
+        if self._unet is not None:
+            seg.check_engine(self._unet)
+        sigma = seg.check_sigma(seg_blur_sigma)
+        self.set_seg_applied_layers(seg_applied_layers)
+        self._seg_sigma = sigma
+
+    def set_seg_applied_layers(self, seg_applied_layers: Union[str, List[str]]):
+        layers = pag.normalize_layers(seg_applied_layers, "seg_applied_layers")
+        self._seg_paths = tuple(seg.select(layers, self.cfg))
+        self._seg_layers = layers
+        if self._seg_sigma is None:
+            self._seg_sigma = seg.DEFAULT_SEG_BLUR_SIGMA
+
+    def disable_seg(self):
+        self._seg_layers = self._seg_paths = self._seg_sigma = None
+
+    @property
+    def seg_applied_layers(self):
+        return None if self._seg_layers is None else list(self._seg_layers)
+
+    @property
+    def seg_blur_sigma(self):
+        return self._seg_sigma
 
     # ---- adaptive projected guidance (APG; Sadat et al. 2024, DESIGN.md section 7) ----
     def enable_apg(self, eta: float = 0.0, norm_threshold: float = 15.0, momentum: float = -0.5):
@@ -373,7 +414,7 @@ class InstantIRPipeline:
         return self._apg
 
     def _main_state(self, ctx, pooled, time_ids, img, Hl, Wl, B, rep, pag_on):
-        """`prepare` of the main UNet: with PAG one more group of B rows, each a copy of its cond row (rows [(rep-1)B, rep B)
+        """`prepare` of the main UNet: with PAG or SEG (`pag_on`) one more group of B rows, each a copy of its cond row (rows [(rep-1)B, rep B)
         of the prompt embeddings, pooled embeddings, time ids and IP tokens)."""
         ip = self._unet.resampler(img)
         if pag_on:
@@ -452,7 +493,7 @@ class InstantIRPipeline:
         self._apply_freeu(self._unet, self._unet_prev)
 
     def _loop_for(self, B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale, pag_on=False,
-                  fresh=False, keep=None, apg_on=False):
+                  fresh=False, keep=None, apg_on=False, seg_on=False):
         """The step's buffers and captured hipGraphs are kept from one call to the next: a second image of the same geometry,
         through the same engines, re-uses them (its hoisted K / V, embeddings and LQ latent are copied into the captured
         tensors) instead of paying the warm-up step, the capture and the graph instantiation again (~0.1 s of a 1.9 s call
@@ -463,7 +504,8 @@ class InstantIRPipeline:
                self.overlap_sft, tuple(None if n is None else (id(n), n.arena_gen, n.inkernel_prefetch) for n in nets),
                self._freeu,           # the FreeU factors are launch arguments of the captured concats
                _sched_form(self.scheduler),   # the sigma schedulers launch the device-scale pack and the history step
-               self._pag_paths if pag_on else None,     # PAG: row count and the identity launches (its scale is a device scalar)
+               self._pag_paths if pag_on and not seg_on else None,   # PAG: row count and the identity launches (its scale is a device scalar)
+               (self._seg_paths, self._seg_sigma) if seg_on else None,   # SEG: row count, the blur launches and their taps (likewise)
                keep is not None,      # a restore map: the step's last launch carries IIR_STEP_KEEP, on buffers only such a loop has
                bool(apg_on))          # APG: iir_apg_project + IIR_STEP_APG in the step (its three parameters travel in the scalar row)
         if not fresh:
@@ -709,8 +751,9 @@ class InstantIRPipeline:
 
     # ---- the call: its stages, in the reference's order -----------------------------------------------------------
     def _check_call(self, color_fix, output_type, cross_attention_kwargs, pag_scale, pag_adaptive_scale, multistep_restore,
-                    guidance_scale=None, guidance_rescale=0.0):
-        """Checks of the arguments `check_inputs` does not see -> (LoRA scale, `pag_scale` with its default, whether PAG runs)."""
+                    guidance_scale=None, guidance_rescale=0.0, seg_scale=None):
+        """Checks of the arguments `check_inputs` does not see -> (LoRA scale, `pag_scale` with its default, whether PAG runs,
+        `seg_scale` with its default, whether SEG runs)."""
         self._check_color_fix(color_fix, output_type)
         if self._apg is not None:
             if guidance_scale is not None and not guidance_scale > 1:
@@ -737,10 +780,15 @@ class InstantIRPipeline:
         if self._pag_layers is not None:
             pag_scale = pag.DEFAULT_PAG_SCALE if pag_scale is None else float(pag_scale)
         pag_on = self._pag_layers is not None and pag_scale > 0
+        if self._seg_layers is None and seg_scale is not None:
+            raise ValueError("seg_scale needs smoothed-energy guidance: call pipe.enable_seg(...) first")
+        if self._seg_layers is not None:
+            seg_scale = seg.check_scale(seg.DEFAULT_SEG_SCALE if seg_scale is None else seg_scale)
+        seg_on = self._seg_layers is not None and seg_scale > 0
         if multistep_restore:
             raise NotImplementedError("multistep_restore passes kwargs the shipped DDPM scheduler does not accept "
                                       "(SURVEY.md Appendix C Q5)")
-        return lora_mult, pag_scale, pag_on
+        return lora_mult, pag_scale, pag_on, seg_scale, seg_on
 
     def _embedding_rows(self, prompt, prompt_2, negative_prompt, negative_prompt_2, ids, prompt_embeds, negative_prompt_embeds,
                         pooled_prompt_embeds, negative_pooled_prompt_embeds, do_cfg, clip_skip, nipp):
@@ -903,7 +951,7 @@ class InstantIRPipeline:
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"], previewer_scheduler=None,
                  reference_latents=None, init_noise=None, step_noises=None, pag_scale: Optional[float] = None,
                  pag_adaptive_scale: float = 0.0, color_fix: Optional[str] = None, color_fix_reference=None, restore_map=None,
-                 map_feather: int = 4, **kwargs):
+                 map_feather: int = 4, seg_scale: Optional[float] = None, **kwargs):
         """Keyword arguments and defaults of pipelines/sdxl_instantir.py:1067-1115.  Two additions for
         bit-reproducible parity runs: `init_noise` (the randn of init_latents) and
         `step_noises` (list of per-step DDPM / Euler-ancestral / DPM++ SDE noises) replace draws from `generator` when given.
@@ -911,6 +959,8 @@ class InstantIRPipeline:
         `image` must be the LQ *latent* (B,4,h,w) here unless a VAE is attached (`image.shape[1] == 4` branch of :1369-1382).
         `pag_scale` / `pag_adaptive_scale` (an addition, after diffusers' PAG pipelines): need `enable_pag`; `pag_scale` None
         means 3.0, and PAG runs when it is > 0 (s_t = max(pag_scale - pag_adaptive_scale * (1000 - t), 0) per step).
+        `seg_scale` (an addition, smoothed-energy guidance): needs `enable_seg`; None means 3.0, SEG runs when it is > 0, and the
+        scale is the same at every step.
         `color_fix` (an addition, after StableSR's colour fixes): None, "wavelet" or "adain" transfers the colour of the LQ image
         onto the final images (never the preview row) after the VAE decode.  The reference is the pixel `image` mapped to
         [0, 1] unless `color_fix_reference` (a [0, 1] tensor or PIL image(s) of the output size) is given.
@@ -926,8 +976,11 @@ class InstantIRPipeline:
         pixel bit for bit.  None touches nothing."""
         if restore_map is not None:
             map_feather = rmap.check_feather(map_feather)
-        lora_mult, pag_scale, pag_on = self._check_call(color_fix, output_type, cross_attention_kwargs, pag_scale, pag_adaptive_scale,
-                                                        multistep_restore, guidance_scale, guidance_rescale)
+        lora_mult, pag_scale, pag_on, seg_scale, seg_on = self._check_call(
+            color_fix, output_type, cross_attention_kwargs, pag_scale, pag_adaptive_scale, multistep_restore, guidance_scale,
+            guidance_rescale, seg_scale)
+        if seg_on:       # SEG rides PAG's row group, step forms and scalar slot: from here on it is "PAG" with a constant scale
+            pag_on, pag_scale, pag_adaptive_scale = True, seg_scale, 0.0
         ids_given = prompt is None and prompt_embeds is None and kwargs.get("prompt_ids") is not None and self.text_encoder is not None
         prompt_embeds_chk = kwargs["prompt_ids"] if ids_given else prompt_embeds      # ids stand in for the prompt in the exclusivity checks
         self.check_inputs(prompt, prompt_embeds_chk, negative_prompt_embeds,
@@ -974,7 +1027,8 @@ class InstantIRPipeline:
             if will_composite:
                 composite = (self._color_fix_reference(None, image, B, nipp), m, map_feather)
 
-        self._unet.set_pag(self._pag_paths if pag_on else None, rep * B)          # (refuses an fp8 engine)
+        self._unet.set_pag(self._pag_paths if pag_on and not seg_on else None, rep * B)          # (refuses an fp8 engine)
+        self._unet.set_seg(self._seg_paths if seg_on else None, rep * B, self._seg_sigma, Hl, Wl)  # (and a grid beyond the blur's limit)
         ids = list(original_size or (height, width)) + list(crops_coords_top_left) + list(target_size or (height, width))     # :965-981
         neg_ids = ids
         if negative_original_size is not None and negative_target_size is not None:   # :1445-1454
@@ -1000,7 +1054,8 @@ class InstantIRPipeline:
             prev = self._unet_prev
             st_prev = None if prev is None else prev.prepare(ctx_, pooled, time_ids, prev.resampler(img), Hl, Wl)
             return self._loop_for(B, rep, Hl, Wl, st, st_prev, st_agg, lq, reference_latents, previewer_scheduler, guidance_rescale,
-                                  pag_on, fresh=fresh, keep=keep_box[0] if keep_box else None, apg_on=self._apg is not None)
+                                  pag_on, fresh=fresh, keep=keep_box[0] if keep_box else None, apg_on=self._apg is not None,
+                                  seg_on=seg_on)
 
         x, noise0 = self._initial_latents(self.scheduler, lq, ts[0], generator, init_noise, init_latents_with_lq, latents)
         if keep_map is not None:
