@@ -15,14 +15,19 @@ def denoise(P, PA, lora, cfg, lq, prompt_embeds, pooled, image_embeds, *, negati
             init_noise=None, step_noises=None, controlnet_conditioning_scale=1.0, control_guidance_start=0.0,
             control_guidance_end=1.0, preview_start=0.0, preview_end=1.0, use_previewer=True, trace=None,
             guidance_rescale=0.0, negative_time_ids=None, adastep_restore=False, reference_latents=None,
-            denoising_end=None, timesteps=None, resume=None, on_step=None):
+            denoising_end=None, timesteps=None, resume=None, on_step=None, main_unet=None, guide=None):
     """Returns the final latents (B,4,h,w).  `lq`: LQ latent (B,4,h,w); `image_embeds`: (2,B,S,E) [neg;pos] under CFG
     (pipelines/sdxl_instantir.py:700-707) else (1,B,S,E).  `trace` (dict) collects per-step tensors when given.
     The loop body follows :1497-1660 statement by statement, including the quirk that a step which skips the
     previewer / Aggregator re-scales the PREVIOUS step's already scaled residuals (:1602-1603).
     Test plumbing (no reference counterpart): `resume = (x, i0, i1)` continues a chain from the latents `x` it had before step
     i0 and stops before step i1 (a default-settings chain carries no other state from step to step: tools/parity_chain30.py runs
-    30 steps at 1024^2 in several sittings); `on_step(i, x)` is called with the latents after every step."""
+    30 steps at 1024^2 in several sittings); `on_step(i, x)` is called with the latents after every step.
+    Guidance methods the reference does not have (PAG, SEG, APG: tests/loop_ref.py) enter through two hooks.
+    `main_unet(P, cfg, xin, t, ctx, text_embeds, tid, ip_main, down, mid) -> e` replaces the one main-UNet call (never the
+    previewer's) and may return more groups of B rows than it was given ([u;] c; p).  `guide(rows, i, t, x, coef) -> eps` replaces
+    only the combination u + g (c - u) (without CFG: the identity): `rows` the tuple of B-row groups, `i` the step index, `x` the
+    step's latents, `coef` = (sigma_t, alpha_t) = ((1 - acp[t]) ** 0.5, acp[t] ** 0.5).  guidance_rescale follows it, c the text prediction."""
     B = lq.shape[0]
     do_cfg = guidance_scale > 1                                            # :1050-1051
     acp = sched.make_alphas_cumprod()
@@ -80,14 +85,17 @@ def denoise(P, PA, lora, cfg, lq, prompt_embeds, pooled, image_embeds, *, negati
             raise NameError("down_block_res_samples")                       # the reference's own failure on step 0 (Q2)
         down = [s * cond_scale for s in down]                                # :1602  (re-scales stale residuals when skipped)
         mid = mid * cond_scale                                               # :1603
-        eps = nets.unet_forward(P, cfg, xin, t, ctx, text_embeds, tid, ip_main, down, mid)              # :1606-1616
+        eps = (main_unet or nets.unet_forward)(P, cfg, xin, t, ctx, text_embeds, tid, ip_main, down, mid)   # :1606-1616
+        rows = eps.chunk(eps.shape[0] // B)                                  # [u;] c, and what a `main_unet` hook appended
         if do_cfg:                                                           # :1619-1621
-            u, c = eps.chunk(2)
-            eps = u + guidance_scale * (c - u)
+            u, c = rows[:2]
+            eps = u + guidance_scale * (c - u) if guide is None else guide(rows, i, t, x, ((1 - acp[t]) ** 0.5, acp[t] ** 0.5))
             if guidance_rescale > 0.0:                                       # rescale_noise_cfg, :181-192 (called at :1623-1626)
                 dims = list(range(1, c.ndim))
                 std_text, std_cfg = c.std(dim=dims, keepdim=True), eps.std(dim=dims, keepdim=True)
                 eps = guidance_rescale * (eps * (std_text / std_cfg)) + (1 - guidance_rescale) * eps
+        elif guide is not None:
+            eps = guide(rows, i, t, x, ((1 - acp[t]) ** 0.5, acp[t] ** 0.5))
         if sampler == "ddim":
             x_next, x0 = sched.ddim_step(acp, eps, t, x, n_steps, eta=eta, noise=None if step_noises is None else step_noises[i])
         else:

@@ -1,22 +1,21 @@
 """GPU: adaptive projected guidance (APG) -- iir_apg_project and iir_sched_step_apg through `ops` against the fp64 restatement
 of tests/apg_ref.py, their bit properties, and the denoising loop against an APG'd fp32 CPU oracle.
 
-The oracle gets APG without editing oracle/: a small loop here restates oracle.pipeline.denoise (DDIM) with the guided eps of
-`apg_ref.apg_eps`, and the sigma-scheduler oracle loop of tests/test_sigma_schedulers_gpu.py gets it through its main UNet
-call, as tests/test_pag_gpu.py does for PAG.
+The oracle loops (oracle.pipeline.denoise, the sigma-scheduler loop of tests/loop_ref.py) get APG through their `guide` hook:
+loop_ref.apg, the guided eps of `apg_ref.apg_eps` with its running average.
 
 Kernel tolerance (measured in the test, printed before it is asserted): the kernel's max |value - fp64| may be at most 4x the
 fp32 restatement's own max |fp32 - fp64| on the same inputs -- 4 covers fma contraction and a different but fixed summation
 order.  {s, alpha} are accumulated in fp64 and held to 1e-6 relative."""
-import math
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 import apg_ref
-import test_pag_gpu as tp
-from test_pag_gpu import dev, env  # noqa: F401  (fixtures)
+import loop_ref as lr
+from loop_ref import dev, env  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -247,7 +246,7 @@ def test_x0_is_the_kernels_own(dev):
 
 
 def test_existing_entries_keep_their_bits(dev):
-    """iir_sched_step, _hist, _pag and _keep (null APG group) against the fp32 statements of test_pag_gpu._ref_step."""
+    """iir_sched_step, _hist, _pag and _keep (null APG group) against the fp32 statements of loop_ref.ref_step."""
     from instantir_amd import ops
     B, H, W = SHAPES[0]
     HW = H * W
@@ -266,7 +265,7 @@ def test_existing_entries_keep_their_bits(dev):
                                ("iir_sched_step_pag", "linear", e_pag, dict(pag_scale=ps)),
                                ("iir_sched_step_keep", "hist", e_pag, dict(pag_scale=ps, hist=True, keep=True))):
         coef = _coef(form)
-        want, want_x0 = tp._ref_step(eg, x, coef, m if form == "hist" else None, nz)
+        want, want_x0 = lr.ref_step(eg, x, coef, m if form == "hist" else None, nz)
         prev, x0 = torch.full((B, C, H, W), 7.0, device=dev), torch.full((B, C, H, W), 7.0, device=dev)
         hist = D(m.clone()) if kw.get("hist") else None
         keep = kept = None
@@ -279,7 +278,7 @@ def test_existing_entries_keep_their_bits(dev):
         ops.sched_step(D(eps16), B, torch.tensor(coef, device=dev), D(x), prev, noise=D(nz), cfg=True, x0_out=x0,
                        pag_scale=kw.get("pag_scale"), hist=hist, keep=keep)
         torch.cuda.synchronize()
-        print(f"{name}: prev / x0 vs the fp32 statements: {tp._ulps(prev.cpu(), want):.2f} / {tp._ulps(x0.cpu(), want_x0):.2f} ulps")
+        print(f"{name}: prev / x0 vs the fp32 statements: {lr.ulps(prev.cpu(), want):.2f} / {lr.ulps(x0.cpu(), want_x0):.2f} ulps")
         assert same_bits(prev, want) and same_bits(x0, want_x0), name
         if hist is not None:
             assert same_bits(hist, want_x0), name
@@ -315,105 +314,24 @@ APG = (0.0, 6.0, -0.5)            # eta, norm_threshold, momentum of the loop te
 LOOP6 = dict(num_inference_steps=6, preview_start=0.25, control_guidance_end=0.75)
 
 
-def _apg32(u, c, x, a_prev, w, sb, sa, par, first):
-    """fp32 guided eps of the APG'd oracles -> (eps, A)"""
-    eps, A, _, _ = apg_ref.apg_eps(u, c, x, a_prev, [w, float(sb), float(sa)], par[0], par[1], 0.0 if first else par[2], fp32=True)
-    return eps.float(), A.float()
-
-
-def apg_denoise(env, par, *, guidance_scale=G, num_inference_steps=6, preview_start=0.25, control_guidance_end=0.75):
-    """oracle.pipeline.denoise (DDIM, CFG) with the guided eps of apg_ref.apg_eps; `par` None = the plain oracle."""
-    from oracle import nets, sched
-    cfg, sd, sda, lora, inp = env
-    P = {k: v.float() for k, v in sd.items()}
-    PA = {k: v.float() for k, v in sda.items()}
-    L = {k: v.float() for k, v in lora.items()}
-    L["scaling"] = 16.0 / cfg.lora_rank
-    lq, B = inp["lq"], inp["B"]
-    acp = sched.make_alphas_cumprod()
-    ts = sched.leading_timesteps(num_inference_steps)
-    n = len(ts)
-    keep, previewing = sched.gating_tables(n, 0.0, control_guidance_end, preview_start, 1.0)
-    ctx, text, image = torch.cat([inp["npe"], inp["pe"]]), torch.cat([inp["npooled"], inp["pooled"]]), torch.cat([lq] * 2)
-    tid = torch.tensor([[128.0, 128, 0, 0, 128, 128]]).repeat(2 * B, 1)
-    ip_main = nets.image_projection(P, [inp["img"]], cfg.resampler)[0]
-    ip_prev = nets.image_projection(P, [inp["img"]], cfg.resampler, L)[0]
-    x = sched.add_noise(acp, lq, inp["init_noise"], [int(ts[0])] * B)
-    down = mid = A = None
-    for i in range(n):
-        t = int(ts[i])
-        xin = torch.cat([x] * 2)
-        cond_scale = torch.cat([torch.ones(B, 1, 1, 1) * keep[i]] * 2)
-        if (cond_scale > 0.1).sum().item() > 0:
-            if previewing[i] > 0:
-                preview = sched.lcm_step(acp, nets.unet_forward(P, cfg, xin, t, ctx, text, tid, ip_prev, lora=L), t, xin)
-            else:
-                preview = image
-            down, mid = nets.aggregator_forward(PA, cfg, image, t, preview, text, tid)
-        down = [s * cond_scale for s in down]
-        mid = mid * cond_scale
-        u, c = nets.unet_forward(P, cfg, xin, t, ctx, text, tid, ip_main, down, mid).chunk(2)
-        if par is None:
-            eps = u + guidance_scale * (c - u)
-        else:
-            eps, A = _apg32(u, c, x, A, guidance_scale, (1 - acp[t]) ** 0.5, acp[t] ** 0.5, par, i == 0)
-        x, _ = sched.ddim_step(acp, eps, t, x, num_inference_steps)
-    return x
-
-
-def apg_dpm_oracle(env, par, monkeypatch, *, guidance_scale=G, n=6):
-    """The DPM++ 2M oracle loop of tests/test_sigma_schedulers_gpu.py with its main UNet call returning [u; c'], c' chosen so
-    that the loop's own u + g (c' - u) is the APG eps."""
-    import test_sigma_schedulers_gpu as sg
-    from oracle import nets
-    spec = sg.spec
-    _, sig = spec.spec_dpm_table(n, "leading", True)
-    orig = nets.unet_forward
-    state = dict(i=0, A=None)
-
-    def unet_forward(P, cfg_, xin, t, ctx, text, tid, ip, down_res=None, mid_res=None, lora=None, emb=None):
-        e = orig(P, cfg_, xin, t, ctx, text, tid, ip, down_res, mid_res, lora=lora, emb=emb)
-        if lora is not None or down_res is None:
-            return e
-        i = state["i"]
-        coef = spec.spec_dpm_coef(sig, i, spec.spec_dpm_second_order(i, n), sde=False)
-        u, c = e.chunk(2)
-        x = xin[:xin.shape[0] // 2]                                    # c_in = 1 in the VP space of DPM++
-        eps, state["A"] = _apg32(u, c, x, state["A"], guidance_scale, np.float32(coef[0]), np.float32(coef[1]), par, i == 0)
-        state["i"] = i + 1
-        return torch.cat([u, u + (eps - u) / guidance_scale])
-    if par is not None:
-        monkeypatch.setattr(nets, "unet_forward", unet_forward)
-    try:
-        return sg._oracle(env, "dpm", n, guidance_scale=guidance_scale, karras=True, **sg.PHASES)
-    finally:
-        monkeypatch.setattr(nets, "unet_forward", orig)
+def _oracles(env, loop, **kw):
+    """(APG'd, plain) of an oracle loop"""
+    return loop(env, guidance_scale=G, guide=lr.apg(G, APG), **kw), loop(env, guidance_scale=G, **kw)
 
 
 def _apg_pipe(env, par=APG, sched=None):
-    pipe = tp._pipe(env, sched)
+    pipe = lr.pipe(env, sched)
     if par is not None:
         pipe.enable_apg(*par)
     return pipe
 
 
-def _call(pipe, inp, **kw):
-    return tp._call(pipe, inp, **{"guidance_scale": G, **LOOP6, **kw})
-
-
-def psnr(got, want, name=None):
-    from conftest import record_psnr
-    mse = ((got.double() - want.double()) ** 2).mean().item()
-    peak = want.abs().max().item()
-    v = 10 * math.log10(peak * peak / max(mse, 1e-30))
-    if name:
-        record_psnr("apg." + name, v)
-    return v
+_call = functools.partial(lr.call, guidance_scale=G, **LOOP6)
 
 
 def _check_loop(tag, got, want, plain):
-    p_or = psnr(plain, want)
-    p, p_plain = psnr(got, want, tag.split()[0]), psnr(got, plain)
+    p_or = lr.psnr(plain, want)
+    p, p_plain = lr.psnr(got, want, "apg." + tag.split()[0]), lr.psnr(got, plain)
     print(f"{tag}: latent PSNR vs APG'd oracle {p:.1f} dB, vs plain oracle {p_plain:.1f} dB; the two oracles {p_or:.1f} dB apart")
     assert p_or < 40.0, p_or                                           # on CPU values alone: a no-op implementation cannot pass
     assert torch.isfinite(got).all() and p >= BAR, p
@@ -422,24 +340,22 @@ def _check_loop(tag, got, want, plain):
 
 def test_loop_matches_apg_oracle(env):
     """Six DDIM steps through every phase (Aggregator-only head, previewed middle, creative tail)."""
-    want, plain = apg_denoise(env, APG), apg_denoise(env, None)
+    want, plain = _oracles(env, lr.denoise, **LOOP6)
     got = _call(_apg_pipe(env), env[4])
     _check_loop("ddim", got, want, plain)
 
 
-def test_dpmpp_2m_karras_matches_apg_oracle(env, monkeypatch):
-    import test_sigma_schedulers_gpu as sg
-    want, plain = apg_dpm_oracle(env, APG, monkeypatch), apg_dpm_oracle(env, None, monkeypatch)
-    got = _call(_apg_pipe(env, sched=sg._sched("dpm", karras=True)), env[4])
+def test_dpmpp_2m_karras_matches_apg_oracle(env):
+    want, plain = _oracles(env, lr.sigma_denoise, kind="dpm", n=6, karras=True, **lr.PHASES)
+    got = _call(_apg_pipe(env, sched=lr.sigma_sched("dpm", karras=True)), env[4])
     _check_loop("dpmpp_2m karras", got, want, plain)
 
 
 def test_graphs_on_off_and_repeat_calls_bit_identical(env):
     """A second call on the cached loop equals the first (the average is reset and beta_t is 0 again), with and without graphs,
     in both scheduler forms."""
-    import test_sigma_schedulers_gpu as sg
     inp = env[4]
-    for sched in (None, sg._sched("dpm", karras=True)):
+    for sched in (None, lr.sigma_sched("dpm", karras=True)):
         pipe = _apg_pipe(env, sched=sched)
         a = _call(pipe, inp, num_inference_steps=3)
         b = _call(pipe, inp, num_inference_steps=3)

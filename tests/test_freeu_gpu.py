@@ -4,27 +4,20 @@
 The oracle is the fp32 torch.fft restatement in tests/test_freeu_cpu.py, which is pinned to the reference's own outputs
 (tests/golden/freeu.npz).  The whole-loop tests FreeU the CPU oracle by swapping `oracle.nets.up_block` for a wrapper that
 applies that restatement by `up_blocks.{i}` index (oracle/ itself is not edited)."""
-import math
+import functools
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+import loop_ref as lr
+from loop_ref import dev, env  # noqa: F401  (fixtures)
 from test_freeu_cpu import apply_freeu, fourier_filter
 
 pytestmark = pytest.mark.gpu
 
 SDXL = (0.9, 0.2, 1.3, 1.4)      # s1, s2, b1, b2: diffusers' SDXL values
 BAR = 50.0
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from instantir_amd import lib
-    lib.load()
-    return torch.device("cuda:0")
 
 
 def _ulp16(a):
@@ -147,14 +140,7 @@ def test_kernels_reproducible_beside_a_busy_stream(dev):
 
 
 # ---- through the pipeline -----------------------------------------------------------------------------------------------
-def psnr(got, want):
-    import inspect
-    from conftest import record_psnr
-    mse = ((got - want) ** 2).mean().item()
-    peak = want.abs().max().item()
-    v = 10 * math.log10(peak * peak / max(mse, 1e-30))
-    record_psnr("freeu." + inspect.stack()[1].function, v)
-    return v
+psnr = lr.psnr_by_caller("freeu")
 
 
 def freeu_up_block(factors):
@@ -177,68 +163,18 @@ def freeu_up_block(factors):
     return up_block
 
 
-@pytest.fixture(scope="module")
-def env(dev):
-    from instantir_amd import weights as W
-    from instantir_amd.config import UNetConfig
-    cfg = UNetConfig.tiny()
-    sd = W.synth_state_dict(W.unet_specs(cfg), 11)
-    sda = W.synth_state_dict(W.aggregator_specs(cfg), 12)
-    lora = W.synth_state_dict(W.lora_specs(cfg), 13)
-    g = torch.Generator().manual_seed(42)
-    B, H = 2, 16
-    inp = dict(
-        B=B, H=H,
-        lq=torch.randn(B, 4, H, H, generator=g) * 0.8,
-        pe=torch.randn(B, cfg.text_len, cfg.cross_attention_dim, generator=g).half().float(),
-        pooled=torch.randn(B, cfg.pooled_dim, generator=g).half().float(),
-        npe=torch.randn(B, cfg.text_len, cfg.cross_attention_dim, generator=g).half().float(),
-        npooled=torch.randn(B, cfg.pooled_dim, generator=g).half().float(),
-        img=torch.randn(2, B, cfg.resampler.seq_len, cfg.resampler.embedding_dim, generator=g).half().float(),
-        init_noise=torch.randn(B, 4, H, H, generator=g),
-    )
-    return cfg, sd, sda, lora, inp
-
-
-def _oracle(cfg, sd, sda, lora, inp, **kw):
-    from oracle import pipeline as OP
-    P = {k: v.float() for k, v in sd.items()}
-    PA = {k: v.float() for k, v in sda.items()}
-    L = {k: v.float() for k, v in lora.items()}
-    L["scaling"] = 16.0 / cfg.lora_rank
-    return OP.denoise(P, PA, L, cfg, inp["lq"], inp["pe"], inp["pooled"], inp["img"], negative_prompt_embeds=inp["npe"],
-                      negative_pooled=inp["npooled"], init_noise=inp["init_noise"], **kw)
-
-
-def _pipe(cfg, sd, sda, lora):
-    from instantir_amd.pipeline import InstantIRPipeline
-    from instantir_amd.schedulers import DDIMScheduler
-    pipe = InstantIRPipeline(cfg, sd, scheduler=DDIMScheduler())
-    pipe.aggregator.load_state_dict(sda)
-    pipe.prepare_previewers(lora, lora_alpha=16)
-    return pipe
-
-
-LOOP = dict(num_inference_steps=8, guidance_scale=7.0, preview_start=0.25, control_guidance_end=0.75)
-
-
-def _call(pipe, inp, **kw):
-    from instantir_amd.schedulers import LCMSingleStepScheduler
-    lcm = LCMSingleStepScheduler.from_config(pipe.scheduler.config)
-    return pipe(image=inp["lq"], prompt_embeds=inp["pe"], pooled_prompt_embeds=inp["pooled"],
-                negative_prompt_embeds=inp["npe"], negative_pooled_prompt_embeds=inp["npooled"],
-                ip_adapter_image_embeds=[inp["img"]], output_type="latent", previewer_scheduler=lcm,
-                init_noise=inp["init_noise"], **{**LOOP, **kw}).images.float().cpu()
+LOOP = dict(guidance_scale=7.0, **lr.LOOP)
+_call = functools.partial(lr.call, **LOOP)
 
 
 def test_identity_factors_bit_identical_to_off(env):
     """enable_freeu(1, 1, 1, 1) is ON (all factors truthy) and runs the FreeU kernels, yet gives the FreeU-off latents bit for
     bit: hipGraphs, two streams, all loop phases."""
     cfg, sd, sda, lora, inp = env
-    pipe = _pipe(cfg, sd, sda, lora)
+    pipe = lr.pipe(env)
     assert pipe.use_graphs and pipe.overlap_streams
     off = _call(pipe, inp)
-    pipe2 = _pipe(cfg, sd, sda, lora)
+    pipe2 = lr.pipe(env)
     pipe2.enable_freeu(1, 1, 1, 1)
     on = _call(pipe2, inp)
     assert pipe2._unet.freeu == (1.0, 1.0, 1.0, 1.0) and pipe2._unet_prev.freeu == (1.0, 1.0, 1.0, 1.0)
@@ -250,10 +186,10 @@ def test_loop_matches_freeu_oracle(env, monkeypatch):
     the FreeU'd oracle loop, and clearly (>= 6 dB) further from the plain oracle."""
     from oracle import nets
     cfg, sd, sda, lora, inp = env
-    plain = _oracle(cfg, sd, sda, lora, inp, sampler="ddim", **LOOP)
+    plain = lr.denoise(env, sampler="ddim", **LOOP)
     monkeypatch.setattr(nets, "up_block", freeu_up_block(SDXL))
-    want = _oracle(cfg, sd, sda, lora, inp, sampler="ddim", **LOOP)
-    pipe = _pipe(cfg, sd, sda, lora)
+    want = lr.denoise(env, sampler="ddim", **LOOP)
+    pipe = lr.pipe(env)
     pipe.enable_freeu(*SDXL)
     got = _call(pipe, inp)
     p, p_plain = psnr(got, want), psnr(got, plain)
@@ -265,14 +201,12 @@ def test_restore_single_step_with_freeu(env, monkeypatch):
     """restore_single_step (one previewer-LoRA pass + LCM step) with FreeU vs the FreeU'd oracle pass."""
     from oracle import nets, sched
     cfg, sd, sda, lora, inp = env
-    pipe = _pipe(cfg, sd, sda, lora)
+    pipe = lr.pipe(env)
     pipe.unet.enable_freeu(*SDXL)            # the unet-level switch: same state
     feats = inp["img"][1:]
     got = pipe.restore_single_step(inp["lq"], inp["pe"], inp["pooled"], ip_adapter_image_embeds=[feats], init_noise=inp["init_noise"],
                                    output_type="latent").images.float().cpu()
-    P = {k: v.float() for k, v in sd.items()}
-    L = {k: v.float() for k, v in lora.items()}
-    L["scaling"] = 16.0 / cfg.lora_rank
+    P, _, L = lr.params(env)
     acp = sched.make_alphas_cumprod()
     B = inp["B"]
     x = sched.add_noise(acp, inp["lq"], inp["init_noise"], [999] * B)
@@ -290,18 +224,18 @@ def test_toggling_between_calls_replays_the_right_graphs(env):
     with that setting, bit for bit."""
     cfg, sd, sda, lora, inp = env
     settings = [None, SDXL, None, (0.9, 0.5, 1.3, 1.4)]
-    pipe = _pipe(cfg, sd, sda, lora)
+    pipe = lr.pipe(env)
     for f in settings:
         if f is None:
             pipe.disable_freeu()
         else:
             pipe.enable_freeu(*f)
         got = _call(pipe, inp)
-        fresh = _pipe(cfg, sd, sda, lora)
+        fresh = lr.pipe(env)
         if f is not None:
             fresh.enable_freeu(*f)
         assert torch.equal(got, _call(fresh, inp)), f
-    assert not torch.equal(got, _call(_pipe(cfg, sd, sda, lora), inp))
+    assert not torch.equal(got, _call(lr.pipe(env), inp))
 
 
 def test_config1_geometry_one_step_with_freeu(dev, monkeypatch):

@@ -1,38 +1,26 @@
 """GPU: perturbed-attention guidance (PAG, Ahn et al. 2024) -- the identity rows of iir_attention_d64_ident_f16, the PAG forms
 of the step launches against fp32 torch, and the denoising loop against a PAG'd fp32 CPU oracle.
 
-The oracle gets PAG without editing oracle/: `oracle.nets.attn_self` is swapped for a wrapper that returns to_out(to_v(x)) for
-the perturbed rows of the selected layers, and a small loop here (the statements of oracle.pipeline.denoise) runs the main UNet
-on [uncond;] cond; perturbed rows, each perturbed row a copy of its cond row's inputs and Aggregator residuals."""
-import math
+The oracle gets PAG without editing oracle/nets.py (tests/loop_ref.py): `oracle.nets.attn_self` is swapped for a wrapper that returns
+to_out(to_v(x)) for the perturbed rows of the selected layers, the oracle loops' `main_unet` hook runs the main UNet on [uncond;]
+cond; perturbed rows, each perturbed row a copy of its cond row's inputs and Aggregator residuals, and their `guide` hook adds
+s_t (c - p)."""
+import functools
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import loop_ref as lr
+from loop_ref import dev, env, pag_oracle_attn  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
 
 BAR = 60.0
 
 
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from instantir_amd import lib
-    lib.load()
-    return torch.device("cuda:0")
-
-
-def psnr(got, want):
-    import inspect
-    from conftest import record_psnr
-    mse = ((got - want) ** 2).mean().item()
-    peak = want.abs().max().item()
-    v = 10 * math.log10(peak * peak / max(mse, 1e-30))
-    record_psnr("pag." + inspect.stack()[1].function, v)
-    return v
+psnr = lr.psnr_by_caller("pag")
 
 
 # ---- identity attention ---------------------------------------------------------------------------------------------------
@@ -96,27 +84,6 @@ def test_identity_attention_reproducible_beside_a_busy_stream(dev):
 
 
 # ---- PAG step launches ------------------------------------------------------------------------------------------------------
-def _ulps(a, b):
-    """max |a - b| in fp32 ulps of max(|a|, |b|), floored at 2^-10 of the tensor's range (as tests/test_sigma_schedulers_gpu.py)"""
-    d = (a.double() - b.double()).abs()
-    floor = max(b.abs().max().item() * 2.0 ** -10, 1e-30)
-    u = torch.finfo(torch.float32).eps * torch.maximum(a.abs(), b.abs()).double().clamp_min(floor)
-    return (d / u).max().item()
-
-
-def _ref_step(e, x, coef, m_prev, noise):
-    g, sb, sa, k0, kx, ke, kn, kh = [torch.tensor(c, dtype=torch.float32) for c in coef]
-    x0 = (x - sb * e) / sa
-    pv = k0 * x0 + kx * x
-    if float(ke) != 0:
-        pv = pv + ke * e
-    if m_prev is not None and float(kh) != 0:
-        pv = pv + kh * m_prev
-    if noise is not None and float(kn) != 0:
-        pv = pv + kn * noise
-    return pv, x0
-
-
 def _pag_eps(e, B, cfg, g, s, fac=None):
     """fp32 guided eps with the PAG term, times the rescale factor `fac` when given, in the kernels' op order; and the fp64
     rescale_noise_cfg ratio std(c) / std(eps) per image."""
@@ -167,8 +134,8 @@ def test_pag_step_matches_fp32(dev, form, cfg, phi, B, H, W):
         # the kernel's factor, as tests/test_sigma_schedulers_gpu.py does)
         want_fac = (phi * ratio + (1 - phi)).float()
         assert ((fac.cpu().double() - want_fac.double()).abs() / want_fac.double()).max().item() <= 2.0 ** -21
-    want, want_x0 = _ref_step(eg, x, coef, m if form == "hist" else None, nz)
-    assert _ulps(prev.cpu(), want) <= 4 and _ulps(x0.cpu(), want_x0) <= 4
+    want, want_x0 = lr.ref_step(eg, x, coef, m if form == "hist" else None, nz)
+    assert lr.ulps(prev.cpu(), want) <= 4 and lr.ulps(x0.cpu(), want_x0) <= 4
 
 
 @pytest.mark.parametrize("form", ["linear", "hist"])
@@ -217,163 +184,8 @@ def test_copy_segments(dev):
 
 
 # ---- the denoising loop ----------------------------------------------------------------------------------------------------
-_PAG = {"paths": None, "ident_from": 0}
-
-
-@pytest.fixture
-def pag_oracle_attn(monkeypatch):
-    """oracle.nets.attn_self with the identity map on rows [ident_from, R) of the selected layers while _PAG['paths'] is set."""
-    from oracle import nets
-    orig = nets.attn_self
-
-    def attn_self(P, path, x, heads, lora=None):
-        out = orig(P, path, x, heads, lora)
-        if _PAG["paths"] is not None and path in _PAG["paths"]:
-            k = _PAG["ident_from"]
-            out = torch.cat([out[:k], nets.linear(P, path + ".to_out.0", nets.linear(P, path + ".to_v", x[k:], lora), lora)])
-        return out
-    monkeypatch.setattr(nets, "attn_self", attn_self)
-    yield
-    _PAG["paths"] = None
-
-
-def _pag_unet(P, cfg, xin, t, ctx, text, tid, ip, down, mid, paths, B):
-    """The main UNet on [xin rows; copies of the last B (cond) rows] with the perturbed rows' self-attention the identity."""
-    from oracle import nets
-    R = xin.shape[0]
-    c = slice(R - B, R)
-    ext = lambda v: torch.cat([v, v[c]])
-    _PAG["paths"], _PAG["ident_from"] = set(paths), R
-    try:
-        return nets.unet_forward(P, cfg, ext(xin), t, ext(ctx), ext(text), ext(tid), ext(ip), [ext(d) for d in down], ext(mid))
-    finally:
-        _PAG["paths"] = None
-
-
-def pag_denoise(env, paths, *, guidance_scale, pag_scale, pag_adaptive_scale=0.0, guidance_rescale=0.0, adastep_restore=False,
-                num_inference_steps=8, preview_start=0.25, control_guidance_end=0.75):
-    """oracle.pipeline.denoise (DDIM) with PAG: eps = u + g (c - u) + s_t (c - p) (or c + s_t (c - p) without CFG), then
-    rescale_noise_cfg with c as the text prediction."""
-    from oracle import nets, sched
-    cfg, sd, sda, lora, inp = env
-    P = {k: v.float() for k, v in sd.items()}
-    PA = {k: v.float() for k, v in sda.items()}
-    L = {k: v.float() for k, v in lora.items()}
-    L["scaling"] = 16.0 / cfg.lora_rank
-    lq, B = inp["lq"], inp["B"]
-    do_cfg = guidance_scale > 1
-    acp = sched.make_alphas_cumprod()
-    ts = sched.leading_timesteps(num_inference_steps)
-    n = len(ts)
-    keep, previewing = sched.gating_tables(n, 0.0, control_guidance_end, preview_start, 1.0)
-    if do_cfg:
-        ctx, text, image = torch.cat([inp["npe"], inp["pe"]]), torch.cat([inp["npooled"], inp["pooled"]]), torch.cat([lq] * 2)
-        img = inp["img"]
-    else:
-        ctx, text, image, img = inp["pe"], inp["pooled"], lq, inp["img"][1:]
-    R = ctx.shape[0]
-    tid = torch.tensor([[128.0, 128, 0, 0, 128, 128]]).repeat(R, 1)
-    ip_main = nets.image_projection(P, [img], cfg.resampler)[0]
-    ip_prev = nets.image_projection(P, [img], cfg.resampler, L)[0]
-    x = sched.add_noise(acp, lq, inp["init_noise"], [int(ts[0])] * B)
-    previewer_mean = torch.zeros_like(x)
-    preview_factor = torch.ones(B, 1, 1, 1)
-    down = mid = preview = None
-    for i in range(n):
-        t = int(ts[i])
-        xin = torch.cat([x] * 2) if do_cfg else x
-        cond_scale = preview_factor.clamp(0.0, 1.0) * keep[i]
-        cond_scale = torch.cat([cond_scale] * 2) if do_cfg else cond_scale
-        if (cond_scale > 0.1).sum().item() > 0:
-            if previewing[i] > 0:
-                eps1 = nets.unet_forward(P, cfg, xin, t, ctx, text, tid, ip_prev, lora=L)
-                preview = sched.lcm_step(acp, eps1, t, xin)
-            else:
-                preview = image
-            down, mid = nets.aggregator_forward(PA, cfg, image, t, preview, text, tid)
-        down = [s * cond_scale for s in down]
-        mid = mid * cond_scale
-        e = _pag_unet(P, cfg, xin, t, ctx, text, tid, ip_main, down, mid, paths, B)
-        s_t = max(pag_scale - pag_adaptive_scale * (1000 - t), 0.0)
-        if do_cfg:
-            u, c, p = e.chunk(3)
-            eps = u + guidance_scale * (c - u) + s_t * (c - p)
-            if guidance_rescale > 0:
-                dims = list(range(1, c.ndim))
-                std_text, std_cfg = c.std(dim=dims, keepdim=True), eps.std(dim=dims, keepdim=True)
-                eps = guidance_rescale * (eps * (std_text / std_cfg)) + (1 - guidance_rescale) * eps
-        else:
-            c, p = e.chunk(2)
-            eps = c + s_t * (c - p)
-        x_next, x0 = sched.ddim_step(acp, eps, t, x, num_inference_steps)
-        if adastep_restore:
-            pv = preview[B:].float()
-            pred_x0_l2 = (pv - x0.float()).pow(2).sum(dim=(1, 2, 3))
-            previewer_l2 = (pv - previewer_mean.float()).pow(2).sum(dim=(1, 2, 3))
-            previewer_mean = preview[B:]
-            preview_factor = (pred_x0_l2 / previewer_l2).reshape(-1, 1, 1, 1)
-        x = x_next
-    return x
-
-
-def _plain_oracle(env, guidance_scale, **kw):
-    from oracle import pipeline as OP
-    cfg, sd, sda, lora, inp = env
-    P = {k: v.float() for k, v in sd.items()}
-    PA = {k: v.float() for k, v in sda.items()}
-    L = {k: v.float() for k, v in lora.items()}
-    L["scaling"] = 16.0 / cfg.lora_rank
-    do_cfg = guidance_scale > 1
-    return OP.denoise(P, PA, L, cfg, inp["lq"], inp["pe"], inp["pooled"], inp["img"] if do_cfg else inp["img"][1:],
-                      negative_prompt_embeds=inp["npe"] if do_cfg else None, negative_pooled=inp["npooled"] if do_cfg else None,
-                      init_noise=inp["init_noise"], sampler="ddim", guidance_scale=guidance_scale, num_inference_steps=8,
-                      preview_start=0.25, control_guidance_end=0.75, **kw)
-
-
-@pytest.fixture(scope="module")
-def env(dev):
-    from instantir_amd import weights as W
-    from instantir_amd.config import UNetConfig
-    cfg = UNetConfig.tiny()
-    sd = W.synth_state_dict(W.unet_specs(cfg), 11)
-    sda = W.synth_state_dict(W.aggregator_specs(cfg), 12)
-    lora = W.synth_state_dict(W.lora_specs(cfg), 13)
-    g = torch.Generator().manual_seed(42)
-    B, H = 2, 16
-    inp = dict(
-        B=B, H=H,
-        lq=torch.randn(B, 4, H, H, generator=g) * 0.8,
-        pe=torch.randn(B, cfg.text_len, cfg.cross_attention_dim, generator=g).half().float(),
-        pooled=torch.randn(B, cfg.pooled_dim, generator=g).half().float(),
-        npe=torch.randn(B, cfg.text_len, cfg.cross_attention_dim, generator=g).half().float(),
-        npooled=torch.randn(B, cfg.pooled_dim, generator=g).half().float(),
-        img=torch.randn(2, B, cfg.resampler.seq_len, cfg.resampler.embedding_dim, generator=g).half().float(),
-        init_noise=torch.randn(B, 4, H, H, generator=g),
-    )
-    return cfg, sd, sda, lora, inp
-
-
-def _pipe(env, sched=None):
-    from instantir_amd.pipeline import InstantIRPipeline
-    from instantir_amd.schedulers import DDIMScheduler
-    cfg, sd, sda, lora, _ = env
-    pipe = InstantIRPipeline(cfg, sd, scheduler=sched if sched is not None else DDIMScheduler())
-    pipe.aggregator.load_state_dict(sda)
-    pipe.prepare_previewers(lora, lora_alpha=16)
-    return pipe
-
-
-LOOP = dict(num_inference_steps=8, preview_start=0.25, control_guidance_end=0.75)
-
-
-def _call(pipe, inp, guidance_scale=7.0, **kw):
-    from instantir_amd.schedulers import LCMSingleStepScheduler
-    lcm = LCMSingleStepScheduler.from_config(pipe.scheduler.config)
-    cfg_on = guidance_scale > 1
-    extra = dict(negative_prompt_embeds=inp["npe"], negative_pooled_prompt_embeds=inp["npooled"]) if cfg_on else {}
-    return pipe(image=inp["lq"], prompt_embeds=inp["pe"], pooled_prompt_embeds=inp["pooled"],
-                ip_adapter_image_embeds=[inp["img"] if cfg_on else inp["img"][1:]], output_type="latent", previewer_scheduler=lcm,
-                init_noise=inp["init_noise"], guidance_scale=guidance_scale, **{**LOOP, **kw}, **extra).images.float().cpu()
+LOOP = lr.LOOP
+_call = functools.partial(lr.call, **LOOP)
 
 
 CASES = {
@@ -392,10 +204,12 @@ def test_loop_matches_pag_oracle(env, pag_oracle_attn, case):
     call_kw, layers, extra = CASES[case]
     cfg = env[0]
     paths = pag.select(layers, pag.attn1_paths(cfg))
-    okw = {k: v for k, v in call_kw.items() if k != "guidance_scale"}
-    want = pag_denoise(env, paths, guidance_scale=call_kw["guidance_scale"], **okw, **extra)
-    plain = _plain_oracle(env, call_kw["guidance_scale"], guidance_rescale=call_kw.get("guidance_rescale", 0.0), **extra)
-    pipe = _pipe(env)
+    okw = dict(scale=call_kw["pag_scale"], adaptive=call_kw.get("pag_adaptive_scale", 0.0))
+    g, phi = call_kw["guidance_scale"], call_kw.get("guidance_rescale", 0.0)
+    want = lr.denoise(env, g, main_unet=lr.pag_unet(paths, env[4]["B"]), guide=lr.perturbed(g, **okw), guidance_rescale=phi,
+                      **LOOP, **extra)
+    plain = lr.denoise(env, g, guidance_rescale=phi, **LOOP, **extra)
+    pipe = lr.pipe(env)
     pipe.enable_pag(layers)
     got = _call(pipe, env[4], **call_kw, **extra)
     p, p_plain = psnr(got, want), psnr(got, plain)
@@ -404,36 +218,19 @@ def test_loop_matches_pag_oracle(env, pag_oracle_attn, case):
     assert p_plain < p - 6, (p, p_plain)
 
 
-def test_dpmpp_2m_karras_adaptive_matches_pag_oracle(env, pag_oracle_attn, monkeypatch):
-    """DPM++ 2M Karras with pag_adaptive_scale > 0 (fractional timesteps reach s_t), against the sigma-scheduler oracle loop of
-    tests/test_sigma_schedulers_gpu.py with its main UNet call PAG'd: [u; c + (s_t / g)(c - p)] makes its u + g (c - u) the
-    PAG-guided eps."""
-    import test_sigma_schedulers_gpu as sg
-    from oracle import nets
+def test_dpmpp_2m_karras_adaptive_matches_pag_oracle(env, pag_oracle_attn):
+    """DPM++ 2M Karras with pag_adaptive_scale > 0 (fractional timesteps reach s_t), against the sigma-scheduler oracle loop with
+    the same two hooks."""
     from instantir_amd import pag
     cfg, inp = env[0], env[4]
     paths = pag.select("mid", pag.attn1_paths(cfg))
     g, s, a = 5.0, 3.0, 0.002
-    plain = sg._oracle(env, "dpm", 8, guidance_scale=g, karras=True, **sg.PHASES)
-    orig = nets.unet_forward
-
-    def unet_forward(P, cfg_, xin, t, ctx, text, tid, ip, down_res=None, mid_res=None, lora=None, emb=None):
-        if lora is not None or down_res is None:
-            return orig(P, cfg_, xin, t, ctx, text, tid, ip, down_res, mid_res, lora=lora, emb=emb)
-        monkeypatch.setattr(nets, "unet_forward", orig)
-        try:
-            e = _pag_unet(P, cfg_, xin, t, ctx, text, tid, ip, down_res, mid_res, paths, xin.shape[0] // 2)
-        finally:
-            monkeypatch.setattr(nets, "unet_forward", unet_forward)
-        u, c, p = e.chunk(3)
-        s_t = max(s - a * (1000 - float(t)), 0.0)
-        return torch.cat([u, c + (s_t / g) * (c - p)])
-    monkeypatch.setattr(nets, "unet_forward", unet_forward)
-    want = sg._oracle(env, "dpm", 8, guidance_scale=g, karras=True, **sg.PHASES)
-    monkeypatch.setattr(nets, "unet_forward", orig)
-    pipe = _pipe(env, sg._sched("dpm", karras=True))
+    plain = lr.sigma_denoise(env, "dpm", 8, guidance_scale=g, karras=True, **lr.PHASES)
+    want = lr.sigma_denoise(env, "dpm", 8, guidance_scale=g, karras=True, main_unet=lr.pag_unet(paths, inp["B"]),
+                            guide=lr.perturbed(g, s, a), **lr.PHASES)
+    pipe = lr.pipe(env, lr.sigma_sched("dpm", karras=True))
     pipe.enable_pag("mid")
-    got = _call(pipe, inp, guidance_scale=g, pag_scale=s, pag_adaptive_scale=a, num_inference_steps=8, **sg.PHASES)
+    got = _call(pipe, inp, guidance_scale=g, pag_scale=s, pag_adaptive_scale=a, num_inference_steps=8, **lr.PHASES)
     p, p_plain = psnr(got, want), psnr(got, plain)
     print(f"dpmpp_2m karras adaptive: latent PSNR vs PAG'd oracle {p:.1f} dB, vs plain oracle {p_plain:.1f} dB")
     assert torch.isfinite(got).all() and p >= BAR, p
@@ -442,12 +239,12 @@ def test_dpmpp_2m_karras_adaptive_matches_pag_oracle(env, pag_oracle_attn, monke
 
 def test_disabled_and_zero_scale_bit_identical_to_never_enabled(env):
     inp = env[4]
-    base = _call(_pipe(env), inp)
-    p = _pipe(env)
+    base = _call(lr.pipe(env), inp)
+    p = lr.pipe(env)
     p.enable_pag("mid")
     p.disable_pag()
     assert torch.equal(_call(p, inp), base)
-    p2 = _pipe(env)
+    p2 = lr.pipe(env)
     p2.enable_pag(["mid", "up_blocks.0"])
     assert torch.equal(_call(p2, inp, pag_scale=0.0), base)
     assert p2._unet.pag is None                                  # scale 0: the plain launches ran
@@ -458,17 +255,17 @@ def test_toggling_between_calls_replays_the_right_graphs(env):
     setting, bit for bit."""
     inp = env[4]
     settings = [None, ("mid", 3.0), None, (["mid", "up_blocks.0"], 3.0), ("mid", 1.5)]
-    pipe = _pipe(env)
+    pipe = lr.pipe(env)
     outs = []
     for st in settings:
         if st is None:
             pipe.disable_pag()
             got = _call(pipe, inp)
-            fresh = _call(_pipe(env), inp)
+            fresh = _call(lr.pipe(env), inp)
         else:
             pipe.enable_pag(st[0])
             got = _call(pipe, inp, pag_scale=st[1])
-            f = _pipe(env)
+            f = lr.pipe(env)
             f.enable_pag(st[0])
             fresh = _call(f, inp, pag_scale=st[1])
         assert torch.equal(got, fresh), st
@@ -478,7 +275,7 @@ def test_toggling_between_calls_replays_the_right_graphs(env):
 
 def test_graphs_on_off_repeat_calls_and_callback_bit_identical(env):
     inp = env[4]
-    pipe = _pipe(env)
+    pipe = lr.pipe(env)
     pipe.enable_pag("mid")
     a = _call(pipe, inp, pag_adaptive_scale=0.001)
     b = _call(pipe, inp, pag_adaptive_scale=0.001)
@@ -509,7 +306,7 @@ def test_composes_with_freeu_reference_latents_and_images_per_prompt(env):
 
     def run(pag_on):
         from instantir_amd.schedulers import LCMSingleStepScheduler
-        p = _pipe(env)
+        p = lr.pipe(env)
         p.enable_freeu(0.9, 0.2, 1.3, 1.4)
         extra = {}
         if pag_on:
@@ -615,7 +412,7 @@ def test_config1_geometry_one_step_with_pag(dev, pag_oracle_attn):
         ip_prev = nets.image_projection(P, [feats], cfg.resampler, L)[0]
         preview = sched.lcm_step(acp, nets.unet_forward(P, cfg, xin, t, ctx, text, tid, ip_prev, lora=L), t, xin)
         down, mid = nets.aggregator_forward(PA, cfg, torch.cat([lq] * 2), t, preview, text, tid)
-        e = _pag_unet(P, cfg, xin, t, ctx, text, tid, ip_main, down, mid, paths, B)
+        e = lr.pag_unet(paths, B)(P, cfg, xin, t, ctx, text, tid, ip_main, down, mid)
         u, c, p = e.chunk(3)
         eps = u + 7.0 * (c - u) + 3.0 * (c - p)
         want, _ = sched.ddpm_step(acp, eps, t, x, 1, noise=sn[0], prev_t=-1)

@@ -1,10 +1,11 @@
 """GPU parity of the whole denoising loop (InstantIRPipeline over HIP) against the CPU oracle loop,
 tiny geometry, identical seeded weights / inputs / noises.  Tolerance: latent PSNR (BASELINE.json
 north_star asks >= 50 dB vs the reference latents at fp16)."""
-import math
-
 import pytest
 import torch
+
+import loop_ref as lr
+from loop_ref import dev, env  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -12,78 +13,17 @@ pytestmark = pytest.mark.gpu
 BAR = 50.0     # BASELINE.json north_star: latent PSNR >= 50 dB against the reference path at fp16
 
 
-def psnr(got, want):
-    import inspect
-    from conftest import record_psnr
-    mse = ((got - want) ** 2).mean().item()
-    peak = want.abs().max().item()
-    v = 10 * math.log10(peak * peak / max(mse, 1e-30))
-    record_psnr("pipeline." + inspect.stack()[1].function, v)
-    return v
-
-
-@pytest.fixture(scope="module")
-def env():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from instantir_amd import lib, weights as W
-    from instantir_amd.config import UNetConfig
-    lib.load()
-    cfg = UNetConfig.tiny()
-    sd = W.synth_state_dict(W.unet_specs(cfg), 11)
-    sda = W.synth_state_dict(W.aggregator_specs(cfg), 12)
-    lora = W.synth_state_dict(W.lora_specs(cfg), 13)
-    g = torch.Generator().manual_seed(42)
-    B, H = 2, 16
-    inp = dict(
-        B=B, H=H,
-        lq=torch.randn(B, 4, H, H, generator=g) * 0.8,
-        pe=torch.randn(B, cfg.text_len, cfg.cross_attention_dim, generator=g).half().float(),
-        pooled=torch.randn(B, cfg.pooled_dim, generator=g).half().float(),
-        npe=torch.randn(B, cfg.text_len, cfg.cross_attention_dim, generator=g).half().float(),
-        npooled=torch.randn(B, cfg.pooled_dim, generator=g).half().float(),
-        img=torch.randn(2, B, cfg.resampler.seq_len, cfg.resampler.embedding_dim, generator=g).half().float(),
-        init_noise=torch.randn(B, 4, H, H, generator=g),
-        noises=[torch.randn(B, 4, H, H, generator=g) for _ in range(8)],
-    )
-    return cfg, sd, sda, lora, inp
-
-
-def _oracle(cfg, sd, sda, lora, inp, **kw):
-    from oracle import pipeline as OP
-    P = {k: v.float() for k, v in sd.items()}
-    PA = {k: v.float() for k, v in sda.items()}
-    L = {k: v.float() for k, v in lora.items()}
-    L["scaling"] = 16.0 / cfg.lora_rank
-    return OP.denoise(P, PA, L, cfg, inp["lq"], inp["pe"], inp["pooled"], inp["img"], negative_prompt_embeds=inp["npe"],
-                      negative_pooled=inp["npooled"], init_noise=inp["init_noise"], **kw)
-
-
-def _pipe(cfg, sd, sda, lora, sched):
-    from instantir_amd.pipeline import InstantIRPipeline
-    pipe = InstantIRPipeline(cfg, sd, scheduler=sched)
-    pipe.aggregator.load_state_dict(sda)
-    pipe.prepare_previewers(lora, lora_alpha=16)
-    return pipe
-
-
-def _call(pipe, inp, **kw):
-    from instantir_amd.schedulers import LCMSingleStepScheduler
-    lcm = LCMSingleStepScheduler.from_config(pipe.scheduler.config)
-    return pipe(image=inp["lq"], prompt_embeds=inp["pe"], pooled_prompt_embeds=inp["pooled"],
-                negative_prompt_embeds=inp["npe"], negative_pooled_prompt_embeds=inp["npooled"],
-                ip_adapter_image_embeds=[inp["img"]], output_type="latent", previewer_scheduler=lcm,
-                init_noise=inp["init_noise"], **kw).images.float().cpu()
+psnr = lr.psnr_by_caller("pipeline")
 
 
 @pytest.mark.parametrize("graphs", [False, True])
 def test_ddim_cfg_loop(env, graphs):
     from instantir_amd.schedulers import DDIMScheduler
     cfg, sd, sda, lora, inp = env
-    want = _oracle(cfg, sd, sda, lora, inp, num_inference_steps=6, guidance_scale=7.0, sampler="ddim")
-    pipe = _pipe(cfg, sd, sda, lora, DDIMScheduler())
+    want = lr.denoise(env, num_inference_steps=6, guidance_scale=7.0, sampler="ddim")
+    pipe = lr.pipe(env, DDIMScheduler())
     pipe.use_graphs = graphs
-    got = _call(pipe, inp, num_inference_steps=6, guidance_scale=7.0)
+    got = lr.call(pipe, inp, num_inference_steps=6, guidance_scale=7.0)
     p = psnr(got, want)
     assert torch.isfinite(got).all() and p >= BAR, p
 
@@ -93,9 +33,9 @@ def test_ddpm_phases_loop(env):
     from instantir_amd.schedulers import DDPMScheduler
     cfg, sd, sda, lora, inp = env
     kw = dict(num_inference_steps=8, guidance_scale=5.0, preview_start=0.25, control_guidance_end=0.75)
-    want = _oracle(cfg, sd, sda, lora, inp, sampler="ddpm", step_noises=inp["noises"], **kw)
-    pipe = _pipe(cfg, sd, sda, lora, DDPMScheduler())
-    got = _call(pipe, inp, step_noises=inp["noises"], **kw)
+    want = lr.denoise(env, sampler="ddpm", step_noises=inp["noises"], **kw)
+    pipe = lr.pipe(env, DDPMScheduler())
+    got = lr.call(pipe, inp, step_noises=inp["noises"], **kw)
     p = psnr(got, want)
     assert torch.isfinite(got).all() and p >= BAR, p
 
@@ -105,10 +45,10 @@ def test_guidance_rescale_loop(env):
     from instantir_amd.schedulers import DDIMScheduler
     cfg, sd, sda, lora, inp = env
     kw = dict(num_inference_steps=4, guidance_scale=7.0, guidance_rescale=0.7)
-    want = _oracle(cfg, sd, sda, lora, inp, sampler="ddim", **kw)
-    plain = _oracle(cfg, sd, sda, lora, inp, sampler="ddim", num_inference_steps=4, guidance_scale=7.0)
-    pipe = _pipe(cfg, sd, sda, lora, DDIMScheduler())
-    got = _call(pipe, inp, **kw)
+    want = lr.denoise(env, sampler="ddim", **kw)
+    plain = lr.denoise(env, sampler="ddim", num_inference_steps=4, guidance_scale=7.0)
+    pipe = lr.pipe(env, DDIMScheduler())
+    got = lr.call(pipe, inp, **kw)
     p = psnr(got, want)
     assert torch.isfinite(got).all() and p >= BAR, p
     assert psnr(got, plain) < p - 6          # the rescale is live: clearly closer to the rescaled oracle than to the plain one
@@ -120,10 +60,10 @@ def test_negative_size_conditioning(env):
     cfg, sd, sda, lora, inp = env
     kw = dict(num_inference_steps=2, guidance_scale=5.0)
     neg = (64, 96, 8, 4, 32, 48)
-    want = _oracle(cfg, sd, sda, lora, inp, sampler="ddim", negative_time_ids=neg, **kw)
-    plain = _oracle(cfg, sd, sda, lora, inp, sampler="ddim", **kw)
-    pipe = _pipe(cfg, sd, sda, lora, DDIMScheduler())
-    got = _call(pipe, inp, negative_original_size=neg[:2], negative_crops_coords_top_left=neg[2:4], negative_target_size=neg[4:], **kw)
+    want = lr.denoise(env, sampler="ddim", negative_time_ids=neg, **kw)
+    plain = lr.denoise(env, sampler="ddim", **kw)
+    pipe = lr.pipe(env, DDIMScheduler())
+    got = lr.call(pipe, inp, negative_original_size=neg[:2], negative_crops_coords_top_left=neg[2:4], negative_target_size=neg[4:], **kw)
     p = psnr(got, want)
     assert p >= BAR and psnr(got, plain) < p - 6, (p, psnr(got, plain))
 
@@ -139,9 +79,9 @@ def test_aggregator_from_unet_emits_zero_residuals(env):
     agg = bare.aggregator.from_unet()
     assert set(agg) == set(sda) and all(agg[k].abs().max().item() == 0 for k in agg if k.startswith("controlnet_"))
     assert torch.equal(agg["ref_conv_in.weight"], sd["conv_in.weight"]) and torch.equal(agg["mid_block.resnets.0.conv1.weight"], sd["mid_block.resnets.0.conv1.weight"])
-    got = _call(bare, inp, num_inference_steps=2, guidance_scale=5.0)
-    want = _oracle(cfg, sd, agg, lora, inp, num_inference_steps=2, guidance_scale=5.0, sampler="ddim")
-    trained = _oracle(cfg, sd, sda, lora, inp, num_inference_steps=2, guidance_scale=5.0, sampler="ddim")
+    got = lr.call(bare, inp, num_inference_steps=2, guidance_scale=5.0)
+    want = lr.denoise((cfg, sd, agg, lora, inp), num_inference_steps=2, guidance_scale=5.0, sampler="ddim")
+    trained = lr.denoise(env, num_inference_steps=2, guidance_scale=5.0, sampler="ddim")
     p = psnr(got, want)
     assert torch.isfinite(got).all() and p >= BAR and psnr(got, trained) < p - 6
 
@@ -154,13 +94,10 @@ def test_no_cfg_single_image(env):
     one["img"] = inp["img"][1:, :1]
     one["B"] = 1
     from oracle import pipeline as OP
-    P = {k: v.float() for k, v in sd.items()}
-    PA = {k: v.float() for k, v in sda.items()}
-    L = {k: v.float() for k, v in lora.items()}
-    L["scaling"] = 16.0 / cfg.lora_rank
+    P, PA, L = lr.params(env)
     want = OP.denoise(P, PA, L, cfg, one["lq"], one["pe"], one["pooled"], one["img"], init_noise=one["init_noise"],
                       num_inference_steps=4, guidance_scale=1.0, sampler="ddim")
-    pipe = _pipe(cfg, sd, sda, lora, DDIMScheduler())
+    pipe = lr.pipe(env, DDIMScheduler())
     from instantir_amd.schedulers import LCMSingleStepScheduler
     got = pipe(image=one["lq"], prompt_embeds=one["pe"], pooled_prompt_embeds=one["pooled"],
                ip_adapter_image_embeds=[one["img"]], output_type="latent", num_inference_steps=4, guidance_scale=1.0,
@@ -176,13 +113,11 @@ def test_single_step_previewer_restoration(env):
     from instantir_amd.schedulers import DDPMScheduler
     from oracle import nets, sched
     cfg, sd, sda, lora, inp = env
-    pipe = _pipe(cfg, sd, sda, lora, DDPMScheduler())
+    pipe = lr.pipe(env, DDPMScheduler())
     feats = inp["img"][1:]
     got = pipe.restore_single_step(inp["lq"], inp["pe"], inp["pooled"], ip_adapter_image_embeds=[feats], init_noise=inp["init_noise"],
                                    output_type="latent").images.float().cpu()
-    P = {k: v.float() for k, v in sd.items()}
-    L = {k: v.float() for k, v in lora.items()}
-    L["scaling"] = 16.0 / cfg.lora_rank
+    P, _, L = lr.params(env)
     acp = sched.make_alphas_cumprod()
     B = inp["B"]
     x = sched.add_noise(acp, inp["lq"], inp["init_noise"], [999] * B)
@@ -206,12 +141,12 @@ def test_adastep_restore_with_reference_latents_and_a_gated_step(env):
     kw = dict(num_inference_steps=5, guidance_scale=5.0, adastep_restore=True, reference_latents=ref, preview_end=0.4,
               controlnet_conditioning_scale=[1.0, 1.0, 0.05, 1.0, 1.0])
     trace = {}
-    want = _oracle(cfg, sd, sda, lora, inp, sampler="ddim", trace=trace, **kw)
+    want = lr.denoise(env, sampler="ddim", trace=trace, **kw)
     modes = [bool((c > 0.1).any()) for c in trace["cond_scale"]]
     assert modes == [True, True, False, True, True]                         # the gated step is really exercised
-    pipe = _pipe(cfg, sd, sda, lora, DDIMScheduler())
-    got = _call(pipe, inp, **kw)
-    plain = _oracle(cfg, sd, sda, lora, inp, sampler="ddim", **{**kw, "adastep_restore": False})
+    pipe = lr.pipe(env, DDIMScheduler())
+    got = lr.call(pipe, inp, **kw)
+    plain = lr.denoise(env, sampler="ddim", **{**kw, "adastep_restore": False})
     p = psnr(got, want)
     assert torch.isfinite(got).all() and p >= BAR and psnr(got, plain) < p - 6, (p, psnr(got, plain))
 
@@ -219,9 +154,9 @@ def test_adastep_restore_with_reference_latents_and_a_gated_step(env):
 def test_adastep_needs_cfg(env):
     from instantir_amd.schedulers import DDIMScheduler
     cfg, sd, sda, lora, inp = env
-    pipe = _pipe(cfg, sd, sda, lora, DDIMScheduler())
+    pipe = lr.pipe(env, DDIMScheduler())
     with pytest.raises(ValueError):
-        _call(pipe, inp, num_inference_steps=2, guidance_scale=1.0, adastep_restore=True)
+        lr.call(pipe, inp, num_inference_steps=2, guidance_scale=1.0, adastep_restore=True)
 
 
 def test_denoising_end_custom_timesteps_and_callback(env):
@@ -231,22 +166,22 @@ def test_denoising_end_custom_timesteps_and_callback(env):
     from instantir_amd.schedulers import DDIMScheduler, DDPMScheduler
     cfg, sd, sda, lora, inp = env
     kw = dict(num_inference_steps=6, guidance_scale=5.0, denoising_end=0.5)
-    want = _oracle(cfg, sd, sda, lora, inp, sampler="ddim", **kw)
-    pipe = _pipe(cfg, sd, sda, lora, DDIMScheduler())
+    want = lr.denoise(env, sampler="ddim", **kw)
+    pipe = lr.pipe(env, DDIMScheduler())
     seen = []
 
     def cb(p_, i, t, kwargs):
         seen.append((i, int(t)))
         return {"latents": kwargs["latents"]}
 
-    got = _call(pipe, inp, callback_on_step_end=cb, **kw)
+    got = lr.call(pipe, inp, callback_on_step_end=cb, **kw)
     assert seen == [(0, 831), (1, 665)]                  # N = 6 timetable 831, 665, 499, ...: cutoff 500 keeps two steps
     p = psnr(got, want)
     assert p >= BAR, p
     tlist = [901, 601, 301, 1]
-    want = _oracle(cfg, sd, sda, lora, inp, sampler="ddpm", timesteps=tlist, guidance_scale=5.0, step_noises=inp["noises"])
-    pipe2 = _pipe(cfg, sd, sda, lora, DDPMScheduler())
-    got = _call(pipe2, inp, timesteps=tlist, guidance_scale=5.0, step_noises=inp["noises"])
+    want = lr.denoise(env, sampler="ddpm", timesteps=tlist, guidance_scale=5.0, step_noises=inp["noises"])
+    pipe2 = lr.pipe(env, DDPMScheduler())
+    got = lr.call(pipe2, inp, timesteps=tlist, guidance_scale=5.0, step_noises=inp["noises"])
     p = psnr(got, want)
     assert p >= BAR, p
 
@@ -257,25 +192,25 @@ def test_callback_may_replace_prompt_embeds(env):
     hoisted again and the remaining steps run on the new context (the result moves, stays finite); a wrong shape is refused."""
     from instantir_amd.schedulers import DDIMScheduler
     cfg, sd, sda, lora, inp = env
-    pipe = _pipe(cfg, sd, sda, lora, DDIMScheduler())
+    pipe = lr.pipe(env, DDIMScheduler())
     kw = dict(num_inference_steps=4, guidance_scale=5.0)
-    base = _call(pipe, inp, **kw)
+    base = lr.call(pipe, inp, **kw)
     seen = []
 
     def same(p_, i, t, k):
         seen.append(tuple(k["prompt_embeds"].shape))
         return {"latents": k["latents"], "prompt_embeds": k["prompt_embeds"], "negative_prompt_embeds": k.get("negative_prompt_embeds")}
 
-    got = _call(pipe, inp, callback_on_step_end=same, callback_on_step_end_tensor_inputs=["latents", "prompt_embeds", "negative_prompt_embeds"], **kw)
+    got = lr.call(pipe, inp, callback_on_step_end=same, callback_on_step_end_tensor_inputs=["latents", "prompt_embeds", "negative_prompt_embeds"], **kw)
     assert torch.equal(got, base) and seen[0] == (2 * inp["B"], cfg.text_len, cfg.cross_attention_dim)
 
     def swap(p_, i, t, k):
         return {"prompt_embeds": (k["prompt_embeds"] * 0.25) if i == 1 else k["prompt_embeds"]}
 
-    moved = _call(pipe, inp, callback_on_step_end=swap, callback_on_step_end_tensor_inputs=["prompt_embeds"], **kw)
+    moved = lr.call(pipe, inp, callback_on_step_end=swap, callback_on_step_end_tensor_inputs=["prompt_embeds"], **kw)
     assert torch.isfinite(moved).all() and not torch.equal(moved, base)
     with pytest.raises(ValueError):
-        _call(pipe, inp, callback_on_step_end=lambda p_, i, t, k: {"prompt_embeds": k["prompt_embeds"][:1]},
+        lr.call(pipe, inp, callback_on_step_end=lambda p_, i, t, k: {"prompt_embeds": k["prompt_embeds"][:1]},
               callback_on_step_end_tensor_inputs=["prompt_embeds"], **kw)
 
 
@@ -287,12 +222,12 @@ def test_num_images_per_prompt(env):
     cfg, sd, sda, lora, inp = env
     one = {k: (v[:1] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == inp["B"] else v) for k, v in inp.items()}
     one["img"] = inp["img"][:, :1]
-    pipe = _pipe(cfg, sd, sda, lora, DDIMScheduler())
+    pipe = lr.pipe(env, DDIMScheduler())
     noise2 = inp["init_noise"]                                             # (2,4,H,H): one row per generated image
-    both = _call(pipe, {**one, "init_noise": noise2}, num_inference_steps=2, guidance_scale=5.0, num_images_per_prompt=2)
+    both = lr.call(pipe, {**one, "init_noise": noise2}, num_inference_steps=2, guidance_scale=5.0, num_images_per_prompt=2)
     assert both.shape[0] == 2
     for r in range(2):
-        single = _call(pipe, {**one, "init_noise": noise2[r:r + 1]}, num_inference_steps=2, guidance_scale=5.0)
+        single = lr.call(pipe, {**one, "init_noise": noise2[r:r + 1]}, num_inference_steps=2, guidance_scale=5.0)
         # same kernels, same inputs: only what depends on the batch size differs -- tile shapes, and with them the grouping of
         # the LayerNorm partial statistics (per column tile of the producing GEMM); measured 61 dB over two steps
         assert psnr(both[r:r + 1], single) >= 55
@@ -304,7 +239,7 @@ def test_ip_adapter_image_defaults_to_image_and_preview_row(env):
     the call runs.  `save_preview_row` (:1564-1567, :1706-1729) returns one preview per previewing step."""
     from instantir_amd.schedulers import DDIMScheduler, LCMSingleStepScheduler
     cfg, sd, sda, lora, inp = env
-    pipe = _pipe(cfg, sd, sda, lora, DDIMScheduler())
+    pipe = lr.pipe(env, DDIMScheduler())
     lcm = LCMSingleStepScheduler.from_config(pipe.scheduler.config)
     base = dict(image=inp["lq"], prompt_embeds=inp["pe"], pooled_prompt_embeds=inp["pooled"], output_type="latent",
                 negative_prompt_embeds=inp["npe"], negative_pooled_prompt_embeds=inp["npooled"], previewer_scheduler=lcm, init_noise=inp["init_noise"], num_inference_steps=3, guidance_scale=5.0)
@@ -327,7 +262,7 @@ def test_ip_adapter_image_defaults_to_image_and_preview_row(env):
 
     pipe.image_encoder = _Enc()
     out, row = pipe(**base, return_dict=False, save_preview_row=True, preview_end=0.7)
-    want = _call(pipe, inp, num_inference_steps=3, guidance_scale=5.0, preview_end=0.7)
+    want = lr.call(pipe, inp, num_inference_steps=3, guidance_scale=5.0, preview_end=0.7)
     assert psnr(out.float().cpu(), want) >= 70
     assert len(row) == 2 and all(r.shape == inp["lq"].shape for r in row)     # steps 0 and 1 preview, step 2 does not
 
@@ -339,14 +274,12 @@ def test_single_step_previewer_restoration_fp8(env):
     from instantir_amd.schedulers import DDPMScheduler
     from oracle import nets, sched
     cfg, sd, sda, lora, inp = env
-    pipe = _pipe(cfg, sd, sda, lora, DDPMScheduler())
+    pipe = lr.pipe(env, DDPMScheduler())
     feats = inp["img"][1:]
     kw = dict(ip_adapter_image_embeds=[feats], init_noise=inp["init_noise"], output_type="latent")
     got8 = pipe.restore_single_step(inp["lq"], inp["pe"], inp["pooled"], fp8=True, **kw).images.float().cpu()
     got16 = pipe.restore_single_step(inp["lq"], inp["pe"], inp["pooled"], **kw).images.float().cpu()
-    P = {k: v.float() for k, v in sd.items()}
-    L = {k: v.float() for k, v in lora.items()}
-    L["scaling"] = 16.0 / cfg.lora_rank
+    P, _, L = lr.params(env)
     acp = sched.make_alphas_cumprod()
     B = inp["B"]
     x = sched.add_noise(acp, inp["lq"], inp["init_noise"], [999] * B)
@@ -368,7 +301,7 @@ def test_adapter_switching_and_lora_scale(env):
     from instantir_amd.schedulers import DDIMScheduler
     cfg, sd, sda, lora, inp = env
     lcm_lora = W.synth_state_dict(W.lora_specs(cfg, W.LCM_LORA_MODULES), 14)
-    pipe = _pipe(cfg, sd, sda, lora, DDIMScheduler())
+    pipe = lr.pipe(env, DDIMScheduler())
     assert pipe.unet.active_adapters() == ["previewer"]
     assert pipe.prepare_previewers(lcm_lora, use_lcm=True, lora_alpha=8) == 8
     assert pipe.unet.active_adapters() == ["lcm"]
@@ -382,45 +315,45 @@ def test_adapter_switching_and_lora_scale(env):
                           inp["pe"], inp["pooled"], inp["img"], negative_prompt_embeds=inp["npe"], negative_pooled=inp["npooled"],
                           init_noise=inp["init_noise"], sampler="ddim", **kw)
 
-    got_lcm = _call(pipe, inp, **kw)
+    got_lcm = lr.call(pipe, inp, **kw)
     assert psnr(got_lcm, oracle(lcm_lora, 8.0 / cfg.lora_rank)) >= BAR
     pipe.unet.set_adapter("previewer")
-    got_prev = _call(pipe, inp, **kw)
+    got_prev = lr.call(pipe, inp, **kw)
     want_prev = oracle(lora, 16.0 / cfg.lora_rank)
     assert psnr(got_prev, want_prev) >= BAR
     assert psnr(got_lcm, want_prev) < BAR - 10                   # the two adapters really differ
-    got_half = _call(pipe, inp, cross_attention_kwargs={"scale": 0.5}, **kw)
+    got_half = lr.call(pipe, inp, cross_attention_kwargs={"scale": 0.5}, **kw)
     assert psnr(got_half, oracle(lora, 0.5 * 16.0 / cfg.lora_rank)) >= BAR
-    assert psnr(_call(pipe, inp, **kw), want_prev) >= BAR         # the unscaled copy is still the default afterwards
+    assert psnr(lr.call(pipe, inp, **kw), want_prev) >= BAR         # the unscaled copy is still the default afterwards
     with pytest.raises(ValueError):
-        _call(pipe, inp, cross_attention_kwargs={"external_kv": None}, **kw)
+        lr.call(pipe, inp, cross_attention_kwargs={"external_kv": None}, **kw)
     with pytest.raises(ValueError):
         pipe.unet.set_adapter("nope")
 
     # Replacing or releasing an engine drops the cached loop (its entry pins the engines it was captured on), and the next call
     # is bit-identical to a freshly built pipeline given the same adapters and inputs.
     def fresh(active):
-        ref = _pipe(cfg, sd, sda, lora, DDIMScheduler())
+        ref = lr.pipe(env, DDIMScheduler())
         ref.prepare_previewers(lcm_lora, use_lcm=True, lora_alpha=8)
         ref.unet.set_adapter(active)
-        return _call(ref, inp, **kw3)
+        return lr.call(ref, inp, **kw3)
 
     kw3 = dict(num_inference_steps=3, guidance_scale=5.0)
     want = {name: fresh(name) for name in ("lcm", "previewer")}
     assert not torch.equal(want["lcm"], want["previewer"])
-    _call(pipe, inp, **kw3)                                        # (`previewer` is active)
+    lr.call(pipe, inp, **kw3)                                        # (`previewer` is active)
     assert pipe._loop_cache is not None
     pipe.unet.set_adapter("lcm")
     assert pipe._loop_cache is None
-    assert torch.equal(_call(pipe, inp, **kw3), want["lcm"])
+    assert torch.equal(lr.call(pipe, inp, **kw3), want["lcm"])
     assert pipe._loop_cache is not None
     pipe.prepare_previewers(lora, lora_alpha=16)                   # a second time: releases the merged `previewer` copies
     assert pipe._loop_cache is None and pipe.unet.active_adapters() == ["previewer"]
-    assert torch.equal(_call(pipe, inp, **kw3), want["previewer"])
+    assert torch.equal(lr.call(pipe, inp, **kw3), want["previewer"])
     assert pipe._loop_cache is not None
     pipe.aggregator.load_state_dict(sda)
     assert pipe._loop_cache is None
-    assert torch.equal(_call(pipe, inp, **kw3), want["previewer"])
+    assert torch.equal(lr.call(pipe, inp, **kw3), want["previewer"])
 
 
 def test_step_graphs_are_reused_across_calls(env, monkeypatch):
@@ -432,25 +365,25 @@ def test_step_graphs_are_reused_across_calls(env, monkeypatch):
     inp_b = dict(inp)
     for k in ("lq", "pe", "pooled", "npe", "npooled", "img", "init_noise"):
         inp_b[k] = (torch.randn(inp[k].shape, generator=g) * 0.7).half().float()
-    pipe = _pipe(cfg, sd, sda, lora, DDIMScheduler())
+    pipe = lr.pipe(env, DDIMScheduler())
     kw = dict(num_inference_steps=4, guidance_scale=7.0)
-    a1 = _call(pipe, inp, **kw)
+    a1 = lr.call(pipe, inp, **kw)
     loop = pipe._loop_cache[1]
-    b1 = _call(pipe, inp_b, **kw)
+    b1 = lr.call(pipe, inp_b, **kw)
     assert pipe._loop_cache[1] is loop, "second call of the same geometry built a new loop"
-    a2 = _call(pipe, inp, **kw)
+    a2 = lr.call(pipe, inp, **kw)
     assert pipe._loop_cache[1] is loop
     assert torch.equal(a1, a2) and not torch.equal(a1, b1)
     # a different number of rows (no classifier-free guidance): a new loop, and back again
     inp_c = dict(inp, img=inp["img"][1:])
-    c1 = _call(pipe, inp_c, num_inference_steps=4, guidance_scale=1.0)
+    c1 = lr.call(pipe, inp_c, num_inference_steps=4, guidance_scale=1.0)
     assert pipe._loop_cache[1] is not loop
-    a3 = _call(pipe, inp, **kw)
+    a3 = lr.call(pipe, inp, **kw)
     assert torch.equal(a1, a3)
     monkeypatch.setenv("IIR_LOOP_CACHE", "0")
-    fresh = _pipe(cfg, sd, sda, lora, DDIMScheduler())
-    assert torch.equal(_call(fresh, inp_b, **kw), b1)
-    assert torch.equal(_call(fresh, inp_c, num_inference_steps=4, guidance_scale=1.0), c1)
+    fresh = lr.pipe(env, DDIMScheduler())
+    assert torch.equal(lr.call(fresh, inp_b, **kw), b1)
+    assert torch.equal(lr.call(fresh, inp_c, num_inference_steps=4, guidance_scale=1.0), c1)
 
 
 def test_from_modules_matches_the_state_dict_constructor(env):
@@ -471,8 +404,8 @@ def test_from_modules_matches_the_state_dict_constructor(env):
 
     pipe = InstantIRPipeline.from_modules(unet=Mod(sd), aggregator=Mod(sda), scheduler=DDIMScheduler(), unet_config=cfg)
     pipe.prepare_previewers(lora, lora_alpha=16)
-    ref = _pipe(cfg, sd, sda, lora, DDIMScheduler())
+    ref = lr.pipe(env, DDIMScheduler())
     kw = dict(num_inference_steps=3, guidance_scale=7.0)
-    assert torch.equal(_call(pipe, inp, **kw), _call(ref, inp, **kw))
+    assert torch.equal(lr.call(pipe, inp, **kw), lr.call(ref, inp, **kw))
     with pytest.raises(ValueError):
         InstantIRPipeline.from_modules(scheduler=DDIMScheduler())

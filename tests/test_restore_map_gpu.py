@@ -5,24 +5,19 @@ select), iir_map_pool_max_f32 against torch's max_pool2d, iir_region_composite_f
 Loop level: the fused map against the contract applied through `callback_on_step_end` (the mechanism a caller had before),
 bit for bit, with hipGraph capture on; the two ends of the map; pixels in, pixels out; the cached loop; the CLI.
 No tolerance anywhere: every comparison is on bits."""
+import functools
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import loop_ref as lr
+from loop_ref import dev  # noqa: F401  (fixture)
+
 pytestmark = pytest.mark.gpu
 
 N_STEPS = 6
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from instantir_amd import lib
-    lib.load()
-    return torch.device("cuda:0")
 
 
 def bits(t):
@@ -232,24 +227,8 @@ def test_composite_refuses_mismatched_inputs(dev):
 # ---- the loop -----------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def env(dev):
-    from instantir_amd import weights as Wt
-    from instantir_amd.config import UNetConfig
-    cfg = UNetConfig.tiny()
-    sd = Wt.synth_state_dict(Wt.unet_specs(cfg), 11)
-    sda = Wt.synth_state_dict(Wt.aggregator_specs(cfg), 12)
-    lora = Wt.synth_state_dict(Wt.lora_specs(cfg), 13)
-    g = torch.Generator().manual_seed(42)
-    Bn, Hl = 2, 16
-    inp = dict(
-        lq=torch.randn(Bn, 4, Hl, Hl, generator=g) * 0.8,
-        pe=torch.randn(Bn, cfg.text_len, cfg.cross_attention_dim, generator=g).half().float(),
-        pooled=torch.randn(Bn, cfg.pooled_dim, generator=g).half().float(),
-        npe=torch.randn(Bn, cfg.text_len, cfg.cross_attention_dim, generator=g).half().float(),
-        npooled=torch.randn(Bn, cfg.pooled_dim, generator=g).half().float(),
-        img=torch.randn(2, Bn, cfg.resampler.seq_len, cfg.resampler.embedding_dim, generator=g).half().float(),
-        init_noise=torch.randn(Bn, 4, Hl, Hl, generator=g),
-        noises=[torch.randn(Bn, 4, Hl, Hl, generator=g) for _ in range(N_STEPS)],
-    )
+    cfg, sd, sda, lora, inp = lr.tiny_env(noises=N_STEPS)
+    Hl = inp["H"]
     # two different maps: every threshold of the 6-step table occurs as a value (with its neighbours), plus 0, 0.3 and 1
     thr = torch.tensor([(N_STEPS - 1 - i) / N_STEPS for i in range(N_STEPS)], dtype=torch.float32)
     vals = torch.cat([thr, torch.nextafter(thr, torch.tensor(1.0)), torch.tensor([0.0, 0.3, 1.0, 1.0])])
@@ -260,22 +239,12 @@ def env(dev):
 
 
 def _pipe(env, sched):
-    from instantir_amd.pipeline import InstantIRPipeline
-    cfg, sd, sda, lora, _ = env
-    pipe = InstantIRPipeline(cfg, sd, scheduler=sched)
-    pipe.aggregator.load_state_dict(sda)
-    pipe.prepare_previewers(lora, lora_alpha=16)
+    pipe = lr.pipe(env, sched)
     assert pipe.use_graphs                                            # hipGraph capture is the default, and stays on here
     return pipe
 
 
-def _call(pipe, inp, **kw):
-    from instantir_amd.schedulers import LCMSingleStepScheduler
-    lcm = LCMSingleStepScheduler.from_config(pipe.scheduler.config)
-    return pipe(image=inp["lq"], prompt_embeds=inp["pe"], pooled_prompt_embeds=inp["pooled"], negative_prompt_embeds=inp["npe"],
-                negative_pooled_prompt_embeds=inp["npooled"], ip_adapter_image_embeds=[inp["img"]], output_type="latent",
-                previewer_scheduler=lcm, init_noise=inp["init_noise"], num_inference_steps=N_STEPS, guidance_scale=5.0,
-                **kw).images.float().cpu()
+_call = functools.partial(lr.call, num_inference_steps=N_STEPS, guidance_scale=5.0)
 
 
 def _contract_callback(inp, m, dev, seen):

@@ -1,7 +1,8 @@
 """GPU: smoothed-energy guidance (SEG; Hong 2024) -- iir_seg_blur_q_f16 element-wise against the fp64 restatement of
 tests/seg_ref.py, the denoising loop against the CPU fp32 oracle with its self-attention in SEG form (seg_ref.swap_attn_self;
-oracle/ is not edited), and the bit-identity of everything SEG must not touch.  Loop geometry, pipelines and the PAG'd oracle
-are those of tests/test_pag_gpu.py."""
+oracle/nets.py is not edited), and the bit-identity of everything SEG must not touch.  Loop geometry, pipelines and the oracles are
+those of tests/loop_ref.py."""
+import functools
 import math
 import os
 
@@ -10,8 +11,9 @@ import pytest
 import torch
 
 import seg_ref
+import loop_ref as lr
 import test_pag_gpu as tp
-from test_pag_gpu import dev, env, pag_oracle_attn  # noqa: F401  (fixtures)
+from loop_ref import dev, env, pag_oracle_attn  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -137,125 +139,14 @@ def seg_oracle_attn(monkeypatch, pag_oracle_attn):
     seg_ref.SEG["paths"] = None
 
 
-_ORACLES = {}
-
-
-def _main_unet(kind, P, cfg, xin, t, ctx, text, tid, ip, down, mid, paths, B, sigma):
-    """[u;] c [; p] of the main UNet: `kind` None (no perturbed rows), "pag" or "seg"."""
-    from oracle import nets
-    if kind is None:
-        return nets.unet_forward(P, cfg, xin, t, ctx, text, tid, ip, down, mid)
-    if kind == "pag":
-        return tp._pag_unet(P, cfg, xin, t, ctx, text, tid, ip, down, mid, paths, B)
-    return seg_ref.seg_unet(P, cfg, xin, t, ctx, text, tid, ip, down, mid, paths, B, sigma)
-
-
-def ddim_oracle(env, kind, layers=None, *, guidance_scale, scale=0.0, sigma=100.0, guidance_rescale=0.0, apg=None,
-                num_inference_steps=8, preview_start=0.25, control_guidance_end=0.75):
-    """oracle.pipeline.denoise (DDIM) with eps = u + g (c - u) + s (c - p) (c + s (c - p) without CFG; with `apg` the CFG part
-    is apg_ref's, as the step kernel composes them), then rescale_noise_cfg with c as the text prediction.  Results are kept:
-    the plain and PAG'd oracles serve several cases."""
-    import test_apg_gpu as ta
-    from instantir_amd import pag
-    from oracle import nets, sched
-    key = (kind, str(layers), guidance_scale, scale if kind else 0.0, sigma if kind == "seg" else 0.0, guidance_rescale, apg,
-           num_inference_steps)
-    if key in _ORACLES:
-        return _ORACLES[key]
-    cfg, sd, sda, lora, inp = env
-    paths = pag.select(layers, pag.attn1_paths(cfg)) if kind else None
-    P = {k: v.float() for k, v in sd.items()}
-    PA = {k: v.float() for k, v in sda.items()}
-    L = {k: v.float() for k, v in lora.items()}
-    L["scaling"] = 16.0 / cfg.lora_rank
-    lq, B = inp["lq"], inp["B"]
-    do_cfg = guidance_scale > 1
-    acp = sched.make_alphas_cumprod()
-    ts = sched.leading_timesteps(num_inference_steps)
-    n = len(ts)
-    keep, previewing = sched.gating_tables(n, 0.0, control_guidance_end, preview_start, 1.0)
-    if do_cfg:
-        ctx, text, image = torch.cat([inp["npe"], inp["pe"]]), torch.cat([inp["npooled"], inp["pooled"]]), torch.cat([lq] * 2)
-        img = inp["img"]
-    else:
-        ctx, text, image, img = inp["pe"], inp["pooled"], lq, inp["img"][1:]
-    R = ctx.shape[0]
-    tid = torch.tensor([[128.0, 128, 0, 0, 128, 128]]).repeat(R, 1)
-    ip_main = nets.image_projection(P, [img], cfg.resampler)[0]
-    ip_prev = nets.image_projection(P, [img], cfg.resampler, L)[0]
-    x = sched.add_noise(acp, lq, inp["init_noise"], [int(ts[0])] * B)
-    down = mid = A = None
-    for i in range(n):
-        t = int(ts[i])
-        xin = torch.cat([x] * 2) if do_cfg else x
-        cond_scale = torch.ones(R, 1, 1, 1) * keep[i]
-        if (cond_scale > 0.1).sum().item() > 0:
-            if previewing[i] > 0:
-                preview = sched.lcm_step(acp, nets.unet_forward(P, cfg, xin, t, ctx, text, tid, ip_prev, lora=L), t, xin)
-            else:
-                preview = image
-            down, mid = nets.aggregator_forward(PA, cfg, image, t, preview, text, tid)
-        down = [s * cond_scale for s in down]
-        mid = mid * cond_scale
-        e = _main_unet(kind, P, cfg, xin, t, ctx, text, tid, ip_main, down, mid, paths, B, sigma)
-        rows = e.chunk(e.shape[0] // B)
-        c = rows[1] if do_cfg else rows[0]
-        if do_cfg and apg is not None:
-            eps, A = ta._apg32(rows[0], c, x, A, guidance_scale, (1 - acp[t]) ** 0.5, acp[t] ** 0.5, apg, i == 0)
-        else:
-            eps = rows[0] + guidance_scale * (c - rows[0]) if do_cfg else c
-        if kind:
-            eps = eps + scale * (c - rows[-1])
-        if do_cfg and guidance_rescale > 0:
-            dims = list(range(1, c.ndim))
-            eps = guidance_rescale * (eps * (c.std(dim=dims, keepdim=True) / eps.std(dim=dims, keepdim=True))) + (1 - guidance_rescale) * eps
-        x, _ = sched.ddim_step(acp, eps, t, x, num_inference_steps)
-    _ORACLES[key] = x
-    return x
-
-
-def dpm_oracle(env, kind, layers, monkeypatch, *, guidance_scale, scale, sigma=100.0, n=8):
-    """The DPM++ 2M Karras oracle loop of tests/test_sigma_schedulers_gpu.py with its main UNet call perturbed:
-    [u; c + (s / g)(c - p)] makes the loop's own u + g (c - u) the guided eps (as test_pag_gpu does for PAG)."""
-    import test_sigma_schedulers_gpu as sg
-    from instantir_amd import pag
-    from oracle import nets
-    paths = pag.select(layers, pag.attn1_paths(env[0])) if kind else None
-    orig = nets.unet_forward
-
-    def unet_forward(P, cfg_, xin, t, ctx, text, tid, ip, down_res=None, mid_res=None, lora=None, emb=None):
-        if lora is not None or down_res is None:
-            return orig(P, cfg_, xin, t, ctx, text, tid, ip, down_res, mid_res, lora=lora, emb=emb)
-        monkeypatch.setattr(nets, "unet_forward", orig)
-        try:
-            e = _main_unet(kind, P, cfg_, xin, t, ctx, text, tid, ip, down_res, mid_res, paths, xin.shape[0] // 2, sigma)
-        finally:
-            monkeypatch.setattr(nets, "unet_forward", unet_forward)
-        u, c, p = e.chunk(3)
-        return torch.cat([u, c + (scale / guidance_scale) * (c - p)])
-    if kind:
-        monkeypatch.setattr(nets, "unet_forward", unet_forward)
-    try:
-        return sg._oracle(env, "dpm", n, guidance_scale=guidance_scale, karras=True, **sg.PHASES)
-    finally:
-        monkeypatch.setattr(nets, "unet_forward", orig)
-
-
-def psnr(got, want, name=None):
-    from conftest import record_psnr
-    mse = ((got.double() - want.double()) ** 2).mean().item()
-    peak = want.abs().max().item()
-    v = 10 * math.log10(peak * peak / max(mse, 1e-30))
-    if name:
-        record_psnr("seg." + name, v)
-    return v
+_call = functools.partial(lr.call, **lr.LOOP)
 
 
 def _check_loop(tag, got, want, plain, pagd):
-    o_plain, o_pag = psnr(plain, want), psnr(pagd, want)
+    o_plain, o_pag = lr.psnr(plain, want), lr.psnr(pagd, want)
     print(f"{tag}: the SEG'd oracle is {o_plain:.1f} dB from the plain oracle and {o_pag:.1f} dB from the PAG'd one")
     assert o_plain <= BAR - GAP and o_pag <= BAR - GAP, (o_plain, o_pag)      # on CPU values alone: a no-op or PAG-like blur cannot pass
-    p, p_plain, p_pag = psnr(got, want, tag), psnr(got, plain), psnr(got, pagd)
+    p, p_plain, p_pag = lr.psnr(got, want, "seg." + tag), lr.psnr(got, plain), lr.psnr(got, pagd)
     print(f"{tag}: latent PSNR vs SEG'd oracle {p:.1f} dB, vs plain oracle {p_plain:.1f} dB, vs PAG'd oracle {p_pag:.1f} dB")
     assert torch.isfinite(got).all() and p >= BAR, p
     assert p_plain <= p - GAP and p_pag <= p - GAP, (p, p_plain, p_pag)
@@ -277,7 +168,7 @@ CASES = {
 
 
 def _seg_pipe(env, layers, sigma=100.0, sched=None, apg=None):
-    pipe = tp._pipe(env, sched)
+    pipe = lr.pipe(env, sched)
     pipe.enable_seg(layers, seg_blur_sigma=sigma)
     if apg is not None:
         pipe.enable_apg(*apg)
@@ -290,33 +181,35 @@ def test_loop_matches_seg_oracle(env, seg_oracle_attn, case):
     oracle, and the plain oracle and the PAG'd oracle of the same layers each at least 10 dB further away."""
     call_kw, layers, sigma, apg = CASES[case]
     g, s, phi = call_kw["guidance_scale"], call_kw["seg_scale"], call_kw.get("guidance_rescale", 0.0)
-    want = ddim_oracle(env, "seg", layers, guidance_scale=g, scale=s, sigma=sigma, guidance_rescale=phi, apg=apg)
-    plain = ddim_oracle(env, None, guidance_scale=g, guidance_rescale=phi, apg=apg)
-    pagd = ddim_oracle(env, "pag", layers, guidance_scale=g, scale=s, guidance_rescale=phi, apg=apg)
-    got = tp._call(_seg_pipe(env, layers, sigma, apg=apg), env[4], **call_kw)
+    want = lr.guided(env, "seg", layers, guidance_scale=g, scale=s, sigma=sigma, guidance_rescale=phi, apg_par=apg)
+    plain = lr.guided(env, None, guidance_scale=g, guidance_rescale=phi, apg_par=apg)
+    pagd = lr.guided(env, "pag", layers, guidance_scale=g, scale=s, guidance_rescale=phi, apg_par=apg)
+    got = _call(_seg_pipe(env, layers, sigma, apg=apg), env[4], **call_kw)
     _check_loop(case, got, want, plain, pagd)
 
 
-def test_dpmpp_2m_karras_matches_seg_oracle(env, seg_oracle_attn, monkeypatch):
-    import test_sigma_schedulers_gpu as sg
+def test_dpmpp_2m_karras_matches_seg_oracle(env, seg_oracle_attn):
+    """The sigma-scheduler oracle loop (DPM++ 2M Karras) with the hooks of the DDIM cases."""
+    from instantir_amd import pag
     g, s = 5.0, 6.0                  # (the scale of the `mid` cases: see CASES)
-    want = dpm_oracle(env, "seg", "mid", monkeypatch, guidance_scale=g, scale=s)
-    plain = dpm_oracle(env, None, None, monkeypatch, guidance_scale=g, scale=0.0)
-    pagd = dpm_oracle(env, "pag", "mid", monkeypatch, guidance_scale=g, scale=s)
-    got = tp._call(_seg_pipe(env, "mid", sched=sg._sched("dpm", karras=True)), env[4], guidance_scale=g, seg_scale=s,
-                   num_inference_steps=8, **sg.PHASES)
+    paths, B = pag.select("mid", pag.attn1_paths(env[0])), env[4]["B"]
+    oracle = functools.partial(lr.sigma_denoise, env, "dpm", 8, guidance_scale=g, karras=True, **lr.PHASES)
+    want = oracle(main_unet=lr.seg_unet(paths, B, 100.0), guide=lr.perturbed(g, s))
+    plain = oracle()
+    pagd = oracle(main_unet=lr.pag_unet(paths, B), guide=lr.perturbed(g, s))
+    got = _call(_seg_pipe(env, "mid", sched=lr.sigma_sched("dpm", karras=True)), env[4], guidance_scale=g, seg_scale=s)
     _check_loop("dpmpp_2m_karras", got, want, plain, pagd)
 
 
 # ---- bit-identity ------------------------------------------------------------------------------------------------------------------
 def test_disabled_and_zero_scale_bit_identical_to_never_enabled(env):
     inp = env[4]
-    base = tp._call(tp._pipe(env), inp)
+    base = _call(lr.pipe(env), inp)
     p = _seg_pipe(env, "mid")
     p.disable_seg()
-    assert torch.equal(tp._call(p, inp), base)
+    assert torch.equal(_call(p, inp), base)
     p2 = _seg_pipe(env, ["mid", "up_blocks.0"])
-    assert torch.equal(tp._call(p2, inp, seg_scale=0.0), base)
+    assert torch.equal(_call(p2, inp, seg_scale=0.0), base)
     assert p2._unet.seg is None and p2._unet.pag is None            # scale 0: the plain launches ran
 
 
@@ -340,11 +233,11 @@ def test_toggling_seg_pag_off_replays_the_right_graphs(env):
 
     fresh = {}
     for st in set(settings):
-        f = tp._pipe(env)
-        fresh[st] = tp._call(f, inp, **apply(f, st))
-    pipe, loops = tp._pipe(env), []
+        f = lr.pipe(env)
+        fresh[st] = _call(f, inp, **apply(f, st))
+    pipe, loops = lr.pipe(env), []
     for st in settings:
-        assert torch.equal(tp._call(pipe, inp, **apply(pipe, st)), fresh[st]), st
+        assert torch.equal(_call(pipe, inp, **apply(pipe, st)), fresh[st]), st
         loops.append(pipe._loop_cache[1])
     assert loops[4] is loops[5] and loops[3] is not loops[4] and loops[0] is not loops[1] and loops[1] is not loops[2]
     assert len({fresh[st].numpy().tobytes() for st in fresh}) == len(fresh)          # five states, five results
@@ -353,12 +246,12 @@ def test_toggling_seg_pag_off_replays_the_right_graphs(env):
 def test_graphs_on_off_and_repeat_calls_bit_identical(env):
     inp = env[4]
     pipe = _seg_pipe(env, ["mid", "up_blocks.0"], 2.0)
-    a = tp._call(pipe, inp)
-    b = tp._call(pipe, inp)
+    a = _call(pipe, inp)
+    b = _call(pipe, inp)
     pipe.use_graphs = False
-    c = tp._call(pipe, inp)
+    c = _call(pipe, inp)
     pipe.use_graphs, pipe.overlap_streams = True, False
-    d = tp._call(pipe, inp)
+    d = _call(pipe, inp)
     assert torch.equal(a, b) and torch.equal(a, c) and torch.equal(a, d)
 
 
@@ -373,9 +266,9 @@ def test_composes_with_restore_map_adastep_and_callback(env):
         seen.append(i)
         return {}
     kw = dict(restore_map=rmap, adastep_restore=True, callback_on_step_end=cb)
-    a = tp._call(_seg_pipe(env, "mid"), inp, **kw)
-    b = tp._call(_seg_pipe(env, "mid"), inp, **kw)
-    c = tp._call(tp._pipe(env), inp, **kw)
+    a = _call(_seg_pipe(env, "mid"), inp, **kw)
+    b = _call(_seg_pipe(env, "mid"), inp, **kw)
+    c = _call(lr.pipe(env), inp, **kw)
     assert torch.isfinite(a).all() and torch.equal(a, b) and not torch.equal(a, c) and seen[:8] == list(range(8))
 
 
@@ -486,6 +379,6 @@ def test_config1_geometry_one_step_with_seg(dev, seg_oracle_attn):
         eps = u + 7.0 * (c - u) + 3.0 * (c - p)
         want, _ = sched.ddpm_step(acp, eps, t, x, 1, noise=sn[0], prev_t=-1)
         plain, _ = sched.ddpm_step(acp, u + 7.0 * (c - u), t, x, 1, noise=sn[0], prev_t=-1)
-    v, v_plain = psnr(got, want, "config1_one_step"), psnr(got, plain)
+    v, v_plain = lr.psnr(got, want, "seg.config1_one_step"), lr.psnr(got, plain)
     print(f"configs[1] geometry, one step with SEG (mid): latent PSNR vs CPU fp32 oracle {v:.1f} dB, vs the unguided-by-SEG step {v_plain:.1f} dB")
     assert v >= 50.0, v

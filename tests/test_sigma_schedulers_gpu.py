@@ -1,7 +1,7 @@
 """GPU: the Euler / Euler-ancestral / DPM++ 2M schedulers on the HIP path -- iir_sched_step_hist(_f32) and
 iir_pack_latent_dscale against fp32 torch, the public `.step()` over whole timetables, and the denoising loop at the tiny
 geometry against the DDIM loop (Euler is DDIM in VP space) and against an fp32 CPU loop composed here from `oracle.nets`
-with the fp64 scheduler restatement of tests/test_sigma_schedulers_cpu.py."""
+with the fp64 scheduler restatement of tests/test_sigma_schedulers_cpu.py (tests/loop_ref.py: sigma_denoise)."""
 import math
 import os
 
@@ -9,52 +9,16 @@ import numpy as np
 import pytest
 import torch
 
+import loop_ref as lr
 import test_sigma_schedulers_cpu as spec
+from loop_ref import dev, env  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 BAR = 50.0
 
 
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from instantir_amd import lib
-    lib.load()
-    return torch.device("cuda:0")
-
-
-def psnr(got, want):
-    import inspect
-    from conftest import record_psnr
-    mse = ((got.double() - want.double()) ** 2).mean().item()
-    peak = want.abs().max().item()
-    v = 10 * math.log10(peak * peak / max(mse, 1e-30))
-    record_psnr("sigma." + inspect.stack()[1].function, v)
-    return v
-
-
-def _ref_step(e, x, coef, m_prev, noise):
-    """The kernels' fp32 op order: x0 = (x - sb*e)/sa; prev = k0*x0 + kx*x (+ ke*e) (+ kh*m) (+ kn*noise)."""
-    g, sb, sa, k0, kx, ke, kn, kh = [torch.tensor(c, dtype=torch.float32) for c in coef]
-    x0 = (x - sb * e) / sa
-    pv = k0 * x0 + kx * x
-    if float(ke) != 0:
-        pv = pv + ke * e
-    if float(kh) != 0:
-        pv = pv + kh * m_prev
-    if noise is not None and float(kn) != 0:
-        pv = pv + kn * noise
-    return pv, x0
-
-
-def _ulps(a, b):
-    """max |a - b| in fp32 ulps of max(|a|, |b|), floored at 2^-10 of the tensor's range (cancellation near zero)"""
-    d = (a.double() - b.double()).abs()
-    floor = max(b.abs().max().item() * 2.0 ** -10, 1e-30)
-    u = torch.finfo(torch.float32).eps * torch.maximum(a.abs(), b.abs()).double().clamp_min(floor)
-    return (d / u).max().item()
+psnr = lr.psnr_by_caller("sigma")
 
 
 # ---- kernels --------------------------------------------------------------------------------------------------------------
@@ -85,8 +49,8 @@ def test_sched_step_hist_matches_fp32(dev, B, H, W, cfg, extra):
         e = u + torch.tensor(coef[0]) * (t - u)
         if fac is not None:
             e = e * fac.view(B, 1, 1, 1)
-    want, want_x0 = _ref_step(e, x, coef, m, nz)
-    assert _ulps(prev.cpu(), want) <= 4 and _ulps(x0.cpu(), want_x0) <= 4
+    want, want_x0 = lr.ref_step(e, x, coef, m, nz)
+    assert lr.ulps(prev.cpu(), want) <= 4 and lr.ulps(x0.cpu(), want_x0) <= 4
     assert torch.equal(hist.cpu(), x0.cpu())                 # the plane now holds this step's x0
 
 
@@ -193,126 +157,7 @@ def test_public_step_over_a_timetable(dev, name):
 
 
 # ---- the denoising loop -------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def env(dev):
-    from instantir_amd import weights as W
-    from instantir_amd.config import UNetConfig
-    cfg = UNetConfig.tiny()
-    sd = W.synth_state_dict(W.unet_specs(cfg), 11)
-    sda = W.synth_state_dict(W.aggregator_specs(cfg), 12)
-    lora = W.synth_state_dict(W.lora_specs(cfg), 13)
-    g = torch.Generator().manual_seed(42)
-    B, H = 2, 16
-    inp = dict(
-        B=B, H=H,
-        lq=torch.randn(B, 4, H, H, generator=g) * 0.8,
-        pe=torch.randn(B, cfg.text_len, cfg.cross_attention_dim, generator=g).half().float(),
-        pooled=torch.randn(B, cfg.pooled_dim, generator=g).half().float(),
-        npe=torch.randn(B, cfg.text_len, cfg.cross_attention_dim, generator=g).half().float(),
-        npooled=torch.randn(B, cfg.pooled_dim, generator=g).half().float(),
-        img=torch.randn(2, B, cfg.resampler.seq_len, cfg.resampler.embedding_dim, generator=g).half().float(),
-        init_noise=torch.randn(B, 4, H, H, generator=g),
-        noises=[torch.randn(B, 4, H, H, generator=g) for _ in range(8)],
-    )
-    return cfg, sd, sda, lora, inp
-
-
-def _pipe(env, sched):
-    from instantir_amd.pipeline import InstantIRPipeline
-    cfg, sd, sda, lora, _ = env
-    pipe = InstantIRPipeline(cfg, sd, scheduler=sched)
-    pipe.aggregator.load_state_dict(sda)
-    pipe.prepare_previewers(lora, lora_alpha=16)
-    return pipe
-
-
-def _call(pipe, inp, **kw):
-    from instantir_amd.schedulers import LCMSingleStepScheduler
-    lcm = LCMSingleStepScheduler.from_config(pipe.scheduler.config)
-    return pipe(image=inp["lq"], prompt_embeds=inp["pe"], pooled_prompt_embeds=inp["pooled"],
-                negative_prompt_embeds=inp["npe"], negative_pooled_prompt_embeds=inp["npooled"],
-                ip_adapter_image_embeds=[inp["img"]], output_type="latent", previewer_scheduler=lcm,
-                init_noise=inp["init_noise"], **kw).images.float().cpu()
-
-
-def _oracle(env, kind, n, guidance_scale=5.0, preview_start=0.0, control_guidance_end=1.0, step_noises=None, karras=False,
-            adastep_restore=False):
-    """fp32 CPU loop, pipelines/sdxl_instantir.py:1385-1660 with a sigma scheduler: add_noise in the scheduler's space,
-    UNet / Aggregator input scale_model_input(cat([x]*2), t) at the float t, LCM preview on the scaled input at int(t),
-    the step from the fp64 restatement (spec_*) applied in fp32."""
-    from oracle import nets, sched
-    cfg, sd, sda, lora, inp = env
-    P = {k: v.float() for k, v in sd.items()}
-    PA = {k: v.float() for k, v in sda.items()}
-    L = {k: v.float() for k, v in lora.items()}
-    L["scaling"] = 16.0 / cfg.lora_rank
-    B = inp["B"]
-    acp = sched.make_alphas_cumprod()
-    if kind.startswith("euler"):
-        ts, sig = spec.spec_euler_table(n, "leading", karras)
-    else:
-        ts, sig = spec.spec_dpm_table(n, "leading", karras)
-    keep, previewing = sched.gating_tables(n, 0.0, control_guidance_end, preview_start, 1.0)
-    tid = torch.tensor([[128.0, 128, 0, 0, 128, 128]]).repeat(2 * B, 1)
-    ctx, text = torch.cat([inp["npe"], inp["pe"]]), torch.cat([inp["npooled"], inp["pooled"]])
-    image = torch.cat([inp["lq"]] * 2)
-    ip_main = nets.image_projection(P, [inp["img"]], cfg.resampler)[0]
-    ip_prev = nets.image_projection(P, [inp["img"]], cfg.resampler, L)[0]
-    vp = kind.startswith("dpm")
-    a0 = 1 / math.sqrt(sig[0] ** 2 + 1)
-    x = (a0 * inp["lq"] + (sig[0] * a0) * inp["init_noise"]) if vp else inp["lq"] + sig[0] * inp["init_noise"]
-    m = None
-    preview_factor = torch.ones(B, 1, 1, 1)
-    previewer_mean = torch.zeros_like(x)
-    down = mid = None
-    for i in range(n):
-        t = ts[i]
-        c_in = 1.0 if vp else float(np.float32(1 / math.sqrt(sig[i] ** 2 + 1)))
-        xin = torch.cat([x] * 2) * c_in
-        cond_scale = torch.cat([preview_factor.clamp(0.0, 1.0) * keep[i]] * 2)
-        if (cond_scale > 0.1).sum().item() > 0:
-            if previewing[i] > 0:
-                eps1 = nets.unet_forward(P, cfg, xin, t, ctx, text, tid, ip_prev, lora=L)
-                preview = sched.lcm_step(acp, eps1, int(t), xin)
-            else:
-                preview = image
-            down, mid = nets.aggregator_forward(PA, cfg, image, t, preview, text, tid)
-        down = [s * cond_scale for s in down]
-        mid = mid * cond_scale
-        eps = nets.unet_forward(P, cfg, xin, t, ctx, text, tid, ip_main, down, mid)
-        u, c = eps.chunk(2)
-        eps = u + guidance_scale * (c - u)
-        if kind == "euler":
-            coef = spec.spec_euler_coef(sig, i)
-        elif kind == "euler_a":
-            coef = spec.spec_euler_coef(sig, i, ancestral=True)
-        else:
-            coef = spec.spec_dpm_coef(sig, i, spec.spec_dpm_second_order(i, n), sde=kind == "dpm_sde")
-        c32 = [0.0] + [float(np.float32(v)) for v in coef[:6]] + [float(np.float32(coef[6]))]
-        nz = step_noises[i] if step_noises is not None else None
-        x_next, x0 = _ref_step(eps, x, c32, m, nz)
-        m = x0
-        if adastep_restore:
-            pv = preview[B:].float()
-            pred_x0_l2 = (pv - x0).pow(2).sum(dim=(1, 2, 3))
-            previewer_l2 = (pv - previewer_mean).pow(2).sum(dim=(1, 2, 3))
-            previewer_mean = preview[B:]
-            preview_factor = (pred_x0_l2 / previewer_l2).reshape(-1, 1, 1, 1)
-        x = x_next
-    return x
-
-
-def _sched(kind, karras=False):
-    from instantir_amd import schedulers as S
-    if kind == "euler":
-        return S.EulerDiscreteScheduler(use_karras_sigmas=karras)
-    if kind == "euler_a":
-        return S.EulerAncestralDiscreteScheduler()
-    return S.DPMSolverMultistepScheduler(use_karras_sigmas=karras,
-                                         algorithm_type="sde-dpmsolver++" if kind == "dpm_sde" else "dpmsolver++")
-
-
-PHASES = dict(preview_start=0.25, control_guidance_end=0.75)     # creative tail, Aggregator-only head, previewed middle
+PHASES = lr.PHASES
 
 
 @pytest.mark.parametrize("kind,karras,noises", [("dpm", True, False), ("dpm_sde", False, True), ("euler", True, False),
@@ -322,8 +167,8 @@ def test_loop_matches_fp32_oracle(env, kind, karras, noises):
     n = 8
     kw = dict(num_inference_steps=n, guidance_scale=5.0, **PHASES)
     sn = inp["noises"] if noises else None
-    want = _oracle(env, kind, n, step_noises=sn, karras=karras, **PHASES)
-    got = _call(_pipe(env, _sched(kind, karras)), inp, step_noises=sn, **kw)
+    want = lr.sigma_denoise(env, kind, n, step_noises=sn, karras=karras, **PHASES)
+    got = lr.call(lr.pipe(env, lr.sigma_sched(kind, karras)), inp, step_noises=sn, **kw)
     p = psnr(got, want)
     print(f"{kind} karras={karras}: latent PSNR vs fp32 oracle {p:.1f} dB")
     assert torch.isfinite(got).all() and p >= BAR, p
@@ -331,8 +176,8 @@ def test_loop_matches_fp32_oracle(env, kind, karras, noises):
 
 def test_adastep_restore_dpm_matches_oracle(env):
     inp = env[4]
-    want = _oracle(env, "dpm", 6, karras=True, adastep_restore=True)
-    got = _call(_pipe(env, _sched("dpm", True)), inp, num_inference_steps=6, guidance_scale=5.0, adastep_restore=True)
+    want = lr.sigma_denoise(env, "dpm", 6, karras=True, adastep_restore=True)
+    got = lr.call(lr.pipe(env, lr.sigma_sched("dpm", True)), inp, num_inference_steps=6, guidance_scale=5.0, adastep_restore=True)
     p = psnr(got, want)
     assert torch.isfinite(got).all() and p >= BAR, p
 
@@ -349,9 +194,9 @@ def test_euler_is_the_ddim_loop_in_vp_space(env):
             seen[key].append(kw["latents"].float().cpu().clone())
             return {}
         return cb
-    e = _sched("euler")
-    _call(_pipe(env, e), inp, num_inference_steps=n, guidance_scale=5.0, callback_on_step_end=rec("e"), **PHASES)
-    _call(_pipe(env, DDIMScheduler()), inp, num_inference_steps=n, guidance_scale=5.0, callback_on_step_end=rec("d"), **PHASES)
+    e = lr.sigma_sched("euler")
+    lr.call(lr.pipe(env, e), inp, num_inference_steps=n, guidance_scale=5.0, callback_on_step_end=rec("e"), **PHASES)
+    lr.call(lr.pipe(env, DDIMScheduler()), inp, num_inference_steps=n, guidance_scale=5.0, callback_on_step_end=rec("d"), **PHASES)
     for i in range(n - 1):
         s = float(e.sigmas[i + 1])
         p = psnr(seen["e"][i] / math.sqrt(s * s + 1), seen["d"][i])
@@ -362,21 +207,21 @@ def test_graphs_on_off_and_repeat_calls_bit_identical(env):
     from instantir_amd.schedulers import DDPMScheduler
     inp = env[4]
     kw = dict(num_inference_steps=6, guidance_scale=5.0, step_noises=inp["noises"], **PHASES)
-    pipe = _pipe(env, _sched("dpm_sde", False))
+    pipe = lr.pipe(env, lr.sigma_sched("dpm_sde", False))
     pipe.use_graphs = False
-    eager = _call(pipe, inp, **kw)
+    eager = lr.call(pipe, inp, **kw)
     pipe.use_graphs = True
-    g1 = _call(pipe, inp, **kw)
-    g2 = _call(pipe, inp, **kw)                   # the loop is adopted: the history is reset
+    g1 = lr.call(pipe, inp, **kw)
+    g2 = lr.call(pipe, inp, **kw)                   # the loop is adopted: the history is reset
     assert torch.equal(eager, g1) and torch.equal(g1, g2)
     dd = DDPMScheduler()
-    pipe_d = _pipe(env, dd)
-    want_d = _call(pipe_d, inp, **kw)
+    pipe_d = lr.pipe(env, dd)
+    want_d = lr.call(pipe_d, inp, **kw)
     dpm = pipe.scheduler
     pipe.scheduler = dd
-    assert torch.equal(_call(pipe, inp, **kw), want_d)
+    assert torch.equal(lr.call(pipe, inp, **kw), want_d)
     pipe.scheduler = dpm
-    assert torch.equal(_call(pipe, inp, **kw), g1)
+    assert torch.equal(lr.call(pipe, inp, **kw), g1)
 
 
 def test_prompt_embeds_replaced_mid_loop_keeps_history(env):
@@ -384,19 +229,19 @@ def test_prompt_embeds_replaced_mid_loop_keeps_history(env):
     values (a new tensor) gives the uninterrupted result bit for bit."""
     inp = env[4]
     kw = dict(num_inference_steps=6, guidance_scale=5.0, **PHASES)
-    pipe = _pipe(env, _sched("dpm", True))
-    want = _call(pipe, inp, **kw)
+    pipe = lr.pipe(env, lr.sigma_sched("dpm", True))
+    want = lr.call(pipe, inp, **kw)
 
     def cb(p, i, t, d):
         return {"prompt_embeds": d["prompt_embeds"].clone()} if i == 2 else {}
-    got = _call(pipe, inp, callback_on_step_end=cb, callback_on_step_end_tensor_inputs=["latents", "prompt_embeds"], **kw)
+    got = lr.call(pipe, inp, callback_on_step_end=cb, callback_on_step_end_tensor_inputs=["latents", "prompt_embeds"], **kw)
     assert torch.equal(got, want)
 
 
 def test_timesteps_argument_refused(env):
     inp = env[4]
     with pytest.raises(ValueError, match="timesteps"):
-        _call(_pipe(env, _sched("euler")), inp, timesteps=[999, 500, 1], guidance_scale=5.0)
+        lr.call(lr.pipe(env, lr.sigma_sched("euler")), inp, timesteps=[999, 500, 1], guidance_scale=5.0)
 
 
 def test_cli_dpmpp_2m_karras_equals_python_api(tmp_path, dev):
