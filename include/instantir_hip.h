@@ -413,6 +413,25 @@ int iir_map_pool_max_f32(const float* map_px, int32_t B, int32_t H, int32_t W, i
 int64_t iir_region_composite_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int iir_region_composite_f32(const float* decoded, const float* original, const float* map_px, int32_t B, int32_t C, int32_t H,
                              int32_t W, int32_t r, void* ws, int64_t ws_bytes, float* out, void* stream);
+/* LQ fidelity guidance (an addition with no reference call site; lineage and contract in DESIGN.md section 7 "LQ fidelity"):
+ * after a scheduler step, pull the step's predicted clean latent toward the LQ latent.  All planes fp32 planar
+ * (planes = B * C, H, W), wc = device fp32[2] {w, c}, read at launch:
+ *   d = lq - x0_in;  delta = w * LP(d);  x0_out = x0_in + delta;  prev = prev + c * delta;  hist = x0_out (when given)
+ * (no FMA contraction in these).  LP is a separable Gaussian of `radius` r, taps[2r + 1] (device fp32, normalised, read at
+ * launch), x then y; along each axis the taps that fall outside the image are dropped and the sum is divided by the sum of
+ * the taps that stayed:  LPx(d)[y][x] = (sum_j taps[j] * d[y][x + j - r]) / (sum_j taps[j]) over 0 <= x + j - r < W, both sums
+ * in index order, the first with fmaf; so LP(const) = const at the borders too.  radius 0: LP is the identity, taps is not
+ * read and no filter arithmetic runs.  A workgroup owns an IIR_LQ_FIDELITY_TILE^2 output tile of one plane and stages the tile
+ * plus its halo in LDS; neighbours read x0_in through their halos, so x0_out must not be x0_in.  prev and hist are read /
+ * written by the thread that owns the pixel.  Every global load is unconditional from a clamped address; no atomics: equal
+ * inputs give equal bits.
+ * IIR_EINVAL, before any HIP call: a NULL x0_in, lq, wc, prev or x0_out; radius < 0 or > IIR_LQ_FIDELITY_MAX_RADIUS; NULL taps
+ * with radius > 0; planes, H or W <= 0 (planes <= 65535, H, W <= 32768); x0_out == x0_in, or any output plane (prev, x0_out,
+ * hist) equal to an input plane or to another output plane. */
+#define IIR_LQ_FIDELITY_MAX_RADIUS 24
+#define IIR_LQ_FIDELITY_TILE 32
+int iir_lq_fidelity_f32(const float* x0_in, const float* lq, const float* taps, int32_t radius, const float* wc, int32_t planes,
+                        int32_t H, int32_t W, float* prev, float* x0_out, float* hist, void* stream);
 /* Batched copy of disjoint byte ranges in one launch: `jobs` = device int64[njobs][3] {src address, dst address, n16}, each
  * job copying n16 x 16 bytes (addresses 16-byte aligned); max_units = the largest n16.  PAG uses it to give the perturbed
  * rows of every Aggregator residual the cond rows' values. */

@@ -152,6 +152,7 @@ SIGNATURES = {
     "iir_map_pool_max_f32": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P]),
     "iir_region_composite_workspace_bytes": (C.c_int64, [_I32, _I32, _I32]),
     "iir_region_composite_f32": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P, _P]),
+    "iir_lq_fidelity_f32": (C.c_int, [_P, _P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
     "iir_copy_segments": (C.c_int, [_P, _I32, _I64, _P]),
     "iir_lcm_step": (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
     "iir_sched_step_f32": (C.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P]),

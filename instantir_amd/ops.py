@@ -951,3 +951,29 @@ def region_composite(decoded, original, map_px, feather, out=None, ws=None):
     L.check(h.iir_region_composite_f32(decoded.data_ptr(), original.data_ptr(), map_px.data_ptr(), B, Cc, H, W, r, ws.data_ptr(),
                                        ws.numel() * ws.element_size(), out.data_ptr(), _stream()), "iir_region_composite_f32")
     return out
+
+
+LQ_FIDELITY_MAX_RADIUS = 24     # IIR_LQ_FIDELITY_MAX_RADIUS
+LQ_FIDELITY_TILE = 32           # IIR_LQ_FIDELITY_TILE: the output tile a workgroup owns, per axis
+
+
+def lq_fidelity(x0, lq, wc, prev, x0_out, taps=None, hist=None):
+    """LQ fidelity guidance behind a scheduler step (iir_lq_fidelity_f32; DESIGN.md section 7 "LQ fidelity"): with
+    delta = w * LP(lq - x0), x0_out = x0 + delta, prev += c * delta (in place) and, when given, hist = x0_out.  x0, lq, prev,
+    x0_out, hist: fp32 (B, C, H, W) of one shape, each a tensor of its own (x0_out may not be x0: neighbouring tiles read x0);
+    `wc`: fp32 CUDA {w, c}, read at launch time; `taps`: the 2 r + 1 normalised fp32 Gaussian taps of LP on the device, None
+    for r = 0 (LP = identity, no filter arithmetic)."""
+    _chk_f32(x0, "lq_fidelity: x0", 4)
+    n = x0.numel()
+    _chk_group("lq_fidelity:", (("lq", lq, n), ("prev", prev, n), ("x0_out", x0_out, n), ("wc", wc, 2))
+               + ((("hist", hist, n),) if hist is not None else ()))
+    r = 0
+    if taps is not None:
+        _chk_f32(taps, "lq_fidelity: taps", 1)
+        if taps.numel() % 2 != 1 or taps.numel() // 2 > LQ_FIDELITY_MAX_RADIUS:
+            raise ValueError(f"lq_fidelity: taps must hold 2 r + 1 values with r <= {LQ_FIDELITY_MAX_RADIUS}, got {taps.numel()}")
+        r = taps.numel() // 2
+    B, Cc, H, W = x0.shape
+    L.check(L.load().iir_lq_fidelity_f32(x0.data_ptr(), lq.data_ptr(), _p(taps) if r else None, r, wc.data_ptr(), B * Cc, H, W,
+                                         prev.data_ptr(), x0_out.data_ptr(), _p(hist), _stream()), "iir_lq_fidelity_f32")
+    return x0_out

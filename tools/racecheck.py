@@ -85,5 +85,31 @@ for apB in (1, 8):
         ok = ap_name != "identity" or bool(((first[:ap_x.numel()] - ap_ref.flatten()).abs() <= 1e-4 + 1e-5 * ap_ref.flatten().abs()).all())
         bad_total += (not ok) + nd
         print(f"{'apg_project + sched_step_apg B=%d %s' % (apB, ap_name):56s} ref_ok={ok} nondeterministic_runs={nd}/{REP - 1}", flush=True)
+# LQ fidelity guidance: iir_lq_fidelity_f32 at 128^2 latents (x0', prev in place and the history plane; against torch's conv form of
+# the interior, where no tap is dropped), radius 0 (the one-thread-per-element launch), 5 and 24 (the tile launch)
+from instantir_amd import lq_fidelity as lqf
+lf_x0, lf_z, lf_p0 = (torch.randn(1, 4, 128, 128, generator=g).to(dev) for _ in range(3))
+lf_wc = torch.tensor([0.75, 0.625], device=dev)
+for lf_sigma in (0.0, 1.5, 8.0):
+    lf_t = lqf.taps(lf_sigma)
+    lf_taps = torch.tensor(lf_t, dtype=torch.float64).float().to(dev) if lf_t else None
+    lf_r = lqf.radius(lf_sigma)
+    lf_d = lf_z - lf_x0
+    if lf_r:
+        k2 = torch.outer(lf_taps, lf_taps)[None, None].repeat(4, 1, 1, 1)
+        lf_d = F.pad(F.conv2d(lf_d, k2, groups=4), [lf_r] * 4)
+    lf_want = lf_x0 + 0.75 * lf_d
+    first = None; nd = 0
+    for it in range(REP):
+        p, o, hs = lf_p0.clone(), torch.zeros_like(lf_x0), torch.zeros_like(lf_x0)
+        ops.lq_fidelity(lf_x0, lf_z, lf_wc, p, o, taps=lf_taps, hist=hs)
+        torch.cuda.synchronize()
+        cat = torch.cat([o.flatten(), p.flatten(), hs.flatten()])
+        if first is None: first = cat
+        elif not torch.equal(cat, first): nd += 1
+    inner = (slice(None), slice(None), slice(lf_r, 128 - lf_r), slice(lf_r, 128 - lf_r))
+    ok = bool(((first[:lf_x0.numel()].view_as(lf_x0)[inner] - lf_want[inner]).abs() <= 1e-4).all())
+    bad_total += (not ok) + nd
+    print(f"{'lq_fidelity 1x4x128x128 sigma %g (radius %d)' % (lf_sigma, lf_r):56s} ref_ok={ok} nondeterministic_runs={nd}/{REP - 1}", flush=True)
 print("TOTAL anomalies:", bad_total)
 sys.exit(1 if bad_total else 0)

@@ -255,4 +255,16 @@ for apB in (1, 8):
         ops.sched_step(ap_eps, apB, ap_coef, ap_x, o, noise=ap_nz, apg=(a, sa, ap_par))
     screen(f"apg_project + sched_step_apg B={apB} (CFG + DDPM noise)", apg_launch, [(apB, 4, 128, 128), (apB, 4, 128, 128), (2 * apB,)],
            dtype=torch.float32)
+# LQ fidelity guidance: the launch behind the step at 128^2 and 256^2 latents, both kernels (radius 0, 5, 24), x0' / prev / history
+from instantir_amd import lq_fidelity as lqf
+for lfH in (128, 256):
+    lf_x0, lf_z, lf_p0 = (torch.randn(1, 4, lfH, lfH, generator=g).to(dev) for _ in range(3))
+    lf_wc = torch.tensor([0.75, 0.625], device=dev)
+    for lf_sigma in (0.0, 1.5, 8.0):
+        lf_t = lqf.taps(lf_sigma)
+        lf_taps = torch.tensor(lf_t, dtype=torch.float64).float().to(dev) if lf_t else None
+        def lf_launch(o, p, hs):
+            p.copy_(lf_p0)
+            ops.lq_fidelity(lf_x0, lf_z, lf_wc, p, o, taps=lf_taps, hist=hs)
+        screen(f"lq_fidelity 1x4x{lfH}x{lfH} sigma {lf_sigma:g}", lf_launch, [(1, 4, lfH, lfH)] * 3, dtype=torch.float32)
 print("kernels with run-to-run differences:", bad)
