@@ -14,6 +14,9 @@ epilogues -- with `rows[m]` the physical output row of logical row m (`y_img_row
            * wscale[n] * a_scale (fp8 forms; the fp8-weight form first rounds the activations to E4M3 as the kernel does);
            bias, row bias [m // rows_per_rb]; the activation (SiLU, exact-erf GELU, x * sigmoid(1.702 x));
            paired epilogues on the `pair_rows` layout: GEGLU value * gelu(gate), SFT h * (gamma + 1) + beta.
+           With `ln_in = (partials, colsum, eps)` (GEMM only) the value before the activation is the LayerNorm fold
+           rstd * (a @ w.T - mean * colsum) + bias; it and its shift are restated in tests/gemm_fused_ref.py (`ln_fold`), which also
+           holds the references of the statistics a launch leaves (`ln_out`, `gn_out`).
   want   what the kernel stores under its documented order (epilogue comment of gemm_conv.hip): y1 = round_E(p), then
            round_E((y1 + res) * out_scale), `res` read through the `res_img_rows` remap; paired epilogues round once (then times
            out_scale); fp32 output: p * out_scale unrounded.  Columns >= tr_from of an `out_t` launch are the caller's to transpose.
@@ -187,8 +190,12 @@ def reference(kind, spec, c_gelu=None):
     S = A.abs() @ Wm.abs().T
     if scale is not None:
         v, S = v * scale[None, :], S * scale.abs()[None, :]
-    assert s.get("ln_in") is None, "the LayerNorm fold is not restated here"
-    if s.get("bias") is not None:
+    fold = None
+    if s.get("ln_in") is not None:          # the LayerNorm fold: restated, with its shift, in tests/gemm_fused_ref.py
+        import gemm_fused_ref
+        assert kind == "gemm" and s.get("rowbias") is None and s.get("out_dtype") is None and epi != EPI_SFT, "ln_in: a GEMM without row bias, 2-byte output"
+        v, fold = gemm_fused_ref.ln_fold(s, v, S, g)          # v: rstd * (a w^T - mean colsum) + bias; fold: its shift
+    elif s.get("bias") is not None:
         v = v + s["bias"].double()[None, :]
     if s.get("rowbias") is not None:
         v = v + s["rowbias"].double()[torch.arange(M) // s.get("rows_per_rb", 1)]
@@ -198,7 +205,7 @@ def reference(kind, spec, c_gelu=None):
 
     if epi == EPI_PLAIN:
         p = activation(v, act)
-        d = 2 * g * S * LIPSCHITZ[act]
+        d = 2 * g * S * LIPSCHITZ[act] if fold is None else fold * LIPSCHITZ[act]
         if act == ACT_GELU:
             d = d + c_gelu * v.abs()
         r = res.double()[res_rows] if res is not None else torch.zeros((), dtype=torch.float64)
@@ -210,7 +217,11 @@ def reference(kind, spec, c_gelu=None):
     else:
         val, par = unpair(v)
         Sv, Sp = unpair(S)
-        if epi == EPI_GEGLU:
+        if epi == EPI_GEGLU and fold is not None:          # the product rule on the two folded shifts
+            p = val * gelu(par)
+            dv, dp = unpair(fold)
+            d = gelu(par).abs() * dv + val.abs() * 1.13 * dp + 1.13 * dv * dp + c_gelu * val.abs()
+        elif epi == EPI_GEGLU:
             p = val * gelu(par)
             d = 2 * (gelu(par).abs() * g * Sv + val.abs() * 1.13 * g * Sp + 1.13 * g * Sv * g * Sp) + c_gelu * val.abs()
         elif epi == EPI_SFT:

@@ -57,8 +57,9 @@ softmax       t = x - max (u |t|), exp(t) = v_exp(t * log2e): u |t| for each of 
 crossed at the rounding moves a whole ulp.  fp16 results below the smallest normal go through the same image (numpy rounds into
 the subnormals as the hardware conversion does).  Nothing here comes from a kernel's output; no term is measured.
 
-Out of scope: offsets beyond 2 GiB; a softmax row that is entirely -inf; the GroupNorm partials a GEMM / conv writes and the
-LayerNorm fold of the GEMM (tests/gemm_conv_ref.py still asserts `ln_in is None`).
+Out of scope: offsets beyond 2 GiB; a softmax row that is entirely -inf.  The GroupNorm partials a GEMM / conv writes (`gn_out`),
+its LayerNorm partials (`ln_out`) and the LayerNorm fold of the GEMM (`ln_in`) are restated in tests/gemm_fused_ref.py, which hands
+the partials of a producing launch to `gnp_reference_of` here.
 """
 import collections
 import functools
@@ -197,6 +198,21 @@ def silu64(f):
         return f / (1.0 + np.exp(-f))
 
 
+def gnp_stats64(part, R, G):
+    """The `partials=` form on ANY fp32 partials (R * HW / 64, C, 2): per (image, group) mean, var and the error of the kernel's."""
+    slabs, C = part.shape[0] // R, part.shape[1]
+    cpg = C // G
+    pt = np.asarray(part).astype(np.float64).reshape(R, slabs, G, cpg, 2)
+    pm = pt[..., 0].transpose(0, 2, 1, 3).reshape(R, G, -1)
+    mean = pm.mean(-1)
+    dp = np.abs(pm - mean[..., None])
+    var = (pt[..., 1].transpose(0, 2, 1, 3).reshape(R, G, -1).sum(-1) + 64.0 * (dp ** 2).sum(-1)) / (pm.shape[-1] * 64.0)
+    k = 28
+    e_mean = (g_(k) + U) * np.abs(pm).max(-1)
+    e_var = 2 * dp.max(-1) * e_mean + e_mean ** 2 + (g_(k) + 5 * U) * var
+    return mean, var, e_mean, e_var, dict(chain=k)
+
+
 @functools.lru_cache(maxsize=8)
 def _gn_stats64(shape, dtype, mode, partials):
     """Per (image, group): mean, var, and the error of the kernel's mean / var (see the module docstring) with its terms."""
@@ -204,15 +220,7 @@ def _gn_stats64(shape, dtype, mode, partials):
     geo = gn_geo(R, HW, C, G)
     cpg = C // G
     if partials:
-        pt = gn_partials(shape, dtype, mode).astype(np.float64).reshape(R, HW // 64, G, cpg, 2)
-        pm = pt[..., 0].transpose(0, 2, 1, 3).reshape(R, G, -1)
-        mean = pm.mean(-1)
-        dp = np.abs(pm - mean[..., None])
-        var = (pt[..., 1].transpose(0, 2, 1, 3).reshape(R, G, -1).sum(-1) + 64.0 * (dp ** 2).sum(-1)) / (pm.shape[-1] * 64.0)
-        k = 28
-        e_mean = (g_(k) + U) * np.abs(pm).max(-1)
-        e_var = 2 * dp.max(-1) * e_mean + e_mean ** 2 + (g_(k) + 5 * U) * var
-        terms = dict(chain=k)
+        return gnp_stats64(gn_partials(shape, dtype, mode), R, G)
     else:
         v = gn_input(shape, dtype, mode)[1].reshape(R, HW, G, cpg)
         mean = v.mean((1, 3))
@@ -238,12 +246,23 @@ def gn_reference(cs, rounding=True):
     o = cs.opt
     mode, eps, silu, partials = o["mode"], o["eps"], o["silu"], cs.kind == "gnp"
     _, v, gm, bt = gn_input(cs.shape, cs.dtype, mode)
-    gm, bt = gm.double().numpy(), bt.double().numpy()
-    mean, var, e_mean, e_var, terms = _gn_stats64(cs.shape, cs.dtype, mode, partials)
+    stats = _gn_stats64(cs.shape, cs.dtype, mode, partials)
+    return _gn_apply(cs.name, cs.shape, cs.dtype, v, gm.double().numpy(), bt.double().numpy(), stats, eps, silu, rounding)
+
+
+def gnp_reference_of(name, shape, dtype, v, gm, bt, part, eps, silu):
+    """`gn_reference` of the `partials=` form for operands that do not come from `gn_input`: v (R, HW, C) the stored x as float64,
+    gm / bt float64 (C,), part the fp32 partials a producing launch left (tests/test_gemm_fused_every_build_gpu.py)."""
+    return _gn_apply(name, shape, dtype, v, gm, bt, gnp_stats64(part, shape[0], shape[3]), eps, silu, True)
+
+
+def _gn_apply(name, shape, dtype, v, gm, bt, stats, eps, silu, rounding):
+    R, HW, C, G = shape
+    mean, var, e_mean, e_var, terms = stats
     cpg = C // G
     rstd = 1.0 / np.sqrt(var + eps)
     r = e_var / (var + eps) + 2 * U
-    assert r.max() < 2.0 ** -5, (cs.name, r.max())
+    assert r.max() < 2.0 ** -5, (name, r.max())
     rel = r / (2 * (1 - r)) + 3 * U
     ex = lambda t: np.repeat(t, cpg, axis=1)[:, None, :]           # (R, G) -> (R, 1, C)
     a = ex(rstd) * gm
@@ -259,7 +278,7 @@ def gn_reference(cs, rounding=True):
     if not rounding:
         return value
     terms = dict(terms, rstd_rel=float(rel.max()))
-    return _finish(value, slack, cs.dtype, terms)
+    return _finish(value, slack, dtype, terms)
 
 
 def _finish(value, slack, dtype, terms, fp8=False):
