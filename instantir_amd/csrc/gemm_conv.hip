@@ -33,6 +33,9 @@ constexpr int BK = 64;   // halfs per K tile = one 128-byte LDS row
 // `lgkmcnt(0)` right behind them -- one exposed LDS round trip (~200 cycles with four waves reading and the LDS-DMA writing) per
 // half step, with one wave per SIMD nothing else to cover it.  A scheduling barrier after each read group keeps the source order.
 #define IIR_PIN() __builtin_amdgcn_sched_barrier(0)
+// The epilogue's lambdas are instantiated once per form; left to its size heuristics hipcc turns the larger ones into CALLS in the
+// loader-wave builds (912 B of scratch per lane, a wave per SIMD lost, flat instead of LDS / global accesses).
+#define IIR_INLINE __attribute__((always_inline))
 constexpr int PF_TOUCHES = 4;   // prefetch touches per lane per launch (x 128 B x threads = up to 128-256 KiB per workgroup)
 
 // GroupNorm-partial write-out (gn_out): 64-row slabs written side by side, and whether its LDS fits behind the staged output tile.
@@ -603,76 +606,111 @@ __global__ __launch_bounds__(128 * WAVES_M * (LW ? 2 : 1), (WAVES_M == 2 ? 2 : 1
         ms[i] = min(m0 + lrs[i], g.M - 1);                 // tail rows: computed from clamped operands, dropped in phase 2
         rss[i] = (g.ln_in && !xdone) ? rowstat[lrs[i]] : make_float2(1.f, 0.f);
     }
-    if (!paired) {
+    // What every form shares runs first, in place: the fp8 scales and the affine step (LayerNorm fold about the column sum, bias).
+    // Columns past N read their constants at N - 4 (clamped) and are computed; phase 2 never writes them out.
 #pragma unroll
-        for (int j = 0; j < NI; ++j) {
-            const int lc = wn * WN + j * 16 + fq * 4;
-            const int n = n0 + lc;
-            if (n >= g.N) continue;
-            float sc[4] = {1.f, 1.f, 1.f, 1.f}, c0[4] = {0.f, 0.f, 0.f, 0.f}, c1[4] = {0.f, 0.f, 0.f, 0.f};
-            if (W8 || F8) { const f32x4 ws = *(const f32x4*)(g.wscale + n); for (int t = 0; t < 4; ++t) sc[t] = ws[t] * g.a_scale; }
-            for (int t = 0; t < 4; ++t) { c1[t] = pre_c1[j][t]; c0[t] = (float)pre_c0[j][t]; }
+    for (int j = 0; j < NI; ++j) {
+        float sc[4] = {1.f, 1.f, 1.f, 1.f};
+        if constexpr (W8 || F8) {
+            const f32x4 ws = *(const f32x4*)(g.wscale + min(n0 + wn * WN + j * 16 + fq * 4, g.N - 4));
+            for (int t = 0; t < 4; ++t) sc[t] = ws[t] * g.a_scale;
+        }
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+            for (int t = 0; t < 4; ++t)
+                acc[i][j][t] = iir::epi_affine((W8 || F8) ? acc[i][j][t] * sc[t] : acc[i][j][t], rss[i], pre_c1[j][t], (float)pre_c0[j][t]);
+    }
+    // The rest -- plain / GEGLU / SFT, the activation, row bias or none -- is decided once, below this lambda, and is a compile-time
+    // value inside it: the executed path of a launch is one straight-line block over its (j, i) quads, with no test per column group.
+    // Paired columns: in every 16-column group of the (row-permuted) weight the first 8 are the "value" rows and the next 8 their
+    // partners (gate for GEGLU; beta for SFT).  A lane holds 4 consecutive columns, so value lanes (fq = 0,1) and their partners
+    // (fq + 2) sit 32 lanes apart: one cross-half swap per register (iir::xhalf_swap, v_permlane32_swap: VALU, no LDS round trip).
+    auto phase1 = [&](auto epi_tag, auto act_tag, auto rb_tag) IIR_INLINE {
+        constexpr int FORM = decltype(epi_tag)::value, ACT = decltype(act_tag)::value;
+        constexpr bool RB = decltype(rb_tag)::value;
+        int rb_row[RB ? MI : 1];
+        long res_row[FORM == IIR_EPI_SFT ? MI : 1];
+        if constexpr (RB) {
+#pragma unroll
+            for (int i = 0; i < MI; ++i) rb_row[i] = ms[i] / g.rows_per_rb;
+        }
+        if constexpr (FORM == IIR_EPI_SFT) {
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
-                const int lr = lrs[i];
-                float v[4];
-                for (int t = 0; t < 4; ++t) v[t] = (W8 || F8) ? acc[i][j][t] * sc[t] : acc[i][j][t];
-                for (int t = 0; t < 4; ++t) v[t] = iir::epi_affine(v[t], rss[i], c1[t], c0[t]);
-                if (g.rowbias) { E4 b = *(const E4*)(g.rowbias + (long)(ms[i] / g.rows_per_rb) * g.ldrb + n); for (int t = 0; t < 4; ++t) v[t] += (float)b[t]; }
-                // (twin of iir::epi_act, gemm_geo.h: as a call it grows the scratch of the two 256x320 builds)
-                if (g.act == IIR_ACT_SILU) for (int t = 0; t < 4; ++t) v[t] = silu_f(v[t]);
-                else if (g.act == IIR_ACT_GELU) for (int t = 0; t < 4; ++t) v[t] = gelu_erf_f(v[t]);
-                else if (g.act == IIR_ACT_QUICKGELU) for (int t = 0; t < 4; ++t) v[t] = quick_gelu_f(v[t]);
-                E4 o;
-                for (int t = 0; t < 4; ++t) o[t] = (E)v[t];
-                *(E4*)(ct + lr * cs + lc * 2) = o;
+                long mr = ms[i];
+                if (CONV && g.res_img_rows) { const int hw = g.Ho * g.Wo, img = ms[i] / hw; mr = (long)img * g.res_img_rows + (ms[i] - img * hw); }
+                res_row[i] = mr;
             }
         }
-    } else {
-        // paired columns: in every 16-column group of the (row-permuted) weight the first 8 are the "value" rows and
-        // the next 8 their partners (gate for GEGLU; beta for SFT).  A lane holds 4 consecutive columns, so value
-        // lanes (fq = 0,1) fetch their partner from lane + 32 (fq + 2) with one cross-half exchange per register.
+        // What a column group loads at this point (row bias, the SFT `h`) is requested at its top, for all its rows at once.
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
-            const int n = n0 + wn * WN + j * 16 + fq * 4;           // permuted column held by this lane
-            const bool in_n = n < g.N;
-            float sc[4] = {1.f, 1.f, 1.f, 1.f}, c0[4] = {0.f, 0.f, 0.f, 0.f}, c1[4] = {0.f, 0.f, 0.f, 0.f};
-            if ((W8 || F8) && in_n) { const f32x4 ws = *(const f32x4*)(g.wscale + n); for (int t = 0; t < 4; ++t) sc[t] = ws[t] * g.a_scale; }
-            for (int t = 0; t < 4; ++t) { c1[t] = pre_c1[j][t]; c0[t] = (float)pre_c0[j][t]; }
+            const int lc = wn * WN + j * 16 + fq * 4;                   // (permuted) column held by this lane, inside the tile
+            const int nl = min(n0 + lc, g.N - 4);                       // where its column constants are read
+            E4 rbv[RB ? MI : 1], hv[FORM == IIR_EPI_SFT ? MI : 1];
+            if constexpr (RB) {
+#pragma unroll
+                for (int i = 0; i < MI; ++i) rbv[i] = *(const E4*)(g.rowbias + (long)rb_row[i] * g.ldrb + nl);
+            }
+            if constexpr (FORM == IIR_EPI_SFT) {      // (gate lanes fetch their value lane's quad: in range, never used)
+                const int col = min(n0 / 2 + (wn * WN + j * 16) / 2 + (fq & 1) * 4, g.N / 2 - 4);
+#pragma unroll
+                for (int i = 0; i < MI; ++i) hv[i] = *(const E4*)(g.res + res_row[i] * g.ldr + col);
+            }
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
                 const int lr = lrs[i];
                 float a[4];
-                for (int t = 0; t < 4; ++t) a[t] = (W8 || F8) ? acc[i][j][t] * sc[t] : acc[i][j][t];
-                for (int t = 0; t < 4; ++t) a[t] = iir::epi_affine(a[t], rss[i], c1[t], c0[t]);
-                float b[4];
-                for (int t = 0; t < 4; ++t) b[t] = __shfl_xor(a[t], 32, 64);     // all lanes take part in the exchange
-                if (g.epi == IIR_EPI_GEGLU) {
-                    // (Twin of iir::geglu_pair, gemm_geo.h, which gemm8.hip calls: as a call it costs the bf16 64x64 build a wave per SIMD.)
+                for (int t = 0; t < 4; ++t) a[t] = acc[i][j][t];
+                if constexpr (FORM == IIR_EPI_PLAIN) {
+                    if constexpr (RB) for (int t = 0; t < 4; ++t) a[t] += (float)rbv[i][t];
+                    // (twin of iir::epi_act, gemm_geo.h: as a call it grows the scratch of the two 256x320 builds)
+                    if constexpr (ACT == IIR_ACT_SILU) for (int t = 0; t < 4; ++t) a[t] = silu_f(a[t]);
+                    else if constexpr (ACT == IIR_ACT_GELU) for (int t = 0; t < 4; ++t) a[t] = gelu_erf_f(a[t]);
+                    else if constexpr (ACT == IIR_ACT_QUICKGELU) for (int t = 0; t < 4; ++t) a[t] = quick_gelu_f(a[t]);
+                    E4 o;
+                    for (int t = 0; t < 4; ++t) o[t] = (E)iir::rounded_f32(a[t]);
+                    *(E4*)(ct + lr * cs + lc * 2) = o;
+                } else if constexpr (FORM == IIR_EPI_GEGLU) {
                     // value * gelu(gate): the erf evaluation (14 VALU + v_rcp + v_exp per element) is the cost of this epilogue
                     // -- kbench 2048x10240x1280: 865 TFLOP/s plain, 735 with value lanes alone doing all four columns -- so
                     // both lanes of a pair work: the value lane finishes columns 0,1 of the quad, its gate lane columns 2,3.
-                    if (!in_n) continue;
-                    const bool gate = fq >= 2;
-                    const int lco = (wn * WN + j * 16) / 2 + (fq & 1) * 4 + (gate ? 2 : 0);
-                    const float v0 = gate ? b[2] : a[0], v1 = gate ? b[3] : a[1], g0 = gate ? a[2] : b[0], g1 = gate ? a[3] : b[1];
                     typedef E E2 __attribute__((ext_vector_type(2)));
-                    E2 o2 = {(E)(v0 * gelu_erf_f(g0)), (E)(v1 * gelu_erf_f(g1))};
-                    *(E2*)(ct + lr * cs + lco * 2) = o2;
-                    continue;
+                    // (twin of iir::geglu_pair, gemm_geo.h, with its swap)
+                    float v0, g0, v1, g1;
+                    iir::xhalf_swap(a[0], a[2], v0, g0);
+                    iir::xhalf_swap(a[1], a[3], v1, g1);
+                    const E2 o2 = {(E)iir::rounded_f32(v0 * gelu_erf_f(g0)), (E)iir::rounded_f32(v1 * gelu_erf_f(g1))};
+                    *(E2*)(ct + lr * cs + ((wn * WN + j * 16) / 2 + iir::geglu_col(fq)) * 2) = o2;
+                } else {
+                    // IIR_EPI_SFT: h * (gamma + 1) + beta, h from `res`; the value lanes store
+                    float own, b[4];
+                    for (int t = 0; t < 4; ++t) iir::xhalf_swap(a[t], a[t], own, b[t]);
+                    if (fq < 2) {
+                        const int lco = (wn * WN + j * 16) / 2 + fq * 4;        // output column inside the tile
+                        const E4 h = hv[i];
+                        E4 o;
+                        for (int t = 0; t < 4; ++t) o[t] = (E)iir::rounded_f32(fmaf((float)h[t], a[t] + 1.0f, b[t]));
+                        *(E4*)(ct + lr * cs + lco * 2) = o;
+                    }
                 }
-                if (fq >= 2 || !in_n) continue;
-                const int lco = (wn * WN + j * 16) / 2 + fq * 4;        // output column inside the tile
-                long mr = ms[i];
-                if (CONV && g.res_img_rows) { const int hw = g.Ho * g.Wo, img = ms[i] / hw; mr = (long)img * g.res_img_rows + (ms[i] - img * hw); }
-                E4 o;
-                {   // IIR_EPI_SFT: h * (gamma + 1) + beta, h from `res`
-                    E4 h = *(const E4*)(g.res + mr * g.ldr + n0 / 2 + lco);
-                    for (int t = 0; t < 4; ++t) o[t] = (E)((float)h[t] * (a[t] + 1.0f) + b[t]);
-                }
-                *(E4*)(ct + lr * cs + lco * 2) = o;
             }
         }
+    };
+    using iir::form_tag;
+    if (g.epi == IIR_EPI_GEGLU) phase1(form_tag<IIR_EPI_GEGLU>{}, form_tag<IIR_ACT_NONE>{}, std::false_type{});
+    else if (g.epi == IIR_EPI_SFT) phase1(form_tag<IIR_EPI_SFT>{}, form_tag<IIR_ACT_NONE>{}, std::false_type{});
+    else {
+        auto plain = [&](auto rb_tag) IIR_INLINE {
+            switch (g.act) {
+                case IIR_ACT_SILU: phase1(form_tag<IIR_EPI_PLAIN>{}, form_tag<IIR_ACT_SILU>{}, rb_tag); break;
+                case IIR_ACT_GELU: phase1(form_tag<IIR_EPI_PLAIN>{}, form_tag<IIR_ACT_GELU>{}, rb_tag); break;
+                case IIR_ACT_QUICKGELU: phase1(form_tag<IIR_EPI_PLAIN>{}, form_tag<IIR_ACT_QUICKGELU>{}, rb_tag); break;
+                default: phase1(form_tag<IIR_EPI_PLAIN>{}, form_tag<IIR_ACT_NONE>{}, rb_tag); break;
+            }
+        };
+        if (g.rowbias) plain(std::true_type{});
+        else plain(std::false_type{});
     }
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // tile complete

@@ -3,6 +3,7 @@
 #include "common.h"
 #include "../../include/instantir_hip.h"
 #include <math.h>
+#include <type_traits>
 
 namespace iir {
 
@@ -66,7 +67,8 @@ struct Geo {   // per-launch constants shared by GEMM and CONV paths
 
 // ---- what the 4-wave kernel (gemm_conv.hip) and the 8-wave kernel (gemm8.hip) share: the two must agree bit for bit.  Of
 // ln_row_stat, epi_act and geglu_pair gemm_conv.hip keeps its own text ("twin of", with the measurements behind each form): as
-// calls they grow the scratch of its 256x320 builds or cost its bf16 64x64 build a wave per SIMD.
+// calls they grow the scratch of its 256x320 builds or cost its 64x64 builds a wave per SIMD; xhalf_swap
+// and form_tag it shares.
 
 // XCD-aware tile order.  Workgroups b, b+8, b+16, ... share an XCD (= one private L2).  The tile grid is cut into 8 rectangles
 // (xm x 8/xm), one per XCD, chosen on the host (xcd_partition) to minimise the operand bytes each L2 has to pull over the
@@ -145,6 +147,11 @@ __device__ __forceinline__ float rounded_f32(float x) {
     asm("" : "+v"(x));
     return x;
 }
+
+// A launch-uniform choice (epilogue form, activation) handed to a generic lambda as a compile-time value: the caller
+// tests the flag once and the lambda's body holds no run-time test of it.
+template <int V>
+using form_tag = std::integral_constant<int, V>;
 
 // (ACT is a compile-time value: the caller decides the activation once per chunk, outside its unrolled quad loops)
 template <int ACT>

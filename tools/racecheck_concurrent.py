@@ -110,6 +110,11 @@ c1w = rnd(1280, 1, 1, 640, scale=0.04)
 screen("conv1x1 2x64x64 640->1280", lambda o: ops.conv2d(cx, c1w, o, ksize=1), [(2 * 64 * 64, 1280)])
 sx, sw, sb, sres = rnd(2, 32, 32, 256), pair_rows(rnd(1280, 3, 3, 256, scale=0.02), rnd(1280, 3, 3, 256, scale=0.02)), pair_rows(rnd(1280), rnd(1280)), rnd(2 * 32 * 32, 1280)
 screen("conv3x3 SFT epilogue 2x32x32 256->2x1280", lambda o: ops.conv2d(sx, sw, o, bias=sb, res=sres, epi=ops.EPI_SFT), [(2 * 32 * 32, 1280)])
+# the 4-wave kernel's pair exchange (GEGLU on its own tiles; tile = 0 sends this shape to the 8-wave kernel) and its row-bias form
+for tile in (24, 55):
+    screen(f"gemm4 GEGLU 2048x10240x1280 tile {tile}", lambda o: ops.gemm(x, wp, o, bias=bp, epi=ops.EPI_GEGLU, tile=tile), [(M, N // 2)])
+crb = rnd(2, 640)
+screen("gemm4 conv3x3 2x64x64 640->640 row bias + SiLU", lambda o: ops.conv2d(cx, cw, o, bias=cb, rowbias=crb, rows_per_rb=64 * 64, act=ops.ACT_SILU), [(2 * 64 * 64, 640)])
 l2x, l2w = rnd(2, 32, 32, 1280), rnd(1280, 3, 3, 1280, scale=0.01)
 screen("conv3x3 2x32x32 1280->1280 tile 55 (loader waves)", lambda o: ops.conv2d(l2x, l2w, o, tile=55), [(2 * 32 * 32, 1280)])
 # pointwise / glue
