@@ -481,6 +481,38 @@ int iir_colorfix_wavelet_f32(const float* content, const float* style, float* ou
 int iir_colorfix_adain_f32(const float* content, const float* style, float* out, int32_t B, int32_t C, int32_t H, int32_t W,
                            void* ws, int64_t ws_bytes, void* stream);
 
+/* One axis of a separable, antialiased resize with PIL's filter definitions: the device form of `Image.resize` at
+ * infer.py:31-66 (resize_img, Image.BILINEAR to the working size), infer.py:224-225 (back to the requested output size) and
+ * the image processors of SURVEY Appendix A (bicubic shortest-edge resize, centre crop, normalise); contract in DESIGN.md
+ * section 7 "Resampling".  A resize is the axis-0 (horizontal) launch followed by the axis-1 (vertical) launch, PIL's order.
+ *   src: fp32 planar (N, C, H, W), or with src_u8 uint8 interleaved (N, H, W, C), values kept in 0..255 units.
+ *   dst: fp32 planar (N, C, h, w): exactly the output window, dense.
+ *   The launch resamples `axis` (0: x, 1: y) from its source size to out_size; the other axis keeps its size.  The tables are
+ *   PIL's precompute_coeffs layout on the device: bounds int32[out_size][2] {first tap, tap count}, weights
+ *   fp32[out_size][ksize], zero padded.  out[o] = sum_k weights[o][k] * src[first(o) + k] over k < count(o), in index order with
+ *   fmaf from 0.  First tap and count are clamped into the source axis, so no table makes the kernel read outside src.
+ *   Window (y0, x0, h, w), in the coordinates of this launch's full output (rows: out_size or H, columns: out_size or W): only
+ *   those samples are computed and stored.  Then, in this order:
+ *     quantize: v = min(max(floor(v + 0.5), 0), 255)   (PIL's 8-bit pass: round half up, clip)
+ *     clamp:    v = min(max(v, lo), hi)
+ *     scale / bias (device fp32[C], either may be NULL): v = v * scale[c], then v = v + bias[c]   (two roundings)
+ * No atomics, no LDS: equal inputs give equal bits, and a windowed launch gives the bits of that window of the full launch.
+ * IIR_EINVAL, before any HIP call: a NULL desc, src, dst, bounds or weights; N, C, H, W, out_size or ksize <= 0; H, W or
+ * out_size > IIR_RESAMPLE_MAX_SIDE; N * C > 65535; axis not 0 or 1; a window that is empty or not inside the output;
+ * h * w or out_size * ksize beyond a 31-bit grid; clamp with lo > hi or NaN; dst overlapping src. */
+#define IIR_RESAMPLE_MAX_SIDE 32768
+typedef struct {
+    const void* src; int32_t src_u8;
+    float* dst;
+    int32_t N, C, H, W;
+    int32_t axis, out_size;
+    const int32_t* bounds; const float* weights; int32_t ksize;
+    int32_t y0, x0, h, w;
+    int32_t quantize, clamp; float lo, hi;
+    const float* scale; const float* bias;
+} IirResampleDesc;
+int iir_resample_pass(const IirResampleDesc* desc, void* stream);
+
 int iir_transpose_f16(const void* in, int64_t ldi, int32_t rows, int32_t cols, void* out, int64_t ldo, int32_t rows_pad,
                       void* stream);
 /* Measurement hook (bench.py roofline leg; no reference counterpart): arm a start/stop event pair and the NEXT

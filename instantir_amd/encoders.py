@@ -191,9 +191,43 @@ class HipDinov2(_VisionTower):
     __call__ = forward
 
 
-def dinov2_preprocess(images, size=256, crop=224, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+def _preprocess_geometry(w0, h0, size, crop):
+    """(resized (H, W), crop window (top, left, crop, crop)) of the image processors: shortest edge to `size`, centre crop."""
+    s = size / min(w0, h0)
+    nw, nh = max(crop, round(w0 * s)), max(crop, round(h0 * s))
+    return (nh, nw), ((nh - crop) // 2, (nw - crop) // 2, crop, crop)
+
+
+def _preprocess_device(images, size, crop, mean, std, device):
+    """The image processors on the device: one uint8 upload per image size, a bicubic resize in quantised mode (what PIL does to
+    an 8-bit image) with the centre crop as the launch's window and rescale + normalise as its per-channel affine
+    (v / (255 std) - mean / std).  PIL image(s), or a tensor of 0..255-valued pixels ((N, 3, H, W) float or (N, H, W, 3) uint8)."""
+    from . import resample as RS
+    scale, bias = tuple(1.0 / (255.0 * s) for s in std), tuple(-m / s for m, s in zip(mean, std))
+    if torch.is_tensor(images):
+        groups = [images]
+    else:
+        groups = [im.convert("RGB") for im in (images if isinstance(images, (list, tuple)) else [images])]
+        if len({im.size for im in groups}) == 1:
+            groups = [groups]                                            # one size: one upload, one launch pair
+    out = []
+    for g in groups:
+        batch, kind = RS.as_batch(g)
+        h0, w0 = batch.shape[1:3] if kind == "u8" else batch.shape[2:4]
+        full, window = _preprocess_geometry(w0, h0, size, crop)
+        out.append(RS.resize_images(batch, full, "bicubic", device, quantize=True, window=window, scale=scale, bias=bias))
+    return out[0] if len(out) == 1 else torch.cat(out)
+
+
+def dinov2_preprocess(images, size=256, crop=224, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), device=None):
     """AutoImageProcessor of facebook/dinov2-* (BitImageProcessor): bicubic resize of the shortest edge to 256,
-    centre crop 224, rescale 1/255, ImageNet normalise (SURVEY.md Appendix A "Image I/O").  PIL in, fp32 NCHW out."""
+    centre crop 224, rescale 1/255, ImageNet normalise (SURVEY.md Appendix A "Image I/O").  PIL in, fp32 NCHW out.
+    With a `device` the same steps run there (`_preprocess_device`; a tensor of 0..255-valued pixels is accepted as well) and
+    the result stays on it; at most 1 LSB from the host form before normalisation."""
+    if device is not None:
+        return _preprocess_device(images, size, crop, mean, std, device)
+    if torch.is_tensor(images):
+        raise ValueError("a tensor as the raw image needs `device=`: the host form takes PIL images")
     import numpy as np
     from PIL import Image
     out = []
@@ -208,10 +242,10 @@ def dinov2_preprocess(images, size=256, crop=224, mean=(0.485, 0.456, 0.406), st
     return torch.from_numpy(np.stack(out)).permute(0, 3, 1, 2).contiguous()
 
 
-def clip_preprocess(images, size=224, mean=(0.48145466, 0.4578275, 0.40821073), std=(0.26862954, 0.26130258, 0.27577711)):
+def clip_preprocess(images, size=224, mean=(0.48145466, 0.4578275, 0.40821073), std=(0.26862954, 0.26130258, 0.27577711), device=None):
     """`CLIPImageProcessor()` with its defaults (module/ip_adapter/utils.py:114-118): bicubic resize of the shortest edge to
-    224, centre crop 224, rescale 1/255, CLIP normalise.  PIL in, fp32 NCHW out."""
-    return dinov2_preprocess(images, size=size, crop=size, mean=mean, std=std)
+    224, centre crop 224, rescale 1/255, CLIP normalise.  PIL in, fp32 NCHW out; `device`: as for `dinov2_preprocess`."""
+    return dinov2_preprocess(images, size=size, crop=size, mean=mean, std=std, device=device)
 
 
 class HipCLIPVision(_VisionTower):

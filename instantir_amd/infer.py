@@ -33,11 +33,10 @@ DEFAULT_NEG_PROMPT = "blurry, out of focus, unclear, depth of field, over-smooth
                 watermark, signature, jpeg artifacts, deformed, lowres"
 
 
-def resize_img(input_image, max_side=1024, min_side=768, width=None, height=None, pad_to_max_side=False,
-               mode=Image.BILINEAR, base_pixel_number=64):
-    """infer.py:31-66: requested output size, then min side -> 768, max side -> 1024, floor to a multiple of 64.
-    Returns (resized image, (out_w, out_h)) -- the second item is what the result is resized back to."""
-    w, h = input_image.size
+def resize_plan(size, max_side=1024, min_side=768, width=None, height=None, base_pixel_number=64):
+    """The sizes of infer.py:31-66 for an input of `size` = (w, h): requested output size, then min side -> 768, max side ->
+    1024, floor to a multiple of 64.  Returns ((work_w, work_h), (out_w, out_h))."""
+    w, h = size
     if width is not None and height is not None:
         out_w, out_h = width, height
     elif width is not None:
@@ -53,7 +52,14 @@ def resize_img(input_image, max_side=1024, min_side=768, width=None, height=None
     if max(w, h) > max_side:
         r = max_side / max(w, h)
         w, h = round(r * w), round(r * h)
-    wn, hn = (w // base_pixel_number) * base_pixel_number, (h // base_pixel_number) * base_pixel_number
+    return ((w // base_pixel_number) * base_pixel_number, (h // base_pixel_number) * base_pixel_number), (out_w, out_h)
+
+
+def resize_img(input_image, max_side=1024, min_side=768, width=None, height=None, pad_to_max_side=False,
+               mode=Image.BILINEAR, base_pixel_number=64):
+    """infer.py:31-66: the sizes of `resize_plan`, the resize with PIL on the host.
+    Returns (resized image, (out_w, out_h)) -- the second item is what the result is resized back to."""
+    (wn, hn), (out_w, out_h) = resize_plan(input_image.size, max_side, min_side, width, height, base_pixel_number)
     input_image = input_image.resize([wn, hn], mode)
     if pad_to_max_side:
         canvas = np.ones([max_side, max_side, 3], dtype=np.uint8) * 255
@@ -159,7 +165,24 @@ def build_parser():
                         "a directory holding one map per input file name; white = restore freely, black = keep the input pixels")
     p.add_argument("--map_feather", type=int, default=4, help="half width in pixels of the seam between kept and restored pixels "
                                                               "(pipe(..., map_feather=N)); 0 = hard paste; default 4")
+    p.add_argument("--device_resize", action="store_true",
+                   help="resize on the device instead of with PIL on the host: the same sizes, the inputs passed as they are "
+                        "with pipe(..., work_size=, output_size=, resample=); the image encoder's preprocessing moves to the device too")
+    p.add_argument("--resample", choices=["bilinear", "bicubic", "lanczos"], default=None,
+                   help="filter of --device_resize (default bilinear, the reference's); refused without --device_resize")
     return p
+
+
+def apply_device_resize(pipe, args):
+    """`--device_resize [--resample F]` -> whether the call resizes on the device, and its filter (an addition: the reference
+    resizes with PIL twice).  `--resample` without `--device_resize` is refused; `pipe` None only checks the flags."""
+    on = bool(getattr(args, "device_resize", False))
+    flt = getattr(args, "resample", None)
+    if flt is not None and not on:
+        raise SystemExit("--resample needs --device_resize (the host path resizes with PIL's bilinear filter, as the reference does)")
+    if on and pipe is not None:
+        pipe.enable_device_preprocess()
+    return on, flt or "bilinear"
 
 
 def build_pipeline(args, device):
@@ -300,6 +323,7 @@ def apply_restore_map(args, names, size):
 
 
 def main(args, device, rank=0, world=1):
+    apply_device_resize(None, args)              # (a flag error should not wait for the weights to load)
     pipe, lcm_scheduler = build_pipeline(args, device)
     apply_freeu(pipe, args)
     apply_scheduler(pipe, args)
@@ -308,6 +332,7 @@ def main(args, device, rank=0, world=1):
     apply_apg(pipe, args)
     pag_kw.update(apply_color_fix(args))
     apply_vae_flash_attention(pipe, args)
+    device_resize, resample = apply_device_resize(pipe, args)
     post_fix = f"_{args.post_fix}" if args.post_fix else ""
     out_dir = f"{args.out_path}/{post_fix}"
     os.makedirs(out_dir, exist_ok=True)
@@ -315,14 +340,22 @@ def main(args, device, rank=0, world=1):
     batches = plan_batches(args.test_path, os.path.join(args.out_path, post_fix), args.batch_size)
     for lq_batch in shard_batches(batches, rank, world):
         generator = torch.Generator(device=device).manual_seed(args.seed)                # infer.py:172: fresh per batch
-        lq, out_sizes = [], []
+        lq, out_sizes, work_sizes = [], [], []
         for name in lq_batch:
             path = args.test_path if os.path.isfile(args.test_path) else os.path.join(args.test_path, name)
-            im, out_size = resize_img(Image.open(path).convert("RGB"), width=args.width, height=args.height)
+            im = Image.open(path).convert("RGB")
+            if device_resize:
+                work, out_size = resize_plan(im.size, width=args.width, height=args.height)
+                work_sizes.append(work)
+            else:
+                im, out_size = resize_img(im, width=args.width, height=args.height)
             lq.append(im)
             out_sizes.append(out_size)
         if len({im.size for im in lq}) != 1:
             raise ValueError("images of one batch must share a size after resize_img (use --width/--height or --batch_size 1)")
+        if device_resize and len(set(out_sizes)) != 1:
+            raise ValueError("images of one batch must share an output size with --device_resize (use --batch_size 1)")
+        work_w, work_h = work_sizes[0] if device_resize else lq[0].size
         # infer.py:191-210: `--prompt` / `--neg_prompt` are nargs="*" LISTS and the reference multiplies the list by the batch
         # (`prompt = args.prompt * len(lq)`): `--prompt "a photo" "a drawing"` with one image asks for two restorations, one per
         # entry; with several images AND several entries the pipeline's own batch check (:1316-1319) rejects the call.
@@ -330,7 +363,9 @@ def main(args, device, rank=0, world=1):
         negs = (list(args.neg_prompt) if args.neg_prompt else [DEFAULT_NEG_PROMPT]) * len(lq)
         kw = dict(image=lq, num_inference_steps=args.num_inference_steps, generator=generator, guidance_scale=args.cfg,
                   previewer_scheduler=lcm_scheduler, preview_start=args.preview_start, control_guidance_end=args.creative_start,
-                  **pag_kw, **apply_restore_map(args, lq_batch, lq[0].size))
+                  **pag_kw, **apply_restore_map(args, lq_batch, (work_w, work_h)))
+        if device_resize:
+            kw.update(work_size=(work_h, work_w), output_size=(out_sizes[0][1], out_sizes[0][0]), resample=resample)
         if args.synthetic:
             g = torch.Generator().manual_seed(args.seed)
             n = len(lq)
@@ -340,10 +375,14 @@ def main(args, device, rank=0, world=1):
                       negative_pooled_prompt_embeds=torch.randn(n, cfg.pooled_dim, generator=g),
                       ip_adapter_image_embeds=[torch.randn(2 if args.cfg > 1 else 1, n, cfg.resampler.seq_len, cfg.resampler.embedding_dim, generator=g)])
         else:
-            kw.update(prompt=prompts, negative_prompt=negs, ip_adapter_image=lq)
+            kw.update(prompt=prompts, negative_prompt=negs)
+            if not device_resize:          # (on the device the default stands in: the working image, preprocessed there)
+                kw.update(ip_adapter_image=lq)
         images = pipe(**kw).images
         for i, (rec, out_size) in enumerate(zip(images, out_sizes)):
-            rec.resize([out_size[0], out_size[1]], Image.BILINEAR).save(f"{out_dir}/{lq_batch[i]}")
+            if not device_resize:
+                rec = rec.resize([out_size[0], out_size[1]], Image.BILINEAR)
+            rec.save(f"{out_dir}/{lq_batch[i]}")
 
 
 if __name__ == "__main__":

@@ -108,6 +108,19 @@ class SchedDesc(C.Structure):
     ]
 
 
+class ResampleDesc(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("src_u8", C.c_int32),
+        ("dst", C.c_void_p),
+        ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("axis", C.c_int32), ("out_size", C.c_int32),
+        ("bounds", C.c_void_p), ("weights", C.c_void_p), ("ksize", C.c_int32),
+        ("y0", C.c_int32), ("x0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("quantize", C.c_int32), ("clamp", C.c_int32), ("lo", C.c_float), ("hi", C.c_float),
+        ("scale", C.c_void_p), ("bias", C.c_void_p),
+    ]
+
+
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # symbol -> (restype, argtypes); must list every function declared in include/instantir_hip.h
@@ -163,6 +176,7 @@ SIGNATURES = {
     "iir_colorfix_workspace_bytes": (C.c_int64, [_I32, _I32, _I32, _I32]),
     "iir_colorfix_wavelet_f32": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P]),
     "iir_colorfix_adain_f32": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P]),
+    "iir_resample_pass": (C.c_int, [C.POINTER(ResampleDesc), _P]),
     "iir_transpose_f16": (C.c_int, [_P, _I64, _I32, _I32, _P, _I64, _I32, _P]),
     "iir_timing_event_create": (C.c_void_p, []),
     "iir_timing_event_destroy": (None, [_P]),

@@ -977,3 +977,65 @@ def lq_fidelity(x0, lq, wc, prev, x0_out, taps=None, hist=None):
     L.check(L.load().iir_lq_fidelity_f32(x0.data_ptr(), lq.data_ptr(), _p(taps) if r else None, r, wc.data_ptr(), B * Cc, H, W,
                                          prev.data_ptr(), x0_out.data_ptr(), _p(hist), _stream()), "iir_lq_fidelity_f32")
     return x0_out
+
+
+def _resample_pass(src, u8, dst, dims, axis, out_size, tables, win, quantize, clamp, scale, bias):
+    bounds, weights, ksize = tables
+    d = L.ResampleDesc()
+    d.src, d.src_u8, d.dst = src.data_ptr(), int(u8), dst.data_ptr()
+    d.N, d.C, d.H, d.W = dims
+    d.axis, d.out_size = axis, out_size
+    d.bounds, d.weights, d.ksize = bounds.data_ptr(), weights.data_ptr(), ksize
+    d.y0, d.x0, d.h, d.w = win
+    d.quantize, d.clamp = int(quantize), int(clamp is not None)
+    d.lo, d.hi = clamp if clamp is not None else (0.0, 0.0)
+    d.scale, d.bias = _p(scale), _p(bias)
+    L.check(L.load().iir_resample_pass(C.byref(d), _stream()), "iir_resample_pass")
+
+
+def resample(src, size, filter="bilinear", quantize=False, window=None, clamp=None, scale=None, bias=None, out=None):
+    """Antialiased resize with PIL's filter definitions (iir_resample_pass; DESIGN.md section 7 "Resampling").  `src`: a
+    contiguous CUDA tensor, fp32 planar (N, C, H, W) or uint8 interleaved (N, H, W, C) (0..255 units are kept); `size` =
+    (H, W) of the full output; `filter` one of resample.FILTERS.  The horizontal pass runs first, then the vertical one, an
+    axis that keeps its size is skipped, and equal sizes with no option are a plain copy.
+    `quantize`: every pass ends in floor(v + 0.5) clamped to [0, 255] -- PIL's arithmetic on an 8-bit image.
+    `window` = (y0, x0, h, w): only that part of the output is computed and returned.
+    `clamp` = (lo, hi), then `scale` / `bias` (a number, one per channel, or an fp32 tensor of C): v * scale[c] + bias[c],
+    both on the last pass.  Returns fp32 (N, C, h, w) (`out` when given; it may not overlap `src`)."""
+    from . import resample as RS
+    (oh, ow), win, clamp = RS.check_args(size, filter, quantize, window, clamp)
+    if not torch.is_tensor(src) or src.dim() != 4 or src.dtype not in (torch.float32, torch.uint8) or not src.is_contiguous():
+        raise ValueError("resample: src must be a contiguous 4-D tensor, fp32 (N, C, H, W) or uint8 (N, H, W, C), got "
+                         f"{getattr(src, 'dtype', type(src))} {tuple(getattr(src, 'shape', ()))}")
+    u8 = src.dtype == torch.uint8
+    N, Cc, H, W = (src.shape[0], src.shape[3], src.shape[1], src.shape[2]) if u8 else src.shape
+    if min(N, Cc, H, W) <= 0 or H > RS.MAX_SIDE or W > RS.MAX_SIDE or N * Cc > RS.MAX_PLANES:
+        raise ValueError(f"resample: unsupported geometry N={N} C={Cc} H={H} W={W} (sides <= {RS.MAX_SIDE}, N * C <= {RS.MAX_PLANES})")
+    y0, x0, h, w = win
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (N, Cc, h, w) or not out.is_contiguous() \
+                or out.device != src.device:
+            raise ValueError(f"resample: out must be a contiguous fp32 tensor of shape {(N, Cc, h, w)} on src's device")
+        lo_s, lo_o = src.data_ptr(), out.data_ptr()
+        if lo_s < lo_o + out.numel() * 4 and lo_o < lo_s + src.numel() * src.element_size():
+            raise ValueError("resample: out overlaps src")
+    if not src.is_cuda:
+        raise ValueError("resample: src must be a CUDA tensor (there is no host path)")
+    dev = src.device
+    scale, bias = RS.channel_vector(scale, Cc, dev, "scale"), RS.channel_vector(bias, Cc, dev, "bias")
+    if out is None:
+        out = torch.empty(N, Cc, h, w, dtype=torch.float32, device=dev)
+    last = (quantize, clamp, scale, bias)
+    if (oh, ow) == (H, W):
+        if not u8 and window is None and not quantize and clamp is None and scale is None and bias is None:
+            return out.copy_(src)
+        _resample_pass(src, u8, out, (N, Cc, H, W), 0, W, RS.device_tables(W, W, None, dev), win, *last)
+    elif oh == H:
+        _resample_pass(src, u8, out, (N, Cc, H, W), 0, ow, RS.device_tables(W, ow, filter, dev), win, *last)
+    elif ow == W:
+        _resample_pass(src, u8, out, (N, Cc, H, W), 1, oh, RS.device_tables(H, oh, filter, dev), win, *last)
+    else:
+        mid = torch.empty(N, Cc, H, w, dtype=torch.float32, device=dev)          # the window's columns of every source row
+        _resample_pass(src, u8, mid, (N, Cc, H, W), 0, ow, RS.device_tables(W, ow, filter, dev), (0, x0, H, w), quantize, None, None, None)
+        _resample_pass(mid, False, out, (N, Cc, H, w), 1, oh, RS.device_tables(H, oh, filter, dev), (y0, 0, h, w), *last)
+    return out

@@ -195,6 +195,7 @@ class InstantIRPipeline:
         self._seg_layers = self._seg_paths = None   # smoothed-energy guidance: the same pair for enable_seg ...
         self._seg_sigma = None                      # ... and its blur sigma
         self._apg = None                            # adaptive projected guidance: (eta, norm_threshold, momentum) or None
+        self._device_preprocess = False             # encode_image preprocesses PIL images on the device: enable_device_preprocess
 
     # ---- reference surface ----------------------------------------------------------------------
     @classmethod
@@ -616,8 +617,69 @@ class InstantIRPipeline:
         if self.image_encoder is None:
             raise NotImplementedError("pass `ip_adapter_image_embeds` or attach an image encoder (encoders.HipDinov2)")
         pre = clip_preprocess if isinstance(self.image_encoder, HipCLIPVision) else dinov2_preprocess
-        px = image if torch.is_tensor(image) else pre(image)
+        px = image if torch.is_tensor(image) else pre(image, device=self.device if self._device_preprocess else None)
         return self.image_encoder.encode_image_pair(px)
+
+    def enable_device_preprocess(self):
+        """`encode_image` preprocesses PIL images on the device (one uint8 upload, ops.resample with the crop as its window and
+        the normalisation as its affine) instead of PIL on the host; at most 1 LSB from it before normalisation.  Off by default."""
+        self._device_preprocess = True
+
+    def disable_device_preprocess(self):
+        self._device_preprocess = False
+
+    # ---- device-side resize around the call (an addition; DESIGN.md section 7 "Resampling") ------------------------
+    @staticmethod
+    def _check_resize(work_size, output_size, resample, output_type, image=None, multiple=8):
+        """Checks of `work_size` / `output_size` / `resample` -> the two sizes as (H, W) int tuples (or None)."""
+        from . import resample as RS
+        if resample not in RS.FILTERS:
+            raise ValueError(f"resample must be one of {RS.FILTERS}, got {resample!r}")
+        if work_size is None and output_size is None:
+            if resample != "bilinear":
+                raise ValueError(f"resample={resample!r} needs work_size or output_size: nothing is resampled without them")
+            return None, None
+        if work_size is not None:
+            work_size = RS.check_size(work_size, "work_size", multiple)
+            if torch.is_tensor(image) and image.dim() == 4 and image.shape[1] == 4:
+                raise ValueError("work_size resamples pixels: `image` is an LQ latent (B,4,h,w)")
+        if output_size is not None:
+            output_size = RS.check_size(output_size, "output_size")
+            if output_type == "latent":
+                raise ValueError("output_size resamples decoded pixels: output_type='latent' leaves none to resample")
+        return work_size, output_size
+
+    def _resample_input(self, image, work_size, resample):
+        """A pixel `image` of any size (PIL, numpy or a [0,1] tensor) at `work_size`, fp32 (n,3,H,W) in [0,1] on the device.
+        8-bit inputs use quantised mode (PIL's semantics for such an image), float inputs float mode with a clamp to [0,1]."""
+        from . import resample as RS
+        if not torch.is_tensor(image) and not hasattr(image, "ndim"):
+            image = [im.convert("RGB") if hasattr(im, "convert") else im for im in (image if isinstance(image, (list, tuple)) else [image])]
+        batch, kind = RS.as_batch(image)
+        if batch.shape[-1 if kind == "u8" else 1] != 3:
+            raise ValueError(f"work_size takes RGB pixels, got {tuple(batch.shape)}")
+        if kind == "u8":
+            return RS.resize_images(batch, work_size, resample, self.device, quantize=True, scale=1.0 / 255.0)
+        if batch.min() < 0:
+            raise ValueError("work_size takes a float `image` in [0, 1]; this one has negative values (already normalised?)")
+        return RS.resize_images(batch, work_size, resample, self.device, quantize=False, clamp=(0.0, 1.0))
+
+    def _preprocess_work_image(self, image):
+        """The working image (fp32 (n,3,H,W) in [0,1] on the device) as the image encoder's input: rounded to 8 bits -- the raw
+        image a PIL copy of it would be -- and preprocessed on the device; `encode_image` takes the result as it stands."""
+        from .encoders import HipCLIPVision, clip_preprocess, dinov2_preprocess
+        pre = clip_preprocess if isinstance(self.image_encoder, HipCLIPVision) else dinov2_preprocess
+        return pre((image * 255).round(), device=self.device)
+
+    def _resample_output(self, img, output_size, resample, output_type):
+        """The final [0,1] images (fp32 (B,3,H,W) on the device) at `output_size`, in the form `output_type` asks for.  'pil':
+        rounded to 8 bits as `vae.to_output` rounds, then resampled in quantised mode, so the result is comparable with PIL's
+        resize of the plain call's PIL output; 'np' / 'pt': float mode with a clamp to [0,1]."""
+        if output_type == "pil":
+            from PIL import Image
+            out8 = ops.resample((img * 255).round(), output_size, resample, quantize=True)
+            return [Image.fromarray(a) for a in out8.permute(0, 2, 3, 1).to(torch.uint8).cpu().numpy()]
+        return self.vae.to_output(ops.resample(img.contiguous(), output_size, resample, clamp=(0.0, 1.0)), output_type)
 
     def prepare_ip_adapter_image_embeds(self, ip_adapter_image, do_cfg, batch=None):
         """:672-707 for one IP adapter: [(2 n, Bimg, S, E)] = cat([zero-image features, image features]) under CFG, each stacked
@@ -682,16 +744,17 @@ class InstantIRPipeline:
             image = self.vae.encode_to_latent(image, eps=vae_noise)
         return image.to(self.device, torch.float32)
 
-    def _decode_output(self, latents, output_type, color_fix=None, reference=None, composite=None):
+    def _decode_output(self, latents, output_type, color_fix=None, reference=None, composite=None, resize=None):
         """VAE decode of the final latents; with `color_fix` the decoded [0,1] image is corrected in place on the device
         (ops.colorfix) before it becomes 'np' / 'pil'; with `composite` = (original, pixel map, feather) of a restore map the
-        kept region then gets the input's own pixels back (ops.region_composite, in place).  :1706-1729: any `output_type` but
-        'latent' needs the VAE."""
+        kept region then gets the input's own pixels back (ops.region_composite, in place); with `resize` = (output size,
+        filter) the result is then resampled on the device (`_resample_output`).  :1706-1729: any `output_type` but 'latent'
+        needs the VAE."""
         if output_type == "latent":
             return latents
         if self.vae is None:
             raise NotImplementedError("output_type other than 'latent' needs a VAE attached to the pipeline")
-        if color_fix is None and composite is None:
+        if color_fix is None and composite is None and resize is None:
             return self.vae.decode_latent(latents, output_type)          # tiles when `vae.enable_tiling()` is on
         img = self.vae.decode_latent(latents, "pt").contiguous()
         if color_fix is not None:
@@ -699,6 +762,8 @@ class InstantIRPipeline:
         if composite is not None:
             original, map_px, feather = composite
             ops.region_composite(img, original, map_px, feather, out=img)
+        if resize is not None:
+            return self._resample_output(img, resize[0], resize[1], output_type)
         return self.vae.to_output(img, output_type)
 
     # ---- single-step previewer restoration (BASELINE configs[4]; spec train_previewer_lora.py:118-145) ------------
@@ -951,7 +1016,8 @@ class InstantIRPipeline:
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"], previewer_scheduler=None,
                  reference_latents=None, init_noise=None, step_noises=None, pag_scale: Optional[float] = None,
                  pag_adaptive_scale: float = 0.0, color_fix: Optional[str] = None, color_fix_reference=None, restore_map=None,
-                 map_feather: int = 4, seg_scale: Optional[float] = None, **kwargs):
+                 map_feather: int = 4, seg_scale: Optional[float] = None, work_size=None, output_size=None,
+                 resample: str = "bilinear", **kwargs):
         """Keyword arguments and defaults of pipelines/sdxl_instantir.py:1067-1115.  Two additions for
         bit-reproducible parity runs: `init_noise` (the randn of init_latents) and
         `step_noises` (list of per-step DDPM / Euler-ancestral / DPM++ SDE noises) replace draws from `generator` when given.
@@ -973,7 +1039,17 @@ class InstantIRPipeline:
         given as pixels and `output_type` is not "latent", the final images (never the preview row) are composited with the
         input after the decode and `color_fix`: a box window of half width `map_feather` pixels (default 4; 0 = hard paste)
         over [map > 0] weights decoded against input, and a pixel whose window lies wholly in the kept region is the input
-        pixel bit for bit.  None touches nothing."""
+        pixel bit for bit.  None touches nothing.
+        `work_size` / `output_size` / `resample` (an addition: the resizes of infer.py:31-66 and :224-225 on the device, with
+        PIL's filter definitions; `resample` one of "bilinear", "bicubic", "lanczos").  `work_size` = (H, W), multiples of 8: a
+        pixel `image` of any size (PIL, numpy or a [0, 1] tensor) is resampled to it before anything else looks at it -- the
+        result is what the VAE encodes, the default colour-fix reference, the composite's original and the default
+        `ip_adapter_image` (then preprocessed on the device); 8-bit inputs resample as PIL resamples an 8-bit image, float
+        tensors in float mode with a clamp to [0, 1]; `restore_map` sizes refer to the working size.  `output_size` = (H, W):
+        the final images (never the preview row) are resampled after the decode, `color_fix` and the composite; "pil" rounds
+        to 8 bits first and resamples as PIL would, "np" / "pt" resample in float mode with a clamp to [0, 1].  With all
+        three at their defaults nothing is resampled."""
+        work_size, output_size = self._check_resize(work_size, output_size, resample, output_type, image, self.vae_scale_factor)
         if restore_map is not None:
             map_feather = rmap.check_feather(map_feather)
         lora_mult, pag_scale, pag_on, seg_scale, seg_on = self._check_call(
@@ -998,6 +1074,8 @@ class InstantIRPipeline:
             negative_pooled_prompt_embeds, do_cfg, clip_skip, nipp)
         B = ctx.shape[0] // rep
         pb = B // nipp                                                             # `batch_size` of :1304-1315
+        if work_size is not None:                                                  # before anything else looks at the image
+            image = self._resample_input(image, work_size, resample)
         n_img = 1 if hasattr(image, "size") and not torch.is_tensor(image) and not isinstance(image, (list, tuple)) else len(image)
         assert pb == n_img or n_img == 1                                          # :1310-1315
         if ip_adapter_image is None and ip_adapter_image_embeds is None:           # :1278-1279 (see Q15 in the header)
@@ -1005,6 +1083,8 @@ class InstantIRPipeline:
                 raise ValueError("`image` is an LQ latent (B,4,h,w): it cannot stand in for `ip_adapter_image` (the image encoder takes "
                                  "pixels); pass `ip_adapter_image` or `ip_adapter_image_embeds`")
             ip_adapter_image = image
+            if work_size is not None and self.image_encoder is not None:
+                ip_adapter_image = self._preprocess_work_image(image)
 
         # -- the LQ latent (:1369-1379)
         image = self._prepare_image(image)
@@ -1064,7 +1144,8 @@ class InstantIRPipeline:
                                        guidance_scale, eta, generator, step_noises, pag_scale, pag_adaptive_scale, adastep_restore,
                                        save_preview_row, callback_on_step_end, callback_on_step_end_tensor_inputs,
                                        negative_prompt_embeds, masked=keep_map is not None)
-        image_out = self._decode_output(x, output_type, color_fix, cf_ref, composite)
+        image_out = self._decode_output(x, output_type, color_fix, cf_ref, composite,
+                                        (output_size, resample) if output_size is not None else None)
         if save_preview_row and self.vae is not None and output_type != "latent":     # :1706-1729 (decoded independently, Q4)
             preview_row = [self.vae.decode_latent(pl, output_type) for pl in preview_row]
         if not return_dict:

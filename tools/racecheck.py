@@ -11,9 +11,12 @@ REP = int(os.environ.get("REP", "30"))
 g = torch.Generator().manual_seed(1)
 rnd = lambda *s, scale=1.0: (torch.randn(*s, generator=g) * scale).half()
 bad_total = 0
+ONLY = os.environ.get("ONLY")          # run only the cases whose name contains this substring (the unnamed blocks below always run)
 
 def screen(name, launch, want, outs_shape, rtol=4e-3, atol=4e-3):
     global bad_total
+    if ONLY and ONLY not in name:
+        return
     first = None; nd = 0; where = None
     for it in range(REP):
         outs = [torch.zeros(s, dtype=torch.half, device=dev) for s in outs_shape]
@@ -111,5 +114,31 @@ for lf_sigma in (0.0, 1.5, 8.0):
     ok = bool(((first[:lf_x0.numel()].view_as(lf_x0)[inner] - lf_want[inner]).abs() <= 1e-4).all())
     bad_total += (not ok) + nd
     print(f"{'lq_fidelity 1x4x128x128 sigma %g (radius %d)' % (lf_sigma, lf_r):56s} ref_ok={ok} nondeterministic_runs={nd}/{REP - 1}", flush=True)
+# device resampling (ops.resample): float mode against torch's antialiased interpolate (bilinear, bicubic; the same definition),
+# quantised mode against the same interpolate one axis at a time with floor(v + 0.5) clamped to [0, 255] after each (the clip
+# between the passes is part of the mode), both source layouts; bit-identical over REP launches
+def rs_ref(x, out, f, q):
+    if not q:
+        return F.interpolate(x, size=out, mode=f, antialias=True, align_corners=False)
+    for size in ((x.shape[2], out[1]), out):
+        x = (F.interpolate(x, size=size, mode=f, antialias=True, align_corners=False) + 0.5).floor().clamp(0, 255)
+    return x
+for (rs_in, rs_out, rs_f) in [((384, 512), (768, 1024), "bilinear"), ((1024, 1024), (256, 256), "bicubic"), ((1024, 1024), (2048, 2048), "lanczos"),
+                              ((257, 131), (129, 67), "bicubic")]:
+    rs_u8 = torch.randint(0, 256, (1, rs_in[0], rs_in[1], 3), generator=g, dtype=torch.uint8).to(dev)
+    rs_f32 = rs_u8.permute(0, 3, 1, 2).float().contiguous()
+    for rs_src, rs_name in ((rs_u8, "uint8"), (rs_f32, "fp32")):
+        for rs_q in (False, True):
+            first = None; nd = 0
+            for it in range(REP):
+                o = ops.resample(rs_src, rs_out, rs_f, quantize=rs_q)
+                torch.cuda.synchronize()
+                if first is None: first = o
+                elif not torch.equal(o, first): nd += 1
+            # quantised: a sample on a rounding boundary may flip in either pass, and a flipped intermediate moves the second sum by < 1
+            ok = rs_f == "lanczos" or bool(((first - rs_ref(rs_f32, rs_out, rs_f, rs_q)).abs() <= (2.0 if rs_q else 1e-2)).all())
+            bad_total += (not ok) + nd
+            print(f"{'resample %s %dx%d->%dx%d %s%s' % (rs_f, *rs_in, *rs_out, rs_name, ' quantised' if rs_q else ''):56s} ref_ok={ok} "
+                  f"nondeterministic_runs={nd}/{REP - 1}", flush=True)
 print("TOTAL anomalies:", bad_total)
 sys.exit(1 if bad_total else 0)

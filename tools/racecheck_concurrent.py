@@ -272,4 +272,15 @@ for lfH in (128, 256):
             p.copy_(lf_p0)
             ops.lq_fidelity(lf_x0, lf_z, lf_wc, p, o, taps=lf_taps, hist=hs)
         screen(f"lq_fidelity 1x4x{lfH}x{lfH} sigma {lf_sigma:g}", lf_launch, [(1, 4, lfH, lfH)] * 3, dtype=torch.float32)
+# device resampling (ops.resample): the product's three shapes, both source layouts, float and quantised mode, window and affine
+for (rs_in, rs_out, rs_f, rs_win) in [((384, 512), (768, 1024), "bilinear", None), ((1024, 1024), (256, 256), "bicubic", (16, 16, 224, 224)),
+                                      ((1024, 1024), (2048, 2048), "lanczos", None), ((257, 131), (129, 67), "lanczos", None)]:
+    rs_u8 = torch.randint(0, 256, (1, rs_in[0], rs_in[1], 3), generator=g, dtype=torch.uint8).to(dev)
+    rs_f32 = rs_u8.permute(0, 3, 1, 2).float().contiguous()
+    rs_shape = [(1, 3) + (tuple(rs_win[2:]) if rs_win else rs_out)]
+    for rs_src, rs_name in ((rs_u8, "uint8"), (rs_f32, "fp32")):
+        for rs_q in (False, True):
+            screen(f"resample {rs_f} {rs_in[0]}x{rs_in[1]}->{rs_out[0]}x{rs_out[1]} {rs_name}{' quantised' if rs_q else ''}{' window' if rs_win else ''}",
+                   lambda o: ops.resample(rs_src, rs_out, rs_f, quantize=rs_q, window=rs_win, scale=1 / 255.0, bias=-0.5, out=o), rs_shape,
+                   dtype=torch.float32)
 print("kernels with run-to-run differences:", bad)
