@@ -586,15 +586,36 @@ def adaln_batch(table, njobs, rows, max_C, ldmod, rows_per_mod, tr_rows, tr_bstr
                                          _stream()), "iir_adaln_batch_f16")
 
 
+def _refuse(who, ok, msg):
+    """The pointwise entries get pointers: what a launch would touch outside a tensor is refused here, before any library call."""
+    if not ok:
+        raise ValueError(f"{who}: {msg}")
+
+
+def _chk_rows2d(who, name, t, rows, cols):
+    """2-D fp16 / bf16 view with unit column stride that holds `rows` x `cols` (exactly `rows` rows, at least `cols` columns)."""
+    _refuse(who, t.dim() == 2 and t.dtype in _DT and t.stride(1) == 1 and t.shape[0] == rows and t.shape[1] >= cols,
+            f"{name} must be a 2-D fp16 / bf16 view of {rows} rows and at least {cols} unit-stride columns, got {t.dtype} "
+            f"{tuple(t.shape)} {t.stride()}")
+
+
 def sinusoid(vals, out, dim, col_off=0):
     """vals fp32 (rows, n_vals) device tensor; out 2-D fp16 view."""
+    _refuse("sinusoid", vals.dim() == 2 and vals.dtype == torch.float32 and vals.is_contiguous(),
+            f"vals must be a contiguous 2-D fp32 tensor, got {vals.dtype} {tuple(vals.shape)} {vals.stride()}")
     rows, n_vals = vals.shape
+    _refuse("sinusoid", out.dim() == 2 and out.dtype == torch.float16 and out.stride(1) == 1 and col_off >= 0 and out.shape[0] >= rows
+            and out.shape[1] >= col_off + n_vals * dim,
+            f"out must be a 2-D fp16 view of at least {rows} x ({col_off} + {n_vals} * {dim}), got {out.dtype} {tuple(out.shape)}")
     L.check(L.load().iir_sinusoid_f16(vals.data_ptr(), n_vals, rows, dim, out.data_ptr(), out.stride(0), col_off,
                                       _stream()), "iir_sinusoid_f16")
     return out
 
 
 def silu(x, out):
+    _refuse("silu", x.dtype == torch.float16 and out.dtype == torch.float16 and x.is_contiguous() and out.is_contiguous()
+            and out.numel() == x.numel(),
+            f"x and out must be contiguous fp16 tensors of one size, got {x.dtype} {tuple(x.shape)} and {out.dtype} {tuple(out.shape)}")
     L.check(L.load().iir_silu_f16(x.data_ptr(), out.data_ptr(), x.numel(), _stream()), "iir_silu_f16")
     return out
 
@@ -603,6 +624,15 @@ def copy_add(src, dst, dst_off=0, add=None, add_scale=None, rows_per_scale=1):
     """dst[:, dst_off:dst_off+C] = src + add * add_scale[row // rows_per_scale]."""
     _chk2d(src, "src"); _chk2d(dst, "dst")
     M, Cc = src.shape
+    _refuse("copy_add", dst_off >= 0 and dst.shape[0] >= M and dst.shape[1] >= dst_off + Cc,
+            f"dst {tuple(dst.shape)} does not hold {M} rows of {Cc} columns from column {dst_off}")
+    if add is not None:
+        _chk2d(add, "add")
+        _refuse("copy_add", tuple(add.shape) == (M, Cc), f"add {tuple(add.shape)} must have src's shape {(M, Cc)}")
+    if add_scale is not None:
+        _refuse("copy_add", rows_per_scale > 0 and add_scale.dtype == torch.float32 and add_scale.is_contiguous()
+                and add_scale.numel() >= -(-M // max(rows_per_scale, 1)),
+                f"add_scale must be contiguous fp32 with a value per {rows_per_scale} of {M} rows, got {add_scale.dtype} {add_scale.numel()}")
     L.check(L.load().iir_copy_add_f16(src.data_ptr(), src.stride(0), dst.data_ptr(), dst.stride(0), dst_off, M, Cc,
                                       _p(add), add.stride(0) if add is not None else 0, _p(add_scale), rows_per_scale,
                                       _stream()), "iir_copy_add_f16")
@@ -670,6 +700,8 @@ def pack_latent(x, out, rep=1, scale=1.0):
     element) read at launch time (iir_pack_latent_dscale)."""
     B, Cc, H, Wd = x.shape
     assert x.dtype == torch.float32 and x.is_contiguous() and out.dtype in _DT
+    _refuse("pack_latent", rep > 0, f"rep must be positive, got {rep}")
+    _chk_rows2d("pack_latent", "out", out, rep * B * H * Wd, Cc)
     h, args = L.load(), (x.data_ptr(), B, Cc, H * Wd, out.data_ptr(), out.stride(0), rep)
     if torch.is_tensor(scale):
         assert scale.dtype == torch.float32 and scale.is_cuda and scale.numel() >= 1
@@ -683,6 +715,7 @@ def unpack_latent(x2d, out):
     """x2d fp16 view (R*H*W, ld) -> out fp32 (R,C,H,W)."""
     R, Cc, H, Wd = out.shape
     assert out.dtype == torch.float32 and out.is_contiguous() and x2d.dtype in _DT
+    _chk_rows2d("unpack_latent", "x2d", x2d, R * H * Wd, Cc)
     L.check(L.load().iir_unpack_latent_t(x2d.data_ptr(), x2d.stride(0), R, Cc, H * Wd, out.data_ptr(), _DT[x2d.dtype], _stream()),
             "iir_unpack_latent_t")
     return out
@@ -792,6 +825,14 @@ def copy_segments(table, njobs, max_units):
 
 def lcm_step(eps2d, B, rep, coef, x, out2d, out_nchw=None):
     _, Cc, H, Wd = x.shape
+    _refuse("lcm_step", B > 0 and rep > 0 and x.dtype == torch.float32 and x.is_contiguous() and x.shape[0] == B,
+            f"x must be contiguous fp32 ({B}, C, H, W) with rep > 0, got {x.dtype} {tuple(x.shape)}, rep {rep}")
+    for name, t2 in (("eps2d", eps2d), ("out2d", out2d)):
+        _refuse("lcm_step", t2.dtype == torch.float16, f"{name} must be fp16, got {t2.dtype}")
+        _chk_rows2d("lcm_step", name, t2, rep * B * H * Wd, Cc)
+    if out_nchw is not None:
+        _refuse("lcm_step", out_nchw.dtype == torch.float32 and out_nchw.is_contiguous() and tuple(out_nchw.shape) == (rep * B, Cc, H, Wd),
+                f"out_nchw must be contiguous fp32 {(rep * B, Cc, H, Wd)}, got {out_nchw.dtype} {tuple(out_nchw.shape)}")
     L.check(L.load().iir_lcm_step(eps2d.data_ptr(), eps2d.stride(0), B, rep, Cc, H * Wd, coef.data_ptr(), x.data_ptr(),
                                   out2d.data_ptr(), out2d.stride(0), _p(out_nchw), _stream()), "iir_lcm_step")
     return out2d
@@ -800,6 +841,8 @@ def lcm_step(eps2d, B, rep, coef, x, out2d, out_nchw=None):
 def transpose(x, out, rows_pad):
     _chk2d(x, "x"); _chk2d(out, "out")
     rows, cols = x.shape
+    _refuse("transpose", out.shape[0] >= cols and out.shape[1] >= rows_pad >= rows,
+            f"out {tuple(out.shape)} does not hold {cols} rows of rows_pad = {rows_pad} >= {rows} columns")
     L.check(L.load().iir_transpose_f16(x.data_ptr(), x.stride(0), rows, cols, out.data_ptr(), out.stride(0), rows_pad,
                                        _stream()), "iir_transpose_f16")
     return out
@@ -857,6 +900,8 @@ def softmax_rows_f32(s, p):
 def blend_tiles(a, b, extent, vertical):
     """In-place seam blend of fp32 NCHW tile `b` with its upper (vertical) or left neighbour `a`."""
     assert a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
+    _refuse("blend_tiles", a.dim() == 4 and b.dim() == 4 and a.shape[0] * a.shape[1] == b.shape[0] * b.shape[1],
+            f"a {tuple(a.shape)} and b {tuple(b.shape)} must be 4-D with equal plane counts")
     L.check(L.load().iir_blend_tiles_f32(a.data_ptr(), b.data_ptr(), a.shape[0] * a.shape[1], a.shape[2], a.shape[3], b.shape[2],
                                          b.shape[3], extent, int(vertical), _stream()), "iir_blend_tiles_f32")
     return b
