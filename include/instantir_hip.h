@@ -513,6 +513,47 @@ typedef struct {
 } IirResampleDesc;
 int iir_resample_pass(const IirResampleDesc* desc, void* stream);
 
+/* Full-reference image quality, per image: MSE (for PSNR) and SSIM with the definitions restoration papers use (basicsr's
+ * calculate_psnr / calculate_ssim); no reference counterpart, contract in DESIGN.md section 7 "Image metrics".
+ *   a, b: two images of one shape, N images of C in {1, 3} channels, each independently fp32 planar (N, C, H, W) on a [0, 1]
+ *     scale or, with a_u8 / b_u8, uint8 interleaved (N, H, W, C).  All arithmetic is in 0..255 units: an fp32 source is
+ *     multiplied by 255 (fp32), and with a_quantize / b_quantize then taken to min(max(floor(v + 0.5), 0), 255) in fp32, the
+ *     8-bit image that would be saved; without the flag nothing is rounded.  The flags are ignored for a uint8 source.
+ *   crop_border = c >= 0: c pixels are dropped on every side of both images first; H' = H - 2c, W' = W - 2c.
+ *   y_channel (C = 3): both images become the one channel Y = 16 + (65.481 R + 128.553 G + 24.966 B) / 255, not rounded.
+ *   MSE  = mean of (a - b)^2 over every remaining channel and pixel (PSNR = 10 log10(255^2 / MSE) is the caller's, in fp64).
+ *   SSIM = per channel, the mean over the (H' - 10) x (W' - 10) positions at which the 11 x 11 window lies inside the image of
+ *     (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)), C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, with the
+ *     windowed moments mu = E[.], s = E[.^2] - mu^2, s12 = E[ab] - mu1 mu2 under the window g g^T, g_j = exp(-(j - 5)^2 / 4.5)
+ *     normalised to sum 1; then the mean over channels.
+ *   what: IIR_METRIC_PSNR (the MSE), IIR_METRIC_SSIM, or both; the MSE alone runs no filter.
+ *   out: double[N][2] = {MSE, SSIM}; an entry that `what` leaves out is written as NaN.
+ *   ws: iir_image_metrics_workspace_bytes(desc) bytes, 8-byte aligned: two fp64 partial sums per workgroup (-1 for a
+ *     descriptor whose geometry this entry refuses; the pointers are not looked at).
+ * A workgroup owns an IIR_METRICS_TILE^2 tile of one SSIM map, filters the five moments of its tile (taps in index order,
+ * fmaf from 0, along x then y; the moments are taken about 128, which variances and covariances do not see) and sums its map
+ * values and the squared differences of its own pixels in a fixed order; a second launch adds the partial sums in fp64.  No
+ * atomics: equal inputs give equal bits.  With two 8-bit sources (uint8 or quantised) and no y_channel the sum of squared
+ * differences is exact: the MSE carries the rounding of its final division alone.
+ * IIR_EINVAL, before any HIP call: a NULL desc, a, b, out or ws; N, C, H or W <= 0; H or W > 32768; C not 1 or 3; y_channel
+ * with C = 1; crop_border < 0; `what` 0 or with a bit outside the two; H' or W' <= 0, or < 11 when SSIM is asked for;
+ * N * channels > 65535 or a grid beyond 31 bits; ws too small or ws / out not 8-byte aligned. */
+#define IIR_METRICS_TILE 32
+#define IIR_METRIC_PSNR 1u
+#define IIR_METRIC_SSIM 2u
+typedef struct {
+    const void* a; const void* b;
+    int32_t a_u8, b_u8;
+    int32_t a_quantize, b_quantize;
+    int32_t N, C, H, W;
+    int32_t crop_border, y_channel;
+    uint32_t what;
+    void* ws; int64_t ws_bytes;
+    double* out;
+} iir_metrics_desc;
+int64_t iir_image_metrics_workspace_bytes(const iir_metrics_desc* d);
+int iir_image_metrics(const iir_metrics_desc* d, void* stream);
+
 int iir_transpose_f16(const void* in, int64_t ldi, int32_t rows, int32_t cols, void* out, int64_t ldo, int32_t rows_pad,
                       void* stream);
 /* Measurement hook (bench.py roofline leg; no reference counterpart): arm a start/stop event pair and the NEXT

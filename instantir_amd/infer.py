@@ -13,6 +13,8 @@ Extension (not in the reference): `--synthetic {tiny,sdxl}` builds every network
 driver can be exercised without checkpoints (none are available offline); with it the text prompt is replaced by
 seeded embeddings because no tokenizer vocabulary exists here.  `--apg ETA NORM_THRESHOLD MOMENTUM` turns adaptive projected
 guidance on (`pipe.enable_apg(...)`: the CFG update's saturating parallel part down-weighted, its norm clamped, with momentum).
+`--gt_path DIR` scores every saved image against the file of the same name in DIR (PSNR / SSIM on the device,
+`instantir_amd.metrics`), `--input_fidelity` against its own input file; the figures go to `metrics.json` in the output directory.
 """
 from __future__ import annotations
 
@@ -170,7 +172,77 @@ def build_parser():
                         "with pipe(..., work_size=, output_size=, resample=); the image encoder's preprocessing moves to the device too")
     p.add_argument("--resample", choices=["bilinear", "bicubic", "lanczos"], default=None,
                    help="filter of --device_resize (default bilinear, the reference's); refused without --device_resize")
+    p.add_argument("--gt_path", type=str, default=None, metavar="DIR",
+                   help="score every saved image against the file of the same name in DIR (at the output size): PSNR / SSIM per "
+                        "file and on average, written to metrics.json in the output directory (instantir_amd.metrics)")
+    p.add_argument("--metrics", choices=["psnr", "ssim"], nargs="+", default=None,
+                   help="the figures of --gt_path / --input_fidelity (default: psnr ssim)")
+    p.add_argument("--metrics_y", action="store_true", help="score the BT.601 luma channel alone, as super-resolution tables do")
+    p.add_argument("--metrics_crop", type=int, default=None, metavar="N", help="drop N border pixels on every side before scoring")
+    p.add_argument("--input_fidelity", action="store_true",
+                   help="score every saved image, resized to its input's size (bicubic), against the input file as it was read: "
+                        "how far the restoration moved from what it was given; needs no ground truth")
     return p
+
+
+def apply_metrics(args):
+    """`--gt_path DIR` / `--input_fidelity` with `--metrics`, `--metrics_y`, `--metrics_crop` -> the scoring settings, or None
+    when nothing is scored (an addition: the reference's infer.py reports no figures).  An option flag without either of the
+    two is refused, as is a GT directory that does not exist."""
+    gt = getattr(args, "gt_path", None)
+    fidelity = bool(getattr(args, "input_fidelity", False))
+    names, y, crop = getattr(args, "metrics", None), bool(getattr(args, "metrics_y", False)), getattr(args, "metrics_crop", None)
+    if gt is None and not fidelity:
+        for flag, on in (("--metrics", names is not None), ("--metrics_y", y), ("--metrics_crop", crop is not None)):
+            if on:
+                raise SystemExit(f"{flag} needs --gt_path or --input_fidelity")
+        return None
+    if crop is not None and crop < 0:
+        raise SystemExit(f"--metrics_crop must be >= 0, got {crop}")
+    if gt is not None and not os.path.isdir(gt):
+        raise SystemExit(f"--gt_path {gt} is not a directory")
+    names = tuple(n for n in ("psnr", "ssim") if n in (names or ("psnr", "ssim")))
+    return {"gt_path": gt, "input_fidelity": fidelity, "metrics": names, "y_channel": y, "crop_border": int(crop or 0)}
+
+
+def gt_image(setup, name, size):
+    """The ground truth of input `name` at `size` = (width, height); a missing file or another size ends the run, naming it."""
+    path = os.path.join(setup["gt_path"], name)
+    if not os.path.isfile(path):
+        raise SystemExit(f"--gt_path: {path} does not exist (every input needs a file of its own name)")
+    im = Image.open(path).convert("RGB")
+    if im.size != tuple(size):
+        raise SystemExit(f"--gt_path: {path} is {im.size[0]}x{im.size[1]} but the output is {size[0]}x{size[1]}")
+    return im
+
+
+def score_saved(setup, saved_path, gt, original, device):
+    """The figures of one saved file, from the 8-bit image as it was saved (read back): {"psnr", "ssim"} against `gt`,
+    {"input_psnr", "input_ssim"} against `original`, whichever were asked for."""
+    from . import metrics as M
+    saved = Image.open(saved_path).convert("RGB")
+    kw = dict(metrics=setup["metrics"], crop_border=setup["crop_border"], y_channel=setup["y_channel"], device=device)
+    row = {}
+    try:
+        if gt is not None:
+            row.update({k: v[0] for k, v in M.evaluate(saved, gt, **kw).items() if not k.endswith("_mean")})
+        if original is not None:
+            row.update({"input_" + k: v[0] for k, v in M.input_fidelity(saved, original, **kw).items() if not k.endswith("_mean")})
+    except ValueError as e:
+        raise SystemExit(f"{saved_path}: {e}")
+    return row
+
+
+def write_metrics(setup, rows, out_dir, rank=0, world=1):
+    """metrics.json (metrics.rank{r}.json with more than one rank): the settings, the per-file figures and their means; returns
+    the summary line."""
+    import json
+    keys = sorted({k for row in rows.values() for k in row})
+    mean = {k: float(sum(row[k] for row in rows.values()) / len(rows)) for k in keys} if rows else {}
+    path = os.path.join(out_dir, "metrics.json" if world == 1 else f"metrics.rank{rank}.json")
+    with open(path, "w") as f:
+        json.dump({"settings": setup, "files": rows, "mean": mean}, f, indent=1, sort_keys=True)
+    return f"metrics over {len(rows)} file(s): " + ", ".join(f"{k} {mean[k]:.4f}" for k in keys) + f" -> {path}"
 
 
 def apply_device_resize(pipe, args):
@@ -324,6 +396,7 @@ def apply_restore_map(args, names, size):
 
 def main(args, device, rank=0, world=1):
     apply_device_resize(None, args)              # (a flag error should not wait for the weights to load)
+    scoring = apply_metrics(args)
     pipe, lcm_scheduler = build_pipeline(args, device)
     apply_freeu(pipe, args)
     apply_scheduler(pipe, args)
@@ -338,12 +411,14 @@ def main(args, device, rank=0, world=1):
     os.makedirs(out_dir, exist_ok=True)
     cfg = pipe.cfg
     batches = plan_batches(args.test_path, os.path.join(args.out_path, post_fix), args.batch_size)
+    scores = {}
     for lq_batch in shard_batches(batches, rank, world):
         generator = torch.Generator(device=device).manual_seed(args.seed)                # infer.py:172: fresh per batch
-        lq, out_sizes, work_sizes = [], [], []
+        lq, out_sizes, work_sizes, originals = [], [], [], []
         for name in lq_batch:
             path = args.test_path if os.path.isfile(args.test_path) else os.path.join(args.test_path, name)
             im = Image.open(path).convert("RGB")
+            originals.append(im)
             if device_resize:
                 work, out_size = resize_plan(im.size, width=args.width, height=args.height)
                 work_sizes.append(work)
@@ -356,6 +431,7 @@ def main(args, device, rank=0, world=1):
         if device_resize and len(set(out_sizes)) != 1:
             raise ValueError("images of one batch must share an output size with --device_resize (use --batch_size 1)")
         work_w, work_h = work_sizes[0] if device_resize else lq[0].size
+        gts = [gt_image(scoring, n, s) for n, s in zip(lq_batch, out_sizes)] if scoring and scoring["gt_path"] else None
         # infer.py:191-210: `--prompt` / `--neg_prompt` are nargs="*" LISTS and the reference multiplies the list by the batch
         # (`prompt = args.prompt * len(lq)`): `--prompt "a photo" "a drawing"` with one image asks for two restorations, one per
         # entry; with several images AND several entries the pipeline's own batch check (:1316-1319) rejects the call.
@@ -383,6 +459,11 @@ def main(args, device, rank=0, world=1):
             if not device_resize:
                 rec = rec.resize([out_size[0], out_size[1]], Image.BILINEAR)
             rec.save(f"{out_dir}/{lq_batch[i]}")
+            if scoring:
+                scores[lq_batch[i]] = score_saved(scoring, f"{out_dir}/{lq_batch[i]}", gts[i] if gts else None,
+                                                  originals[i] if scoring["input_fidelity"] else None, device)
+    if scoring:
+        print(write_metrics(scoring, scores, out_dir, rank, world))
 
 
 if __name__ == "__main__":

@@ -121,6 +121,22 @@ class ResampleDesc(C.Structure):
     ]
 
 
+METRIC_PSNR, METRIC_SSIM = 1, 2                            # IIR_METRIC_*: the bits of MetricsDesc.what
+
+
+class MetricsDesc(C.Structure):
+    _fields_ = [
+        ("a", C.c_void_p), ("b", C.c_void_p),
+        ("a_u8", C.c_int32), ("b_u8", C.c_int32),
+        ("a_quantize", C.c_int32), ("b_quantize", C.c_int32),
+        ("N", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("crop_border", C.c_int32), ("y_channel", C.c_int32),
+        ("what", C.c_uint32),
+        ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
+        ("out", C.c_void_p),
+    ]
+
+
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # symbol -> (restype, argtypes); must list every function declared in include/instantir_hip.h
@@ -177,6 +193,8 @@ SIGNATURES = {
     "iir_colorfix_wavelet_f32": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P]),
     "iir_colorfix_adain_f32": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P]),
     "iir_resample_pass": (C.c_int, [C.POINTER(ResampleDesc), _P]),
+    "iir_image_metrics_workspace_bytes": (C.c_int64, [C.POINTER(MetricsDesc)]),
+    "iir_image_metrics": (C.c_int, [C.POINTER(MetricsDesc), _P]),
     "iir_transpose_f16": (C.c_int, [_P, _I64, _I32, _I32, _P, _I64, _I32, _P]),
     "iir_timing_event_create": (C.c_void_p, []),
     "iir_timing_event_destroy": (None, [_P]),

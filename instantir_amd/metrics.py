@@ -1,0 +1,189 @@
+"""PSNR and SSIM of restored images on the device (an addition: the reference's `losses/` covers the training side only).
+
+The definitions are the ones restoration papers report (basicsr's `calculate_psnr` / `calculate_ssim`; DESIGN.md section 7
+"Image metrics"), the arithmetic is one launch pair of `ops.image_metrics` per call, and what comes back are Python floats:
+
+    from instantir_amd import metrics
+    metrics.psnr(restored, gt)                       # a float for one image, a list for a batch
+    metrics.evaluate(restored, gt, crop_border=4, y_channel=True)
+    metrics.input_fidelity(restored, lq)             # no ground truth: how far did the restoration move from its input
+
+Images are what the pipeline returns and what a user has: a PIL image or a list of them, a uint8 numpy array (H, W), (H, W, C)
+or (N, H, W, C), a float numpy array of the same layouts on a [0, 1] scale (`output_type="np"`), a uint8 tensor in those
+layouts, or a float tensor (C, H, W) / (N, C, H, W) on a [0, 1] scale (`output_type="pt"`).  An 8-bit source is uploaded as
+uint8.  There is no host path: without the library and a GPU the calls raise.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+METRICS = ("psnr", "ssim")
+WINDOW = 11
+
+
+def _pil_array(im, arg):
+    if im.mode not in ("L", "RGB"):
+        im = im.convert("RGB")
+    a = np.array(im)
+    return a[:, :, None] if a.ndim == 2 else a
+
+
+def _host_source(x, arg):
+    """-> (host tensor in the kernel's layout: uint8 (N, H, W, C) or fp32 (N, C, H, W); whether the argument was one image)."""
+    from PIL import Image
+    if isinstance(x, Image.Image):
+        return torch.from_numpy(np.ascontiguousarray(_pil_array(x, arg)[None])), True
+    if isinstance(x, (list, tuple)):
+        if not x or not all(isinstance(im, Image.Image) for im in x):
+            raise ValueError(f"{arg}: a list must hold PIL images (at least one)")
+        arrs = [_pil_array(im, arg) for im in x]
+        if len({a.shape for a in arrs}) != 1:
+            raise ValueError(f"{arg}: the images of a list must share a size and a mode, got {sorted({a.shape for a in arrs})}")
+        return torch.from_numpy(np.stack(arrs)), False
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+        channels_last = True
+    elif torch.is_tensor(x):
+        channels_last = x.dtype == torch.uint8
+    else:
+        raise ValueError(f"{arg}: expected a PIL image, a list of PIL images, a numpy array or a tensor, got {type(x).__name__}")
+    if x.dtype != torch.uint8 and not x.dtype.is_floating_point:
+        raise ValueError(f"{arg}: expected uint8 or floating-point values, got {x.dtype}")
+    single = x.dim() < 4
+    if channels_last:                   # (H, W), (H, W, C), (N, H, W, C)
+        if x.dim() == 2:
+            x = x[None, :, :, None]
+        elif x.dim() == 3:
+            x = x[None]
+    elif x.dim() == 3:                  # (C, H, W)
+        x = x[None]
+    if x.dim() != 4:
+        raise ValueError(f"{arg}: expected an image or a batch of images, got shape {tuple(x.shape)}")
+    if x.dtype != torch.uint8:
+        x = x.float()
+        if channels_last:
+            x = x.permute(0, 3, 1, 2)
+    return x, single
+
+
+def _dims(t):
+    return tuple(t.shape[i] for i in (0, 3, 1, 2)) if t.dtype == torch.uint8 else tuple(t.shape)
+
+
+def _check_options(who, what, crop_border, y_channel, quantize):
+    names = (what,) if isinstance(what, str) else tuple(what)
+    if not names or any(w not in METRICS for w in names):
+        raise ValueError(f"{who}: metrics must name one or both of {METRICS}, got {what!r}")
+    if isinstance(crop_border, bool) or not isinstance(crop_border, int) or crop_border < 0:
+        raise ValueError(f"{who}: crop_border must be an integer >= 0, got {crop_border!r}")
+    if isinstance(quantize, (bool, np.bool_)):
+        quantize = (bool(quantize), bool(quantize))
+    try:
+        qa, qb = (bool(q) for q in quantize)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: quantize must be a flag or a pair of flags (for a, for b), got {quantize!r}") from None
+    return tuple(n for n in METRICS if n in names), (qa, qb)
+
+
+def _check_pair(who, ta, tb, names, crop_border, y_channel, arg_b="b"):
+    da, db = _dims(ta), _dims(tb)
+    if da != db:
+        raise ValueError(f"{who}: {arg_b} is (N, C, H, W) = {db} but its counterpart is {da}")
+    N, C, H, W = da
+    if C not in (1, 3):
+        raise ValueError(f"{who}: a and b must have 1 or 3 channels, got {C}")
+    if y_channel and C != 3:
+        raise ValueError(f"{who}: y_channel needs 3 channels, got {C}")
+    side = WINDOW if "ssim" in names else 1
+    if min(H, W) - 2 * crop_border < side:
+        raise ValueError(f"{who}: crop_border {crop_border} leaves less than {side} pixel(s) per side of {H}x{W}"
+                         + (" (the SSIM window is 11 x 11)" if "ssim" in names else ""))
+
+
+def _device(device):
+    if device is not None:
+        return torch.device(device)
+    if not torch.cuda.is_available():
+        raise RuntimeError("instantir_amd.metrics needs an MI355X: the metrics have no host path")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def psnr_from_mse(mse):
+    """10 log10(255^2 / MSE) in fp64; inf for identical images."""
+    return math.inf if mse == 0 else 10.0 * math.log10(255.0 ** 2 / mse)
+
+
+def _score(ta, tb, names, crop_border, y_channel, quantize, device):
+    from . import ops
+    dev = _device(device)
+    out = ops.image_metrics(ta.to(dev).contiguous(), tb.to(dev).contiguous(), crop_border=crop_border, y_channel=bool(y_channel),
+                            quantize=quantize, what=names).cpu().tolist()
+    res = {}
+    if "psnr" in names:
+        res["psnr"] = [psnr_from_mse(row[0]) for row in out]
+    if "ssim" in names:
+        res["ssim"] = [float(row[1]) for row in out]
+    return res
+
+
+def _run(who, a, b, names, crop_border, y_channel, quantize, device):
+    names, quantize = _check_options(who, names, crop_border, y_channel, quantize)
+    ta, single_a = _host_source(a, "a")
+    tb, single_b = _host_source(b, "b")
+    _check_pair(who, ta, tb, names, crop_border, y_channel)
+    return _score(ta, tb, names, crop_border, y_channel, quantize, device), single_a and single_b
+
+
+def psnr(a, b, crop_border=0, y_channel=False, quantize=False, device=None):
+    """PSNR in dB of `a` against `b`: a float for one image, a list of floats for a batch; inf for identical images."""
+    res, single = _run("psnr", a, b, ("psnr",), crop_border, y_channel, quantize, device)
+    return res["psnr"][0] if single else res["psnr"]
+
+
+def ssim(a, b, crop_border=0, y_channel=False, quantize=False, device=None):
+    """SSIM (11 x 11 Gaussian window, sigma 1.5, valid positions only) of `a` against `b`: a float or a list of floats."""
+    res, single = _run("ssim", a, b, ("ssim",), crop_border, y_channel, quantize, device)
+    return res["ssim"][0] if single else res["ssim"]
+
+
+def _with_means(res):
+    for name in list(res):
+        res[name + "_mean"] = float(sum(res[name]) / len(res[name]))
+    return res
+
+
+def evaluate(a, b, metrics=METRICS, crop_border=0, y_channel=False, quantize=False, device=None):
+    """Both figures in one launch pair: {"psnr": [per image], "ssim": [per image], "psnr_mean": .., "ssim_mean": ..} (only the
+    metrics asked for).  `quantize` (a flag, or one per argument) rounds a float source to the 8-bit image that would be saved."""
+    res, _ = _run("evaluate", a, b, metrics, crop_border, y_channel, quantize, device)
+    return _with_means(res)
+
+
+def input_fidelity(restored, lq, filter="bicubic", metrics=METRICS, crop_border=0, y_channel=False, device=None):
+    """How far the restoration moved from what it was given: `restored` is brought to the size of `lq` with `ops.resample`
+    (PIL's `filter`; quantised mode when both are 8-bit, untouched at equal sizes) and scored against `lq`.  Returns what
+    `evaluate` returns."""
+    from . import ops
+    from .resample import FILTERS
+    if filter not in FILTERS:
+        raise ValueError(f"input_fidelity: filter must be one of {tuple(FILTERS)}, got {filter!r}")
+    names, _ = _check_options("input_fidelity", metrics, crop_border, y_channel, False)
+    tr, _ = _host_source(restored, "restored")
+    tl, _ = _host_source(lq, "lq")
+    dr, dl = _dims(tr), _dims(tl)
+    if dr[:2] != dl[:2]:
+        raise ValueError(f"input_fidelity: restored holds (N, C) = {dr[:2]} but lq {dl[:2]}")
+    quantize = (False, False)
+    dev = _device(device) if dr[2:] != dl[2:] else None
+    if dr[2:] != dl[2:]:
+        both_u8 = tr.dtype == torch.uint8 and tl.dtype == torch.uint8
+        if tr.dtype == torch.uint8:
+            tr = ops.resample(tr.to(dev), dl[2:], filter, quantize=both_u8, scale=1.0 / 255.0)
+        else:
+            tr = ops.resample(tr.to(dev).contiguous(), dl[2:], filter, clamp=(0.0, 1.0))
+        quantize = (both_u8, False)
+    _check_pair("input_fidelity", tr, tl, names, crop_border, y_channel, arg_b="lq")
+    return _with_means(_score(tr, tl, names, crop_border, y_channel, quantize, dev if dev is not None else device))

@@ -1084,3 +1084,69 @@ def resample(src, size, filter="bilinear", quantize=False, window=None, clamp=No
         _resample_pass(src, u8, mid, (N, Cc, H, W), 0, ow, RS.device_tables(W, ow, filter, dev), (0, x0, H, w), quantize, None, None, None)
         _resample_pass(mid, False, out, (N, Cc, H, w), 1, oh, RS.device_tables(H, oh, filter, dev), (y0, 0, h, w), *last)
     return out
+
+
+METRICS = ("psnr", "ssim")
+METRICS_WINDOW = 11            # the SSIM window per axis: a cropped side below it has no SSIM
+METRICS_TILE = 32              # IIR_METRICS_TILE: the SSIM-map tile a workgroup owns, per axis
+
+
+def _metrics_source(t, name):
+    if not torch.is_tensor(t) or t.dim() != 4 or t.dtype not in (torch.float32, torch.uint8) or not t.is_contiguous():
+        raise ValueError(f"image_metrics: {name} must be a contiguous 4-D tensor, fp32 (N, C, H, W) in [0, 1] or uint8 (N, H, W, C), got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    u8 = t.dtype == torch.uint8
+    return u8, (tuple(t.shape[i] for i in (0, 3, 1, 2)) if u8 else tuple(t.shape))
+
+
+def image_metrics(a, b, crop_border=0, y_channel=False, quantize=(False, False), what=("psnr", "ssim"), ws=None):
+    """Per-image MSE and SSIM of two image batches (iir_image_metrics; DESIGN.md section 7 "Image metrics").  `a`, `b`:
+    contiguous CUDA tensors of one device and one logical shape, each fp32 planar (N, C, H, W) on a [0, 1] scale or uint8
+    interleaved (N, H, W, C), C 1 or 3; the arithmetic is in 0..255 units.  `crop_border`: pixels dropped on every side first;
+    `y_channel` (C = 3): score the BT.601 luma alone; `quantize` = (for a, for b): an fp32 source is first rounded to the 8-bit
+    image that would be saved; `what`: "psnr", "ssim" or both (a name or a sequence of names).  Returns fp64 (N, 2) =
+    {MSE, SSIM} on the device; a column that `what` leaves out holds NaN.  PSNR = 10 log10(255^2 / MSE) is the caller's
+    (instantir_amd.metrics).  `ws`: a byte workspace of at least iir_image_metrics_workspace_bytes (allocated here when absent)."""
+    names = (what,) if isinstance(what, str) else tuple(what)
+    if not names or any(w not in METRICS for w in names):
+        raise ValueError(f"image_metrics: what must name one or both of {METRICS}, got {what!r}")
+    a_u8, dims = _metrics_source(a, "a")
+    b_u8, dims_b = _metrics_source(b, "b")
+    if dims_b != dims:
+        raise ValueError(f"image_metrics: b is (N, C, H, W) = {dims_b} but a is {dims}")
+    N, Cc, H, W = dims
+    if Cc not in (1, 3):
+        raise ValueError(f"image_metrics: a and b must have 1 or 3 channels, got {Cc}")
+    if y_channel and Cc != 3:
+        raise ValueError("image_metrics: y_channel needs 3 channels")
+    if isinstance(crop_border, bool) or not isinstance(crop_border, int) or crop_border < 0:
+        raise ValueError(f"image_metrics: crop_border must be an integer >= 0, got {crop_border!r}")
+    try:
+        qa, qb = (bool(q) for q in quantize)
+    except (TypeError, ValueError):
+        raise ValueError(f"image_metrics: quantize must be a pair of flags (for a, for b), got {quantize!r}") from None
+    need_side = METRICS_WINDOW if "ssim" in names else 1
+    if min(N, H, W) <= 0 or min(H, W) - 2 * crop_border < need_side:
+        raise ValueError(f"image_metrics: {H}x{W} with crop_border {crop_border} leaves less than {need_side} pixel(s) per side"
+                         + (" (the SSIM window is 11 x 11)" if "ssim" in names else ""))
+    if not a.is_cuda or not b.is_cuda or a.device != b.device:
+        raise ValueError(f"image_metrics: a and b must be CUDA tensors on one device (there is no host path), got {a.device} and {b.device}")
+    d = L.MetricsDesc()
+    d.a, d.b, d.a_u8, d.b_u8 = a.data_ptr(), b.data_ptr(), int(a_u8), int(b_u8)
+    d.a_quantize, d.b_quantize = int(qa), int(qb)
+    d.N, d.C, d.H, d.W = N, Cc, H, W
+    d.crop_border, d.y_channel = crop_border, int(bool(y_channel))
+    d.what = (L.METRIC_PSNR if "psnr" in names else 0) | (L.METRIC_SSIM if "ssim" in names else 0)
+    h = L.load()
+    need = h.iir_image_metrics_workspace_bytes(C.byref(d))
+    if need < 0:
+        raise ValueError(f"image_metrics: unsupported geometry N={N} C={Cc} H={H} W={W} crop_border={crop_border}")
+    if ws is None:
+        ws = torch.empty(need // 8, dtype=torch.float64, device=a.device)
+    elif not torch.is_tensor(ws) or not ws.is_cuda or ws.device != a.device or not ws.is_contiguous() \
+            or ws.numel() * ws.element_size() < need or ws.data_ptr() % 8:
+        raise ValueError(f"image_metrics: ws needs {need} contiguous, 8-byte aligned bytes on the images' device")
+    out = torch.empty(N, 2, dtype=torch.float64, device=a.device)
+    d.ws, d.ws_bytes, d.out = ws.data_ptr(), ws.numel() * ws.element_size(), out.data_ptr()
+    L.check(h.iir_image_metrics(C.byref(d), _stream()), "iir_image_metrics")
+    return out
