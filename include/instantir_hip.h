@@ -554,6 +554,63 @@ typedef struct {
 int64_t iir_image_metrics_workspace_bytes(const iir_metrics_desc* d);
 int iir_image_metrics(const iir_metrics_desc* d, void* stream);
 
+/* Synthetic degradation: the three operations of the Real-ESRGAN second-order chain (utils/degradation_pipeline.py:230-336,
+ * which runs them through basicsr's filter2D, random_add_gaussian_noise_pt and DiffJPEG) that resampling does not cover;
+ * contract here and in DESIGN.md section 7 "Synthetic degradation".  Images are fp32 planar (N, C, H, W), contiguous, in
+ * [0, 1].  All three: every global load is unconditional from a clamped address, only stores are guarded, no atomics, sums in
+ * a fixed order, multiply-adds written as fmaf and nothing else fused: equal inputs give equal bits.
+ *
+ * iir_filter2d_f32: per-image k x k correlation with reflect padding (no edge pixel repeated), the reference's filter2D:
+ *   out[n,c,y,x] = sum_i sum_j taps[n,i,j] * in[n,c,refl(y + i - r),refl(x + j - r)],  r = (ksize - 1) / 2,
+ *   refl(t) = -t for t < 0, 2 (L - 1) - t for t >= L;  i the outer and j the inner loop, both in index order, fmaf from 0.
+ *   taps: device fp32 (N, ksize, ksize), read at launch.  A workgroup owns an IIR_FILTER2D_TILE^2 output tile of one plane and
+ *   stages the tile, its halo and the image's taps in LDS.
+ *   IIR_EINVAL, before any HIP call: a NULL in, taps or out; N, C, H or W <= 0; H or W > 32768; N * C > 65535; ksize even,
+ *   < 1 or > IIR_FILTER2D_MAX_KSIZE; H <= r or W <= r (one reflection must do); out overlapping in (neighbours read it).
+ *
+ * iir_add_gaussian_noise_f32: out = min(max(in + (sigma[n] / 255) * z, 0), 1), sigma device fp32[N] in 0..255 units (the
+ *   caller keeps it in [0, 255]), z a pure function of (seed, noise_stream, n, c, y, x), whatever the launch geometry:
+ *     (r0, r1, r2, r3) = Philox4x32-10(counter = (y * W + x, n, gray ? 0 : c, noise_stream), key = (seed low 32, seed high 32))
+ *     u1 = ((float)(r0 >> 8) + 0.5f) * 2^-24,  u2 = ((float)(r1 >> 8) + 0.5f) * 2^-24      (fp32, round to nearest even)
+ *     z  = sqrtf(-2 logf(u1)) * cospif(2 u2)
+ *   The sum (r >> 8) + 0.5 is exact below 2^23 and has 25 significant bits from there on, where it rounds to the even
+ *   neighbour; u is therefore in (0, 1], u1 = 1 (one r0 >> 8 in 2^24) gives z = 0, and |z| <= sqrt(50 ln 2) < 5.9.  The fp64
+ *   restatement starts from these fp32 u1, u2.  With `gray` the channels of a pixel share z.  sigma[n] / 255, its product
+ *   with z and the sum with `in` are three fp32 roundings.  out may be in (pointwise).
+ *   IIR_EINVAL, before any HIP call: a NULL in, sigma or out; N, C, H or W <= 0; H * W >= 2^32; more than 2^31 - 1 workgroups
+ *   of 256 elements; out overlapping in without being equal to it.
+ *
+ * iir_jpeg_roundtrip_f32: what a baseline 4:2:0 JPEG encode + decode at quality q = quality[n] (device fp32[N], clamped to
+ *   [1, 99] by the kernel) does to an image, without entropy coding (the role of DiffJPEG(differentiable=False)); C must be 3.
+ *   In fp32, in this order (every fmaf is one rounding, every other operation rounds on its own):
+ *     R, G, B = 255 * min(max(v, 0), 1)
+ *     Y  = fmaf(0.114, B, fmaf(0.587, G, 0.299 * R))
+ *     Cb = fmaf(0.5, B, fmaf(-0.331264, G, -0.168736 * R)) + 128
+ *     Cr = fmaf(-0.081312, B, fmaf(-0.418688, G, 0.5 * R)) + 128
+ *     the image is extended to a multiple of 16 by edge replication (the clamped address);
+ *     chroma sample (i, j) = ((p[2i][2j] + p[2i][2j+1]) + (p[2i+1][2j] + p[2i+1][2j+1])) * 0.25
+ *     per 8 x 8 block X (sample - 128), with D[u][k] = a(u) cos((2k + 1) u pi / 16), a(0) = sqrt(1/8), a(u > 0) = 1/2, formed
+ *     in fp64 and rounded to fp32, every sum over k = 0..7 in index order with fmaf from 0:
+ *       t[y][v] = sum_k D[v][k] X[y][k];   c[u][v] = sum_k D[u][k] t[k][v]                      (u: vertical frequency)
+ *       f = (q < 50 ? 5000 / q : 200 - 2 q) / 100;   step = T[u][v] * f;   c' = rintf(c / step) * step   (ties to even)
+ *       s[u][x] = sum_k D[k][x] c'[u][k];  X'[y][x] = sum_k D[k][y] s[k][x];   sample' = X' + 128
+ *     T: ITU-T T.81 Annex K table K.1 for Y, K.2 for Cb / Cr, neither rounded nor clamped after scaling;
+ *     chroma upsampled by replication;  d_b = Cb' - 128, d_r = Cr' - 128
+ *     R = fmaf(1.402, d_r, Y');  G = fmaf(-0.714136, d_r, fmaf(-0.344136, d_b, Y'));  B = fmaf(1.772, d_b, Y')
+ *     out = min(max(., 0), 255) / 255
+ *   One wave per 16 x 16 MCU, four per workgroup; a wave loads nothing but its own MCU and all of it before its first store,
+ *   so out may be in.
+ *   IIR_EINVAL, before any HIP call: a NULL in, quality or out; C != 3; N, H or W <= 0; N > 65535; H or W > 32768; out
+ *   overlapping in without being equal to it. */
+#define IIR_FILTER2D_MAX_KSIZE 21
+#define IIR_FILTER2D_TILE 32
+int iir_filter2d_f32(const float* in, const float* taps, int32_t N, int32_t C, int32_t H, int32_t W, int32_t ksize, float* out,
+                     void* stream);
+int iir_add_gaussian_noise_f32(const float* in, const float* sigma, int32_t N, int32_t C, int32_t H, int32_t W, uint64_t seed,
+                               uint32_t noise_stream, int32_t gray, float* out, void* stream);
+int iir_jpeg_roundtrip_f32(const float* in, const float* quality, int32_t N, int32_t C, int32_t H, int32_t W, float* out,
+                           void* stream);
+
 int iir_transpose_f16(const void* in, int64_t ldi, int32_t rows, int32_t cols, void* out, int64_t ldo, int32_t rows_pad,
                       void* stream);
 /* Measurement hook (bench.py roofline leg; no reference counterpart): arm a start/stop event pair and the NEXT

@@ -15,6 +15,9 @@ seeded embeddings because no tokenizer vocabulary exists here.  `--apg ETA NORM_
 guidance on (`pipe.enable_apg(...)`: the CFG update's saturating parallel part down-weighted, its norm clamped, with momentum).
 `--gt_path DIR` scores every saved image against the file of the same name in DIR (PSNR / SSIM on the device,
 `instantir_amd.metrics`), `--input_fidelity` against its own input file; the figures go to `metrics.json` in the output directory.
+`--degrade PRESET_OR_JSON [--degrade_seed N]` treats the files of `--test_path` as clean images: each is degraded on the device
+(`instantir_amd.degrade`), the 8-bit result stands in for the file that was read and is saved with its recipe under `lq/` in the
+output directory, and unless told otherwise the run scores its restorations against the clean files.
 """
 from __future__ import annotations
 
@@ -182,7 +185,53 @@ def build_parser():
     p.add_argument("--input_fidelity", action="store_true",
                    help="score every saved image, resized to its input's size (bicubic), against the input file as it was read: "
                         "how far the restoration moved from what it was given; needs no ground truth")
+    p.add_argument("--degrade", type=str, default=None, metavar="PRESET_OR_JSON",
+                   help="the files of --test_path are clean images: degrade each on the device first, with a recipe sampled from "
+                        "the preset (realesrgan, bicubic) per (--degrade_seed, file name) or read from a recipe JSON file; the "
+                        "8-bit LQ image and its recipe go to lq/ in the output directory, and --gt_path defaults to --test_path")
+    p.add_argument("--degrade_seed", type=int, default=None, metavar="N", help="seed of --degrade's recipes and noise (default 0)")
     return p
+
+
+def apply_degrade(args):
+    """`--degrade PRESET_OR_JSON [--degrade_seed N]` -> {"spec", "seed"} or None (an addition: the reference's infer.py reads
+    LQ files that something else made).  Refused: the seed without the flag, a negative seed, an unknown preset or an unreadable
+    JSON, and a recipe that leaves the LQ at 1 / sf of the size (`resize_lq` false) together with a ground-truth comparison.
+    Without `--gt_path` and `--input_fidelity`, `--gt_path` becomes the directory of `--test_path`: the clean files."""
+    spec, seed = getattr(args, "degrade", None), getattr(args, "degrade_seed", None)
+    if spec is None:
+        if seed is not None:
+            raise SystemExit("--degrade_seed needs --degrade")
+        return None
+    seed = 0 if seed is None else seed
+    if seed < 0:
+        raise SystemExit(f"--degrade_seed must be >= 0, got {seed}")
+    from . import degrade as D
+    try:
+        probe = D.load_recipe(spec, seed, "")
+    except ValueError as e:
+        raise SystemExit(f"--degrade: {e}")
+    if getattr(args, "gt_path", None) is None and not getattr(args, "input_fidelity", False):
+        args.gt_path = args.test_path if os.path.isdir(args.test_path) else (os.path.dirname(args.test_path) or ".")
+    if not probe.resize_lq and getattr(args, "gt_path", None) is not None:
+        raise SystemExit("--degrade: this recipe leaves the LQ at 1 / sf of the clean size (resize_lq false), which cannot be "
+                         "scored against --gt_path")
+    return {"spec": spec, "seed": int(seed)}
+
+
+def degraded_input(setup, im, name, out_dir, device):
+    """The clean image `im` of file `name` -> its LQ image as the 8-bit PIL image the run goes on with; saved as PNG to
+    <out_dir>/lq/<name>, its recipe to <out_dir>/lq/<stem>.json.  One launch chain per file, seeded by (seed, name): a file's LQ
+    does not depend on its batch."""
+    from . import degrade as D
+    recipe = D.load_recipe(setup["spec"], setup["seed"], name)
+    lq = Image.fromarray(D.quantize_u8(D.degrade([im], recipe, seed=D.noise_seed(setup["seed"], name), device=device))[0])
+    lq_dir = os.path.join(out_dir, "lq")
+    os.makedirs(lq_dir, exist_ok=True)
+    lq.save(os.path.join(lq_dir, name), format="PNG")
+    with open(os.path.join(lq_dir, os.path.splitext(name)[0] + ".json"), "w") as f:
+        f.write(recipe.to_json())
+    return lq
 
 
 def apply_metrics(args):
@@ -396,6 +445,7 @@ def apply_restore_map(args, names, size):
 
 def main(args, device, rank=0, world=1):
     apply_device_resize(None, args)              # (a flag error should not wait for the weights to load)
+    degrading = apply_degrade(args)              # (before apply_metrics: it may set --gt_path)
     scoring = apply_metrics(args)
     pipe, lcm_scheduler = build_pipeline(args, device)
     apply_freeu(pipe, args)
@@ -418,6 +468,8 @@ def main(args, device, rank=0, world=1):
         for name in lq_batch:
             path = args.test_path if os.path.isfile(args.test_path) else os.path.join(args.test_path, name)
             im = Image.open(path).convert("RGB")
+            if degrading:
+                im = degraded_input(degrading, im, name, out_dir, device)
             originals.append(im)
             if device_resize:
                 work, out_size = resize_plan(im.size, width=args.width, height=args.height)

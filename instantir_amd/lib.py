@@ -195,6 +195,9 @@ SIGNATURES = {
     "iir_resample_pass": (C.c_int, [C.POINTER(ResampleDesc), _P]),
     "iir_image_metrics_workspace_bytes": (C.c_int64, [C.POINTER(MetricsDesc)]),
     "iir_image_metrics": (C.c_int, [C.POINTER(MetricsDesc), _P]),
+    "iir_filter2d_f32": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "iir_add_gaussian_noise_f32": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, C.c_uint64, C.c_uint32, _I32, _P, _P]),
+    "iir_jpeg_roundtrip_f32": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     "iir_transpose_f16": (C.c_int, [_P, _I64, _I32, _I32, _P, _I64, _I32, _P]),
     "iir_timing_event_create": (C.c_void_p, []),
     "iir_timing_event_destroy": (None, [_P]),

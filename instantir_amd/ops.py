@@ -1150,3 +1150,115 @@ def image_metrics(a, b, crop_border=0, y_channel=False, quantize=(False, False),
     d.ws, d.ws_bytes, d.out = ws.data_ptr(), ws.numel() * ws.element_size(), out.data_ptr()
     L.check(h.iir_image_metrics(C.byref(d), _stream()), "iir_image_metrics")
     return out
+
+
+FILTER2D_MAX_KSIZE = 21        # IIR_FILTER2D_MAX_KSIZE
+JPEG_QUALITY_RANGE = (1.0, 99.0)
+
+
+def _chk_image(who, t, name="x"):
+    if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()) or min(t.shape) <= 0:
+        raise ValueError(f"{who}: {name} must be a contiguous, non-empty fp32 (N, C, H, W) tensor, got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+
+
+def _chk_image_out(who, x, out, in_place):
+    """`out` for an image launch: x's shape and device; the same tensor as x only where `in_place`, never a shifted view."""
+    if out is None:
+        return torch.empty_like(x)
+    _chk_image(who, out, "out")
+    if out.shape != x.shape or out.device != x.device:
+        raise ValueError(f"{who}: out must have x's shape and device")
+    lo_x, lo_o, nbytes = x.data_ptr(), out.data_ptr(), x.numel() * 4
+    if lo_x < lo_o + nbytes and lo_o < lo_x + nbytes and not (in_place and lo_x == lo_o):
+        raise ValueError(f"{who}: out overlaps x" + ("" if in_place else " (neighbouring tiles read x: it cannot run in place)"))
+    return out
+
+
+def _per_image(who, name, value, N, lo, hi, device):
+    """A per-image launch parameter as fp32 (N,) on `device`: a number for every image, N numbers, or a tensor of N values
+    (checked on the host: a device tensor is read back); every value finite and in [lo, hi]."""
+    if torch.is_tensor(value):
+        vals = value.detach().to("cpu", torch.float64).reshape(-1)
+    else:
+        try:
+            vals = torch.tensor([float(value)] * N if isinstance(value, (int, float)) else [float(v) for v in value], dtype=torch.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: {name} must be a number or one number per image, got {value!r}") from None
+    if vals.numel() != N:
+        raise ValueError(f"{who}: {name} must hold one value per image ({N}), got {vals.numel()}")
+    if not bool(((vals >= lo) & (vals <= hi)).all()):
+        raise ValueError(f"{who}: {name} must lie in [{lo:g}, {hi:g}], got {vals.tolist()}")
+    return vals.to(torch.float32).to(device)
+
+
+def _chk_cuda(who, *tensors):
+    if any(not t.is_cuda for t in tensors) or len({t.device for t in tensors}) != 1:
+        raise ValueError(f"{who}: the tensors must be CUDA tensors on one device (there is no host path), got "
+                         f"{[str(t.device) for t in tensors]}")
+
+
+def filter2d(x, taps, out=None):
+    """Per-image k x k blur with reflect padding (iir_filter2d_f32; DESIGN.md section 7 "Synthetic degradation"): x fp32
+    (N, C, H, W); taps fp32 (N, k, k) or (k, k) for every image, k odd, <= 21, H and W > (k - 1) / 2.  `out` may not be x."""
+    who = "filter2d"
+    _chk_image(who, x)
+    N, Cc, H, W = x.shape
+    if not (torch.is_tensor(taps) and taps.dtype == torch.float32 and taps.dim() in (2, 3)):
+        raise ValueError(f"{who}: taps must be an fp32 (N, k, k) or (k, k) tensor, got {getattr(taps, 'dtype', type(taps))} "
+                         f"{tuple(getattr(taps, 'shape', ()))}")
+    if taps.dim() == 2:
+        taps = taps.unsqueeze(0).expand(N, -1, -1)
+    k = taps.shape[-1]
+    if taps.shape[0] != N or taps.shape[1] != k or k % 2 != 1 or k > FILTER2D_MAX_KSIZE:
+        raise ValueError(f"{who}: taps must be ({N}, k, k) with k odd and <= {FILTER2D_MAX_KSIZE}, got {tuple(taps.shape)}")
+    if min(H, W) <= (k - 1) // 2:
+        raise ValueError(f"{who}: a {k} x {k} kernel needs H, W > {(k - 1) // 2} (one reflection), got {H}x{W}")
+    if H > 32768 or W > 32768 or N * Cc > 65535:
+        raise ValueError(f"{who}: unsupported geometry N={N} C={Cc} H={H} W={W} (sides <= 32768, N * C <= 65535)")
+    out = _chk_image_out(who, x, out, in_place=False)
+    _chk_cuda(who, x, taps, out)
+    taps = taps.contiguous()
+    L.check(L.load().iir_filter2d_f32(x.data_ptr(), taps.data_ptr(), N, Cc, H, W, k, out.data_ptr(), _stream()), "iir_filter2d_f32")
+    return out
+
+
+def add_gaussian_noise(x, sigma, seed, stream=0, gray=False, out=None):
+    """out = clamp(x + (sigma[n] / 255) z, 0, 1) with z ~ N(0, 1) a pure function of (seed, stream, n, c, y, x) through
+    Philox4x32-10 (iir_add_gaussian_noise_f32; DESIGN.md section 7 "Synthetic degradation").  x fp32 (N, C, H, W); `sigma`: a
+    number or one per image, in 0..255 units, in [0, 255]; `seed` an integer in [0, 2^64); `stream` in [0, 2^32): stages of one
+    recipe take different streams; `gray`: one z per pixel for all channels.  `out` may be x."""
+    who = "add_gaussian_noise"
+    _chk_image(who, x)
+    N, Cc, H, W = x.shape
+    for name, v, top in (("seed", seed, 1 << 64), ("stream", stream, 1 << 32)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < top:
+            raise ValueError(f"{who}: {name} must be an integer in [0, 2^{top.bit_length() - 1}), got {v!r}")
+    if H * W >= 1 << 32 or (x.numel() + 255) // 256 > 0x7fffffff:
+        raise ValueError(f"{who}: unsupported geometry N={N} C={Cc} H={H} W={W}")
+    out = _chk_image_out(who, x, out, in_place=True)
+    sig = _per_image(who, "sigma", sigma, N, 0.0, 255.0, "cpu")
+    _chk_cuda(who, x, out)
+    sig = sig.to(x.device)
+    L.check(L.load().iir_add_gaussian_noise_f32(x.data_ptr(), sig.data_ptr(), N, Cc, H, W, seed, stream, int(bool(gray)), out.data_ptr(),
+                                                _stream()), "iir_add_gaussian_noise_f32")
+    return out
+
+
+def jpeg_roundtrip(x, quality, out=None):
+    """What a baseline 4:2:0 JPEG encode + decode at `quality` does to x, without entropy coding (iir_jpeg_roundtrip_f32;
+    DESIGN.md section 7 "Synthetic degradation").  x fp32 (N, 3, H, W) in [0, 1]; `quality`: a number or one per image, in
+    [1, 99].  `out` may be x."""
+    who = "jpeg_roundtrip"
+    _chk_image(who, x)
+    N, Cc, H, W = x.shape
+    if Cc != 3:
+        raise ValueError(f"{who}: x must have 3 channels, got {Cc}")
+    if H > 32768 or W > 32768 or N > 65535:
+        raise ValueError(f"{who}: unsupported geometry N={N} H={H} W={W} (sides <= 32768, N <= 65535)")
+    out = _chk_image_out(who, x, out, in_place=True)
+    q = _per_image(who, "quality", quality, N, *JPEG_QUALITY_RANGE, "cpu")
+    _chk_cuda(who, x, out)
+    q = q.to(x.device)
+    L.check(L.load().iir_jpeg_roundtrip_f32(x.data_ptr(), q.data_ptr(), N, Cc, H, W, out.data_ptr(), _stream()), "iir_jpeg_roundtrip_f32")
+    return out
