@@ -18,7 +18,9 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-KSIZE_MAX = 21                                       # IIR_FILTER2D_MAX_KSIZE
+from .lib import MACROS
+
+KSIZE_MAX = MACROS["IIR_FILTER2D_MAX_KSIZE"]
 KERNEL_SIZES = tuple(range(7, KSIZE_MAX + 1, 2))     # utils/degradation_pipeline.py:106
 PRESETS = ("realesrgan", "bicubic")
 

@@ -18,8 +18,10 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .lib import MACROS
+
 DEFAULT_DECAY = 2.0
-MAX_RADIUS = 24                 # IIR_LQ_FIDELITY_MAX_RADIUS: ceil(3 sigma) of the largest low-pass the launch takes
+MAX_RADIUS = MACROS["IIR_LQ_FIDELITY_MAX_RADIUS"]     # ceil(3 sigma) of the largest low-pass the launch takes
 MIN_LOWPASS, MAX_LOWPASS = 0.25, 8.0
 
 

@@ -22,7 +22,7 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
-_DT = {torch.float16: 0, torch.bfloat16: 1}       # IIR_DT_F16 / IIR_DT_BF16
+_DT = {torch.float16: L.MACROS["IIR_DT_F16"], torch.bfloat16: L.MACROS["IIR_DT_BF16"]}
 
 
 def _chk2d(t, name, dtype=torch.float16):
@@ -639,7 +639,7 @@ def copy_add(src, dst, dst_off=0, add=None, add_scale=None, rows_per_scale=1):
     return dst
 
 
-FREEU_SLABS = 16          # IIR_FREEU_SLABS
+FREEU_SLABS = L.MACROS["IIR_FREEU_SLABS"]
 
 
 def freeu_partials_floats(rows, H, W, C):
@@ -675,7 +675,7 @@ def freeu_concat(x, skip, dst, partials, H, W, b, s, dst_off=0, mid_add=None, ad
     return dst
 
 
-SEG_MAX_EXTENT = 128      # IIR_SEG_MAX_EXTENT
+SEG_MAX_EXTENT = L.MACROS["IIR_SEG_MAX_EXTENT"]
 
 
 def seg_blur_q(q, images, H, W, wy=None, wx=None, mean=False):
@@ -908,7 +908,7 @@ def blend_tiles(a, b, extent, vertical):
 
 
 COLOR_FIX_MODES = ("wavelet", "adain")
-MAX_MAP_FEATHER = 512      # IIR_REGION_MAX_FEATHER
+MAX_MAP_FEATHER = L.MACROS["IIR_REGION_MAX_FEATHER"]
 
 
 def colorfix(content, style, mode, out=None, ws=None):
@@ -998,8 +998,8 @@ def region_composite(decoded, original, map_px, feather, out=None, ws=None):
     return out
 
 
-LQ_FIDELITY_MAX_RADIUS = 24     # IIR_LQ_FIDELITY_MAX_RADIUS
-LQ_FIDELITY_TILE = 32           # IIR_LQ_FIDELITY_TILE: the output tile a workgroup owns, per axis
+LQ_FIDELITY_MAX_RADIUS = L.MACROS["IIR_LQ_FIDELITY_MAX_RADIUS"]
+LQ_FIDELITY_TILE = L.MACROS["IIR_LQ_FIDELITY_TILE"]           # the output tile a workgroup owns, per axis
 
 
 def lq_fidelity(x0, lq, wc, prev, x0_out, taps=None, hist=None):
@@ -1088,7 +1088,7 @@ def resample(src, size, filter="bilinear", quantize=False, window=None, clamp=No
 
 METRICS = ("psnr", "ssim")
 METRICS_WINDOW = 11            # the SSIM window per axis: a cropped side below it has no SSIM
-METRICS_TILE = 32              # IIR_METRICS_TILE: the SSIM-map tile a workgroup owns, per axis
+METRICS_TILE = L.MACROS["IIR_METRICS_TILE"]       # the SSIM-map tile a workgroup owns, per axis
 
 
 def _metrics_source(t, name):
@@ -1152,7 +1152,7 @@ def image_metrics(a, b, crop_border=0, y_channel=False, quantize=(False, False),
     return out
 
 
-FILTER2D_MAX_KSIZE = 21        # IIR_FILTER2D_MAX_KSIZE
+FILTER2D_MAX_KSIZE = L.MACROS["IIR_FILTER2D_MAX_KSIZE"]
 JPEG_QUALITY_RANGE = (1.0, 99.0)
 
 

@@ -19,9 +19,11 @@ import math
 import numpy as np
 import torch
 
+from .lib import MACROS
+
 FILTERS = ("bilinear", "bicubic", "lanczos")
 SUPPORT = {"bilinear": 1.0, "bicubic": 2.0, "lanczos": 3.0}
-MAX_SIDE = 32768            # IIR_RESAMPLE_MAX_SIDE
+MAX_SIDE = MACROS["IIR_RESAMPLE_MAX_SIDE"]
 MAX_PLANES = 65535          # N * C of one launch
 
 

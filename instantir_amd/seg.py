@@ -11,11 +11,12 @@ import math
 from typing import List, Tuple
 
 from . import pag
+from .lib import MACROS
 
 DEFAULT_SEG_SCALE = 3.0
 DEFAULT_SEG_BLUR_SIGMA = 100.0
 MEAN_ABOVE = 9999.0            # a sigma beyond this (inf included) replaces the blur by the image's mean query
-MAX_EXTENT = 128               # IIR_SEG_MAX_EXTENT: tokens per grid axis the blur launch takes (a 2048^2 image at level 1)
+MAX_EXTENT = MACROS["IIR_SEG_MAX_EXTENT"]      # tokens per grid axis the blur launch takes (a 2048^2 image at level 1)
 
 
 def check_sigma(seg_blur_sigma) -> float:

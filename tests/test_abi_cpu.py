@@ -19,6 +19,14 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(h, s), s
     h.iir_abi_version.restype = ctypes.c_int
     assert h.iir_abi_version() == 3
+    # and the other way round: every function the library exports under the iir_ prefix is one the header declares
+    import shutil
+    import subprocess
+    nm = shutil.which("nm") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-nm")
+    out = subprocess.run([nm, "-D", "--defined-only", lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = [line.split()[2] for line in out.splitlines() if len(line.split()) == 3 and line.split()[1] == "T"]
+    assert len(exported) >= len(lib.SIGNATURES)
+    assert [s for s in exported if s.startswith("iir_") and s not in lib.SIGNATURES] == []
 
 
 def test_k_split_workspace_has_left_the_abi():
@@ -46,23 +54,158 @@ def test_positional_step_entries_have_left_the_abi():
     assert "iir_sched_step(const iir_sched_desc* d, void* stream)" in text
 
 
-def test_descriptor_layouts_match_header():
-    """ctypes mirrors of the structs: natural alignment, sizes as a C compiler lays them out."""
+def _kind(t):
+    """A ctypes restype / argtype / field type as the probe program prints it: class, size and, for a pointer to a declared
+    struct, which struct."""
+    if t is None:
+        return "void 0 -"
+    if t is ctypes.c_void_p:
+        return "pointer %d -" % ctypes.sizeof(t)
+    if hasattr(t, "contents"):
+        return "pointer %d %s" % (ctypes.sizeof(t), t._type_.__name__)
+    code = t._type_
+    return "%s %d -" % ("float" if code in "fd" else "signed" if code.islower() else "unsigned", ctypes.sizeof(t))
+
+
+def _abi_facts(header):
+    """Everything `cheader` derived from a header, as {key: value} strings: the layout of every struct and field, the class of
+    every return value and parameter, the value of every macro."""
+    facts = {"macro " + name: str(value) for name, value in header.macros.items()}
+    for name, cls in header.structs.items():
+        facts["struct " + name] = "%d %d" % (ctypes.sizeof(cls), ctypes.alignment(cls))
+        for field, _ in cls._fields_:
+            facts["field %s.%s" % (name, field)] = "%d %d" % (getattr(cls, field).offset, getattr(cls, field).size)
+    for name, (restype, params) in header.functions.items():
+        facts["arity " + name] = str(len(params))
+        for i, t in enumerate([restype] + [ct for _, ct in params]):
+            facts["type %s %d" % (name, i - 1)] = _kind(t)            # -1: the return value
+    return facts
+
+
+_PROBE = r"""
+#include <cstddef>
+#include <cstdio>
+#include <type_traits>
+#include "%(header)s"
+template <class T> const char* struct_name() { return "-"; }
+%(names)s
+template <class T> void kind(const char* fn, int i) {
+    using U = std::remove_cv_t<T>;
+    const char* k = std::is_void_v<U> ? "void" : std::is_pointer_v<U> ? "pointer" : std::is_floating_point_v<U> ? "float"
+                  : !std::is_integral_v<U> ? "other" : std::is_signed_v<U> ? "signed" : "unsigned";
+    size_t size = 0;
+    if constexpr (!std::is_void_v<U>) size = sizeof(U);
+    std::printf("type %%s %%d|%%s %%zu %%s\n", fn, i, k, size, struct_name<std::remove_cv_t<std::remove_pointer_t<U>>>());
+}
+template <class F> struct signature;
+template <class R, class... A> struct signature<R (*)(A...)> {
+    static void print(const char* fn) {
+        std::printf("arity %%s|%%zu\n", fn, sizeof...(A));
+        int i = -1;
+        kind<R>(fn, i++);
+        (kind<A>(fn, i++), ...);
+    }
+};
+int main() {
+%(body)s
+}
+"""
+
+
+def _probe_source(header, header_path):
+    """The C++17 program that prints the same facts as `_abi_facts`, as the compiler sees the header at `header_path`."""
+    names = ['template <> const char* struct_name<%s>() { return "%s"; }' % (s, s) for s in header.structs]
+    body = ['std::printf("macro %s|%%lld\\n", (long long)%s);' % (m, m) for m in header.macros]
+    for s, cls in header.structs.items():
+        body.append('std::printf("struct %s|%%zu %%zu\\n", sizeof(%s), alignof(%s));' % (s, s, s))
+        body += ['std::printf("field %s.%s|%%zu %%zu\\n", offsetof(%s, %s), sizeof(%s::%s));' % (s, f, s, f, s, f) for f, _ in cls._fields_]
+    body += ['signature<decltype(&%s)>::print("%s");' % (f, f) for f in header.functions]        # unevaluated: nothing to link
+    return _PROBE % dict(header=header_path, names="\n".join(names), body="\n".join("    " + b for b in body))
+
+
+def _compiler_facts(header, header_path, workdir):
     import shutil
     import subprocess
-    import tempfile
-    sizes = (ctypes.sizeof(lib.GemmDesc), ctypes.sizeof(lib.ConvDesc), ctypes.sizeof(lib.AttnKV), ctypes.sizeof(lib.AttnDesc),
-             ctypes.sizeof(lib.AdaLNJob), ctypes.sizeof(lib.SchedDesc))
-    assert all(s % 8 == 0 for s in sizes) and sizes[2] == 56
-    if shutil.which("gcc"):      # ask the C compiler itself
-        with tempfile.TemporaryDirectory() as td:
-            src = os.path.join(td, "sz.c")
-            open(src, "w").write('#include <stdio.h>\n#include "%s"\nint main(){printf("%%zu %%zu %%zu %%zu %%zu %%zu", sizeof(iir_gemm_desc),'
-                                 'sizeof(iir_conv_desc), sizeof(iir_attn_kv), sizeof(iir_attn_desc), sizeof(iir_adaln_job),'
-                                 'sizeof(iir_sched_desc));}' % lib.HEADER_PATH)
-            subprocess.run(["gcc", src, "-o", os.path.join(td, "sz")], check=True)
-            out = subprocess.run([os.path.join(td, "sz")], capture_output=True, text=True, check=True).stdout
-        assert tuple(int(x) for x in out.split()) == sizes
+    import pytest
+    rocm_clang = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
+    cxx = shutil.which("g++") or shutil.which("c++") or (rocm_clang if os.path.exists(rocm_clang) else None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler (g++, c++ or ROCm's clang++) to ask about the header's layout")
+    src, exe = os.path.join(workdir, "abi_probe.cpp"), os.path.join(workdir, "abi_probe")
+    with open(src, "w") as f:
+        f.write(_probe_source(header, header_path))
+    subprocess.run([cxx, "-std=c++17", src, "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
+    return dict(line.split("|") for line in out.splitlines())
+
+
+def test_derived_binding_matches_the_compiler(tmp_path):
+    """Everything the binding derives from the header, against a host C++ compiler that includes the same header: sizeof and
+    alignof of every struct, offsetof and sizeof of every field, the class and size of every return value and parameter (and the
+    struct behind a struct pointer), the value of every macro.  A field or function the header lacks fails at compile time."""
+    header = lib.HEADER
+    derived = _abi_facts(header)
+    assert len(header.structs) >= 8 and len(header.functions) >= 62 and len(header.macros) >= 27 and len(derived) > 600
+    assert all(ctypes.sizeof(s) % 8 == 0 for s in header.structs.values()) and ctypes.sizeof(lib.AttnKV) == 56
+    compiled = _compiler_facts(header, lib.HEADER_PATH, str(tmp_path))
+    assert {k: (v, compiled.get(k)) for k, v in derived.items() if v != compiled.get(k)} == {}
+    assert sorted(derived) == sorted(compiled)
+    # the names the package exports are those classes and values
+    exported = dict(iir_attn_kv=lib.AttnKV, iir_gemm_desc=lib.GemmDesc, iir_conv_desc=lib.ConvDesc, iir_attn_desc=lib.AttnDesc,
+                    iir_adaln_job=lib.AdaLNJob, iir_sched_desc=lib.SchedDesc, IirResampleDesc=lib.ResampleDesc,
+                    iir_metrics_desc=lib.MetricsDesc)
+    assert list(header.structs) == list(exported) and all(header.structs[n] is exported[n] for n in exported)
+    assert lib.MACROS is header.macros and sorted(lib.SIGNATURES) == sorted(header.functions)
+
+
+def test_signatures_follow_the_type_rule_but_for_device_tables():
+    """lib.SIGNATURES is the header's prototypes under cheader's type rule.  lib.DEVICE_TABLES, the one exception, names
+    parameters the header has, each a pointer to a declared struct that the rule alone binds as POINTER(struct); there the
+    binding takes an integer device address."""
+    import pytest
+    assert lib.DEVICE_TABLES == {("iir_adaln_batch_f16", "jobs_dev")}
+    seen = set()
+    for fn, (restype, params) in lib.HEADER.functions.items():
+        bound_ret, bound = lib.SIGNATURES[fn]
+        assert bound_ret is restype and len(bound) == len(params), fn
+        for (param, ct), b in zip(params, bound):
+            if (fn, param) in lib.DEVICE_TABLES:
+                seen.add((fn, param))
+                assert ct is ctypes.POINTER(lib.AdaLNJob) and b is ctypes.c_void_p, (fn, param)
+                b.from_param(0x7F0000001000)
+                with pytest.raises(TypeError):
+                    ct.from_param(0x7F0000001000)
+            else:
+                assert b is ct, (fn, param)
+    assert seen == lib.DEVICE_TABLES
+
+
+def _mutated_facts(tmp_path, old, new):
+    from instantir_amd import cheader
+    text = open(lib.HEADER_PATH).read()
+    assert text.count(old) == 1
+    path = tmp_path / "mutated.h"
+    path.write_text(text.replace(old, new))
+    real, mutated = _abi_facts(lib.HEADER), _abi_facts(cheader.parse_file(str(path)))
+    assert sorted(real) == sorted(mutated)
+    return {k: (real[k], mutated[k]) for k in real if real[k] != mutated[k]}
+
+
+def test_swapped_fields_change_exactly_their_offsets(tmp_path):
+    """Two adjacent int32_t fields of iir_gemm_desc swapped in a copy of the header: the facts the compiler is asked about differ
+    in those two offsets and nowhere else, so the comparison above sees such a swap."""
+    diff = _mutated_facts(tmp_path, "int32_t epi, act;\n    float out_scale;               /* 0 means 1",
+                          "int32_t act, epi;\n    float out_scale;               /* 0 means 1")
+    epi, act = lib.GemmDesc.epi.offset, lib.GemmDesc.act.offset
+    assert act == epi + 4
+    assert diff == {"field iir_gemm_desc.epi": ("%d 4" % epi, "%d 4" % act), "field iir_gemm_desc.act": ("%d 4" % act, "%d 4" % epi)}
+
+
+def test_widened_parameter_changes_exactly_its_type(tmp_path):
+    """One int32_t parameter of iir_layernorm_f16 declared int64_t in a copy of the header: one fact differs."""
+    diff = _mutated_facts(tmp_path, "int32_t rows, int32_t C, const void* gamma,\n                      const void* beta",
+                          "int64_t rows, int32_t C, const void* gamma,\n                      const void* beta")
+    assert diff == {"type iir_layernorm_f16 4": ("signed 4 -", "signed 8 -")}
 
 
 def test_invalid_arguments_are_rejected_without_a_gpu():
