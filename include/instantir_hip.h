@@ -611,6 +611,57 @@ int iir_add_gaussian_noise_f32(const float* in, const float* sigma, int32_t N, i
 int iir_jpeg_roundtrip_f32(const float* in, const float* quality, int32_t N, int32_t C, int32_t H, int32_t W, float* out,
                            void* stream);
 
+/* LPIPS v0.1, net = vgg: the perceptual distance the reference builds as `lpips.LPIPS(net='vgg')` at losses/losses.py:81-95,
+ * on the device; contract here and in DESIGN.md section 7 "LPIPS".  The thirteen 3x3 convs of VGG-16 `features` run through
+ * iir_conv2d_nhwc_f16 with a bias and IIR_ACT_NONE on an (a, b) pair stacked as one batch; the three entries below are what
+ * lies between those convs.  16-bit tensors are fp16 or bf16 by `dtype` (IIR_DT_*), NHWC rows; all arithmetic is fp32 unless
+ * stated.  All three: every global load is unconditional from a clamped address and masked in registers, only stores are
+ * guarded, 64-bit offsets, no atomics, sums in a fixed order: equal inputs give equal bits.
+ *
+ * iir_lpips_prep (the scaling layer in front of the first conv, losses/losses.py:81-95): src is one of the sources of
+ *   iir_image_metrics, N images of 3 channels, fp32 planar (N, 3, H, W) on a [0, 1] scale or, with src_u8, uint8 interleaved
+ *   (N, H, W, 3).  x = u / 255 (one fp32 division) for uint8, the stored fp32 value otherwise, so a uint8 image and its fp32
+ *   copy give equal bits; then in fp64  s_c = ((2 x - 1) - affine[c]) / affine[3 + c]  with affine = device fp64[6]
+ *   {shift[3], scale[3]} (LPIPS: shift -0.030, -0.088, -0.188; scale 0.458, 0.448, 0.450), rounded to fp32 and then to the
+ *   16-bit type.  out: (N * H * W) rows of pixel stride ldo; columns [0, 3) receive s, columns [3, IIR_LPIPS_CPAD) zeros (the K
+ *   tile the conv's first layer reads), columns past that keep their bits.  The affine is NOT folded into the first conv: the
+ *   conv zero-pads in the scaled space.
+ *   IIR_EINVAL, before any HIP call: a NULL src, affine or out; N, H or W <= 0; H or W > 32768; ldo < IIR_LPIPS_CPAD or
+ *   ldo % 8; out not 16-byte aligned; another dtype; a grid beyond 31 bits; out overlapping src.
+ *
+ * iir_relu_f16 (the nn.ReLU after each conv that is neither tapped nor pooled, losses/losses.py:81-95): in place over the
+ *   (rows, C) matrix x of row stride ld; a negative value, -0 and -inf included, becomes +0, everything else (NaN too) keeps
+ *   its bits; columns [C, ld) are not touched.
+ *   IIR_EINVAL, before any HIP call: a NULL or not 16-byte aligned x; rows or C <= 0; C % 8; ld < C or ld % 8; another dtype;
+ *   a grid beyond 31 bits.
+ *
+ * iir_lpips_tap (one tap of losses/losses.py:81-95: nn.ReLU, normalize_tensor, the 1x1 `lin` layer, the spatial average; and
+ *   the nn.MaxPool2d(2, 2) the features go on through): x holds the tapped conv's PRE-activation rows (bias added, no ReLU)
+ *   of 2 * pairs images of H x W pixels and C channels, pixel stride ldx: images [0, pairs) are the `a` half, image
+ *   pairs + i is the `b` partner of image i.  Per pair and pixel p, with a = relu(x_a(p)), b = relu(x_b(p)):
+ *     ra = 1 / (sqrt(sum_c a_c^2) + 1e-10), rb likewise;  d(p) = sum_c lin_w[c] * (a_c * ra - b_c * rb)^2
+ *     out[pair] = (sum_p d(p)) / (H * W)                     (double[pairs])
+ *   so a pixel whose channels are all zero gives 0.  Products into sums are fmaf; a lane sums its 8 channels in index order,
+ *   the C / 8 lanes of a pixel add by a butterfly; d(p) of a 2x2 quad are added in fp32 in raster order, quads in fp64 (a
+ *   workgroup in a fixed order into ws, then a second launch over ws in index order).
+ *   dmap (optional): fp32 (pairs, H, W) receives d(p): LPIPS's spatial=True.
+ *   pooled (optional; H, W >= 2): (2 * pairs) images of (H / 2) x (W / 2) pixels (floor: an odd last row or column is scored
+ *   and not pooled), pixel stride ldp, stacked as x is: the channel-wise maximum of relu(x) over each 2x2 quad, exact.  It is
+ *   formed from the registers the distance was formed from: a tapped activation is read once.
+ *   lin_w: device fp32[C].  ws: iir_lpips_tap_workspace_bytes(pairs, H, W, C) bytes, 8-byte aligned (-1 for a geometry this
+ *   entry refuses).
+ *   IIR_EINVAL, before any HIP call: a NULL x, lin_w, ws or out; pairs, H, W or C <= 0; pairs > 65535; H or W > 32768;
+ *   C % 8 or C > IIR_LPIPS_MAX_C; ldx < C or ldx % 8; x not 16-byte aligned; pooled with H or W < 2, ldp < C, ldp % 8 or not
+ *   16-byte aligned; ws too small or ws / out not 8-byte aligned; another dtype; pooled or dmap overlapping x. */
+#define IIR_LPIPS_CPAD 64
+#define IIR_LPIPS_MAX_C 512
+int iir_lpips_prep(const void* src, int32_t src_u8, int32_t N, int32_t H, int32_t W, const double* affine, void* out, int64_t ldo,
+                   int32_t dtype, void* stream);
+int iir_relu_f16(void* x, int64_t ld, int64_t rows, int32_t C, int32_t dtype, void* stream);
+int64_t iir_lpips_tap_workspace_bytes(int32_t pairs, int32_t H, int32_t W, int32_t C);
+int iir_lpips_tap(const void* x, int64_t ldx, int32_t pairs, int32_t H, int32_t W, int32_t C, const float* lin_w, int32_t dtype,
+                  float* dmap, void* pooled, int64_t ldp, void* ws, int64_t ws_bytes, double* out, void* stream);
+
 int iir_transpose_f16(const void* in, int64_t ldi, int32_t rows, int32_t cols, void* out, int64_t ldo, int32_t rows_pad,
                       void* stream);
 /* Measurement hook (bench.py roofline leg; no reference counterpart): arm a start/stop event pair and the NEXT

@@ -15,6 +15,7 @@ seeded embeddings because no tokenizer vocabulary exists here.  `--apg ETA NORM_
 guidance on (`pipe.enable_apg(...)`: the CFG update's saturating parallel part down-weighted, its norm clamped, with momentum).
 `--gt_path DIR` scores every saved image against the file of the same name in DIR (PSNR / SSIM on the device,
 `instantir_amd.metrics`), `--input_fidelity` against its own input file; the figures go to `metrics.json` in the output directory.
+`--lpips_path PATH [--lpips_lin_path PATH]` adds LPIPS (VGG-16, `instantir_amd.lpips`) to each scored pair.
 `--degrade PRESET_OR_JSON [--degrade_seed N]` treats the files of `--test_path` as clean images: each is degraded on the device
 (`instantir_amd.degrade`), the 8-bit result stands in for the file that was read and is saved with its recipe under `lq/` in the
 output directory, and unless told otherwise the run scores its restorations against the clean files.
@@ -185,6 +186,11 @@ def build_parser():
     p.add_argument("--input_fidelity", action="store_true",
                    help="score every saved image, resized to its input's size (bicubic), against the input file as it was read: "
                         "how far the restoration moved from what it was given; needs no ground truth")
+    p.add_argument("--lpips_path", type=str, default=None, metavar="PATH",
+                   help="add LPIPS (VGG-16) to every pair --gt_path / --input_fidelity score: a whole lpips.LPIPS state dict, or a "
+                        "torchvision VGG-16 state dict together with --lpips_lin_path (instantir_amd.lpips)")
+    p.add_argument("--lpips_lin_path", type=str, default=None, metavar="PATH",
+                   help="the lin layers of LPIPS (lpips' vgg.pth) when --lpips_path is a torchvision VGG-16 state dict")
     p.add_argument("--degrade", type=str, default=None, metavar="PRESET_OR_JSON",
                    help="the files of --test_path are clean images: degrade each on the device first, with a recipe sampled from "
                         "the preset (realesrgan, bicubic) per (--degrade_seed, file name) or read from a recipe JSON file; the "
@@ -254,6 +260,32 @@ def apply_metrics(args):
     return {"gt_path": gt, "input_fidelity": fidelity, "metrics": names, "y_channel": y, "crop_border": int(crop or 0)}
 
 
+def apply_lpips(args):
+    """`--lpips_path PATH [--lpips_lin_path PATH]` -> {"path", "lin_path"}, or None without the flag (an addition: the reference
+    builds LPIPS for training only, losses/losses.py:81-95).  Refused: the lin file without the flag, the flag without a
+    comparison to add the figure to, and a file that does not exist."""
+    path, lin = getattr(args, "lpips_path", None), getattr(args, "lpips_lin_path", None)
+    if path is None:
+        if lin is not None:
+            raise SystemExit("--lpips_lin_path needs --lpips_path")
+        return None
+    if getattr(args, "gt_path", None) is None and not getattr(args, "input_fidelity", False):
+        raise SystemExit("--lpips_path needs --gt_path or --input_fidelity")
+    for flag, f in (("--lpips_path", path), ("--lpips_lin_path", lin)):
+        if f is not None and not os.path.isfile(f):
+            raise SystemExit(f"{flag} {f} is not a file")
+    return {"path": path, "lin_path": lin}
+
+
+def build_lpips(setup, device):
+    """The LPIPS model of `apply_lpips`' settings on `device`; a file that is not one of the two formats ends the run."""
+    from .lpips import LPIPS
+    try:
+        return LPIPS.from_files(setup["path"], setup["lin_path"], device=device)
+    except ValueError as e:
+        raise SystemExit(f"--lpips_path: {e}")
+
+
 def gt_image(setup, name, size):
     """The ground truth of input `name` at `size` = (width, height); a missing file or another size ends the run, naming it."""
     path = os.path.join(setup["gt_path"], name)
@@ -265,12 +297,14 @@ def gt_image(setup, name, size):
     return im
 
 
-def score_saved(setup, saved_path, gt, original, device):
+def score_saved(setup, saved_path, gt, original, device, lpips_model=None):
     """The figures of one saved file, from the 8-bit image as it was saved (read back): {"psnr", "ssim"} against `gt`,
-    {"input_psnr", "input_ssim"} against `original`, whichever were asked for."""
+    {"input_psnr", "input_ssim"} against `original`, whichever were asked for; with an `lpips_model` "lpips" / "input_lpips" too."""
     from . import metrics as M
     saved = Image.open(saved_path).convert("RGB")
     kw = dict(metrics=setup["metrics"], crop_border=setup["crop_border"], y_channel=setup["y_channel"], device=device)
+    if lpips_model is not None:
+        kw["lpips_model"] = lpips_model
     row = {}
     try:
         if gt is not None:
@@ -447,7 +481,9 @@ def main(args, device, rank=0, world=1):
     apply_device_resize(None, args)              # (a flag error should not wait for the weights to load)
     degrading = apply_degrade(args)              # (before apply_metrics: it may set --gt_path)
     scoring = apply_metrics(args)
+    lpips_setup = apply_lpips(args)
     pipe, lcm_scheduler = build_pipeline(args, device)
+    lpips_model = build_lpips(lpips_setup, device) if lpips_setup else None
     apply_freeu(pipe, args)
     apply_scheduler(pipe, args)
     pag_kw = apply_pag(pipe, args)
@@ -513,9 +549,9 @@ def main(args, device, rank=0, world=1):
             rec.save(f"{out_dir}/{lq_batch[i]}")
             if scoring:
                 scores[lq_batch[i]] = score_saved(scoring, f"{out_dir}/{lq_batch[i]}", gts[i] if gts else None,
-                                                  originals[i] if scoring["input_fidelity"] else None, device)
+                                                  originals[i] if scoring["input_fidelity"] else None, device, lpips_model)
     if scoring:
-        print(write_metrics(scoring, scores, out_dir, rank, world))
+        print(write_metrics(dict(scoring, lpips=lpips_setup) if lpips_setup else scoring, scores, out_dir, rank, world))
 
 
 if __name__ == "__main__":

@@ -155,17 +155,37 @@ def _with_means(res):
     return res
 
 
-def evaluate(a, b, metrics=METRICS, crop_border=0, y_channel=False, quantize=False, device=None):
+def _lpips_scores(who, a, b, model, device):
+    d = None if device is None else torch.device(device)
+    if d is not None and (d.type != model.device.type or (d.index is not None and d.index != model.device.index)):
+        raise ValueError(f"{who}: the LPIPS model lives on {model.device}, not on {d}")
+    return model(a, b).cpu().tolist()
+
+
+def lpips(a, b, model, device=None):
+    """LPIPS of `a` against `b` under `model` (an `instantir_amd.lpips.LPIPS`; DESIGN.md section 7 "LPIPS"): a float for one
+    image, a list of floats for a batch; 0 for identical images.  The whole image is scored: LPIPS has no crop, luma or
+    quantise option."""
+    _, single_a = _host_source(a, "a")
+    _, single_b = _host_source(b, "b")
+    out = _lpips_scores("lpips", a, b, model, device)
+    return out[0] if single_a and single_b else out
+
+
+def evaluate(a, b, metrics=METRICS, crop_border=0, y_channel=False, quantize=False, device=None, lpips_model=None):
     """Both figures in one launch pair: {"psnr": [per image], "ssim": [per image], "psnr_mean": .., "ssim_mean": ..} (only the
-    metrics asked for).  `quantize` (a flag, or one per argument) rounds a float source to the 8-bit image that would be saved."""
+    metrics asked for).  `quantize` (a flag, or one per argument) rounds a float source to the 8-bit image that would be saved.
+    With an `lpips_model` the result gains "lpips" and "lpips_mean" (of the whole, uncropped RGB images)."""
     res, _ = _run("evaluate", a, b, metrics, crop_border, y_channel, quantize, device)
+    if lpips_model is not None:
+        res["lpips"] = _lpips_scores("evaluate", a, b, lpips_model, device)
     return _with_means(res)
 
 
-def input_fidelity(restored, lq, filter="bicubic", metrics=METRICS, crop_border=0, y_channel=False, device=None):
+def input_fidelity(restored, lq, filter="bicubic", metrics=METRICS, crop_border=0, y_channel=False, device=None, lpips_model=None):
     """How far the restoration moved from what it was given: `restored` is brought to the size of `lq` with `ops.resample`
     (PIL's `filter`; quantised mode when both are 8-bit, untouched at equal sizes) and scored against `lq`.  Returns what
-    `evaluate` returns."""
+    `evaluate` returns ("lpips" included when an `lpips_model` is given: of the resized restoration against `lq`)."""
     from . import ops
     from .resample import FILTERS
     if filter not in FILTERS:
@@ -186,4 +206,7 @@ def input_fidelity(restored, lq, filter="bicubic", metrics=METRICS, crop_border=
             tr = ops.resample(tr.to(dev).contiguous(), dl[2:], filter, clamp=(0.0, 1.0))
         quantize = (both_u8, False)
     _check_pair("input_fidelity", tr, tl, names, crop_border, y_channel, arg_b="lq")
-    return _with_means(_score(tr, tl, names, crop_border, y_channel, quantize, dev if dev is not None else device))
+    res = _score(tr, tl, names, crop_border, y_channel, quantize, dev if dev is not None else device)
+    if lpips_model is not None:
+        res["lpips"] = _lpips_scores("input_fidelity", tr, tl, lpips_model, device)
+    return _with_means(res)

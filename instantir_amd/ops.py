@@ -1262,3 +1262,130 @@ def jpeg_roundtrip(x, quality, out=None):
     q = q.to(x.device)
     L.check(L.load().iir_jpeg_roundtrip_f32(x.data_ptr(), q.data_ptr(), N, Cc, H, W, out.data_ptr(), _stream()), "iir_jpeg_roundtrip_f32")
     return out
+
+
+LPIPS_CPAD = L.MACROS["IIR_LPIPS_CPAD"]           # channels of the prepared image: the K tile the first conv reads
+LPIPS_MAX_C = L.MACROS["IIR_LPIPS_MAX_C"]         # widest tap one wave holds
+LPIPS_SHIFT = (-0.030, -0.088, -0.188)            # the scaling layer of LPIPS v0.1
+LPIPS_SCALE = (0.458, 0.448, 0.450)
+
+
+def _chk_rows16(who, name, t, rows, cols):
+    """2-D fp16 / bf16 view of exactly `rows` rows and at least `cols` unit-stride columns whose rows a 16-byte access may address."""
+    _refuse(who, torch.is_tensor(t) and t.dim() == 2 and t.dtype in _DT and t.stride(1) == 1 and t.shape[0] == rows and t.shape[1] >= cols
+            and t.stride(0) % 8 == 0 and t.stride(0) >= cols,
+            f"{name} must be a 2-D fp16 / bf16 view of {rows} rows and at least {cols} unit-stride columns with a row stride that is a "
+            f"multiple of 8, got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} {t.stride() if torch.is_tensor(t) else ()}")
+    _refuse(who, not t.is_cuda or t.data_ptr() % 16 == 0, f"{name} must be 16-byte aligned")
+
+
+def lpips_affine(device, shift=LPIPS_SHIFT, scale=LPIPS_SCALE):
+    """The scaling layer as iir_lpips_prep reads it: fp64 (6,) = {shift[3], scale[3]} on `device`."""
+    vals = [float(v) for v in tuple(shift) + tuple(scale)]
+    if len(vals) != 6 or not all(v == v and abs(v) != float("inf") for v in vals) or any(v == 0.0 for v in vals[3:]):
+        raise ValueError(f"lpips_affine: shift and scale must hold 3 finite values each, no scale 0, got {shift!r} {scale!r}")
+    return torch.tensor(vals, dtype=torch.float64, device=device)
+
+
+def lpips_prep(src, out, affine=None):
+    """The scaling layer of LPIPS in front of VGG's first conv (iir_lpips_prep; DESIGN.md section 7 "LPIPS").  `src`: a contiguous
+    source of `image_metrics` with 3 channels, fp32 (N, 3, H, W) in [0, 1] or uint8 (N, H, W, 3).  `out`: 2-D fp16 / bf16 view of
+    N * H * W rows and at least LPIPS_CPAD columns: columns [0, 3) receive ((2 x - 1) - shift) / scale, [3, LPIPS_CPAD) zeros.
+    `affine`: `lpips_affine(...)` (LPIPS's constants when absent)."""
+    who = "lpips_prep"
+    if not torch.is_tensor(src) or src.dim() != 4 or src.dtype not in (torch.float32, torch.uint8) or not src.is_contiguous():
+        raise ValueError(f"{who}: src must be a contiguous 4-D tensor, fp32 (N, 3, H, W) in [0, 1] or uint8 (N, H, W, 3), got "
+                         f"{getattr(src, 'dtype', type(src))} {tuple(getattr(src, 'shape', ()))}")
+    u8 = src.dtype == torch.uint8
+    N, Cc, H, W = (tuple(src.shape[i] for i in (0, 3, 1, 2)) if u8 else tuple(src.shape))
+    _refuse(who, Cc == 3, f"src must have 3 channels, got {Cc}")
+    _refuse(who, min(N, H, W) > 0 and max(H, W) <= 32768 and N * H * W * (LPIPS_CPAD // 8) <= 0x7fffffff * 256,
+            f"unsupported geometry N={N} H={H} W={W}")
+    _chk_rows16(who, "out", out, N * H * W, LPIPS_CPAD)
+    if affine is not None:
+        _refuse(who, torch.is_tensor(affine) and affine.dtype == torch.float64 and tuple(affine.shape) == (6,) and affine.is_contiguous(),
+                "affine must be a contiguous fp64 (6,) tensor {shift[3], scale[3]} (lpips_affine)")
+    _chk_cuda(who, src, out, *(() if affine is None else (affine,)))
+    if affine is None:
+        affine = lpips_affine(src.device)
+    L.check(L.load().iir_lpips_prep(src.data_ptr(), int(u8), N, H, W, affine.data_ptr(), out.data_ptr(), out.stride(0), _DT[out.dtype],
+                                    _stream()), "iir_lpips_prep")
+    return out
+
+
+def relu_(x):
+    """In-place ReLU of a 2-D fp16 / bf16 view (iir_relu_f16): a negative value becomes +0, NaN stays; columns % 8 == 0."""
+    who = "relu_"
+    _refuse(who, torch.is_tensor(x) and x.dim() == 2 and min(x.shape) > 0, f"x must be a non-empty 2-D tensor, got {tuple(getattr(x, 'shape', ()))}")
+    rows, Cc = x.shape
+    _refuse(who, Cc % 8 == 0, f"the column count must be a multiple of 8, got {Cc}")
+    _chk_rows16(who, "x", x, rows, Cc)
+    _chk_cuda(who, x)
+    L.check(L.load().iir_relu_f16(x.data_ptr(), x.stride(0), rows, Cc, _DT[x.dtype], _stream()), "iir_relu_f16")
+    return x
+
+
+def _chk_tap_geometry(who, pairs, H, W, Cc):
+    for name, v in (("pairs", pairs), ("H", H), ("W", W)):
+        _refuse(who, not isinstance(v, bool) and isinstance(v, int) and v > 0, f"{name} must be a positive integer, got {v!r}")
+    _refuse(who, pairs <= 65535 and max(H, W) <= 32768, f"unsupported geometry pairs={pairs} H={H} W={W} (pairs <= 65535, sides <= 32768)")
+    _refuse(who, Cc > 0 and Cc % 8 == 0 and Cc <= LPIPS_MAX_C, f"the channel count must be a multiple of 8 up to {LPIPS_MAX_C}, got {Cc}")
+
+
+def lpips_tap_workspace_bytes(pairs, H, W, C):
+    """Bytes of fp64 partial sums `lpips_tap` needs for `pairs` image pairs of H x W pixels and C channels."""
+    _chk_tap_geometry("lpips_tap_workspace_bytes", pairs, H, W, C)
+    need = L.load().iir_lpips_tap_workspace_bytes(pairs, H, W, C)
+    _refuse("lpips_tap_workspace_bytes", need >= 0, f"unsupported geometry pairs={pairs} H={H} W={W} C={C}")
+    return int(need)
+
+
+def lpips_tap(x, pairs, H, W, lin_w, pooled=None, dmap=None, ws=None, out=None):
+    """One LPIPS tap (iir_lpips_tap; DESIGN.md section 7 "LPIPS").  `x`: 2-D fp16 / bf16 view of 2 * pairs * H * W rows, the
+    pre-activation output of the tapped conv for the `a` images followed by their `b` partners; its column count C is the tap's
+    width.  `lin_w`: fp32 (C,), the 1x1 `lin` layer.  Returns fp64 (pairs,): the mean over pixels of
+    sum_c lin_w[c] (a^_c - b^_c)^2 on the unit-normalised ReLU outputs.  `dmap`: fp32 (pairs, H, W) that receives the per-pixel
+    term; `pooled`: 2-D view of 2 * pairs * (H // 2) * (W // 2) rows and C columns that receives the 2x2 max-pooled ReLU output;
+    `ws`: a byte workspace of at least `lpips_tap_workspace_bytes` (allocated here when absent)."""
+    who = "lpips_tap"
+    _refuse(who, torch.is_tensor(x) and x.dim() == 2, f"x must be a 2-D tensor, got {tuple(getattr(x, 'shape', ()))}")
+    Cc = x.shape[1]
+    _chk_tap_geometry(who, pairs, H, W, Cc)
+    _chk_rows16(who, "x", x, 2 * pairs * H * W, Cc)
+    _refuse(who, torch.is_tensor(lin_w) and lin_w.dtype == torch.float32 and tuple(lin_w.shape) == (Cc,) and lin_w.is_contiguous(),
+            f"lin_w must be a contiguous fp32 ({Cc},) tensor, got {getattr(lin_w, 'dtype', type(lin_w))} {tuple(getattr(lin_w, 'shape', ()))}")
+    tensors = [x, lin_w]
+    if pooled is not None:
+        _refuse(who, min(H, W) >= 2, f"a {H}x{W} tap has no 2x2 quad to pool")
+        _chk_rows16(who, "pooled", pooled, 2 * pairs * (H // 2) * (W // 2), Cc)
+        _refuse(who, pooled.dtype == x.dtype and pooled.shape[1] == Cc, f"pooled must have x's dtype and {Cc} columns")
+        tensors.append(pooled)
+    if dmap is not None:
+        _refuse(who, torch.is_tensor(dmap) and dmap.dtype == torch.float32 and tuple(dmap.shape) == (pairs, H, W) and dmap.is_contiguous(),
+                f"dmap must be a contiguous fp32 ({pairs}, {H}, {W}) tensor")
+        tensors.append(dmap)
+    if out is not None:
+        _refuse(who, torch.is_tensor(out) and out.dtype == torch.float64 and tuple(out.shape) == (pairs,) and out.is_contiguous(),
+                f"out must be a contiguous fp64 ({pairs},) tensor")
+        tensors.append(out)
+    _chk_cuda(who, *tensors)
+    lo_x, hi_x = x.data_ptr(), x.data_ptr() + x.shape[0] * x.stride(0) * 2          # whole rows, as the entry counts them
+    for name, t in (("pooled", pooled), ("dmap", dmap)):
+        if t is not None:
+            nbytes = t.shape[0] * t.stride(0) * 2 if t is pooled else t.numel() * 4
+            _refuse(who, not (t.data_ptr() < hi_x and lo_x < t.data_ptr() + nbytes), f"{name} overlaps x (other pixels of x are still to be read)")
+    h = L.load()
+    need = h.iir_lpips_tap_workspace_bytes(pairs, H, W, Cc)
+    _refuse(who, need >= 0, f"unsupported geometry pairs={pairs} H={H} W={W} C={Cc}")
+    if ws is None:
+        ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
+    else:
+        _refuse(who, torch.is_tensor(ws) and ws.is_cuda and ws.device == x.device and ws.is_contiguous()
+                and ws.numel() * ws.element_size() >= need and ws.data_ptr() % 8 == 0,
+                f"ws needs {need} contiguous, 8-byte aligned bytes on x's device")
+    if out is None:
+        out = torch.empty(pairs, dtype=torch.float64, device=x.device)
+    L.check(h.iir_lpips_tap(x.data_ptr(), x.stride(0), pairs, H, W, Cc, lin_w.data_ptr(), _DT[x.dtype], _p(dmap), _p(pooled),
+                            0 if pooled is None else pooled.stride(0), ws.data_ptr(), ws.numel() * ws.element_size(), out.data_ptr(),
+                            _stream()), "iir_lpips_tap")
+    return out
