@@ -662,6 +662,42 @@ int64_t iir_lpips_tap_workspace_bytes(int32_t pairs, int32_t H, int32_t W, int32
 int iir_lpips_tap(const void* x, int64_t ldx, int32_t pairs, int32_t H, int32_t W, int32_t C, const float* lin_w, int32_t dtype,
                   float* dmap, void* pooled, int64_t ldp, void* ws, int64_t ws_bytes, double* out, void* stream);
 
+/* NIQE (Mittal et al. 2013, as basicsr's calculate_niqe restates the MATLAB release), the device part: the per-block signed
+ * moments of the luma's natural-scene statistics at two scales; no reference counterpart, contract here and in DESIGN.md
+ * section 7 "NIQE".  The AGGD fit, the 36 features per block, the Gaussian model and the distance are the host's, in fp64
+ * (instantir_amd/niqe.py).
+ *   src: one of the sources of iir_image_metrics: N images of C in {1, 3} channels, fp32 planar (N, C, H, W) on a [0, 1] scale
+ *     or, with src_u8, uint8 interleaved (N, H, W, C).  crop_border = c >= 0 drops c pixels on every side: H' = H - 2c,
+ *     W' = W - 2c.  C = 3 becomes Y = 16 + (65.481 R + 128.553 G + 24.966 B) / 255 with R, G, B in 0..255 units (the fp32
+ *     operations of iir_image_metrics' y_channel), C = 1 is taken as grey; the grey value is then rounded to
+ *     min(max(floor(v + 0.5), 0), 255), and all arithmetic from here is in 0..255 units.
+ *   Block grid: nbh = H' / 96, nbw = W' / 96 (floor); the image is the top-left (96 nbh) x (96 nbw) part of the cropped image.
+ *     Nothing below sees a pixel outside that part, and no such pixel is read.
+ *   Scale 2: the half-size image by MATLAB's imresize(., 0.5) (bicubic, antialiased), which at this factor is the separable
+ *     filter [-3, -9, 29, 111, 111, 29, -9, -3] / 256: output o of an axis reads inputs 2o - 3 .. 2o + 4 at symmetric indices
+ *     (-1 - i for i < 0, 2n - 1 - i for i >= n), along y first and then along x, taps in index order, fmaf from 0, neither
+ *     rounded nor clipped.  Its blocks are 48 x 48 on the same grid.
+ *   MSCN, per scale: g_j = exp(-(j - 3)^2 / (2 (7/6)^2)), j = 0..6, normalised to sum 1 in fp64 and rounded to fp32;
+ *     mu = G * x, sigma = sqrt(|G * x^2 - mu^2|) with the window applied along x then y (taps in index order, fmaf from 0) and
+ *     replicate padding at the edge of the block-grid image; m = (x - mu) / (sigma + 1).  Both moments are taken about 128,
+ *     which m does not see.
+ *   Per block, five maps: v0 = m and v1..v4 = m * roll(m, s), s = (0, 1), (1, 0), (1, 1), (1, -1) in (row, column), roll the
+ *     circular shift within the block (numpy.roll).  Of each map, in this order: the count of v < 0, the count of v > 0, the sum
+ *     of v^2 over v < 0, the sum of v^2 over v > 0, the sum of |v|; exact zeros are in neither count.  The 26th value is the
+ *     block's sum of sigma.
+ *   out: double[N][2][nbh * nbw][IIR_NIQE_STATS], scale 1 first, blocks in raster order; out_bytes its size.
+ *   ws: iir_niqe_workspace_bytes(N, C, H, W, crop_border) bytes, 8-byte aligned: the two grey planes (-1 for a geometry this
+ *     entry refuses).
+ * A thread sums at most 24 values per statistic in fp32, then fp64 in a fixed order; counts are integers.  No atomics: equal
+ * inputs give equal bits, and an image's figures do not depend on N.
+ * IIR_EINVAL, before any HIP call: a NULL src, ws or out; N, C, H or W <= 0; H or W > 32768; C not 1 or 3; crop_border < 0;
+ * H' or W' < IIR_NIQE_BLOCK; N > 65535 or a grid beyond 31 bits; ws or out too small or not 8-byte aligned. */
+#define IIR_NIQE_BLOCK 96
+#define IIR_NIQE_STATS 26
+int64_t iir_niqe_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop_border);
+int iir_niqe_stats(const void* src, int32_t src_u8, int32_t N, int32_t C, int32_t H, int32_t W, int32_t crop_border, void* ws,
+                   int64_t ws_bytes, double* out, int64_t out_bytes, void* stream);
+
 int iir_transpose_f16(const void* in, int64_t ldi, int32_t rows, int32_t cols, void* out, int64_t ldo, int32_t rows_pad,
                       void* stream);
 /* Measurement hook (bench.py roofline leg; no reference counterpart): arm a start/stop event pair and the NEXT

@@ -16,6 +16,7 @@ guidance on (`pipe.enable_apg(...)`: the CFG update's saturating parallel part d
 `--gt_path DIR` scores every saved image against the file of the same name in DIR (PSNR / SSIM on the device,
 `instantir_amd.metrics`), `--input_fidelity` against its own input file; the figures go to `metrics.json` in the output directory.
 `--lpips_path PATH [--lpips_lin_path PATH]` adds LPIPS (VGG-16, `instantir_amd.lpips`) to each scored pair.
+`--niqe_path PARAMS` scores every saved image with NIQE (`instantir_amd.niqe`), which needs no second image.
 `--degrade PRESET_OR_JSON [--degrade_seed N]` treats the files of `--test_path` as clean images: each is degraded on the device
 (`instantir_amd.degrade`), the 8-bit result stands in for the file that was read and is saved with its recipe under `lq/` in the
 output directory, and unless told otherwise the run scores its restorations against the clean files.
@@ -191,6 +192,10 @@ def build_parser():
                         "torchvision VGG-16 state dict together with --lpips_lin_path (instantir_amd.lpips)")
     p.add_argument("--lpips_lin_path", type=str, default=None, metavar="PATH",
                    help="the lin layers of LPIPS (lpips' vgg.pth) when --lpips_path is a torchvision VGG-16 state dict")
+    p.add_argument("--niqe_path", type=str, default=None, metavar="PARAMS",
+                   help="score every saved image with NIQE (no ground truth needed) under the pristine model in PARAMS: basicsr's "
+                        "niqe_pris_params.npz, the MATLAB release's .mat, or `python -m instantir_amd.niqe fit`'s output; with "
+                        "--input_fidelity the input file is scored too (input_niqe); --metrics_crop applies")
     p.add_argument("--degrade", type=str, default=None, metavar="PRESET_OR_JSON",
                    help="the files of --test_path are clean images: degrade each on the device first, with a recipe sampled from "
                         "the preset (realesrgan, bicubic) per (--degrade_seed, file name) or read from a recipe JSON file; the "
@@ -249,7 +254,7 @@ def apply_metrics(args):
     names, y, crop = getattr(args, "metrics", None), bool(getattr(args, "metrics_y", False)), getattr(args, "metrics_crop", None)
     if gt is None and not fidelity:
         for flag, on in (("--metrics", names is not None), ("--metrics_y", y), ("--metrics_crop", crop is not None)):
-            if on:
+            if on and not (flag == "--metrics_crop" and getattr(args, "niqe_path", None) is not None):
                 raise SystemExit(f"{flag} needs --gt_path or --input_fidelity")
         return None
     if crop is not None and crop < 0:
@@ -275,6 +280,43 @@ def apply_lpips(args):
         if f is not None and not os.path.isfile(f):
             raise SystemExit(f"{flag} {f} is not a file")
     return {"path": path, "lin_path": lin}
+
+
+def apply_niqe(args):
+    """`--niqe_path PARAMS` -> {"path", "crop_border", "input"}, or None without the flag (an addition: the reference reports no
+    figures).  NIQE needs no comparison: the flag stands on its own, takes `--metrics_crop`, and with `--input_fidelity` scores
+    the input file as well.  Refused: a file that does not exist, a negative crop."""
+    path = getattr(args, "niqe_path", None)
+    if path is None:
+        return None
+    if not os.path.isfile(path):
+        raise SystemExit(f"--niqe_path {path} is not a file")
+    crop = getattr(args, "metrics_crop", None)
+    if crop is not None and crop < 0:
+        raise SystemExit(f"--metrics_crop must be >= 0, got {crop}")
+    return {"path": path, "crop_border": int(crop or 0), "input": bool(getattr(args, "input_fidelity", False))}
+
+
+def build_niqe(setup):
+    """The pristine model of `apply_niqe`'s settings; a file that does not hold one ends the run."""
+    from .niqe import NIQE
+    try:
+        return NIQE.from_file(setup["path"])
+    except (ValueError, OSError) as e:
+        raise SystemExit(f"--niqe_path: {e}")
+
+
+def score_niqe(setup, model, saved_path, original, device):
+    """{"niqe"} of the saved file as it was saved (read back) and, when asked for, {"input_niqe"} of `original`."""
+    from . import metrics as M
+    row = {}
+    try:
+        row["niqe"] = M.niqe(Image.open(saved_path).convert("RGB"), model, crop_border=setup["crop_border"], device=device)
+        if setup["input"]:
+            row["input_niqe"] = M.niqe(original, model, crop_border=setup["crop_border"], device=device)
+    except ValueError as e:
+        raise SystemExit(f"{saved_path}: {e}")
+    return row
 
 
 def build_lpips(setup, device):
@@ -482,6 +524,8 @@ def main(args, device, rank=0, world=1):
     degrading = apply_degrade(args)              # (before apply_metrics: it may set --gt_path)
     scoring = apply_metrics(args)
     lpips_setup = apply_lpips(args)
+    niqe_setup = apply_niqe(args)
+    niqe_model = build_niqe(niqe_setup) if niqe_setup else None
     pipe, lcm_scheduler = build_pipeline(args, device)
     lpips_model = build_lpips(lpips_setup, device) if lpips_setup else None
     apply_freeu(pipe, args)
@@ -550,8 +594,15 @@ def main(args, device, rank=0, world=1):
             if scoring:
                 scores[lq_batch[i]] = score_saved(scoring, f"{out_dir}/{lq_batch[i]}", gts[i] if gts else None,
                                                   originals[i] if scoring["input_fidelity"] else None, device, lpips_model)
-    if scoring:
-        print(write_metrics(dict(scoring, lpips=lpips_setup) if lpips_setup else scoring, scores, out_dir, rank, world))
+            if niqe_setup:
+                scores.setdefault(lq_batch[i], {}).update(score_niqe(niqe_setup, niqe_model, f"{out_dir}/{lq_batch[i]}", originals[i], device))
+    if scoring or niqe_setup:
+        setup = dict(scoring or {})
+        if lpips_setup:
+            setup["lpips"] = lpips_setup
+        if niqe_setup:
+            setup["niqe"] = niqe_setup
+        print(write_metrics(setup, scores, out_dir, rank, world))
 
 
 if __name__ == "__main__":

@@ -172,6 +172,14 @@ def lpips(a, b, model, device=None):
     return out[0] if single_a and single_b else out
 
 
+def niqe(images, model, crop_border=0, device=None):
+    """NIQE of `images` under `model` (an `instantir_amd.niqe.NIQE`; DESIGN.md section 7 "NIQE"): no second image is needed.  A
+    float for one image, a list of floats for a batch; lower is better.  C = 3 is scored on its BT.601 luma."""
+    _, single = _host_source(images, "images")
+    out = model(images, crop_border=crop_border, device=device).tolist()
+    return out[0] if single else out
+
+
 def evaluate(a, b, metrics=METRICS, crop_border=0, y_channel=False, quantize=False, device=None, lpips_model=None):
     """Both figures in one launch pair: {"psnr": [per image], "ssim": [per image], "psnr_mean": .., "ssim_mean": ..} (only the
     metrics asked for).  `quantize` (a flag, or one per argument) rounds a float source to the 8-bit image that would be saved.

@@ -1152,6 +1152,46 @@ def image_metrics(a, b, crop_border=0, y_channel=False, quantize=(False, False),
     return out
 
 
+NIQE_BLOCK, NIQE_STATS = L.MACROS["IIR_NIQE_BLOCK"], L.MACROS["IIR_NIQE_STATS"]
+
+
+def niqe_stats(src, crop_border=0, ws=None):
+    """NIQE's per-block signed moments of a batch of images at two scales (iir_niqe_stats; DESIGN.md section 7 "NIQE").  `src`:
+    a contiguous CUDA tensor, fp32 planar (N, C, H, W) on a [0, 1] scale or uint8 interleaved (N, H, W, C), C 1 or 3 (3 is scored
+    on its BT.601 luma); `crop_border`: pixels dropped on every side first.  Returns fp64 (N, 2, nb, 26) on the device: per
+    scale and 96 x 96 block (48 x 48 at scale 2) in raster order, five statistics of each of the five maps and the sum of sigma;
+    `instantir_amd.niqe.features` takes it from there.  Fewer than two blocks is refused: the score needs a covariance.
+    `ws`: a byte workspace of at least iir_niqe_workspace_bytes (allocated here when absent)."""
+    if not torch.is_tensor(src) or src.dim() != 4 or src.dtype not in (torch.float32, torch.uint8) or not src.is_contiguous():
+        raise ValueError(f"niqe_stats: src must be a contiguous 4-D tensor, fp32 (N, C, H, W) in [0, 1] or uint8 (N, H, W, C), got "
+                         f"{getattr(src, 'dtype', type(src))} {tuple(getattr(src, 'shape', ()))}")
+    u8 = src.dtype == torch.uint8
+    N, Cc, H, W = tuple(src.shape[i] for i in (0, 3, 1, 2)) if u8 else tuple(src.shape)
+    if Cc not in (1, 3):
+        raise ValueError(f"niqe_stats: src must have 1 or 3 channels, got {Cc}")
+    if isinstance(crop_border, bool) or not isinstance(crop_border, int) or crop_border < 0:
+        raise ValueError(f"niqe_stats: crop_border must be an integer >= 0, got {crop_border!r}")
+    nbh, nbw = max(H - 2 * crop_border, 0) // NIQE_BLOCK, max(W - 2 * crop_border, 0) // NIQE_BLOCK
+    if N <= 0 or nbh * nbw < 2:
+        raise ValueError(f"niqe_stats: {H}x{W} with crop_border {crop_border} holds {nbh * nbw} block(s) of {NIQE_BLOCK} x {NIQE_BLOCK}; "
+                         "NIQE needs at least two")
+    if not src.is_cuda:
+        raise ValueError(f"niqe_stats: src must be a CUDA tensor (there is no host path), got {src.device}")
+    h = L.load()
+    need = h.iir_niqe_workspace_bytes(N, Cc, H, W, crop_border)
+    if need < 0:
+        raise ValueError(f"niqe_stats: unsupported geometry N={N} C={Cc} H={H} W={W} crop_border={crop_border}")
+    if ws is None:
+        ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=src.device)
+    elif not torch.is_tensor(ws) or not ws.is_cuda or ws.device != src.device or not ws.is_contiguous() \
+            or ws.numel() * ws.element_size() < need or ws.data_ptr() % 8:
+        raise ValueError(f"niqe_stats: ws needs {need} contiguous, 8-byte aligned bytes on the images' device")
+    out = torch.empty(N, 2, nbh * nbw, NIQE_STATS, dtype=torch.float64, device=src.device)
+    L.check(h.iir_niqe_stats(src.data_ptr(), int(u8), N, Cc, H, W, crop_border, ws.data_ptr(), ws.numel() * ws.element_size(),
+                             out.data_ptr(), out.numel() * 8, _stream()), "iir_niqe_stats")
+    return out
+
+
 FILTER2D_MAX_KSIZE = L.MACROS["IIR_FILTER2D_MAX_KSIZE"]
 JPEG_QUALITY_RANGE = (1.0, 99.0)
 
