@@ -1,7 +1,7 @@
 // LPIPS v0.1 (net = vgg) around the MFMA conv: what the thirteen 3x3 convs of VGG-16 `features` do not do themselves.  The
 // reference builds `lpips.LPIPS(net='vgg')` at losses/losses.py:81-95; contract in include/instantir_hip.h (iir_lpips_prep,
-// iir_relu_f16, iir_lpips_tap) and DESIGN.md section 7 "LPIPS".  Compiled with -ffp-contract=off like metrics.hip: nothing is
-// fused that is not written as fmaf.
+// iir_relu_f16, iir_lpips_tap) and DESIGN.md section 7 "LPIPS".  The summation orders are image_common.h's.  Compiled with
+// -ffp-contract=off: nothing is fused that is not written as fmaf.
 //
 // Three kernels on NHWC 16-bit rows (fp16 or bf16 by `dtype`, fp32 arithmetic):
 //   prep   image (uint8 interleaved or fp32 planar, [0, 1]) -> the scaling layer's output as rows of IIR_LPIPS_CPAD channels,
@@ -21,7 +21,7 @@
 // order (256 strided sequences, then a fixed tree) and divides by H * W.
 // Every global load is unconditional from a clamped address and masked in registers; only stores are guarded.  No atomics, no
 // scratch: equal inputs give equal bits.
-#include "common.h"
+#include "image_common.h"
 #include "../../include/instantir_hip.h"
 
 namespace {
@@ -88,12 +88,6 @@ template <int LP> __device__ __forceinline__ float group_sum(float v) {
     return v;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 struct TapGeo {
     int H, W, C, chunks;      // the tap's extent; chunks = C / 8
     int qh, qw;               // quads per axis, the odd remainder included
@@ -108,7 +102,7 @@ struct TapGeo {
 template <typename E, int LP>
 __global__ __launch_bounds__(NT) void lpips_tap_kernel(const E* x, long ldx, const TapGeo g, const float* lin_w, float* dmap, E* pooled, long ldp,
                                                        double* ws) {
-    __shared__ double red[NT / 64];
+    __shared__ double red[1][NT / 64];
     constexpr int G = NT / LP;
     const int tid = threadIdx.x, lane = tid % LP;
     const long pair = blockIdx.y;
@@ -167,31 +161,17 @@ __global__ __launch_bounds__(NT) void lpips_tap_kernel(const E* x, long ldx, con
         store8(pooled + prow * ldp + col, ma);
         store8(pooled + (prow + g.pb_off) * ldp + col, mb);
     }
-    const double dw = wave_sum_f64(lane == 0 ? (double)dq : 0.0);
-    if ((tid & 63) == 0) red[tid >> 6] = dw;
+    block_sum_stage(red, lane == 0 ? (double)dq : 0.0);
     __syncthreads();
-    if (tid == 0) {
-        double s = red[0];
-#pragma unroll
-        for (int k = 1; k < NT / 64; ++k) s += red[k];
-        ws[pair * gridDim.x + blockIdx.x] = s;
-    }
+    if (tid == 0) ws[pair * gridDim.x + blockIdx.x] = block_sum(red[0]);
 }
 
 // grid (pairs), NT threads: ws holds `parts` partial sums per pair
 __global__ __launch_bounds__(NT) void lpips_final_kernel(const double* ws, int parts, double count, double* out) {
-    __shared__ double r0[NT];
-    const int tid = threadIdx.x;
-    const double* p = ws + (long)blockIdx.x * parts;
-    double q = 0.0;
-    for (int i = tid; i < parts; i += NT) q += p[i];
-    r0[tid] = q;
-    __syncthreads();
-    for (int o = NT / 2; o > 0; o >>= 1) {
-        if (tid < o) r0[tid] += r0[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) out[blockIdx.x] = r0[0] / count;
+    __shared__ double r[1][NT];
+    double sum[1];
+    final_sum_f64<NT, 1>(ws + (long)blockIdx.x * parts, parts, r, sum);
+    if (threadIdx.x == 0) out[blockIdx.x] = sum[0] / count;
 }
 
 int lanes_per_pixel(int C) {
@@ -235,11 +215,6 @@ void tap_dispatch(int lp, const void* x, int64_t ldx, const TapGeo& g, int pairs
         case 32: return tap_launch<E, 32>(x, ldx, g, pairs, parts, lin_w, dmap, pooled, ldp, ws, s);
         default: return tap_launch<E, 64>(x, ldx, g, pairs, parts, lin_w, dmap, pooled, ldp, ws, s);
     }
-}
-
-bool overlap(const void* p, int64_t pbytes, const void* q, int64_t qbytes) {
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + (uintptr_t)qbytes && b < a + (uintptr_t)pbytes;
 }
 
 }  // namespace

@@ -16,7 +16,7 @@
 // Every global load is unconditional, from an address clamped into the cropped image; what a clamped
 // address gave for a pixel outside the image is replaced by 0 in registers, and only stores are guarded.  No atomics, no
 // scratch: equal inputs give equal bits.
-#include "common.h"
+#include "image_common.h"
 #include "../../include/instantir_hip.h"
 
 namespace {
@@ -38,63 +38,31 @@ static_assert(STAGE * 65025 < (1 << 24) && PE * 65025 < (1 << 24), "a thread's s
 #define IIR_SSIM_TAPS {0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c4p-3f, 0x1.10656p-2f, \
                        0x1.b43c4p-3f, 0x1.bff0fep-4f, 0x1.26eb18p-5f, 0x1.f1fe02p-8f, 0x1.0d956cp-10f}
 
-struct Src {
-    const void* p;
-    int u8, quantize;
-};
-
 struct Geo {
     int C, H, W;          // the sources as stored
     int crop, hc, wc;     // dropped border; rows and columns that remain
     int y;                // Y of BT.601 instead of the channels
 };
 
-// channel `ch` of pixel (y, x) of image n in 0..255 units; (y, x) in source coordinates, inside the image
-__device__ __forceinline__ float load255(const Src& s, const Geo& g, int n, int ch, int y, int x) {
-    if (s.u8) return (float)((const uint8_t*)s.p)[(((long)n * g.H + y) * g.W + x) * g.C + ch];
-    float v = ((const float*)s.p)[(((long)n * g.C + ch) * g.H + y) * g.W + x] * 255.0f;
-    if (s.quantize) v = fminf(fmaxf(floorf(v + 0.5f), 0.0f), 255.0f);
-    return v;
-}
-
-__device__ __forceinline__ float pixel(const Src& s, const Geo& g, int n, int plane, int y, int x) {
-    if (!g.y) return load255(s, g, n, plane, y, x);
-    const float r = load255(s, g, n, 0, y, x), gr = load255(s, g, n, 1, y, x), b = load255(s, g, n, 2, y, x);
-    float t = 65.481f * r;
-    t = t + 128.553f * gr;
-    t = t + 24.966f * b;
-    return 16.0f + t / 255.0f;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
+// plane `plane` (a channel, or the luma) of pixel (y, x) of image n in 0..255 units
+__device__ __forceinline__ float pixel(const ImageSrc& s, const Geo& g, int n, int plane, int y, int x) {
+    if (!g.y) return image_load255(s, g.C, g.H, g.W, n, plane, y, x);
+    return luma_bt601(image_load255(s, g.C, g.H, g.W, n, 0, y, x), image_load255(s, g.C, g.H, g.W, n, 1, y, x),
+                      image_load255(s, g.C, g.H, g.W, n, 2, y, x));
 }
 
 // the workgroup's {sum of squared differences, sum of map values} -> ws[2 * slot], ws[2 * slot + 1]
 __device__ __forceinline__ void block_partials(float sq, float sm, double (*red)[NT / 64], long slot, double* ws) {
-    const double dq = wave_sum_f64((double)sq), dm = wave_sum_f64((double)sm);
-    const int tid = threadIdx.x;
-    if ((tid & 63) == 0) {
-        red[0][tid >> 6] = dq;
-        red[1][tid >> 6] = dm;
-    }
+    block_sum_stage(red, sq, sm);
     __syncthreads();
-    if (tid == 0) {
-        double q = red[0][0], m = red[1][0];
-#pragma unroll
-        for (int w = 1; w < NT / 64; ++w) {
-            q += red[0][w];
-            m += red[1][w];
-        }
-        ws[2 * slot] = q;
-        ws[2 * slot + 1] = m;
+    if (threadIdx.x == 0) {
+        ws[2 * slot] = block_sum(red[0]);
+        ws[2 * slot + 1] = block_sum(red[1]);
     }
 }
 
 // grid (ceil((wc - 10) / T), ceil((hc - 10) / T), N * planes), NT threads
-__global__ __launch_bounds__(NT) void metrics_tile_kernel(const Src A, const Src B, const Geo g, int planes, int mh, int mw, double* ws) {
+__global__ __launch_bounds__(NT) void metrics_tile_kernel(const ImageSrc A, const ImageSrc B, const Geo g, int planes, int mh, int mw, double* ws) {
     __shared__ float sa[S * SP], sb[S * SP];     // a - 128, b - 128 over [ty0, ty0 + S) x [tx0, tx0 + S) of the cropped image
     __shared__ float sx[5][S * T];               // their five x-filtered moments over the same rows, the tile's columns
     __shared__ double red[2][NT / 64];
@@ -166,7 +134,7 @@ __global__ __launch_bounds__(NT) void metrics_tile_kernel(const Src A, const Src
 }
 
 // the MSE alone.  grid (ceil(E / (NT * PE)), N), NT threads; E = planes * hc * wc elements per image, plane-major
-__global__ __launch_bounds__(NT) void metrics_mse_kernel(const Src A, const Src B, const Geo g, long E, double* ws) {
+__global__ __launch_bounds__(NT) void metrics_mse_kernel(const ImageSrc A, const ImageSrc B, const Geo g, long E, double* ws) {
     __shared__ double red[2][NT / 64];
     const int n = blockIdx.y;
     const long plane_elems = (long)g.hc * g.wc;
@@ -186,28 +154,13 @@ __global__ __launch_bounds__(NT) void metrics_mse_kernel(const Src A, const Src 
 // grid (N), NT threads: ws holds `parts` {squares, map values} pairs per image
 __global__ __launch_bounds__(NT) void metrics_final_kernel(const double* ws, int parts, double mse_count, double map_count, unsigned what,
                                                            double* out) {
-    __shared__ double r0[NT], r1[NT];
-    const int tid = threadIdx.x;
-    const double* p = ws + 2 * (long)blockIdx.x * parts;
-    double q = 0.0, m = 0.0;
-    for (int i = tid; i < parts; i += NT) {
-        q += p[2 * i];
-        m += p[2 * i + 1];
-    }
-    r0[tid] = q;
-    r1[tid] = m;
-    __syncthreads();
-    for (int o = NT / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            r0[tid] += r0[tid + o];
-            r1[tid] += r1[tid + o];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
+    __shared__ double r[2][NT];
+    double sum[2];
+    final_sum_f64<NT, 2>(ws + 2 * (long)blockIdx.x * parts, parts, r, sum);
+    if (threadIdx.x == 0) {
         const double nan = __builtin_nan("");
-        out[2 * blockIdx.x] = (what & IIR_METRIC_PSNR) ? r0[0] / mse_count : nan;
-        out[2 * blockIdx.x + 1] = (what & IIR_METRIC_SSIM) ? r1[0] / map_count : nan;
+        out[2 * blockIdx.x] = (what & IIR_METRIC_PSNR) ? sum[0] / mse_count : nan;
+        out[2 * blockIdx.x + 1] = (what & IIR_METRIC_SSIM) ? sum[1] / map_count : nan;
     }
 }
 
@@ -259,7 +212,7 @@ extern "C" int iir_image_metrics(const iir_metrics_desc* d, void* stream) {
     if (!d->a || !d->b || !d->out || !d->ws) return IIR_EINVAL;
     if (((uintptr_t)d->ws | (uintptr_t)d->out) & 7) return IIR_EINVAL;
     if (d->ws_bytes < p.parts * d->N * 2 * (int64_t)sizeof(double)) return IIR_EINVAL;
-    const Src A = {d->a, d->a_u8 != 0, d->a_quantize != 0}, B = {d->b, d->b_u8 != 0, d->b_quantize != 0};
+    const ImageSrc A = {d->a, d->a_u8 != 0, d->a_quantize != 0}, B = {d->b, d->b_u8 != 0, d->b_quantize != 0};
     const Geo g = {d->C, d->H, d->W, d->crop_border, p.hc, p.wc, d->y_channel != 0};
     double* ws = (double*)d->ws;
     hipStream_t s = (hipStream_t)stream;

@@ -1,8 +1,8 @@
 // NIQE's device part: the natural-scene statistics of an image's luma at two scales, as per-block signed moments (no reference
 // counterpart; contract in include/instantir_hip.h: iir_niqe_stats, and DESIGN.md section 7 "NIQE").  What is left -- the AGGD
 // fit, the 36 features, the Gaussian model and the distance -- is a few hundred fp64 operations per block on the host
-// (instantir_amd/niqe.py).  Compiled with -ffp-contract=off like metrics.hip: the tap sums are written with fmaf, so they are
-// fused by statement and nothing else is.
+// (instantir_amd/niqe.py).  The pixel read, the luma, the rounding and the summation order are image_common.h's.  Compiled with
+// -ffp-contract=off: the tap sums are written with fmaf, so they are fused by statement and nothing else is.
 //
 // Four launches.  niqe_grey_kernel writes the rounded grey value of every pixel of the block-grid image (the top-left
 // 96 nbh x 96 nbw part of the cropped image) as an fp32 plane into the workspace; pixels outside that part are never read.
@@ -16,7 +16,7 @@
 // (at most 24 terms), goes to fp64, and the workgroup adds in a fixed order (wave butterflies, then the waves in order).
 // Every global load is unconditional from a clamped address; only stores are guarded.  No atomics, no
 // scratch: equal inputs give equal bits.
-#include "common.h"
+#include "image_common.h"
 #include "../../include/instantir_hip.h"
 
 namespace {
@@ -43,30 +43,16 @@ struct Geo {
     int hg, wg;           // the block-grid image: 96 nbh x 96 nbw
 };
 
-// channel `ch` of pixel (y, x) of image n in 0..255 units; (y, x) in source coordinates, inside the image (metrics.hip: load255)
-__device__ __forceinline__ float load255(const void* p, const Geo& g, int n, int ch, int y, int x) {
-    if (g.u8) return (float)((const uint8_t*)p)[(((long)n * g.H + y) * g.W + x) * g.C + ch];
-    return ((const float*)p)[(((long)n * g.C + ch) * g.H + y) * g.W + x] * 255.0f;
-}
-
 // grid (ceil(hg * wg / NPT), N), NPT threads: grey[n][y][x], rounded to the 8-bit grid
 __global__ __launch_bounds__(NPT) void niqe_grey_kernel(const void* src, const Geo g, float* grey) {
     const int n = blockIdx.y;
     const long E = (long)g.hg * g.wg;
     const long e = (long)blockIdx.x * NPT + threadIdx.x, ec = min(e, E - 1);
     const int y = (int)(ec / g.wg), x = (int)(ec - (long)y * g.wg);
-    float v;
-    if (g.C == 3) {                                  // metrics.hip: pixel() with y_channel
-        const float r = load255(src, g, n, 0, g.crop + y, g.crop + x), gr = load255(src, g, n, 1, g.crop + y, g.crop + x),
-                    b = load255(src, g, n, 2, g.crop + y, g.crop + x);
-        float t = 65.481f * r;
-        t = t + 128.553f * gr;
-        t = t + 24.966f * b;
-        v = 16.0f + t / 255.0f;
-    } else {
-        v = load255(src, g, n, 0, g.crop + y, g.crop + x);
-    }
-    v = fminf(fmaxf(floorf(v + 0.5f), 0.0f), 255.0f);
+    const int sy = g.crop + y, sx = g.crop + x;
+    const ImageSrc s = {src, g.u8, 0};
+    const auto ch = [&](int c) { return image_load255(s, g.C, g.H, g.W, n, c, sy, sx); };
+    const float v = round_u8(g.C == 3 ? luma_bt601(ch(0), ch(1), ch(2)) : ch(0));
     if (e < E) grey[n * E + e] = v;
 }
 
@@ -93,12 +79,6 @@ __global__ __launch_bounds__(NPT) void niqe_half_kernel(const float* grey, int h
         acc = fmaf(taps[i], col, acc);
     }
     if (e < E) half[n * E + e] = acc;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 template <int B> struct BlockLds {
@@ -187,26 +167,12 @@ template <int B> __global__ __launch_bounds__(NT) void niqe_block_kernel(const f
         tally(m * s.sm[ru * B + cl], cn[3], cp[3], qn[3], qp[3], ab[3]);              // roll (1, 1)
         tally(m * s.sm[ru * B + cr], cn[4], cp[4], qn[4], qp[4], ab[4]);              // roll (1, -1)
     }
-    const int wave = tid >> 6, lane = tid & 63;
 #pragma unroll
-    for (int q = 0; q < 5; ++q) {
-        const double v0 = wave_sum_f64((double)cn[q]), v1 = wave_sum_f64((double)cp[q]), v2 = wave_sum_f64((double)qn[q]),
-                     v3 = wave_sum_f64((double)qp[q]), v4 = wave_sum_f64((double)ab[q]);
-        if (lane == 0) {
-            s.red[5 * q + 0][wave] = v0;
-            s.red[5 * q + 1][wave] = v1;
-            s.red[5 * q + 2][wave] = v2;
-            s.red[5 * q + 3][wave] = v3;
-            s.red[5 * q + 4][wave] = v4;
-        }
-    }
-    const double vs = wave_sum_f64((double)ssig);
-    if (lane == 0) s.red[NSTAT - 1][wave] = vs;
+    for (int q = 0; q < 5; ++q) block_sum_stage(s.red + 5 * q, cn[q], cp[q], qn[q], qp[q], ab[q]);
+    block_sum_stage(s.red + NSTAT - 1, ssig);
     __syncthreads();
     if (tid < NSTAT) {
-        double a = s.red[tid][0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) a += s.red[tid][w];
+        const double a = block_sum(s.red[tid]);
         out[(long)n * out_image_stride + ((long)blockIdx.y * gridDim.x + blockIdx.x) * NSTAT + tid] = a;
     }
 }

@@ -14,7 +14,7 @@
 // axis before use, so every load is unconditional and inside the source whatever the table holds; only the store is guarded.
 // Taps are summed in index order, nothing is atomic: equal inputs give equal bits, and a windowed launch gives the bits of
 // the same window cut from the full launch.
-#include "common.h"
+#include "image_common.h"
 #include "../../include/instantir_hip.h"
 
 namespace {
@@ -63,16 +63,11 @@ __global__ __launch_bounds__(256) void resample_pass_kernel(const Pass p) {
         const float* s = (const float*)p.src + at;
         for (int k = 0; k < cnt; ++k) acc = fmaf(wr[k], s[k * step], acc);
     }
-    if (p.quantize) acc = fminf(fmaxf(floorf(acc + 0.5f), 0.0f), 255.0f);
+    if (p.quantize) acc = round_u8(acc);
     if (p.clamp) acc = fminf(fmaxf(acc, p.lo), p.hi);
     if (p.scale) acc = acc * p.scale[c];
     if (p.bias) acc = acc + p.bias[c];
     if (e < hw) p.dst[(long)plane * hw + e] = acc;
-}
-
-bool overlap(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
 }
 
 }  // namespace

@@ -23,6 +23,7 @@ import torch
 
 from . import ops
 from .engine import Arena
+from .images import dims, host_source, scoring_device
 from .packing import conv_weight_nhwc
 
 CONVS = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)            # torchvision indices of VGG-16 `features`' convs
@@ -116,11 +117,7 @@ class LPIPS:
     def __init__(self, convs, lins, shift=ops.LPIPS_SHIFT, scale=ops.LPIPS_SCALE, device=None, dtype=torch.float16):
         if dtype not in DTYPES:
             raise ValueError("LPIPS: dtype must be torch.float16 (default) or torch.bfloat16")
-        if device is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError("instantir_amd.lpips needs an MI355X: LPIPS has no host path")
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.device, self.dtype, self.dtype_name = torch.device(device), dtype, DTYPES[dtype]
+        self.device, self.dtype, self.dtype_name = scoring_device(device, "instantir_amd.lpips"), dtype, DTYPES[dtype]
         self.widths = tuple(convs[j][0].shape[0] for j in (1, 3, 6, 9, 12))
         self.padded = tuple(_pad64(c) for c in self.widths)          # the conv reads whole 64-channel K tiles: zero weights and
         self.w, cin = [], ops.LPIPS_CPAD                             #   biases keep the padding channels at exactly 0
@@ -206,10 +203,9 @@ class LPIPS:
         """LPIPS of `a` against `b`, each what `metrics.psnr` accepts (a PIL image or a list of them, a numpy array, a tensor; 3
         channels, [0, 1] scale or 8-bit).  Returns fp64 (N,) on the device, (N, 5) with `layers` (the five taps' terms, whose sum
         over the row is the score); with `spatial` a pair (that, [five fp32 (N, H_l, W_l) maps of the per-pixel terms])."""
-        from . import metrics as M
-        ta, _ = M._host_source(a, "a")
-        tb, _ = M._host_source(b, "b")
-        da, db = M._dims(ta), M._dims(tb)
+        ta, _ = host_source(a, "a")
+        tb, _ = host_source(b, "b")
+        da, db = dims(ta), dims(tb)
         if da != db:
             raise ValueError(f"LPIPS: b is (N, C, H, W) = {db} but its counterpart is {da}")
         N, C, H, W = da

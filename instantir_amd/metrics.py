@@ -20,65 +20,17 @@ import math
 import numpy as np
 import torch
 
+from .images import check_crop, dims, host_source, scoring_device
+
 METRICS = ("psnr", "ssim")
 WINDOW = 11
-
-
-def _pil_array(im, arg):
-    if im.mode not in ("L", "RGB"):
-        im = im.convert("RGB")
-    a = np.array(im)
-    return a[:, :, None] if a.ndim == 2 else a
-
-
-def _host_source(x, arg):
-    """-> (host tensor in the kernel's layout: uint8 (N, H, W, C) or fp32 (N, C, H, W); whether the argument was one image)."""
-    from PIL import Image
-    if isinstance(x, Image.Image):
-        return torch.from_numpy(np.ascontiguousarray(_pil_array(x, arg)[None])), True
-    if isinstance(x, (list, tuple)):
-        if not x or not all(isinstance(im, Image.Image) for im in x):
-            raise ValueError(f"{arg}: a list must hold PIL images (at least one)")
-        arrs = [_pil_array(im, arg) for im in x]
-        if len({a.shape for a in arrs}) != 1:
-            raise ValueError(f"{arg}: the images of a list must share a size and a mode, got {sorted({a.shape for a in arrs})}")
-        return torch.from_numpy(np.stack(arrs)), False
-    if isinstance(x, np.ndarray):
-        x = torch.from_numpy(np.ascontiguousarray(x))
-        channels_last = True
-    elif torch.is_tensor(x):
-        channels_last = x.dtype == torch.uint8
-    else:
-        raise ValueError(f"{arg}: expected a PIL image, a list of PIL images, a numpy array or a tensor, got {type(x).__name__}")
-    if x.dtype != torch.uint8 and not x.dtype.is_floating_point:
-        raise ValueError(f"{arg}: expected uint8 or floating-point values, got {x.dtype}")
-    single = x.dim() < 4
-    if channels_last:                   # (H, W), (H, W, C), (N, H, W, C)
-        if x.dim() == 2:
-            x = x[None, :, :, None]
-        elif x.dim() == 3:
-            x = x[None]
-    elif x.dim() == 3:                  # (C, H, W)
-        x = x[None]
-    if x.dim() != 4:
-        raise ValueError(f"{arg}: expected an image or a batch of images, got shape {tuple(x.shape)}")
-    if x.dtype != torch.uint8:
-        x = x.float()
-        if channels_last:
-            x = x.permute(0, 3, 1, 2)
-    return x, single
-
-
-def _dims(t):
-    return tuple(t.shape[i] for i in (0, 3, 1, 2)) if t.dtype == torch.uint8 else tuple(t.shape)
 
 
 def _check_options(who, what, crop_border, y_channel, quantize):
     names = (what,) if isinstance(what, str) else tuple(what)
     if not names or any(w not in METRICS for w in names):
         raise ValueError(f"{who}: metrics must name one or both of {METRICS}, got {what!r}")
-    if isinstance(crop_border, bool) or not isinstance(crop_border, int) or crop_border < 0:
-        raise ValueError(f"{who}: crop_border must be an integer >= 0, got {crop_border!r}")
+    check_crop(who, crop_border)
     if isinstance(quantize, (bool, np.bool_)):
         quantize = (bool(quantize), bool(quantize))
     try:
@@ -89,7 +41,7 @@ def _check_options(who, what, crop_border, y_channel, quantize):
 
 
 def _check_pair(who, ta, tb, names, crop_border, y_channel, arg_b="b"):
-    da, db = _dims(ta), _dims(tb)
+    da, db = dims(ta), dims(tb)
     if da != db:
         raise ValueError(f"{who}: {arg_b} is (N, C, H, W) = {db} but its counterpart is {da}")
     N, C, H, W = da
@@ -103,14 +55,6 @@ def _check_pair(who, ta, tb, names, crop_border, y_channel, arg_b="b"):
                          + (" (the SSIM window is 11 x 11)" if "ssim" in names else ""))
 
 
-def _device(device):
-    if device is not None:
-        return torch.device(device)
-    if not torch.cuda.is_available():
-        raise RuntimeError("instantir_amd.metrics needs an MI355X: the metrics have no host path")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def psnr_from_mse(mse):
     """10 log10(255^2 / MSE) in fp64; inf for identical images."""
     return math.inf if mse == 0 else 10.0 * math.log10(255.0 ** 2 / mse)
@@ -118,7 +62,7 @@ def psnr_from_mse(mse):
 
 def _score(ta, tb, names, crop_border, y_channel, quantize, device):
     from . import ops
-    dev = _device(device)
+    dev = scoring_device(device)
     out = ops.image_metrics(ta.to(dev).contiguous(), tb.to(dev).contiguous(), crop_border=crop_border, y_channel=bool(y_channel),
                             quantize=quantize, what=names).cpu().tolist()
     res = {}
@@ -131,8 +75,8 @@ def _score(ta, tb, names, crop_border, y_channel, quantize, device):
 
 def _run(who, a, b, names, crop_border, y_channel, quantize, device):
     names, quantize = _check_options(who, names, crop_border, y_channel, quantize)
-    ta, single_a = _host_source(a, "a")
-    tb, single_b = _host_source(b, "b")
+    ta, single_a = host_source(a, "a")
+    tb, single_b = host_source(b, "b")
     _check_pair(who, ta, tb, names, crop_border, y_channel)
     return _score(ta, tb, names, crop_border, y_channel, quantize, device), single_a and single_b
 
@@ -166,8 +110,8 @@ def lpips(a, b, model, device=None):
     """LPIPS of `a` against `b` under `model` (an `instantir_amd.lpips.LPIPS`; DESIGN.md section 7 "LPIPS"): a float for one
     image, a list of floats for a batch; 0 for identical images.  The whole image is scored: LPIPS has no crop, luma or
     quantise option."""
-    _, single_a = _host_source(a, "a")
-    _, single_b = _host_source(b, "b")
+    _, single_a = host_source(a, "a")
+    _, single_b = host_source(b, "b")
     out = _lpips_scores("lpips", a, b, model, device)
     return out[0] if single_a and single_b else out
 
@@ -175,7 +119,7 @@ def lpips(a, b, model, device=None):
 def niqe(images, model, crop_border=0, device=None):
     """NIQE of `images` under `model` (an `instantir_amd.niqe.NIQE`; DESIGN.md section 7 "NIQE"): no second image is needed.  A
     float for one image, a list of floats for a batch; lower is better.  C = 3 is scored on its BT.601 luma."""
-    _, single = _host_source(images, "images")
+    _, single = host_source(images, "images")
     out = model(images, crop_border=crop_border, device=device).tolist()
     return out[0] if single else out
 
@@ -199,13 +143,13 @@ def input_fidelity(restored, lq, filter="bicubic", metrics=METRICS, crop_border=
     if filter not in FILTERS:
         raise ValueError(f"input_fidelity: filter must be one of {tuple(FILTERS)}, got {filter!r}")
     names, _ = _check_options("input_fidelity", metrics, crop_border, y_channel, False)
-    tr, _ = _host_source(restored, "restored")
-    tl, _ = _host_source(lq, "lq")
-    dr, dl = _dims(tr), _dims(tl)
+    tr, _ = host_source(restored, "restored")
+    tl, _ = host_source(lq, "lq")
+    dr, dl = dims(tr), dims(tl)
     if dr[:2] != dl[:2]:
         raise ValueError(f"input_fidelity: restored holds (N, C) = {dr[:2]} but lq {dl[:2]}")
     quantize = (False, False)
-    dev = _device(device) if dr[2:] != dl[2:] else None
+    dev = scoring_device(device) if dr[2:] != dl[2:] else None
     if dr[2:] != dl[2:]:
         both_u8 = tr.dtype == torch.uint8 and tl.dtype == torch.uint8
         if tr.dtype == torch.uint8:

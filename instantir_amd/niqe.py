@@ -22,6 +22,8 @@ import warnings
 
 import numpy as np
 
+from .images import check_crop, dims, host_source, scoring_device
+
 BLOCK = 96
 NFEAT = 36
 SHARPNESS_KEEP = 0.75
@@ -115,24 +117,19 @@ def distance(mu_p, cov_p, mu_d, cov_d):
     return float(np.sqrt(d @ np.linalg.pinv(c) @ d))
 
 
-def _check_crop(who, crop_border):
-    if isinstance(crop_border, bool) or not isinstance(crop_border, int) or crop_border < 0:
-        raise ValueError(f"{who}: crop_border must be an integer >= 0, got {crop_border!r}")
-
-
 def _stats(who, images, crop_border, device):
     """-> (device statistics (N, 2, nb, 26), whether `images` was one image)."""
-    from . import metrics as M, ops
-    _check_crop(who, crop_border)
-    t, single = M._host_source(images, "images")
-    N, C, H, W = M._dims(t)
+    from . import ops
+    check_crop(who, crop_border)
+    t, single = host_source(images, "images")
+    N, C, H, W = dims(t)
     if C not in (1, 3):
         raise ValueError(f"{who}: images must have 1 or 3 channels, got {C}")
     nb = (max(H - 2 * crop_border, 0) // BLOCK) * (max(W - 2 * crop_border, 0) // BLOCK)
     if nb < 2:
         raise ValueError(f"{who}: {H}x{W} with crop_border {crop_border} holds {nb} block(s) of {BLOCK} x {BLOCK}; NIQE needs at "
                          "least two")
-    return ops.niqe_stats(t.to(M._device(device)).contiguous(), crop_border=crop_border), single
+    return ops.niqe_stats(t.to(scoring_device(device, "instantir_amd.niqe")).contiguous(), crop_border=crop_border), single
 
 
 class NIQE:

@@ -11,6 +11,7 @@ import ctypes as C
 import torch
 
 from . import lib as L
+from .images import check_crop
 from .lib import ACT_GELU, ACT_NONE, ACT_QUICKGELU, ACT_SILU, EPI_GEGLU, EPI_PLAIN, EPI_SFT, EPI_XATTN  # noqa: F401
 
 
@@ -592,6 +593,27 @@ def _refuse(who, ok, msg):
         raise ValueError(f"{who}: {msg}")
 
 
+def _image_source(who, t, name, unit=" in [0, 1]"):
+    """An image batch as the image kernels read it -> (whether it is uint8 interleaved, (N, C, H, W))."""
+    if not torch.is_tensor(t) or t.dim() != 4 or t.dtype not in (torch.float32, torch.uint8) or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous 4-D tensor, fp32 (N, C, H, W){unit} or uint8 (N, H, W, C), got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if t.dtype != torch.uint8:
+        return False, tuple(t.shape)
+    N, H, W, Cc = t.shape
+    return True, (N, Cc, H, W)
+
+
+def _workspace(who, ws, need, device, where="the images' device"):
+    """The byte workspace of a launch: the caller's, checked against `need` bytes, or a fresh one when absent."""
+    if ws is None:
+        return torch.empty((need + 7) // 8, dtype=torch.float64, device=device)
+    _refuse(who, torch.is_tensor(ws) and ws.is_cuda and ws.device == device and ws.is_contiguous()
+            and ws.numel() * ws.element_size() >= need and ws.data_ptr() % 8 == 0,
+            f"ws needs {need} contiguous, 8-byte aligned bytes on {where}")
+    return ws
+
+
 def _chk_rows2d(who, name, t, rows, cols):
     """2-D fp16 / bf16 view with unit column stride that holds `rows` x `cols` (exactly `rows` rows, at least `cols` columns)."""
     _refuse(who, t.dim() == 2 and t.dtype in _DT and t.stride(1) == 1 and t.shape[0] == rows and t.shape[1] >= cols,
@@ -1049,11 +1071,7 @@ def resample(src, size, filter="bilinear", quantize=False, window=None, clamp=No
     both on the last pass.  Returns fp32 (N, C, h, w) (`out` when given; it may not overlap `src`)."""
     from . import resample as RS
     (oh, ow), win, clamp = RS.check_args(size, filter, quantize, window, clamp)
-    if not torch.is_tensor(src) or src.dim() != 4 or src.dtype not in (torch.float32, torch.uint8) or not src.is_contiguous():
-        raise ValueError("resample: src must be a contiguous 4-D tensor, fp32 (N, C, H, W) or uint8 (N, H, W, C), got "
-                         f"{getattr(src, 'dtype', type(src))} {tuple(getattr(src, 'shape', ()))}")
-    u8 = src.dtype == torch.uint8
-    N, Cc, H, W = (src.shape[0], src.shape[3], src.shape[1], src.shape[2]) if u8 else src.shape
+    u8, (N, Cc, H, W) = _image_source("resample", src, "src", unit="")
     if min(N, Cc, H, W) <= 0 or H > RS.MAX_SIDE or W > RS.MAX_SIDE or N * Cc > RS.MAX_PLANES:
         raise ValueError(f"resample: unsupported geometry N={N} C={Cc} H={H} W={W} (sides <= {RS.MAX_SIDE}, N * C <= {RS.MAX_PLANES})")
     y0, x0, h, w = win
@@ -1091,14 +1109,6 @@ METRICS_WINDOW = 11            # the SSIM window per axis: a cropped side below 
 METRICS_TILE = L.MACROS["IIR_METRICS_TILE"]       # the SSIM-map tile a workgroup owns, per axis
 
 
-def _metrics_source(t, name):
-    if not torch.is_tensor(t) or t.dim() != 4 or t.dtype not in (torch.float32, torch.uint8) or not t.is_contiguous():
-        raise ValueError(f"image_metrics: {name} must be a contiguous 4-D tensor, fp32 (N, C, H, W) in [0, 1] or uint8 (N, H, W, C), got "
-                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-    u8 = t.dtype == torch.uint8
-    return u8, (tuple(t.shape[i] for i in (0, 3, 1, 2)) if u8 else tuple(t.shape))
-
-
 def image_metrics(a, b, crop_border=0, y_channel=False, quantize=(False, False), what=("psnr", "ssim"), ws=None):
     """Per-image MSE and SSIM of two image batches (iir_image_metrics; DESIGN.md section 7 "Image metrics").  `a`, `b`:
     contiguous CUDA tensors of one device and one logical shape, each fp32 planar (N, C, H, W) on a [0, 1] scale or uint8
@@ -1110,8 +1120,8 @@ def image_metrics(a, b, crop_border=0, y_channel=False, quantize=(False, False),
     names = (what,) if isinstance(what, str) else tuple(what)
     if not names or any(w not in METRICS for w in names):
         raise ValueError(f"image_metrics: what must name one or both of {METRICS}, got {what!r}")
-    a_u8, dims = _metrics_source(a, "a")
-    b_u8, dims_b = _metrics_source(b, "b")
+    a_u8, dims = _image_source("image_metrics", a, "a")
+    b_u8, dims_b = _image_source("image_metrics", b, "b")
     if dims_b != dims:
         raise ValueError(f"image_metrics: b is (N, C, H, W) = {dims_b} but a is {dims}")
     N, Cc, H, W = dims
@@ -1119,8 +1129,7 @@ def image_metrics(a, b, crop_border=0, y_channel=False, quantize=(False, False),
         raise ValueError(f"image_metrics: a and b must have 1 or 3 channels, got {Cc}")
     if y_channel and Cc != 3:
         raise ValueError("image_metrics: y_channel needs 3 channels")
-    if isinstance(crop_border, bool) or not isinstance(crop_border, int) or crop_border < 0:
-        raise ValueError(f"image_metrics: crop_border must be an integer >= 0, got {crop_border!r}")
+    check_crop("image_metrics", crop_border)
     try:
         qa, qb = (bool(q) for q in quantize)
     except (TypeError, ValueError):
@@ -1141,11 +1150,7 @@ def image_metrics(a, b, crop_border=0, y_channel=False, quantize=(False, False),
     need = h.iir_image_metrics_workspace_bytes(C.byref(d))
     if need < 0:
         raise ValueError(f"image_metrics: unsupported geometry N={N} C={Cc} H={H} W={W} crop_border={crop_border}")
-    if ws is None:
-        ws = torch.empty(need // 8, dtype=torch.float64, device=a.device)
-    elif not torch.is_tensor(ws) or not ws.is_cuda or ws.device != a.device or not ws.is_contiguous() \
-            or ws.numel() * ws.element_size() < need or ws.data_ptr() % 8:
-        raise ValueError(f"image_metrics: ws needs {need} contiguous, 8-byte aligned bytes on the images' device")
+    ws = _workspace("image_metrics", ws, need, a.device)
     out = torch.empty(N, 2, dtype=torch.float64, device=a.device)
     d.ws, d.ws_bytes, d.out = ws.data_ptr(), ws.numel() * ws.element_size(), out.data_ptr()
     L.check(h.iir_image_metrics(C.byref(d), _stream()), "iir_image_metrics")
@@ -1162,15 +1167,10 @@ def niqe_stats(src, crop_border=0, ws=None):
     scale and 96 x 96 block (48 x 48 at scale 2) in raster order, five statistics of each of the five maps and the sum of sigma;
     `instantir_amd.niqe.features` takes it from there.  Fewer than two blocks is refused: the score needs a covariance.
     `ws`: a byte workspace of at least iir_niqe_workspace_bytes (allocated here when absent)."""
-    if not torch.is_tensor(src) or src.dim() != 4 or src.dtype not in (torch.float32, torch.uint8) or not src.is_contiguous():
-        raise ValueError(f"niqe_stats: src must be a contiguous 4-D tensor, fp32 (N, C, H, W) in [0, 1] or uint8 (N, H, W, C), got "
-                         f"{getattr(src, 'dtype', type(src))} {tuple(getattr(src, 'shape', ()))}")
-    u8 = src.dtype == torch.uint8
-    N, Cc, H, W = tuple(src.shape[i] for i in (0, 3, 1, 2)) if u8 else tuple(src.shape)
+    u8, (N, Cc, H, W) = _image_source("niqe_stats", src, "src")
     if Cc not in (1, 3):
         raise ValueError(f"niqe_stats: src must have 1 or 3 channels, got {Cc}")
-    if isinstance(crop_border, bool) or not isinstance(crop_border, int) or crop_border < 0:
-        raise ValueError(f"niqe_stats: crop_border must be an integer >= 0, got {crop_border!r}")
+    check_crop("niqe_stats", crop_border)
     nbh, nbw = max(H - 2 * crop_border, 0) // NIQE_BLOCK, max(W - 2 * crop_border, 0) // NIQE_BLOCK
     if N <= 0 or nbh * nbw < 2:
         raise ValueError(f"niqe_stats: {H}x{W} with crop_border {crop_border} holds {nbh * nbw} block(s) of {NIQE_BLOCK} x {NIQE_BLOCK}; "
@@ -1181,11 +1181,7 @@ def niqe_stats(src, crop_border=0, ws=None):
     need = h.iir_niqe_workspace_bytes(N, Cc, H, W, crop_border)
     if need < 0:
         raise ValueError(f"niqe_stats: unsupported geometry N={N} C={Cc} H={H} W={W} crop_border={crop_border}")
-    if ws is None:
-        ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=src.device)
-    elif not torch.is_tensor(ws) or not ws.is_cuda or ws.device != src.device or not ws.is_contiguous() \
-            or ws.numel() * ws.element_size() < need or ws.data_ptr() % 8:
-        raise ValueError(f"niqe_stats: ws needs {need} contiguous, 8-byte aligned bytes on the images' device")
+    ws = _workspace("niqe_stats", ws, need, src.device)
     out = torch.empty(N, 2, nbh * nbw, NIQE_STATS, dtype=torch.float64, device=src.device)
     L.check(h.iir_niqe_stats(src.data_ptr(), int(u8), N, Cc, H, W, crop_border, ws.data_ptr(), ws.numel() * ws.element_size(),
                              out.data_ptr(), out.numel() * 8, _stream()), "iir_niqe_stats")
@@ -1333,11 +1329,7 @@ def lpips_prep(src, out, affine=None):
     N * H * W rows and at least LPIPS_CPAD columns: columns [0, 3) receive ((2 x - 1) - shift) / scale, [3, LPIPS_CPAD) zeros.
     `affine`: `lpips_affine(...)` (LPIPS's constants when absent)."""
     who = "lpips_prep"
-    if not torch.is_tensor(src) or src.dim() != 4 or src.dtype not in (torch.float32, torch.uint8) or not src.is_contiguous():
-        raise ValueError(f"{who}: src must be a contiguous 4-D tensor, fp32 (N, 3, H, W) in [0, 1] or uint8 (N, H, W, 3), got "
-                         f"{getattr(src, 'dtype', type(src))} {tuple(getattr(src, 'shape', ()))}")
-    u8 = src.dtype == torch.uint8
-    N, Cc, H, W = (tuple(src.shape[i] for i in (0, 3, 1, 2)) if u8 else tuple(src.shape))
+    u8, (N, Cc, H, W) = _image_source(who, src, "src")
     _refuse(who, Cc == 3, f"src must have 3 channels, got {Cc}")
     _refuse(who, min(N, H, W) > 0 and max(H, W) <= 32768 and N * H * W * (LPIPS_CPAD // 8) <= 0x7fffffff * 256,
             f"unsupported geometry N={N} H={H} W={W}")
@@ -1417,12 +1409,7 @@ def lpips_tap(x, pairs, H, W, lin_w, pooled=None, dmap=None, ws=None, out=None):
     h = L.load()
     need = h.iir_lpips_tap_workspace_bytes(pairs, H, W, Cc)
     _refuse(who, need >= 0, f"unsupported geometry pairs={pairs} H={H} W={W} C={Cc}")
-    if ws is None:
-        ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
-    else:
-        _refuse(who, torch.is_tensor(ws) and ws.is_cuda and ws.device == x.device and ws.is_contiguous()
-                and ws.numel() * ws.element_size() >= need and ws.data_ptr() % 8 == 0,
-                f"ws needs {need} contiguous, 8-byte aligned bytes on x's device")
+    ws = _workspace(who, ws, need, x.device, where="x's device")
     if out is None:
         out = torch.empty(pairs, dtype=torch.float64, device=x.device)
     L.check(h.iir_lpips_tap(x.data_ptr(), x.stride(0), pairs, H, W, Cc, lin_w.data_ptr(), _DT[x.dtype], _p(dmap), _p(pooled),

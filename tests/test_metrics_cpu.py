@@ -162,21 +162,21 @@ def test_metrics_module_refusals():
 
 def test_host_forms_become_the_kernels_two_layouts():
     from PIL import Image
-    from instantir_amd import metrics as M
+    from instantir_amd import images as M
     arr = np.random.default_rng(1).integers(0, 255, (16, 20, 3), dtype=np.uint8)
     forms = [Image.fromarray(arr), [Image.fromarray(arr)], arr, arr[None], torch.from_numpy(arr), torch.from_numpy(arr[None])]
     for i, x in enumerate(forms):
-        t, single = M._host_source(x, "a")
+        t, single = M.host_source(x, "a")
         assert t.dtype == torch.uint8 and tuple(t.shape) == (1, 16, 20, 3) and np.array_equal(t[0].numpy(), arr)
         assert single == (i in (0, 2, 4))
     as_f = arr.astype(np.float32) / 255
     for x in (as_f, as_f[None], torch.from_numpy(as_f).permute(2, 0, 1), torch.from_numpy(as_f).permute(2, 0, 1)[None].double()):
-        t, _ = M._host_source(x, "a")
+        t, _ = M.host_source(x, "a")
         assert t.dtype == torch.float32 and tuple(t.shape) == (1, 3, 16, 20)
         assert np.array_equal(t[0].permute(1, 2, 0).numpy(), as_f)
-    g, _ = M._host_source(Image.fromarray(arr[:, :, 0]), "a")
+    g, _ = M.host_source(Image.fromarray(arr[:, :, 0]), "a")
     assert tuple(g.shape) == (1, 16, 20, 1)
-    rgba, _ = M._host_source(Image.fromarray(arr).convert("RGBA"), "a")
+    rgba, _ = M.host_source(Image.fromarray(arr).convert("RGBA"), "a")
     assert tuple(rgba.shape) == (1, 16, 20, 3)
 
 
