@@ -91,6 +91,7 @@ typedef struct iir_gemm_desc {
     /* two SDPA calls + add of :1165,:1185,:1192 on it, so C receives `hidden_states + ip_hidden_states` (before to_out) and q never     */
     /* goes to memory.  Needs: fp16, N % 128 == 0 (head dimension 64), M % 64 == 0, xattn_tq % 64 == 0, 1 <= Tkv[0] <= 80,             */
     /* 1 <= Tkv[1] <= 64, ldk / ldvt / batch strides % 8 == 0, no res / rowbias / act / Ct / c_f32 / wscale / *_stats_out.                */
+    /* out_scale multiplies the finished fp16 output (C = fp16(fp16(O) * out_scale)), never q.                                          */
     const iir_attn_kv* xattn_kv;   /* [2]: text K / V^T, IP-token K / V^T (layouts as for iir_attention_d64_f16)                       */
     int32_t xattn_tq;              /* query rows per image (row m belongs to image m / xattn_tq)                                      */
     /* BASELINE configs[4], both operands in fp8: with `wscale` set and a_fp8 != 0, A holds fp8-E4M3 (OCP) BYTES [M][K] too (lda in    */

@@ -277,7 +277,9 @@ def gemm(a, w, out, bias=None, rowbias=None, rows_per_rb=1, res=None, epi=EPI_PL
     ln_out (fp32 (parts, M, 2), parts = ln_parts(M, N, K)): also leave LayerNorm partials of the rows written.
     ln_in = (partials (parts, M, 2) fp32, colsum (N,) fp32, eps): `a` holds raw rows, `w` / `bias` are an `LnFold`'s.
     xattn = (kv, Tq) with epi = EPI_XATTN: `w` is a cross-attention q projection with `attn_q_factor()` folded in; `out` receives the
-    text + IP cross-attention output of those queries (kv: two tuples as for `attention`, Tq: query rows per image)."""
+    text + IP cross-attention output of those queries (kv: two tuples as for `attention`, Tq: query rows per image).  `out_scale`
+    then scales the FINISHED output, not q: out = fp16(fp16(O_text + O_ip) * out_scale), the write-out's product on the stored fp16
+    tile as for every other epilogue (tests/xattn_ref.py states it; tests/test_xattn_every_case_gpu.py runs it at 0.5)."""
     dt = a.dtype
     if isinstance(w, Fp8Weight):
         w, wscale = w.q, w.scale

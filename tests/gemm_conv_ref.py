@@ -21,6 +21,8 @@ epilogues -- with `rows[m]` the physical output row of logical row m (`y_img_row
            round_E((y1 + res) * out_scale), `res` read through the `res_img_rows` remap; paired epilogues round once (then times
            out_scale); fp32 output: p * out_scale unrounded.  Columns >= tr_from of an `out_t` launch are the caller's to transpose.
   bound  the per-element bound on |got - want| (below);  first_order: the closed form it replaces (kept for comparison).
+  lo, hi the admitted interval of stored values itself (2-byte outputs; bound = max(hi - want, want - lo) + tiny): what a consumer
+           of the stored tile may have been handed (tests/xattn_ref.py: the q of the cross-attention epilogue).
 
 The bound.  Let u = 2^-11 (fp16) / 2^-8 (bf16) be the unit roundoff of the element type E, S = sum_k |a_mk * w_nk| (times the
 scales), g = K * 2^-24 the fp32 accumulation bound, L the activation's Lipschitz constant (1.13 for SiLU / GELU / quick-GELU, 1
@@ -79,7 +81,7 @@ LIPSCHITZ = {ACT_NONE: 1.0, ACT_SILU: 1.13, ACT_GELU: 1.13, ACT_QUICKGELU: 1.13}
 UNIT = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
 TINY = {torch.float16: 2.0 ** -24, torch.bfloat16: 2.0 ** -133}
 
-Ref = collections.namedtuple("Ref", "p want bound first_order rows dtype")
+Ref = collections.namedtuple("Ref", "p want bound first_order rows dtype lo hi", defaults=(None, None))
 
 
 def round_e(x, dtype):
@@ -235,7 +237,7 @@ def reference(kind, spec, c_gelu=None):
     lo, hi = second(round_e(p - d, dt)), second(round_e(p + d, dt))
     bound = torch.maximum(hi - want, want - lo) + tiny
     first_order = u * p.abs() + u * want.abs() + d + tiny
-    return Ref(p, want, bound, first_order, rows, dt)
+    return Ref(p, want, bound, first_order, rows, dt, lo, hi)
 
 
 def compare(got, want, bound):

@@ -722,7 +722,9 @@ def test_conv_groupnorm_from_partials(dev, R, H, Cin, Cout, stride, with_res, si
 def test_gemm_cross_attention_epilogue(dev, R, T, heads, K, tk, ti, fold):
     """`attn2.to_q` (LayerNorm folded or not) whose workgroups run the two SDPA calls + add of TA_IPAttnProcessor2_0
     (module/ip_adapter/attention_processor.py:1140,1165,1185,1192) on the q tile they have just finished.  Against (a) the two
-    launches it replaces -- the same q projection, then `iir_attention_d64_f16` -- and (b) torch in fp32 on that q."""
+    launches it replaces -- the same q projection, then `iir_attention_d64_f16` -- and (b) torch in fp32 on that q.
+    (A tolerance on the step's shapes.  Whether every element is RIGHT -- fp64 reference, derived interval, strided and framed
+    operands, every Tkv edge -- is tests/test_xattn_every_case_gpu.py; the recorded bits are `gemm.f16.xattn` of the hash replay.)"""
     from instantir_amd import ops
     g = torch.Generator().manual_seed(R * T + heads + tk)
     C, M = heads * 64, R * T
