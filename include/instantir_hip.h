@@ -663,6 +663,66 @@ int64_t iir_lpips_tap_workspace_bytes(int32_t pairs, int32_t H, int32_t W, int32
 int iir_lpips_tap(const void* x, int64_t ldx, int32_t pairs, int32_t H, int32_t W, int32_t C, const float* lin_w, int32_t dtype,
                   float* dmap, void* pooled, int64_t ldp, void* ws, int64_t ws_bytes, double* out, void* stream);
 
+/* DISTS (Ding et al., "Image Quality Assessment: Unifying Structure and Texture Similarity", TPAMI 2020; VGG-16), the device
+ * part; no reference counterpart, contract here and in DESIGN.md section 7 "DISTS".  For images a, b as (N, 3, H, W) on a
+ * [0, 1] scale:
+ *   stage 0 is the raw image x itself, fp32, never rounded to a 16-bit type;
+ *   the trunk input is h = (x - mean) / std, mean = (0.485, 0.456, 0.406), std = (0.229, 0.224, 0.225): iir_lpips_prep with
+ *     shift = 2 mean - 1 and scale = 2 std;
+ *   stage 1 is convs 0, 2 of torchvision's VGG-16 `features`, each followed by ReLU (64 channels); stages 2..5 apply L2
+ *     pooling to the stage before and then convs (5, 7), (10, 12, 14), (17, 19, 21), (24, 26, 28), each followed by ReLU
+ *     (128, 256, 512, 512 channels); a stage's feature is what its last ReLU leaves: 3 + 64 + 128 + 256 + 512 + 512 = 1475
+ *     channels in all;
+ *   L2 pooling, per channel:  out(i, j) = sqrt(sum_{di, dj in {-1, 0, 1}} g[di] g[dj] x(2i + di, 2j + dj)^2 + 1e-12),
+ *     g = (0.25, 0.5, 0.25) (np.hanning(5)[1:-1], outer product, normalised), zero padding, stride 2, pad 1: output sides
+ *     ceil(H / 2), ceil(W / 2);
+ *   score: with n = H_k W_k pixels per channel c of stage k, mu_a, mu_b the means, s_a^2 = E[a^2] - mu_a^2 (s_b^2 likewise),
+ *     s_ab = E[ab] - mu_a mu_b:  S1 = (2 mu_a mu_b + c1) / (mu_a^2 + mu_b^2 + c1),  S2 = (2 s_ab + c2) / (s_a^2 + s_b^2 + c2),
+ *     c1 = c2 = 1e-6;  DISTS = 1 - sum_c (alpha_c S1_c + beta_c S2_c) / (sum alpha + sum beta).  The divisions by n, S1, S2 and
+ *     the weighting are the host side's (instantir_amd/dists.py, torch fp64 on the device); the entries below give raw sums.
+ * The thirteen convs run through iir_conv2d_nhwc_f16 with a bias and IIR_ACT_NONE on an (a, b) pair stacked as one batch, as
+ * for LPIPS.  16-bit tensors are fp16 or bf16 by `dtype` (IIR_DT_*), NHWC rows with a pixel stride.  All entries: every global
+ * load is unconditional from a clamped address and masked in registers, only stores are guarded, 64-bit offsets, no atomics,
+ * sums in an order that depends on the geometry alone: equal inputs give equal bits.
+ *
+ * iir_dists_l2pool: x holds a stage's last conv's PRE-activation rows (bias added, no ReLU; as iir_lpips_tap takes them) of
+ *   `images` images of H x W pixels and C channels, pixel stride ldx; the ReLU is applied on read.  out: (images, ceil(H / 2),
+ *   ceil(W / 2), C) of pixel stride ldo in the same 16-bit type; columns [C, ldo) keep their bits.  Arithmetic is fp32: the
+ *   squares of 16-bit values and the power-of-two weights are exact, the nine terms are added in raster order of (di, dj), then
+ *   + 1e-12f, sqrtf, one rounding to the 16-bit type.  A tap outside the image is multiplied by 0.  H = W = 1 is legal.
+ *   IIR_EINVAL, before any HIP call: a NULL or not 16-byte aligned x or out; images, H, W or C <= 0; H or W > 32768; C % 8 or
+ *   C > IIR_LPIPS_MAX_C; ldx or ldo < C or % 8; another dtype; out overlapping x; a grid beyond 31 bits.
+ *
+ * iir_dists_stats: x is stacked as for iir_lpips_tap: 2 * pairs images of H x W pixels and C channels, pixel stride ldx, images
+ *   [0, pairs) the `a` half, image pairs + i the `b` partner of image i; PRE-activation rows, the ReLU on read; columns
+ *   [C, ldx) are never read.  out: double[pairs][C][IIR_DISTS_STATS] = {sum a, sum b, sum a^2, sum b^2, sum ab} over the H * W
+ *   pixels.  Every product and every sum is fp64 from the first element: a 16-bit value converts exactly and the product of two
+ *   is exact in fp64, so the only error is the summation's, at most (n - 1) 2^-53 sum |terms|.  A lane adds the pixels it
+ *   strides through in index order, the lanes of a channel group add by a fixed tree in LDS, each workgroup leaves a partial in
+ *   ws, and a second launch adds the partials in a fixed order; the share of a workgroup depends on H * W and C alone, so `pairs` = 2 gives
+ *   each pair the bits of its own launch.
+ *   ws: iir_dists_stats_workspace_bytes(pairs, H, W, C) bytes, 8-byte aligned (-1 for a geometry this entry refuses).
+ *   IIR_EINVAL, before any HIP call: a NULL x, ws or out; pairs, H, W or C <= 0; pairs > 65535; H or W > 32768; C % 8 or
+ *   C > IIR_LPIPS_MAX_C; ldx < C or ldx % 8; x not 16-byte aligned; ws too small or ws / out not 8-byte aligned; another dtype;
+ *   a grid beyond 31 bits.
+ *
+ * iir_dists_image_stats: the same five sums for stage 0, read from the two image sources of iir_lpips_prep: N images of 3
+ *   channels each, both fp32 planar (N, 3, H, W) on a [0, 1] scale or, with src_u8, both uint8 interleaved (N, H, W, 3) with
+ *   x = u / 255 as one fp32 division, so a uint8 image and its fp32 copy give equal bits.  An fp32 value converts to fp64
+ *   exactly; a product of two is rounded once (fma into the sum).  out: double[N][3][IIR_DISTS_STATS].  The reduction is
+ *   iir_dists_stats' (one template).  ws: iir_dists_image_stats_workspace_bytes(N, H, W) bytes, 8-byte aligned.
+ *   IIR_EINVAL, before any HIP call: a NULL src_a, src_b, ws or out; N, H or W <= 0; N > 65535; H or W > 32768; an fp32 source
+ *   not 4-byte aligned; ws too small or ws / out not 8-byte aligned; a grid beyond 31 bits. */
+#define IIR_DISTS_STATS 5
+int iir_dists_l2pool(const void* x, int64_t ldx, int32_t images, int32_t H, int32_t W, int32_t C, int32_t dtype, void* out,
+                     int64_t ldo, void* stream);
+int64_t iir_dists_stats_workspace_bytes(int32_t pairs, int32_t H, int32_t W, int32_t C);
+int iir_dists_stats(const void* x, int64_t ldx, int32_t pairs, int32_t H, int32_t W, int32_t C, int32_t dtype, void* ws,
+                    int64_t ws_bytes, double* out, void* stream);
+int64_t iir_dists_image_stats_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int iir_dists_image_stats(const void* src_a, const void* src_b, int32_t src_u8, int32_t N, int32_t H, int32_t W, void* ws,
+                          int64_t ws_bytes, double* out, void* stream);
+
 /* NIQE (Mittal et al. 2013, as basicsr's calculate_niqe restates the MATLAB release), the device part: the per-block signed
  * moments of the luma's natural-scene statistics at two scales; no reference counterpart, contract here and in DESIGN.md
  * section 7 "NIQE".  The AGGD fit, the 36 features per block, the Gaussian model and the distance are the host's, in fp64

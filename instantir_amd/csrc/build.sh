@@ -41,6 +41,8 @@ hipcc $FLAGS -ffp-contract=off -c lpips.hip -o build/lpips.o &
 pids+=($!)
 hipcc $FLAGS -ffp-contract=off -c niqe.hip -o build/niqe.o &
 pids+=($!)
+hipcc $FLAGS -ffp-contract=off -c dists.hip -o build/dists.o &
+pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT build/gemm_conv.o build/gemm8.o build/attention.o build/attention_hd.o build/attention_1h.o build/norm.o build/pointwise.o build/freeu.o build/colorfix.o build/regionmap.o build/seg.o build/lqfidelity.o build/resample.o build/metrics.o build/degrade.o build/lpips.o build/niqe.o
+hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT build/gemm_conv.o build/gemm8.o build/attention.o build/attention_hd.o build/attention_1h.o build/norm.o build/pointwise.o build/freeu.o build/colorfix.o build/regionmap.o build/seg.o build/lqfidelity.o build/resample.o build/metrics.o build/degrade.o build/lpips.o build/niqe.o build/dists.o
 echo "built $(realpath $OUT)"

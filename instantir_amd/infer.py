@@ -16,6 +16,7 @@ guidance on (`pipe.enable_apg(...)`: the CFG update's saturating parallel part d
 `--gt_path DIR` scores every saved image against the file of the same name in DIR (PSNR / SSIM on the device,
 `instantir_amd.metrics`), `--input_fidelity` against its own input file; the figures go to `metrics.json` in the output directory.
 `--lpips_path PATH [--lpips_lin_path PATH]` adds LPIPS (VGG-16, `instantir_amd.lpips`) to each scored pair.
+`--dists_path PATH [--dists_weights_path PATH]` adds DISTS (VGG-16 with L2 pooling, `instantir_amd.dists`) likewise.
 `--niqe_path PARAMS` scores every saved image with NIQE (`instantir_amd.niqe`), which needs no second image.
 `--degrade PRESET_OR_JSON [--degrade_seed N]` treats the files of `--test_path` as clean images: each is degraded on the device
 (`instantir_amd.degrade`), the 8-bit result stands in for the file that was read and is saved with its recipe under `lq/` in the
@@ -192,6 +193,11 @@ def build_parser():
                         "torchvision VGG-16 state dict together with --lpips_lin_path (instantir_amd.lpips)")
     p.add_argument("--lpips_lin_path", type=str, default=None, metavar="PATH",
                    help="the lin layers of LPIPS (lpips' vgg.pth) when --lpips_path is a torchvision VGG-16 state dict")
+    p.add_argument("--dists_path", type=str, default=None, metavar="PATH",
+                   help="add DISTS (VGG-16) to every pair --gt_path / --input_fidelity score: a whole DISTS state dict, or a "
+                        "torchvision VGG-16 state dict together with --dists_weights_path (instantir_amd.dists)")
+    p.add_argument("--dists_weights_path", type=str, default=None, metavar="PATH",
+                   help="alpha and beta of DISTS (its weights.pt) when --dists_path is a torchvision VGG-16 state dict")
     p.add_argument("--niqe_path", type=str, default=None, metavar="PARAMS",
                    help="score every saved image with NIQE (no ground truth needed) under the pristine model in PARAMS: basicsr's "
                         "niqe_pris_params.npz, the MATLAB release's .mat, or `python -m instantir_amd.niqe fit`'s output; with "
@@ -282,6 +288,23 @@ def apply_lpips(args):
     return {"path": path, "lin_path": lin}
 
 
+def apply_dists(args):
+    """`--dists_path PATH [--dists_weights_path PATH]` -> {"path", "weights_path"}, or None without the flag (an addition: the
+    reference reports no figures).  Refused as `apply_lpips` refuses: the weights file without the flag, the flag without a
+    comparison to add the figure to, and a file that does not exist."""
+    path, weights = getattr(args, "dists_path", None), getattr(args, "dists_weights_path", None)
+    if path is None:
+        if weights is not None:
+            raise SystemExit("--dists_weights_path needs --dists_path")
+        return None
+    if getattr(args, "gt_path", None) is None and not getattr(args, "input_fidelity", False):
+        raise SystemExit("--dists_path needs --gt_path or --input_fidelity")
+    for flag, f in (("--dists_path", path), ("--dists_weights_path", weights)):
+        if f is not None and not os.path.isfile(f):
+            raise SystemExit(f"{flag} {f} is not a file")
+    return {"path": path, "weights_path": weights}
+
+
 def apply_niqe(args):
     """`--niqe_path PARAMS` -> {"path", "crop_border", "input"}, or None without the flag (an addition: the reference reports no
     figures).  NIQE needs no comparison: the flag stands on its own, takes `--metrics_crop`, and with `--input_fidelity` scores
@@ -328,6 +351,15 @@ def build_lpips(setup, device):
         raise SystemExit(f"--lpips_path: {e}")
 
 
+def build_dists(setup, device):
+    """The DISTS model of `apply_dists`' settings on `device`; a file that is not one of the two formats ends the run."""
+    from .dists import DISTS
+    try:
+        return DISTS.from_files(setup["path"], setup["weights_path"], device=device)
+    except ValueError as e:
+        raise SystemExit(f"--dists_path: {e}")
+
+
 def gt_image(setup, name, size):
     """The ground truth of input `name` at `size` = (width, height); a missing file or another size ends the run, naming it."""
     path = os.path.join(setup["gt_path"], name)
@@ -339,14 +371,17 @@ def gt_image(setup, name, size):
     return im
 
 
-def score_saved(setup, saved_path, gt, original, device, lpips_model=None):
+def score_saved(setup, saved_path, gt, original, device, lpips_model=None, dists_model=None):
     """The figures of one saved file, from the 8-bit image as it was saved (read back): {"psnr", "ssim"} against `gt`,
-    {"input_psnr", "input_ssim"} against `original`, whichever were asked for; with an `lpips_model` "lpips" / "input_lpips" too."""
+    {"input_psnr", "input_ssim"} against `original`, whichever were asked for; with an `lpips_model` "lpips" / "input_lpips" too,
+    with a `dists_model` "dists" / "input_dists"."""
     from . import metrics as M
     saved = Image.open(saved_path).convert("RGB")
     kw = dict(metrics=setup["metrics"], crop_border=setup["crop_border"], y_channel=setup["y_channel"], device=device)
     if lpips_model is not None:
         kw["lpips_model"] = lpips_model
+    if dists_model is not None:
+        kw["dists_model"] = dists_model
     row = {}
     try:
         if gt is not None:
@@ -524,10 +559,12 @@ def main(args, device, rank=0, world=1):
     degrading = apply_degrade(args)              # (before apply_metrics: it may set --gt_path)
     scoring = apply_metrics(args)
     lpips_setup = apply_lpips(args)
+    dists_setup = apply_dists(args)
     niqe_setup = apply_niqe(args)
     niqe_model = build_niqe(niqe_setup) if niqe_setup else None
     pipe, lcm_scheduler = build_pipeline(args, device)
     lpips_model = build_lpips(lpips_setup, device) if lpips_setup else None
+    dists_model = build_dists(dists_setup, device) if dists_setup else None
     apply_freeu(pipe, args)
     apply_scheduler(pipe, args)
     pag_kw = apply_pag(pipe, args)
@@ -593,13 +630,16 @@ def main(args, device, rank=0, world=1):
             rec.save(f"{out_dir}/{lq_batch[i]}")
             if scoring:
                 scores[lq_batch[i]] = score_saved(scoring, f"{out_dir}/{lq_batch[i]}", gts[i] if gts else None,
-                                                  originals[i] if scoring["input_fidelity"] else None, device, lpips_model)
+                                                  originals[i] if scoring["input_fidelity"] else None, device, lpips_model,
+                                                  dists_model)
             if niqe_setup:
                 scores.setdefault(lq_batch[i], {}).update(score_niqe(niqe_setup, niqe_model, f"{out_dir}/{lq_batch[i]}", originals[i], device))
     if scoring or niqe_setup:
         setup = dict(scoring or {})
         if lpips_setup:
             setup["lpips"] = lpips_setup
+        if dists_setup:
+            setup["dists"] = dists_setup
         if niqe_setup:
             setup["niqe"] = niqe_setup
         print(write_metrics(setup, scores, out_dir, rank, world))

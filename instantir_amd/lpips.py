@@ -37,21 +37,84 @@ def _pad64(c):
     return (c + 63) // 64 * 64
 
 
+def get_tensor(src, key, who):
+    """`src[key]` as fp32 on the CPU; a missing key raises ValueError naming it (`who`: "LPIPS weights", "DISTS weights")."""
+    if key not in src:
+        raise ValueError(f"{who}: missing key {key}")
+    return src[key].detach().to("cpu", torch.float32)
+
+
+def get_conv(sd, name, cin, who):
+    """(weight (Cout, cin, 3, 3), bias (Cout,)) of the VGG conv stored under `name`, checked: a kernel that is not 3x3, a width
+    that is not a multiple of 8 and a channel count that does not follow from the layer before raise ValueError naming the key."""
+    w, b = get_tensor(sd, name + ".weight", who), get_tensor(sd, name + ".bias", who)
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError(f"{who}: {name}.weight must be a (Cout, Cin, 3, 3) kernel, got {tuple(w.shape)}")
+    if w.shape[0] % 8:
+        raise ValueError(f"{who}: {name}.weight has {w.shape[0]} output channels, not a multiple of 8")
+    if w.shape[1] != cin:
+        raise ValueError(f"{who}: {name}.weight reads {w.shape[1]} channels but the layer before it writes {cin}")
+    if tuple(b.shape) != (w.shape[0],):
+        raise ValueError(f"{who}: {name}.bias must hold {w.shape[0]} values, got {tuple(b.shape)}")
+    return w, b
+
+
+def synthetic_convs(g, widths, name_of, who):
+    """The thirteen seeded convs of a stand-in VGG-16 as state-dict entries `name_of(k, i)`: He-initialised weights
+    (N(0, 2 / fan_in)) and biases 0.02 N(0, 1), drawn in execution order from the generator `g`."""
+    widths = tuple(int(w) for w in widths)
+    if len(widths) != 5 or any(w <= 0 or w % 8 for w in widths):
+        raise ValueError(f"{who}.synthetic: widths must be five positive multiples of 8, got {widths}")
+    sd, cin = {}, 3
+    for k, (idx, cout) in enumerate(zip(SLICES, widths), 1):
+        for i in idx:
+            sd[name_of(k, i) + ".weight"] = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5
+            sd[name_of(k, i) + ".bias"] = torch.randn(cout, generator=g) * 0.02
+            cin = cout
+    return sd, widths
+
+
+def pack_convs(convs, device, dtype):
+    """The convs as `ops.conv2d` reads them, on `device`: NHWC weights and biases in `dtype`, every channel count padded to whole
+    64-channel K tiles; zero weights and biases keep the padding channels at exactly 0."""
+    packed, cin = [], ops.LPIPS_CPAD
+    for w, b in convs:
+        cout = _pad64(w.shape[0])
+        wp = torch.zeros(cout, 3, 3, cin, dtype=dtype)
+        wp[:w.shape[0]] = conv_weight_nhwc(w.to(dtype), cin)
+        bp = torch.zeros(cout, dtype=dtype)
+        bp[:w.shape[0]] = b.to(dtype)
+        packed.append((wp.to(device), bp.to(device)))
+        cin = cout
+    return packed
+
+
+def pair_buffers(arena, half):
+    """The two activation buffers of `half` elements a pair ping-pongs between, from `arena` (grown when it is too small)."""
+    need = 2 * ((half + 127) // 128 * 128)
+    if arena.buf is None or arena.buf.numel() < need:
+        arena.reserve(need)
+    arena.reset()
+    return arena.alloc(1, half)[0], arena.alloc(1, half)[0]
+
+
+def check_pair_geometry(who, H, W, nbytes, why):
+    """Raised before any launch: a side below MIN_SIDE (`why`); a largest activation of a pair (`nbytes`) of 2 GiB or more, the
+    limit of the conv's plain stores."""
+    if min(H, W) < MIN_SIDE:
+        raise ValueError(f"{who}: the smallest side is {MIN_SIDE} ({why}), got {H}x{W}")
+    if nbytes >= 1 << 31:
+        raise ValueError(f"{who} of a {H}x{W} pair: its largest activation ({nbytes} bytes) reaches 2 GiB, beyond what the conv "
+                         "launches have been verified for; score crops or a smaller size")
+
+
 def synthetic_state_dict(seed, widths=VGG_WIDTHS):
     """A whole-`lpips.LPIPS` state dict (format (b) of `parse_state_dict`) of seeded fp32 CPU tensors: He-initialised convs
     (N(0, 2 / fan_in)), biases 0.02 N(0, 1), lin weights uniform in [0, 1) -- all drawn in this order from one
     torch.Generator, the way tests/golden/seeded.py fills its modules."""
-    widths = tuple(int(w) for w in widths)
-    if len(widths) != 5 or any(w <= 0 or w % 8 for w in widths):
-        raise ValueError(f"LPIPS.synthetic: widths must be five positive multiples of 8, got {widths}")
     g = torch.Generator()
     g.manual_seed(int(seed))
-    sd, cin = {}, 3
-    for k, (idx, cout) in enumerate(zip(SLICES, widths), 1):
-        for i in idx:
-            sd[f"net.slice{k}.{i}.weight"] = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5
-            sd[f"net.slice{k}.{i}.bias"] = torch.randn(cout, generator=g) * 0.02
-            cin = cout
+    sd, widths = synthetic_convs(g, widths, lambda k, i: f"net.slice{k}.{i}", "LPIPS")
     for l, c in enumerate(widths):
         sd[f"lin{l}.model.1.weight"] = torch.rand(1, c, 1, 1, generator=g)
     return sd
@@ -72,26 +135,13 @@ def parse_state_dict(sd, lin_sd=None):
         raise ValueError("LPIPS weights: a torchvision VGG-16 state dict needs the lin layers too (lin_path: lpips' vgg.pth, "
                          "keys lin{l}.model.1.weight)")
 
-    def get(src, key):
-        if key not in src:
-            raise ValueError(f"LPIPS weights: missing key {key}")
-        return src[key].detach().to("cpu", torch.float32)
-
+    who = "LPIPS weights"
+    get = lambda src, key: get_tensor(src, key, who)
     convs, lins, cin = [], [], 3
     for k, idx in enumerate(SLICES, 1):
         for i in idx:
-            name = f"net.slice{k}.{i}" if whole else f"features.{i}"
-            w, b = get(sd, name + ".weight"), get(sd, name + ".bias")
-            if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
-                raise ValueError(f"LPIPS weights: {name}.weight must be a (Cout, Cin, 3, 3) kernel, got {tuple(w.shape)}")
-            if w.shape[0] % 8:
-                raise ValueError(f"LPIPS weights: {name}.weight has {w.shape[0]} output channels, not a multiple of 8")
-            if w.shape[1] != cin:
-                raise ValueError(f"LPIPS weights: {name}.weight reads {w.shape[1]} channels but the layer before it writes {cin}")
-            if tuple(b.shape) != (w.shape[0],):
-                raise ValueError(f"LPIPS weights: {name}.bias must hold {w.shape[0]} values, got {tuple(b.shape)}")
-            convs.append((w, b))
-            cin = w.shape[0]
+            convs.append(get_conv(sd, f"net.slice{k}.{i}" if whole else f"features.{i}", cin, who))
+            cin = convs[-1][0].shape[0]
         key = f"lin{k - 1}.model.1.weight"
         lin = get(lin_src, key)
         if lin.numel() != cin or tuple(lin.shape) not in ((1, cin, 1, 1), (cin,)):
@@ -119,16 +169,8 @@ class LPIPS:
             raise ValueError("LPIPS: dtype must be torch.float16 (default) or torch.bfloat16")
         self.device, self.dtype, self.dtype_name = scoring_device(device, "instantir_amd.lpips"), dtype, DTYPES[dtype]
         self.widths = tuple(convs[j][0].shape[0] for j in (1, 3, 6, 9, 12))
-        self.padded = tuple(_pad64(c) for c in self.widths)          # the conv reads whole 64-channel K tiles: zero weights and
-        self.w, cin = [], ops.LPIPS_CPAD                             #   biases keep the padding channels at exactly 0
-        for w, b in convs:
-            cout = _pad64(w.shape[0])
-            wp = torch.zeros(cout, 3, 3, cin, dtype=dtype)
-            wp[:w.shape[0]] = conv_weight_nhwc(w.to(dtype), cin)
-            bp = torch.zeros(cout, dtype=dtype)
-            bp[:w.shape[0]] = b.to(dtype)
-            self.w.append((wp.to(self.device), bp.to(self.device)))
-            cin = cout
+        self.padded = tuple(_pad64(c) for c in self.widths)          # the conv reads whole 64-channel K tiles (pack_convs)
+        self.w = pack_convs(convs, self.device, dtype)
         self.lin = []
         for lin, cp in zip(lins, self.padded):
             lp = torch.zeros(cp, dtype=torch.float32)
@@ -161,23 +203,14 @@ class LPIPS:
     def _check_geometry(self, H, W):
         """Raised before any launch: a side below 16 leaves the fifth tap without a pixel; the largest activation of a pair (both
         images at full resolution in the first slice's channels) must stay below 2 GiB, the limit of the conv's plain stores."""
-        if min(H, W) < MIN_SIDE:
-            raise ValueError(f"LPIPS: the smallest side is {MIN_SIDE} (four 2x2 pools must leave the fifth tap a pixel), got {H}x{W}")
-        nbytes = self._largest_activation_bytes(H, W)
-        if nbytes >= 1 << 31:
-            raise ValueError(f"LPIPS of a {H}x{W} pair: its largest activation ({nbytes} bytes) reaches 2 GiB, beyond what the conv "
-                             "launches have been verified for; score crops or a smaller size")
+        check_pair_geometry("LPIPS", H, W, self._largest_activation_bytes(H, W), "four 2x2 pools must leave the fifth tap a pixel")
 
     # ---- the network --------------------------------------------------------------------------------
     def _pair(self, a, b, H, W, out, maps):
         """One pair through the network: a, b sources of one image each; out fp64 (5, 1) views; maps: five (1, H_l, W_l) or None."""
         o, A = ops, self.arena
         half = max(2 * h * w * c for (h, w), c in zip(self.tap_sizes(H, W), (max(ops.LPIPS_CPAD, self.padded[0]),) + self.padded[1:]))
-        need = 2 * ((half + 127) // 128 * 128)
-        if A.buf is None or A.buf.numel() < need:
-            A.reserve(need)
-        A.reset()
-        cur, other = A.alloc(1, half)[0], A.alloc(1, half)[0]
+        cur, other = pair_buffers(A, half)
         rows = 2 * H * W
         x = cur[:rows * ops.LPIPS_CPAD].view(rows, ops.LPIPS_CPAD)
         o.lpips_prep(a, x[:H * W], self.affine)

@@ -99,11 +99,15 @@ def _with_means(res):
     return res
 
 
-def _lpips_scores(who, a, b, model, device):
+def _model_scores(who, a, b, model, device, name):
     d = None if device is None else torch.device(device)
     if d is not None and (d.type != model.device.type or (d.index is not None and d.index != model.device.index)):
-        raise ValueError(f"{who}: the LPIPS model lives on {model.device}, not on {d}")
+        raise ValueError(f"{who}: the {name} model lives on {model.device}, not on {d}")
     return model(a, b).cpu().tolist()
+
+
+def _lpips_scores(who, a, b, model, device):
+    return _model_scores(who, a, b, model, device, "LPIPS")
 
 
 def lpips(a, b, model, device=None):
@@ -116,6 +120,15 @@ def lpips(a, b, model, device=None):
     return out[0] if single_a and single_b else out
 
 
+def dists(a, b, model, device=None):
+    """DISTS of `a` against `b` under `model` (an `instantir_amd.dists.DISTS`; DESIGN.md section 7 "DISTS"): a float for one
+    image, a list of floats for a batch; 0 for identical images.  The whole image is scored, as for LPIPS."""
+    _, single_a = host_source(a, "a")
+    _, single_b = host_source(b, "b")
+    out = _model_scores("dists", a, b, model, device, "DISTS")
+    return out[0] if single_a and single_b else out
+
+
 def niqe(images, model, crop_border=0, device=None):
     """NIQE of `images` under `model` (an `instantir_amd.niqe.NIQE`; DESIGN.md section 7 "NIQE"): no second image is needed.  A
     float for one image, a list of floats for a batch; lower is better.  C = 3 is scored on its BT.601 luma."""
@@ -124,20 +137,25 @@ def niqe(images, model, crop_border=0, device=None):
     return out[0] if single else out
 
 
-def evaluate(a, b, metrics=METRICS, crop_border=0, y_channel=False, quantize=False, device=None, lpips_model=None):
+def evaluate(a, b, metrics=METRICS, crop_border=0, y_channel=False, quantize=False, device=None, lpips_model=None, dists_model=None):
     """Both figures in one launch pair: {"psnr": [per image], "ssim": [per image], "psnr_mean": .., "ssim_mean": ..} (only the
     metrics asked for).  `quantize` (a flag, or one per argument) rounds a float source to the 8-bit image that would be saved.
-    With an `lpips_model` the result gains "lpips" and "lpips_mean" (of the whole, uncropped RGB images)."""
+    With an `lpips_model` the result gains "lpips" and "lpips_mean" (of the whole, uncropped RGB images), with a `dists_model`
+    "dists" and "dists_mean" likewise."""
     res, _ = _run("evaluate", a, b, metrics, crop_border, y_channel, quantize, device)
     if lpips_model is not None:
         res["lpips"] = _lpips_scores("evaluate", a, b, lpips_model, device)
+    if dists_model is not None:
+        res["dists"] = _model_scores("evaluate", a, b, dists_model, device, "DISTS")
     return _with_means(res)
 
 
-def input_fidelity(restored, lq, filter="bicubic", metrics=METRICS, crop_border=0, y_channel=False, device=None, lpips_model=None):
+def input_fidelity(restored, lq, filter="bicubic", metrics=METRICS, crop_border=0, y_channel=False, device=None, lpips_model=None,
+                   dists_model=None):
     """How far the restoration moved from what it was given: `restored` is brought to the size of `lq` with `ops.resample`
     (PIL's `filter`; quantised mode when both are 8-bit, untouched at equal sizes) and scored against `lq`.  Returns what
-    `evaluate` returns ("lpips" included when an `lpips_model` is given: of the resized restoration against `lq`)."""
+    `evaluate` returns ("lpips" / "dists" included when an `lpips_model` / a `dists_model` is given: of the resized restoration
+    against `lq`)."""
     from . import ops
     from .resample import FILTERS
     if filter not in FILTERS:
@@ -161,4 +179,6 @@ def input_fidelity(restored, lq, filter="bicubic", metrics=METRICS, crop_border=
     res = _score(tr, tl, names, crop_border, y_channel, quantize, dev if dev is not None else device)
     if lpips_model is not None:
         res["lpips"] = _lpips_scores("input_fidelity", tr, tl, lpips_model, device)
+    if dists_model is not None:
+        res["dists"] = _model_scores("input_fidelity", tr, tl, dists_model, device, "DISTS")
     return _with_means(res)

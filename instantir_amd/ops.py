@@ -1359,10 +1359,10 @@ def relu_(x):
     return x
 
 
-def _chk_tap_geometry(who, pairs, H, W, Cc):
-    for name, v in (("pairs", pairs), ("H", H), ("W", W)):
+def _chk_tap_geometry(who, pairs, H, W, Cc, count="pairs"):
+    for name, v in ((count, pairs), ("H", H), ("W", W)):
         _refuse(who, not isinstance(v, bool) and isinstance(v, int) and v > 0, f"{name} must be a positive integer, got {v!r}")
-    _refuse(who, pairs <= 65535 and max(H, W) <= 32768, f"unsupported geometry pairs={pairs} H={H} W={W} (pairs <= 65535, sides <= 32768)")
+    _refuse(who, pairs <= 65535 and max(H, W) <= 32768, f"unsupported geometry {count}={pairs} H={H} W={W} ({count} <= 65535, sides <= 32768)")
     _refuse(who, Cc > 0 and Cc % 8 == 0 and Cc <= LPIPS_MAX_C, f"the channel count must be a multiple of 8 up to {LPIPS_MAX_C}, got {Cc}")
 
 
@@ -1417,4 +1417,117 @@ def lpips_tap(x, pairs, H, W, lin_w, pooled=None, dmap=None, ws=None, out=None):
     L.check(h.iir_lpips_tap(x.data_ptr(), x.stride(0), pairs, H, W, Cc, lin_w.data_ptr(), _DT[x.dtype], _p(dmap), _p(pooled),
                             0 if pooled is None else pooled.stride(0), ws.data_ptr(), ws.numel() * ws.element_size(), out.data_ptr(),
                             _stream()), "iir_lpips_tap")
+    return out
+
+
+DISTS_STATS = L.MACROS["IIR_DISTS_STATS"]         # sum a, sum b, sum a^2, sum b^2, sum ab
+DISTS_MEAN = (0.485, 0.456, 0.406)                # the ImageNet normalisation in front of DISTS's trunk
+DISTS_STD = (0.229, 0.224, 0.225)
+
+
+def dists_affine(device, mean=DISTS_MEAN, std=DISTS_STD):
+    """(x - mean) / std as `lpips_prep` computes it: ((2 x - 1) - shift) / scale with shift = 2 mean - 1, scale = 2 std."""
+    return lpips_affine(device, tuple(2.0 * float(m) - 1.0 for m in mean), tuple(2.0 * float(s) for s in std))
+
+
+def dists_l2pool(x, images, H, W, out=None):
+    """DISTS's L2 pooling (iir_dists_l2pool; DESIGN.md section 7 "DISTS").  `x`: 2-D fp16 / bf16 view of images * H * W rows, the
+    pre-activation output of a stage's last conv (the ReLU is applied on read); its column count C is the width.  Returns `out`, a
+    2-D view of images * ceil(H / 2) * ceil(W / 2) rows and at least C columns of x's dtype (allocated here when absent):
+    sqrt(hann3x3 * relu(x)^2 + 1e-12), stride 2, zero padding 1; columns past C keep their bits."""
+    who = "dists_l2pool"
+    _refuse(who, torch.is_tensor(x) and x.dim() == 2, f"x must be a 2-D tensor, got {tuple(getattr(x, 'shape', ()))}")
+    Cc = x.shape[1]
+    _chk_tap_geometry(who, images, H, W, Cc, count="images")
+    _chk_rows16(who, "x", x, images * H * W, Cc)
+    orows = images * ((H + 1) // 2) * ((W + 1) // 2)
+    _refuse(who, orows * (Cc // 8) <= 0x7fffffff * 256, f"unsupported geometry images={images} H={H} W={W} C={Cc}")
+    if out is None:
+        out = torch.empty(orows, Cc, dtype=x.dtype, device=x.device)
+    _chk_rows16(who, "out", out, orows, Cc)
+    _refuse(who, out.dtype == x.dtype, f"out must have x's dtype {x.dtype}, got {out.dtype}")
+    _chk_cuda(who, x, out)
+    lo_x, hi_x = x.data_ptr(), x.data_ptr() + x.shape[0] * x.stride(0) * 2          # whole rows, as the entry counts them
+    _refuse(who, not (out.data_ptr() < hi_x and lo_x < out.data_ptr() + orows * out.stride(0) * 2),
+            "out overlaps x (other windows of x are still to be read)")
+    L.check(L.load().iir_dists_l2pool(x.data_ptr(), x.stride(0), images, H, W, Cc, _DT[x.dtype], out.data_ptr(), out.stride(0), _stream()),
+            "iir_dists_l2pool")
+    return out
+
+
+def dists_stats_workspace_bytes(pairs, H, W, C):
+    """Bytes of fp64 partial sums `dists_stats` needs for `pairs` image pairs of H x W pixels and C channels."""
+    _chk_tap_geometry("dists_stats_workspace_bytes", pairs, H, W, C)
+    need = L.load().iir_dists_stats_workspace_bytes(pairs, H, W, C)
+    _refuse("dists_stats_workspace_bytes", need >= 0, f"unsupported geometry pairs={pairs} H={H} W={W} C={C}")
+    return int(need)
+
+
+def _chk_stats_out(who, out, rows, Cc, tensors):
+    if out is not None:
+        _refuse(who, torch.is_tensor(out) and out.dtype == torch.float64 and tuple(out.shape) == (rows, Cc, DISTS_STATS) and out.is_contiguous(),
+                f"out must be a contiguous fp64 ({rows}, {Cc}, {DISTS_STATS}) tensor")
+        tensors.append(out)
+
+
+def dists_stats(x, pairs, H, W, ws=None, out=None):
+    """The per-channel sums DISTS compares (iir_dists_stats; DESIGN.md section 7 "DISTS").  `x`: 2-D fp16 / bf16 view of
+    2 * pairs * H * W rows, the pre-activation output of a stage's last conv for the `a` images followed by their `b` partners
+    (the ReLU is applied on read); its column count C is the width.  Returns fp64 (pairs, C, 5): {sum a, sum b, sum a^2, sum b^2,
+    sum ab} over the H * W pixels, every product and sum in fp64.  `ws`: a byte workspace of at least
+    `dists_stats_workspace_bytes` (allocated here when absent)."""
+    who = "dists_stats"
+    _refuse(who, torch.is_tensor(x) and x.dim() == 2, f"x must be a 2-D tensor, got {tuple(getattr(x, 'shape', ()))}")
+    Cc = x.shape[1]
+    _chk_tap_geometry(who, pairs, H, W, Cc)
+    _chk_rows16(who, "x", x, 2 * pairs * H * W, Cc)
+    tensors = [x]
+    _chk_stats_out(who, out, pairs, Cc, tensors)
+    _chk_cuda(who, *tensors)
+    h = L.load()
+    need = h.iir_dists_stats_workspace_bytes(pairs, H, W, Cc)
+    _refuse(who, need >= 0, f"unsupported geometry pairs={pairs} H={H} W={W} C={Cc}")
+    ws = _workspace(who, ws, need, x.device, where="x's device")
+    if out is None:
+        out = torch.empty(pairs, Cc, DISTS_STATS, dtype=torch.float64, device=x.device)
+    L.check(h.iir_dists_stats(x.data_ptr(), x.stride(0), pairs, H, W, Cc, _DT[x.dtype], ws.data_ptr(), ws.numel() * ws.element_size(),
+                              out.data_ptr(), _stream()), "iir_dists_stats")
+    return out
+
+
+def _chk_image_pair(who, a, b):
+    u8, da = _image_source(who, a, "a")
+    u8b, db = _image_source(who, b, "b")
+    _refuse(who, u8 == u8b and da == db, f"a and b must share a dtype and a shape, got {a.dtype} {tuple(a.shape)} and {b.dtype} {tuple(b.shape)}")
+    N, Cc, H, W = da
+    _refuse(who, Cc == 3, f"a and b must have 3 channels, got {Cc}")
+    _refuse(who, min(N, H, W) > 0 and N <= 65535 and max(H, W) <= 32768, f"unsupported geometry N={N} H={H} W={W} (N <= 65535, sides <= 32768)")
+    return u8, N, H, W
+
+
+def dists_image_stats_workspace_bytes(N, H, W):
+    """Bytes of fp64 partial sums `dists_image_stats` needs for N image pairs of H x W pixels."""
+    _chk_tap_geometry("dists_image_stats_workspace_bytes", N, H, W, 8, count="N")
+    need = L.load().iir_dists_image_stats_workspace_bytes(N, H, W)
+    _refuse("dists_image_stats_workspace_bytes", need >= 0, f"unsupported geometry N={N} H={H} W={W}")
+    return int(need)
+
+
+def dists_image_stats(a, b, ws=None, out=None):
+    """`dists_stats` of DISTS's stage 0, the raw images (iir_dists_image_stats): `a`, `b` contiguous sources of `image_metrics`
+    with 3 channels, both fp32 (N, 3, H, W) in [0, 1] or both uint8 (N, H, W, 3) (x = u / 255 in fp32: a uint8 image and its fp32
+    copy give equal bits).  Returns fp64 (N, 3, 5)."""
+    who = "dists_image_stats"
+    u8, N, H, W = _chk_image_pair(who, a, b)
+    tensors = [a, b]
+    _chk_stats_out(who, out, N, 3, tensors)
+    _chk_cuda(who, *tensors)
+    h = L.load()
+    need = h.iir_dists_image_stats_workspace_bytes(N, H, W)
+    _refuse(who, need >= 0, f"unsupported geometry N={N} H={H} W={W}")
+    ws = _workspace(who, ws, need, a.device, where="the images' device")
+    if out is None:
+        out = torch.empty(N, 3, DISTS_STATS, dtype=torch.float64, device=a.device)
+    L.check(h.iir_dists_image_stats(a.data_ptr(), b.data_ptr(), int(u8), N, H, W, ws.data_ptr(), ws.numel() * ws.element_size(), out.data_ptr(),
+                                    _stream()), "iir_dists_image_stats")
     return out
