@@ -38,22 +38,6 @@ constexpr int STATS = IIR_DISTS_STATS;
 constexpr int FINAL_COLS = 32, FINAL_SLICES = NT / FINAL_COLS;
 static_assert(STATS == 5, "sum a, sum b, sum a^2, sum b^2, sum ab");
 
-template <typename E> __device__ __forceinline__ void load8(const E* p, float (&v)[8]) {
-    const typename ET<E>::x8 r = *(const typename ET<E>::x8*)p;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (float)r[i];
-}
-
-template <typename E> __device__ __forceinline__ void store8(E* p, const float (&v)[8]) {
-    typename ET<E>::x8 r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r[i] = (E)v[i];
-    *(typename ET<E>::x8*)p = r;
-}
-
-// NaN stays NaN (a comparison with it is false), so an overflow upstream still shows in the sums
-__device__ __forceinline__ float relu_f(float x) { return x < 0.0f ? 0.0f : x; }
-
 // ---- L2 pooling ------------------------------------------------------------------------------------------------------------
 // grid ceil(images * OH * OW * chunks / NT); a thread owns 8 channels of one output pixel
 template <typename E>

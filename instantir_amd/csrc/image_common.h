@@ -1,6 +1,6 @@
-// What the image kernels (metrics.hip, niqe.hip, lpips.hip, resample.hip) agree on, defined once: which pixel a source holds,
-// the rounding to the 8-bit grid, the BT.601 luma, and the fixed summation orders that make equal inputs give equal bits.
-// Included by those four files only; each is compiled with -ffp-contract=off, so nothing here is fused that is not written as
+// What the image kernels (metrics.hip, niqe.hip, lpips.hip, dists.hip, resample.hip) agree on, defined once: which pixel a source
+// holds, the rounding to the 8-bit grid, the BT.601 luma, the 16-bit channel access and ReLU of the two VGG-16 scorers, and the
+// fixed summation orders that make equal inputs give equal bits.  Included by those five files only; each is compiled with -ffp-contract=off, so nothing here is fused that is not written as
 // fmaf, and every statement below keeps its operands and their order.
 #pragma once
 #include "common.h"
@@ -30,6 +30,23 @@ __device__ __forceinline__ float luma_bt601(float r, float g, float b) {
     t = t + 24.966f * b;
     return 16.0f + t / 255.0f;
 }
+
+// eight consecutive 16-bit channels (fp16 or bf16, 16-byte aligned) as one load or store, held in fp32 (lpips.hip, dists.hip)
+template <typename E> __device__ __forceinline__ void load8(const E* p, float (&v)[8]) {
+    const typename ET<E>::x8 r = *(const typename ET<E>::x8*)p;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = (float)r[i];
+}
+
+template <typename E> __device__ __forceinline__ void store8(E* p, const float (&v)[8]) {
+    typename ET<E>::x8 r;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r[i] = (E)v[i];
+    *(typename ET<E>::x8*)p = r;
+}
+
+// NaN stays NaN (a comparison with it is false), so an overflow upstream still shows in the distance and in the sums
+__device__ __forceinline__ float relu_f(float x) { return x < 0.0f ? 0.0f : x; }
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll

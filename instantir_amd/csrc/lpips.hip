@@ -31,22 +31,6 @@ constexpr int CPAD = IIR_LPIPS_CPAD;
 constexpr int MAX_C = IIR_LPIPS_MAX_C;
 static_assert(CPAD % 8 == 0 && MAX_C == 64 * 8, "one wave holds a pixel");
 
-template <typename E> __device__ __forceinline__ void load8(const E* p, float (&v)[8]) {
-    const typename ET<E>::x8 r = *(const typename ET<E>::x8*)p;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (float)r[i];
-}
-
-template <typename E> __device__ __forceinline__ void store8(E* p, const float (&v)[8]) {
-    typename ET<E>::x8 r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r[i] = (E)v[i];
-    *(typename ET<E>::x8*)p = r;
-}
-
-// NaN stays NaN (a comparison with it is false), so an overflow upstream still shows in the distance
-__device__ __forceinline__ float relu_f(float x) { return x < 0.0f ? 0.0f : x; }
-
 // grid ceil(N * H * W * (CPAD / 8) / NT); a thread owns 8 of a pixel's CPAD output channels
 template <typename E>
 __global__ __launch_bounds__(NT) void lpips_prep_kernel(const void* src, int u8, long pixels, long HW, const double* affine, E* out, long ldo) {

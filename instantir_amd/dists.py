@@ -27,10 +27,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
-from .engine import Arena
-from .images import dims, host_source, scoring_device
-from .lpips import (DTYPES, SLICES, VGG_WIDTHS, _pad64, check_pair_geometry, get_conv, get_tensor, pack_convs, pair_buffers,
-                    synthetic_convs)
+from .vgg import VGG_WIDTHS, PairModel, get_tensor, load_state_dicts, pair_view, read_convs, read_triples, slice_widths, synthetic_convs
 
 STAGES = 6
 C1 = C2 = 1e-6
@@ -65,42 +62,30 @@ def parse_state_dict(sd, weights_sd=None):
     if src is None:
         raise ValueError(f"{WHO}: a torchvision VGG-16 state dict needs alpha and beta too (weights_path: DISTS's weights.pt, "
                          "keys alpha, beta)")
-    convs, cin = [], 3
-    for k, idx in enumerate(SLICES, 1):
-        for i in idx:
-            convs.append(get_conv(sd, f"stage{k}.{i}" if whole else f"features.{i}", cin, WHO))
-            cin = convs[-1][0].shape[0]
-    chns = 3 + sum(convs[j][0].shape[0] for j in (1, 3, 6, 9, 12))
-    vecs = []
+    convs, vecs = read_convs(sd, "stage{k}.{i}" if whole else None, WHO), []
+    chns = 3 + sum(slice_widths(convs))
     for key in ("alpha", "beta"):
         v = get_tensor(src, key, WHO)
         if v.numel() != chns or tuple(v.shape) not in ((1, chns, 1, 1), (chns,)):
             raise ValueError(f"{WHO}: {key} must be shaped (1, {chns}, 1, 1), got {tuple(v.shape)}")
         vecs.append(v.double().reshape(chns).contiguous())
-    mean, std = MEAN, STD
-    if whole and "mean" in sd:
-        for key in ("mean", "std"):
-            if get_tensor(sd, key, WHO).numel() != 3:
-                raise ValueError(f"{WHO}: {key} must hold 3 values, got {tuple(sd[key].shape)}")
-        mean = tuple(get_tensor(sd, "mean", WHO).double().reshape(3).tolist())
-        std = tuple(get_tensor(sd, "std", WHO).double().reshape(3).tolist())
+    mean, std = read_triples(sd if whole else {}, ("mean", "std"), (MEAN, STD), WHO)
     return convs, vecs[0], vecs[1], mean, std
 
 
 def load_weights(path, weights_path=None):
     """`parse_state_dict` of one or two files, each read with safetensors or `torch.load(..., weights_only=True)` on the CPU."""
-    from .loaders import _load_file
-    return parse_state_dict(_load_file(path), None if weights_path is None else _load_file(weights_path))
+    return load_state_dicts(parse_state_dict, path, weights_path)
 
 
-class DISTS:
+class DISTS(PairModel):
+    """`from_state_dict(sd, weights_sd)`, `from_files(vgg_or_dists_path, weights_path)` and `synthetic(seed, widths)` build one."""
+    NAME, MODULE, WHY = "DISTS", "instantir_amd.dists", "as for LPIPS: four halvings must leave the last stage a pixel"
+    STAGE0 = (3,)                                                             # stage 0 is the image: `widths` and `padded` start with it
+    parse_state_dict, synthetic_state_dict = staticmethod(parse_state_dict), staticmethod(synthetic_state_dict)
+
     def __init__(self, convs, alpha, beta, mean=MEAN, std=STD, device=None, dtype=torch.float16):
-        if dtype not in DTYPES:
-            raise ValueError("DISTS: dtype must be torch.float16 (default) or torch.bfloat16")
-        self.device, self.dtype, self.dtype_name = scoring_device(device, "instantir_amd.dists"), dtype, DTYPES[dtype]
-        self.widths = (3,) + tuple(convs[j][0].shape[0] for j in (1, 3, 6, 9, 12))
-        self.padded = (3,) + tuple(_pad64(c) for c in self.widths[1:])        # the conv reads whole 64-channel K tiles (pack_convs)
-        self.w = pack_convs(convs, self.device, dtype)
+        super().__init__(convs, device, dtype)
         # the sums of a pair: one row per (padded) channel, stage after stage.  Padding channels carry a = b = 0, which gives
         # S = 1, so the weighting gathers the real channels only: (STAGES, widest) indices, the tail of a narrower stage
         # pointing at its first channel with weight 0.
@@ -123,22 +108,8 @@ class DISTS:
         self.alpha, self.beta = (wa / total).to(self.device), (wb / total).to(self.device)
         self.mean, self.std = tuple(mean), tuple(std)
         self.affine = ops.dists_affine(self.device, mean, std)
-        self.arena = Arena(self.device, dtype)
         self.ws = None
 
-    @classmethod
-    def from_state_dict(cls, sd, weights_sd=None, device=None, dtype=torch.float16):
-        return cls(*parse_state_dict(sd, weights_sd), device=device, dtype=dtype)
-
-    @classmethod
-    def from_files(cls, vgg_or_dists_path, weights_path=None, device=None, dtype=torch.float16):
-        return cls(*load_weights(vgg_or_dists_path, weights_path), device=device, dtype=dtype)
-
-    @classmethod
-    def synthetic(cls, seed, widths=VGG_WIDTHS, device=None, dtype=torch.float16):
-        return cls.from_state_dict(synthetic_state_dict(seed, widths), device=device, dtype=dtype)
-
-    # ---- geometry -----------------------------------------------------------------------------------
     def stage_sizes(self, H, W):
         """(H_k, W_k) of the six stages: the image twice, then ceil halving by each of the four L2 pools."""
         sizes = [(H, W), (H, W)]
@@ -146,14 +117,6 @@ class DISTS:
             H, W = (H + 1) // 2, (W + 1) // 2
             sizes.append((H, W))
         return sizes
-
-    def _largest_activation_bytes(self, H, W):
-        return 2 * H * W * max(ops.LPIPS_CPAD, self.padded[1]) * 2
-
-    def _check_geometry(self, H, W):
-        """Raised before any launch: the rule of `LPIPS._check_geometry` (a side of at least 16; the largest activation of a pair,
-        both images at full resolution in the first stage's channels, below 2 GiB)."""
-        check_pair_geometry("DISTS", H, W, self._largest_activation_bytes(H, W), "as for LPIPS: four halvings must leave the last stage a pixel")
 
     def _workspace(self, H, W):
         need = max([ops.dists_image_stats_workspace_bytes(1, H, W)]
@@ -165,33 +128,21 @@ class DISTS:
     # ---- the network --------------------------------------------------------------------------------
     def _pair(self, a, b, H, W, sums):
         """One pair through the network: a, b sources of one image each (the same kind); sums: fp64 (offsets[-1], 5)."""
-        o = ops
-        sizes = self.stage_sizes(H, W)
-        half = max(2 * h * w * c for (h, w), c in zip(sizes[1:], (max(ops.LPIPS_CPAD, self.padded[1]),) + self.padded[2:]))
-        cur, other = pair_buffers(self.arena, half)
-        ws = self._workspace(H, W)
+        sizes, ws = self.stage_sizes(H, W)[1:], self._workspace(H, W)
         out = lambda k: sums[self.offsets[k]:self.offsets[k + 1]].view(1, self.padded[k], ops.DISTS_STATS)
-        o.dists_image_stats(a, b, ws=ws, out=out(0))
-        rows = 2 * H * W
-        x = cur[:rows * ops.LPIPS_CPAD].view(rows, ops.LPIPS_CPAD)
-        o.lpips_prep(a, x[:H * W], self.affine)
-        o.lpips_prep(b, x[H * W:], self.affine)
-        j = 0
-        for l, idx in enumerate(SLICES):
-            for i in idx:
-                w, bias = self.w[j]
-                y = other[:rows * w.shape[0]].view(rows, w.shape[0])
-                o.conv2d(x.view(2, H, W, x.shape[1]), w, y, bias=bias)
-                if i != idx[-1]:
-                    o.relu_(y)
-                x, cur, other, j = y, other, cur, j + 1
-            o.dists_stats(x, 1, H, W, ws=ws, out=out(l + 1))
-            if l < 4:
-                h2, w2 = sizes[l + 2]
-                pooled = other[:2 * h2 * w2 * x.shape[1]].view(2 * h2 * w2, x.shape[1])
-                o.dists_l2pool(x, 2, H, W, out=pooled)
-                x, cur, other, H, W = pooled, other, cur, h2, w2
-                rows = 2 * H * W
+        ops.dists_image_stats(a, b, ws=ws, out=out(0))
+
+        def stage(l, x, H, W, other):
+            ops.dists_stats(x, 1, H, W, ws=ws, out=out(l + 1))
+            return ops.dists_l2pool(x, 2, H, W, out=pair_view(other, *sizes[l + 1], x.shape[1])) if l < 4 else None
+        self._trunk(a, b, sizes, stage)
+
+    def _same_kind(self, ta, tb):
+        """Stage 0 reads both sources as one kind: of a mixed pair the uint8 one becomes its fp32 copy, u / 255 in fp32 (on the
+        host: a division)."""
+        if ta.dtype != tb.dtype:
+            ta, tb = (t.permute(0, 3, 1, 2).float() / 255.0 if t.dtype == torch.uint8 else t for t in (ta, tb))
+        return ta, tb
 
     def _terms(self, sums, pixels):
         """fp64 (STAGES, 2): the structure and the texture term of every stage from a pair's sums; their sum is 1 - DISTS."""
@@ -206,28 +157,13 @@ class DISTS:
         """DISTS of `a` against `b`, each what `metrics.psnr` accepts (a PIL image or a list of them, a numpy array, a tensor; 3
         channels, [0, 1] scale or 8-bit).  Returns fp64 (N,) on the device; with `components` a pair (that, fp64 (N, 6, 2): per
         stage the structure term sum_c alpha_c S1_c / ws and the texture term sum_c beta_c S2_c / ws, whose sum is 1 - score)."""
-        ta, _ = host_source(a, "a")
-        tb, _ = host_source(b, "b")
-        da, db = dims(ta), dims(tb)
-        if da != db:
-            raise ValueError(f"DISTS: b is (N, C, H, W) = {db} but its counterpart is {da}")
-        N, C, H, W = da
-        if C != 3:
-            raise ValueError(f"DISTS: a and b must have 3 channels, got {C}")
-        self._check_geometry(H, W)
-        if self.device.type != "cuda":
-            raise ValueError(f"DISTS: the model was built on {self.device}; there is no host path")
-        if ta.dtype != tb.dtype:            # stage 0 reads both sources as one kind: the uint8 one becomes its fp32 copy, u / 255 in fp32
-            ta, tb = (t.permute(0, 3, 1, 2).float() / 255.0 if t.dtype == torch.uint8 else t for t in (ta, tb))      # (on the host: a division)
-        ta, tb = ta.to(self.device).contiguous(), tb.to(self.device).contiguous()
+        ta, tb, (N, H, W) = self._upload(a, b)
         pixels = torch.tensor([float(h * w) for h, w in self.stage_sizes(H, W)], dtype=torch.float64).view(STAGES, 1, 1).to(self.device)
         sums = torch.empty(N, self.offsets[-1], ops.DISTS_STATS, dtype=torch.float64, device=self.device)
         terms = torch.empty(N, STAGES, 2, dtype=torch.float64, device=self.device)
         for n in range(N):
             self._pair(ta[n:n + 1], tb[n:n + 1], H, W, sums[n])
             terms[n] = self._terms(sums[n], pixels)
-        if not bool(torch.isfinite(sums).all()):
-            raise FloatingPointError(f"DISTS produced a non-finite sum (activation overflow): this model stores its activations as "
-                                     f"{self.dtype_name}; build it with dtype=torch.bfloat16")
+        self._check_finite(sums, "sum")
         score = torch.stack([1.0 - terms[n].sum() for n in range(N)])
         return (score, terms) if components else score

@@ -271,38 +271,28 @@ def apply_metrics(args):
     return {"gt_path": gt, "input_fidelity": fidelity, "metrics": names, "y_channel": y, "crop_border": int(crop or 0)}
 
 
-def apply_lpips(args):
-    """`--lpips_path PATH [--lpips_lin_path PATH]` -> {"path", "lin_path"}, or None without the flag (an addition: the reference
-    builds LPIPS for training only, losses/losses.py:81-95).  Refused: the lin file without the flag, the flag without a
-    comparison to add the figure to, and a file that does not exist."""
-    path, lin = getattr(args, "lpips_path", None), getattr(args, "lpips_lin_path", None)
-    if path is None:
-        if lin is not None:
-            raise SystemExit("--lpips_lin_path needs --lpips_path")
-        return None
-    if getattr(args, "gt_path", None) is None and not getattr(args, "input_fidelity", False):
-        raise SystemExit("--lpips_path needs --gt_path or --input_fidelity")
-    for flag, f in (("--lpips_path", path), ("--lpips_lin_path", lin)):
-        if f is not None and not os.path.isfile(f):
-            raise SystemExit(f"{flag} {f} is not a file")
-    return {"path": path, "lin_path": lin}
+# the pair scorers: name -> (path flag, second-file flag, second-file keyword of the settings, module, class)
+PAIR_SCORERS = {"lpips": ("lpips_path", "lpips_lin_path", "lin_path", "lpips", "LPIPS"),
+                "dists": ("dists_path", "dists_weights_path", "weights_path", "dists", "DISTS")}
 
 
-def apply_dists(args):
-    """`--dists_path PATH [--dists_weights_path PATH]` -> {"path", "weights_path"}, or None without the flag (an addition: the
-    reference reports no figures).  Refused as `apply_lpips` refuses: the weights file without the flag, the flag without a
-    comparison to add the figure to, and a file that does not exist."""
-    path, weights = getattr(args, "dists_path", None), getattr(args, "dists_weights_path", None)
+def apply_pair_scorer(name, args):
+    """`--lpips_path PATH [--lpips_lin_path PATH]` -> {"path", "lin_path"}, `--dists_path PATH [--dists_weights_path PATH]` ->
+    {"path", "weights_path"}, or None without the flag (an addition: the reference builds LPIPS for training only,
+    losses/losses.py:81-95, and reports no figures).  Refused: the second file without the flag, the flag without a comparison
+    to add the figure to, and a file that does not exist."""
+    flag, second_flag, second_key = PAIR_SCORERS[name][:3]
+    path, second = getattr(args, flag, None), getattr(args, second_flag, None)
     if path is None:
-        if weights is not None:
-            raise SystemExit("--dists_weights_path needs --dists_path")
+        if second is not None:
+            raise SystemExit(f"--{second_flag} needs --{flag}")
         return None
     if getattr(args, "gt_path", None) is None and not getattr(args, "input_fidelity", False):
-        raise SystemExit("--dists_path needs --gt_path or --input_fidelity")
-    for flag, f in (("--dists_path", path), ("--dists_weights_path", weights)):
+        raise SystemExit(f"--{flag} needs --gt_path or --input_fidelity")
+    for fl, f in ((flag, path), (second_flag, second)):
         if f is not None and not os.path.isfile(f):
-            raise SystemExit(f"{flag} {f} is not a file")
-    return {"path": path, "weights_path": weights}
+            raise SystemExit(f"--{fl} {f} is not a file")
+    return {"path": path, second_key: second}
 
 
 def apply_niqe(args):
@@ -342,22 +332,14 @@ def score_niqe(setup, model, saved_path, original, device):
     return row
 
 
-def build_lpips(setup, device):
-    """The LPIPS model of `apply_lpips`' settings on `device`; a file that is not one of the two formats ends the run."""
-    from .lpips import LPIPS
+def build_pair_scorer(name, setup, device):
+    """The model of `apply_pair_scorer`'s settings on `device`; a file that is not one of its two formats ends the run."""
+    import importlib
+    flag, _, second_key, module, cls = PAIR_SCORERS[name]
     try:
-        return LPIPS.from_files(setup["path"], setup["lin_path"], device=device)
+        return getattr(importlib.import_module("." + module, __package__), cls).from_files(setup["path"], setup[second_key], device=device)
     except ValueError as e:
-        raise SystemExit(f"--lpips_path: {e}")
-
-
-def build_dists(setup, device):
-    """The DISTS model of `apply_dists`' settings on `device`; a file that is not one of the two formats ends the run."""
-    from .dists import DISTS
-    try:
-        return DISTS.from_files(setup["path"], setup["weights_path"], device=device)
-    except ValueError as e:
-        raise SystemExit(f"--dists_path: {e}")
+        raise SystemExit(f"--{flag}: {e}")
 
 
 def gt_image(setup, name, size):
@@ -371,17 +353,14 @@ def gt_image(setup, name, size):
     return im
 
 
-def score_saved(setup, saved_path, gt, original, device, lpips_model=None, dists_model=None):
+def score_saved(setup, saved_path, gt, original, device, models=None):
     """The figures of one saved file, from the 8-bit image as it was saved (read back): {"psnr", "ssim"} against `gt`,
-    {"input_psnr", "input_ssim"} against `original`, whichever were asked for; with an `lpips_model` "lpips" / "input_lpips" too,
-    with a `dists_model` "dists" / "input_dists"."""
+    {"input_psnr", "input_ssim"} against `original`, whichever were asked for; with `models` {"lpips": model} "lpips" /
+    "input_lpips" too, with {"dists": model} "dists" / "input_dists"."""
     from . import metrics as M
     saved = Image.open(saved_path).convert("RGB")
     kw = dict(metrics=setup["metrics"], crop_border=setup["crop_border"], y_channel=setup["y_channel"], device=device)
-    if lpips_model is not None:
-        kw["lpips_model"] = lpips_model
-    if dists_model is not None:
-        kw["dists_model"] = dists_model
+    kw.update({name + "_model": model for name, model in (models or {}).items()})
     row = {}
     try:
         if gt is not None:
@@ -558,13 +537,12 @@ def main(args, device, rank=0, world=1):
     apply_device_resize(None, args)              # (a flag error should not wait for the weights to load)
     degrading = apply_degrade(args)              # (before apply_metrics: it may set --gt_path)
     scoring = apply_metrics(args)
-    lpips_setup = apply_lpips(args)
-    dists_setup = apply_dists(args)
+    pair_setups = {name: apply_pair_scorer(name, args) for name in PAIR_SCORERS}
+    pair_setups = {name: s for name, s in pair_setups.items() if s}
     niqe_setup = apply_niqe(args)
     niqe_model = build_niqe(niqe_setup) if niqe_setup else None
     pipe, lcm_scheduler = build_pipeline(args, device)
-    lpips_model = build_lpips(lpips_setup, device) if lpips_setup else None
-    dists_model = build_dists(dists_setup, device) if dists_setup else None
+    pair_models = {name: build_pair_scorer(name, s, device) for name, s in pair_setups.items()}
     apply_freeu(pipe, args)
     apply_scheduler(pipe, args)
     pag_kw = apply_pag(pipe, args)
@@ -630,16 +608,11 @@ def main(args, device, rank=0, world=1):
             rec.save(f"{out_dir}/{lq_batch[i]}")
             if scoring:
                 scores[lq_batch[i]] = score_saved(scoring, f"{out_dir}/{lq_batch[i]}", gts[i] if gts else None,
-                                                  originals[i] if scoring["input_fidelity"] else None, device, lpips_model,
-                                                  dists_model)
+                                                  originals[i] if scoring["input_fidelity"] else None, device, pair_models)
             if niqe_setup:
                 scores.setdefault(lq_batch[i], {}).update(score_niqe(niqe_setup, niqe_model, f"{out_dir}/{lq_batch[i]}", originals[i], device))
     if scoring or niqe_setup:
-        setup = dict(scoring or {})
-        if lpips_setup:
-            setup["lpips"] = lpips_setup
-        if dists_setup:
-            setup["dists"] = dists_setup
+        setup = dict(scoring or {}, **pair_setups)
         if niqe_setup:
             setup["niqe"] = niqe_setup
         print(write_metrics(setup, scores, out_dir, rank, world))

@@ -102,31 +102,36 @@ def _with_means(res):
 def _model_scores(who, a, b, model, device, name):
     d = None if device is None else torch.device(device)
     if d is not None and (d.type != model.device.type or (d.index is not None and d.index != model.device.index)):
-        raise ValueError(f"{who}: the {name} model lives on {model.device}, not on {d}")
+        raise ValueError(f"{who}: the {name.upper()} model lives on {model.device}, not on {d}")
     return model(a, b).cpu().tolist()
 
 
-def _lpips_scores(who, a, b, model, device):
-    return _model_scores(who, a, b, model, device, "LPIPS")
+def _add_model_scores(res, who, a, b, device, lpips_model, dists_model):
+    """`res` with the per-image scores of the pair models that were given, "lpips" before "dists", and every mean."""
+    for name, model in (("lpips", lpips_model), ("dists", dists_model)):
+        if model is not None:
+            res[name] = _model_scores(who, a, b, model, device, name)
+    return _with_means(res)
+
+
+def _model_metric(name, a, b, model, device):
+    _, single_a = host_source(a, "a")
+    _, single_b = host_source(b, "b")
+    out = _model_scores(name, a, b, model, device, name)
+    return out[0] if single_a and single_b else out
 
 
 def lpips(a, b, model, device=None):
     """LPIPS of `a` against `b` under `model` (an `instantir_amd.lpips.LPIPS`; DESIGN.md section 7 "LPIPS"): a float for one
     image, a list of floats for a batch; 0 for identical images.  The whole image is scored: LPIPS has no crop, luma or
     quantise option."""
-    _, single_a = host_source(a, "a")
-    _, single_b = host_source(b, "b")
-    out = _lpips_scores("lpips", a, b, model, device)
-    return out[0] if single_a and single_b else out
+    return _model_metric("lpips", a, b, model, device)
 
 
 def dists(a, b, model, device=None):
     """DISTS of `a` against `b` under `model` (an `instantir_amd.dists.DISTS`; DESIGN.md section 7 "DISTS"): a float for one
     image, a list of floats for a batch; 0 for identical images.  The whole image is scored, as for LPIPS."""
-    _, single_a = host_source(a, "a")
-    _, single_b = host_source(b, "b")
-    out = _model_scores("dists", a, b, model, device, "DISTS")
-    return out[0] if single_a and single_b else out
+    return _model_metric("dists", a, b, model, device)
 
 
 def niqe(images, model, crop_border=0, device=None):
@@ -143,11 +148,7 @@ def evaluate(a, b, metrics=METRICS, crop_border=0, y_channel=False, quantize=Fal
     With an `lpips_model` the result gains "lpips" and "lpips_mean" (of the whole, uncropped RGB images), with a `dists_model`
     "dists" and "dists_mean" likewise."""
     res, _ = _run("evaluate", a, b, metrics, crop_border, y_channel, quantize, device)
-    if lpips_model is not None:
-        res["lpips"] = _lpips_scores("evaluate", a, b, lpips_model, device)
-    if dists_model is not None:
-        res["dists"] = _model_scores("evaluate", a, b, dists_model, device, "DISTS")
-    return _with_means(res)
+    return _add_model_scores(res, "evaluate", a, b, device, lpips_model, dists_model)
 
 
 def input_fidelity(restored, lq, filter="bicubic", metrics=METRICS, crop_border=0, y_channel=False, device=None, lpips_model=None,
@@ -177,8 +178,4 @@ def input_fidelity(restored, lq, filter="bicubic", metrics=METRICS, crop_border=
         quantize = (both_u8, False)
     _check_pair("input_fidelity", tr, tl, names, crop_border, y_channel, arg_b="lq")
     res = _score(tr, tl, names, crop_border, y_channel, quantize, dev if dev is not None else device)
-    if lpips_model is not None:
-        res["lpips"] = _lpips_scores("input_fidelity", tr, tl, lpips_model, device)
-    if dists_model is not None:
-        res["dists"] = _model_scores("input_fidelity", tr, tl, dists_model, device, "DISTS")
-    return _with_means(res)
+    return _add_model_scores(res, "input_fidelity", tr, tl, device, lpips_model, dists_model)

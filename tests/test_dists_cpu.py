@@ -317,24 +317,24 @@ def test_cli_flags(tmp_path):
     parse = lambda *extra: cli.build_parser().parse_args(["--test_path", "x", "--synthetic", "tiny", *extra])
     weights = tmp_path / "dists.pth"
     torch.save(DS.synthetic_state_dict(1, (8, 8, 8, 8, 8)), str(weights))
-    assert cli.apply_dists(parse()) is None and cli.apply_dists(parse("--input_fidelity")) is None
+    assert cli.apply_pair_scorer("dists", parse()) is None and cli.apply_pair_scorer("dists", parse("--input_fidelity")) is None
     with pytest.raises(SystemExit, match="--dists_path needs --gt_path or --input_fidelity"):
-        cli.apply_dists(parse("--dists_path", str(weights)))
+        cli.apply_pair_scorer("dists", parse("--dists_path", str(weights)))
     with pytest.raises(SystemExit, match="--dists_path needs --gt_path or --input_fidelity"):      # and before any weight is built
         cli.main(parse("--dists_path", str(weights)), "cpu")
     with pytest.raises(SystemExit, match="--dists_weights_path needs --dists_path"):
-        cli.apply_dists(parse("--input_fidelity", "--dists_weights_path", str(weights)))
+        cli.apply_pair_scorer("dists", parse("--input_fidelity", "--dists_weights_path", str(weights)))
     with pytest.raises(SystemExit, match="--dists_path .*none.pth is not a file"):
-        cli.apply_dists(parse("--input_fidelity", "--dists_path", str(tmp_path / "none.pth")))
+        cli.apply_pair_scorer("dists", parse("--input_fidelity", "--dists_path", str(tmp_path / "none.pth")))
     with pytest.raises(SystemExit, match="--dists_weights_path .*none.pth is not a file"):
-        cli.apply_dists(parse("--input_fidelity", "--dists_path", str(weights), "--dists_weights_path", str(tmp_path / "none.pth")))
+        cli.apply_pair_scorer("dists", parse("--input_fidelity", "--dists_path", str(weights), "--dists_weights_path", str(tmp_path / "none.pth")))
     args = parse("--gt_path", str(tmp_path), "--dists_path", str(weights))
-    assert cli.apply_dists(args) == {"path": str(weights), "weights_path": None}
-    assert cli.apply_lpips(args) is None
+    assert cli.apply_pair_scorer("dists", args) == {"path": str(weights), "weights_path": None}
+    assert cli.apply_pair_scorer("lpips", args) is None
     s = cli.apply_metrics(args)                                     # untouched by the flag: exactly its five keys
     assert s == {"gt_path": str(tmp_path), "input_fidelity": False, "metrics": ("psnr", "ssim"), "y_channel": False, "crop_border": 0}
     with pytest.raises(SystemExit):
         parse("--metrics", "dists")
     torch.save({"stage1.0.weight": torch.zeros(8, 3, 3, 3)}, str(tmp_path / "broken.pth"))
     with pytest.raises(SystemExit, match="--dists_path: DISTS weights: missing key"):
-        cli.build_dists({"path": str(tmp_path / "broken.pth"), "weights_path": None}, "cpu")
+        cli.build_pair_scorer("dists", {"path": str(tmp_path / "broken.pth"), "weights_path": None}, "cpu")

@@ -272,23 +272,23 @@ def test_cli_flags(tmp_path):
     parse = lambda *extra: cli.build_parser().parse_args(["--test_path", "x", "--synthetic", "tiny", *extra])
     weights = tmp_path / "lpips.pth"
     torch.save(LP.synthetic_state_dict(1, (8, 8, 8, 8, 8)), str(weights))
-    assert cli.apply_lpips(parse()) is None and cli.apply_lpips(parse("--input_fidelity")) is None
+    assert cli.apply_pair_scorer("lpips", parse()) is None and cli.apply_pair_scorer("lpips", parse("--input_fidelity")) is None
     with pytest.raises(SystemExit, match="--lpips_path needs --gt_path or --input_fidelity"):
-        cli.apply_lpips(parse("--lpips_path", str(weights)))
+        cli.apply_pair_scorer("lpips", parse("--lpips_path", str(weights)))
     with pytest.raises(SystemExit, match="--lpips_path needs --gt_path or --input_fidelity"):      # and before any weight is built
         cli.main(parse("--lpips_path", str(weights)), "cpu")
     with pytest.raises(SystemExit, match="--lpips_lin_path needs --lpips_path"):
-        cli.apply_lpips(parse("--input_fidelity", "--lpips_lin_path", str(weights)))
+        cli.apply_pair_scorer("lpips", parse("--input_fidelity", "--lpips_lin_path", str(weights)))
     with pytest.raises(SystemExit, match="--lpips_path .*none.pth is not a file"):
-        cli.apply_lpips(parse("--input_fidelity", "--lpips_path", str(tmp_path / "none.pth")))
+        cli.apply_pair_scorer("lpips", parse("--input_fidelity", "--lpips_path", str(tmp_path / "none.pth")))
     with pytest.raises(SystemExit, match="--lpips_lin_path .*none.pth is not a file"):
-        cli.apply_lpips(parse("--input_fidelity", "--lpips_path", str(weights), "--lpips_lin_path", str(tmp_path / "none.pth")))
+        cli.apply_pair_scorer("lpips", parse("--input_fidelity", "--lpips_path", str(weights), "--lpips_lin_path", str(tmp_path / "none.pth")))
     args = parse("--gt_path", str(tmp_path), "--lpips_path", str(weights))
-    assert cli.apply_lpips(args) == {"path": str(weights), "lin_path": None}
+    assert cli.apply_pair_scorer("lpips", args) == {"path": str(weights), "lin_path": None}
     s = cli.apply_metrics(args)                                     # untouched by the flag: exactly its five keys
     assert s == {"gt_path": str(tmp_path), "input_fidelity": False, "metrics": ("psnr", "ssim"), "y_channel": False, "crop_border": 0}
     with pytest.raises(SystemExit):
         parse("--metrics", "lpips")
     torch.save({"net.slice1.0.weight": torch.zeros(8, 3, 3, 3)}, str(tmp_path / "broken.pth"))
     with pytest.raises(SystemExit, match="--lpips_path: LPIPS weights: missing key"):
-        cli.build_lpips({"path": str(tmp_path / "broken.pth"), "lin_path": None}, "cpu")
+        cli.build_pair_scorer("lpips", {"path": str(tmp_path / "broken.pth"), "lin_path": None}, "cpu")

@@ -81,7 +81,7 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--iters", type=int, default=3)
     args = ap.parse_args()
-    from instantir_amd import lib, lpips as LP, ops
+    from instantir_amd import lib, lpips as LP, ops, vgg as VG
     lib.load()
     if not torch.cuda.is_available():
         raise SystemExit("lpips_bench needs an MI355X: there is nothing to time on the host")
@@ -103,14 +103,14 @@ def main():
         print(f"{side}x{side} pair, fp16: {total / 1e3:.2f} ms per call (windows {min(us['pair']) / 1e3:.2f} .. {max(us['pair']) / 1e3:.2f} ms); "
               f"empty call {empty:.0f} us; score {float(model(a, b)[0]):.4f}", flush=True)
         timed = TimedOps(ops)
-        LP.ops = timed
+        LP.ops = VG.ops = timed              # (the tap is launched from lpips.py, the trunk from vgg.py)
         try:
             runs = []
             for _ in range(args.windows):
                 model(a, b)
                 runs.append(timed.take())
         finally:
-            LP.ops = ops
+            LP.ops = VG.ops = ops
         launches = [(runs[0][i][0], statistics.median(r[i][1] for r in runs), runs[0][i][2], runs[0][i][3]) for i in range(len(runs[0]))]
         summed = sum(t for _, t, _, _ in launches)
         for kind in ("conv2d", "lpips_prep", "relu_", "lpips_tap"):
